@@ -12,13 +12,17 @@ Infinity Cache.
 Throughput mode: ``--streams S`` (default 4) solver handles per GPU, each on its own HIP stream, take the K steps
 round robin; ``ms_per_step`` is elapsed / K, ``batch_latency_ms`` is one batch solved alone.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (contract in the task
+description) with the headline figure and the solve statistics of the timed steps; ``--dump-outputs DIR`` also writes
+what the last timed step returned (``dump_outputs``).  ``--full`` adds the measurements that take runs of their own:
+  ``batch_latency_ms``, ``value_single_call``  one batch solved alone, once per input set;
   ``roofline``      dominant kernel, EXCLUSIVE durations: a one-stream leg outside the timed region with HIP events
                     around every kernel of the handle's stream (so that kernel time x launches <= the leg's wall
                     time); algorithmic bytes = SURVEY.md 8(d)'s per-solve figure (compulsory I/O + iterations x
                     stage workspace) x the solves of one launch; ``traffic`` = HBM bytes per launch from the
                     committed PMC passes (profiles/);
   ``legs``          the other robots of the metric on the same box: panda (configs[3]) and boxer (configs[2]);
+  ``extra.cfg5``    the mixed-fleet loop below, ``--cfg5-steps`` control steps;
   ``cpu_baseline``  the CPU oracle port on this box's host cores, bounded sample, thread-scaling row.
 
 ``--config cfg5``: BASELINE configs[4], the mixed fleet as a device-resident closed loop (a step = one control step
@@ -66,6 +70,10 @@ def parse():
     ap.add_argument("--batch", type=int, default=0, help="instances per GPU (default: BASELINE batch of the config)")
     ap.add_argument("--streams", type=int, default=4, help="solver handles per GPU, each on its own HIP stream")
     ap.add_argument("--input-sets", type=int, default=6, help="distinct resident input sets the steps rotate through")
+    ap.add_argument("--full", action="store_true", help="also measure beyond the headline figure: exclusive per-kernel leg "
+                    "(batch_latency_ms, value_single_call, roofline), full-chip launch, panda / boxer legs, extra.cfg5 and "
+                    "cpu_baseline; the --no-* options below switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="headline config only (no panda / boxer legs)")
     ap.add_argument("--no-full-chip", action="store_true", help="skip the one-launch-fills-the-chip leg (profiles: keeps the kernel average to launches of one batch)")
@@ -93,6 +101,24 @@ def survey_bytes_per_solve(d, iters_mean):
     ws = 16 * N * (nx * nv + 2 * nx + 2 * nv + nv * (nv + 1) // 2 + nh + nh * nv)
     fl = N * (7.0 / 3.0 * nx ** 3 + 4 * nx ** 2 * nw + 2 * nx * nw ** 2 + nw ** 3 / 3.0) + 2.0 * N * nh * nv ** 2
     return io, ws, io + iters_mean * ws, fl
+
+
+DUMP_MAX_BYTES = 60 << 20   # under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """``--dump-outputs``: ``arrays`` (name -> host array, axis 0 = instances) as out_dir/<name>.npy in float64 (the
+    int32 flags and counts convert exactly).  Above ``max_bytes`` in all, every array keeps the same share of its
+    instances, a seeded sample in index order, so that two builds dumped with the same arguments compare row for row."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > max_bytes:
+            n = a.shape[0]
+            a = a[np.sort(np.random.default_rng(seed).permutation(n)[: n * max_bytes // total])]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 class Leg:
@@ -170,6 +196,12 @@ class Leg:
     def stats(self):
         o = self.outs[0]
         return o["exit"].cpu().numpy(), o["iters"].cpu().numpy(), o["kkt"].cpu().numpy()
+
+    def last_outputs(self, steps):
+        """what the last of ``steps`` steps of run() returned: step j of a run goes to handle j % S"""
+        o = self.outs[(steps - 1) % self.S]
+        return {name: o[key].cpu().numpy() for name, key in
+                (("z", "z"), ("exitflag", "exit"), ("iters", "iters"), ("kkt", "kkt"), ("obj", "obj"))}
 
     def close(self):
         for s in self.solvers:
@@ -316,12 +348,13 @@ def cpu_baseline(leg, gpu_z, gpu_exit, Solver, make_scenario, local_rank):
     }
 
 
-def run_cfg5(args, fleet, dev, rank, world, dd, fence, steps, warmup, cdev=None):
+def run_cfg5(args, fleet, dev, rank, world, dd, fence, steps, warmup, cdev=None, dump_dir=None):
     """BASELINE configs[4] on this rank's shard: the device-resident closed loop (scene packing + solve + plant step +
     shifted plan + warm multipliers + goal hand-over), timed like the headline (barrier + synchronize on both sides,
     max over ranks).  A STEADY loop: no episodes, no resets of the fleet -- an instance takes a new goal when it
     arrives, an instance whose solve failed goes back to its start state (rmpc_retarget_device); the statistics of
-    every control step are summed on the device.  Returns value / ms_per_step / config / loop / per_fleet on rank 0."""
+    every control step are summed on the device.  Returns value / ms_per_step / config / loop / per_fleet on rank 0.
+    ``dump_dir``: rank 0 writes every block's plan, flags and next state of the last control step there."""
     import numpy as np
     part = fleet.partition_mixed(8192 * world, world)[rank]
     counts = {k: hi - lo for k, (lo, hi) in part.items()}
@@ -348,6 +381,9 @@ def run_cfg5(args, fleet, dev, rank, world, dd, fence, steps, warmup, cdev=None)
     fence()
     gc.enable()
     elapsed = fleet.max_over_ranks(time.perf_counter() - t0, dd, cdev or dev)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"%s_%s" % (f["name"], name): f[key].cpu().numpy() for f in shard.fleets for name, key in
+                                (("z", "z"), ("exitflag", "ef"), ("iters", "it"), ("kkt", "kkt"), ("obj", "obj"), ("x", "x"))})
     ss = shard.steady_stats(reset=True)
     NST = 13   # acc (5) + events (4) + more (4) per fleet
     st = np.array([np.concatenate([ss[k]["acc"], ss[k]["events"], ss[k]["more"]]) for k in ("cfg2", "cfg3", "cfg4")]).ravel()
@@ -485,7 +521,7 @@ def main():
 
     # ------------------------------------------------------------------ cfg5: mixed-fleet closed loop
     if cfg == "cfg5":
-        res = run_cfg5(args, fleet, dev, rank, world, dd, fence, args.steps, max(3, args.warmup), cdev)
+        res = run_cfg5(args, fleet, dev, rank, world, dd, fence, args.steps, max(3, args.warmup), cdev, args.dump_outputs)
         if rank == 0:
             print(json.dumps(dict(base, **res)))
         if world > 1:
@@ -498,20 +534,22 @@ def main():
     S = max(1, min(args.streams, args.steps))
     leg = Leg(cfg, B, S, max(1, args.input_sets), dev, 1000 + 101 * rank)   # every rank owns different instances
     elapsed = timed(leg, args.steps, args.warmup, fence)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, leg.last_outputs(args.steps))
     elapsed_max = fleet.max_over_ranks(elapsed, dd, cdev)     # RCCL all-reduce(MAX)
     exitflag, iters, kkt = leg.stats()
     # RCCL all-gather of the solve statistics per rank (56 B): the only other collective
     allstats = fleet.gather_stats(fleet.solve_stats(exitflag, iters, kkt), dd, cdev)
     latency_ms, excl_wall_ms, prof = (None, None, None)
     n_excl = 0
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         # whole rotations of the input sets, so that the exclusive average and the rocprofv3 average of a
         # --streams 1 run (profiles/) cover the same mix of instances
         n_excl = 2 * max(1, args.input_sets)
         latency_ms, excl_wall_ms, prof = leg.exclusive(n_excl)
     passes = leg.solvers[0].last_passes()
     full_chip = None
-    if not args.no_kernel_events and not args.no_full_chip and cfg == "cfg2":
+    if args.full and not args.no_kernel_events and not args.no_full_chip and cfg == "cfg2":
         # the same kernel with the chip full from ONE launch: a batch of S x B instances on one stream (what the
         # S overlapped streams of the timed region add up to), exclusive HIP-event duration
         big = Leg(cfg, B * S, 1, 2, dev, 3000 + 101 * rank)
@@ -523,7 +561,7 @@ def main():
         big.close()
 
     legs = {}
-    if not args.no_legs and cfg == "cfg2":
+    if args.full and not args.no_legs and cfg == "cfg2":
         # the other robots of the metric, same box, same run (shorter legs)
         for other in ("cfg4", "cfg3"):
             lo = Leg(other, DEFAULT_BATCH[other], S, 4, dev, 2000 + 101 * rank)
@@ -545,7 +583,7 @@ def main():
     # BASELINE configs[4] (mixed fleet, 100 Hz loop) in the same line: 400 consecutive control steps of the steady loop
     # (`--config cfg5` runs it alone under the bench contract)
     cfg5_extra = None
-    if not args.no_legs and cfg == "cfg2" and world == 1:
+    if args.full and not args.no_legs and cfg == "cfg2" and world == 1:
         cfg5_extra = run_cfg5(args, fleet, dev, rank, world, dd, fence, args.cfg5_steps, 10)
 
     if rank == 0:
@@ -596,7 +634,7 @@ def main():
             out["legs"] = legs
         if cfg5_extra:
             out["extra"] = {"cfg5": cfg5_extra}
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(leg, None, None, Solver, make_scenario, local_rank)
         print(json.dumps(out))
     if world > 1:

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 R=$PWD
 TAG=${1:-r02}
 CFG=${2:-cfg2}
-B="--config $CFG --no-cpu-baseline --no-legs"
+B="--full --config $CFG --no-cpu-baseline --no-legs"
 rm -rf gpurun_out/prof_${TAG}_${CFG}*
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_${TAG}_${CFG}_s4 -- python3 bench.py $B --steps 24 --warmup 4 > gpurun_out/prof_${TAG}_${CFG}_s4.json 2> gpurun_out/prof_${TAG}_${CFG}_s4.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_${TAG}_${CFG}_s1 -- python3 bench.py $B --steps 12 --warmup 2 --streams 1 --no-full-chip > gpurun_out/prof_${TAG}_${CFG}_s1.json 2> gpurun_out/prof_${TAG}_${CFG}_s1.err
