@@ -7,7 +7,8 @@ cd "$(dirname "$0")/../.."
 OBJ=tests/host/host_sweep_asan.o
 OUT=tests/host/libhost_sweep_asan.so
 SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
-if [ ! -f $OBJ ] || [ tests/host/host_sweep.cpp -nt $OBJ ] || [ robot_mpcs_amd/csrc/rmpc_kernels.hip -nt $OBJ ]; then
+if [ ! -f $OBJ ] || [ tests/host/host_sweep.cpp -nt $OBJ ] || [ robot_mpcs_amd/csrc/rmpc_kernels.hip -nt $OBJ ] || \
+   [ robot_mpcs_amd/csrc/rmpc_riccati.hpp -nt $OBJ ]; then
   /opt/rocm/bin/hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -fno-omit-frame-pointer $SAN -ferror-limit=0 -fPIC \
     -DRMPC_SOURCE_HASH='"host"' -DRMPC_DEV_VARIANTS=0x25 -Irobot_mpcs_amd/csrc -Iinclude -c tests/host/host_sweep.cpp -o $OBJ
 fi
