@@ -94,14 +94,22 @@ EXPORTED_SYMBOLS = [
 _lib = None
 
 
+def source_files():
+    """The files the library is built from (csrc/sources.txt), None when they are not shipped alongside."""
+    root = os.path.dirname(_HERE)
+    try:
+        with open(os.path.join(_HERE, "csrc", "sources.txt")) as f:
+            paths = [os.path.join(root, ln.strip()) for ln in f if ln.strip() and not ln.startswith("#")]
+    except OSError:
+        return None
+    return paths if all(os.path.exists(p) for p in paths) else None
+
+
 def _source_hash():
     """Hash of the sources next to the library (None when they are not shipped alongside)."""
     import hashlib
-    root = os.path.dirname(_HERE)
-    paths = [os.path.join(_HERE, "csrc", "rmpc_kernels.hip"), os.path.join(_HERE, "csrc", "rmpc_model.hpp"),
-             os.path.join(_HERE, "csrc", "rmpc_spec_gen.hpp"), os.path.join(_HERE, "csrc", "rmpc_arm_fused.hpp"),
-             os.path.join(_HERE, "csrc", "rmpc_riccati.hpp"), os.path.join(root, "include", "rmpc.h")]
-    if not all(os.path.exists(p) for p in paths):
+    paths = source_files()
+    if paths is None:
         return None
     h = hashlib.sha256()
     for p in paths:

@@ -11,7 +11,8 @@
 
 #ifdef RMPC_RIC_STAMPS
 // development aid: cycles per phase of the recursion, summed over the wavefronts of all launches
-__device__ long long g_rst[8];
+// (static: one copy per translation unit, read through the unit's entries of the variant table)
+static __device__ long long g_rst[8];
 struct RicStamps {
   long long acc[8], t0;
   __device__ __forceinline__ void start() {

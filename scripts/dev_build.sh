@@ -1,11 +1,12 @@
 #!/bin/bash
-# development aid: quick one-unit build of a subset of the kernel variants into csrc/librmpc_hip_dev.so
-#   scripts/dev_build.sh 0x4 [-DRMPC_STAMPS ...]     (bit i = variant i of RMPC_VARIANTS: 0 point robot, 2 panda, 5 boxer + slack,
-#                                                      6 .. 9 chains n = 2, 4, 5, 6)
+# development aid: quick build of a subset of the kernel variants into csrc/librmpc_hip_dev.so -- the host unit and ONE
+# variant unit holding the variants of the mask (__graft_entry__.compile_library)
+#   scripts/dev_build.sh 0x4 [-DRMPC_STAMPS ...]     (bit i = variant i of RMPC_VARIANTS in rmpc_variants.hip: 0 point robot,
+#                                                      2 panda, 5 boxer + slack, 6 .. 10 chains n = 2, 4, 5, 6, 8)
 # use with RMPC_ALLOW_STALE=1 RMPC_LIB_PATH=$PWD/robot_mpcs_amd/csrc/librmpc_hip_dev.so
 set -e
-cd "$(dirname "$0")/../robot_mpcs_amd/csrc"
+cd "$(dirname "$0")/.."
 mask=${1:-0x3f}; shift || true
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DRMPC_SOURCE_HASH='"dev"' -DRMPC_DEV_VARIANTS=$mask "$@" \
-  -o librmpc_hip_dev.so rmpc_kernels.hip
-ls -la librmpc_hip_dev.so
+python -c 'import sys, __graft_entry__ as g; g.compile_library(g.CSRC + "/librmpc_hip_dev.so", "dev", [int(sys.argv[1], 0)], sys.argv[2:])' \
+  "$mask" "$@"
+ls -la robot_mpcs_amd/csrc/librmpc_hip_dev.so

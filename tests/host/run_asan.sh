@@ -1,16 +1,20 @@
 #!/bin/bash
 # Builds tests/host/host_sweep.cpp for x86 with AddressSanitizer + UBSan and runs tests/host/check_host_sweeps.py under it
-# (the compile takes ~7 minutes: the whole device file is instantiated for the host).
+# (the host unit rmpc_host.hip, with the device code it includes, compiled for the host; the harness instantiates the
+#  sweeps of three variants).
 #   bash tests/host/run_asan.sh > profiles/rNN_host_device_functions_asan_ubsan.log 2>&1
 set -e
 cd "$(dirname "$0")/../.."
 OBJ=tests/host/host_sweep_asan.o
 OUT=tests/host/libhost_sweep_asan.so
 SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
-if [ ! -f $OBJ ] || [ tests/host/host_sweep.cpp -nt $OBJ ] || [ robot_mpcs_amd/csrc/rmpc_kernels.hip -nt $OBJ ] || \
-   [ robot_mpcs_amd/csrc/rmpc_riccati.hpp -nt $OBJ ]; then
+stale=0
+for f in tests/host/host_sweep.cpp tests/host/host_prelude.h $(grep -v '^#' robot_mpcs_amd/csrc/sources.txt); do
+  if [ ! -f $OBJ ] || [ $f -nt $OBJ ]; then stale=1; fi
+done
+if [ $stale = 1 ]; then
   /opt/rocm/bin/hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -fno-omit-frame-pointer $SAN -ferror-limit=0 -fPIC \
-    -DRMPC_SOURCE_HASH='"host"' -DRMPC_DEV_VARIANTS=0x25 -Irobot_mpcs_amd/csrc -Iinclude -c tests/host/host_sweep.cpp -o $OBJ
+    -DRMPC_SOURCE_HASH='"host"' -Irobot_mpcs_amd/csrc -Iinclude -c tests/host/host_sweep.cpp -o $OBJ
 fi
 # (the symbol the registration code refers to: the device code bundle of this file -- there is none)
 FAT=$(nm -u $OBJ | awk '/__hip_fatbin_/{print $2}' | head -1)

@@ -10,7 +10,6 @@ out wrong in a different way".  Rebuilds that view in a development library and 
       runtime tables once, the view three times (the LDS / scratch / workspace poisoned before the second and third)
 """
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -29,9 +28,8 @@ def build(extra):
     try:
         with open(g.HEADER, "w") as f:
             f.write(text)
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-               '-DRMPC_SOURCE_HASH="dev"', "-DRMPC_DEV_VARIANTS=0x4"] + extra + ["-o", "librmpc_hip_dev.so", "rmpc_kernels.hip"]
-        subprocess.check_call(cmd, cwd=CSRC)
+        import __graft_entry__
+        __graft_entry__.compile_library(os.path.join(CSRC, "librmpc_hip_dev.so"), "dev", masks=[0x4], extra=extra)
     finally:
         with open(g.HEADER, "w") as f:
             f.write(committed)
