@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""Point robots (cfg2 model) crossing a store on routes from the global planner, entirely on the device -- the fleet
+form of examples/boxer_example_global.py of the reference: one global path per robot at step 0
+(``plan_batch``: cost-to-go fields of the distinct goals on the enlarged map, one descent per robot), then every
+control step ``RouteFollower.step`` (get_local_goal: the next waypoint becomes the scene's goal) ->
+``solve_scene_device`` -> ``advance_device``.  Nothing crosses PCIe between control steps; the statistics are
+accumulated on the device and read once at the end.
+
+The shelves are not constraints of the MPC (as in the reference's global example); only the margin of the enlarged map
+keeps the robots away from them.  The map is enlarged as the reference does it: the values its PNG round trip yields
+(``png_values``: 68/256 free, 253/256 occupied) through ``get_enlarged_obstacles`` (3 x 3 mean > 0.29 at
+size_robot = 0.45), which blocks every cell next to a shelf.  Goals are 10 .. 20 m away, behind at least one shelf.
+
+    python examples/fleet_global_route.py [--robots 256] [--steps 1200] [--seed 0] [--aisle 4] [--gap 3] [--shelf 2]
+                                          [--size-robot 0.45] [--threshold 1.3]
+
+Prints one JSON line: arrivals at the final goal (within the fleet's ARRIVE_TOL), the control step by which 50 / 90 /
+100 % of the arrivals happened, failed solves, the least clearance between a robot's centre and a raw-occupied cell
+(and how many robots reached 0), and ms per control step.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+# the store: 41 x 41 cells of 0.45 m centred on the origin (inside the point robot's +-10 m joint limits)
+H = W = 41
+CELL = 0.45
+X0 = Y0 = -9.0
+SIZE_ROBOT = 0.45     # k = 1: every cell that touches a shelf is blocked
+
+
+def pick_routes(raw, free, B, rng):
+    """B (start, goal) cell pairs: both free on the enlarged map, 10 .. 20 m apart, the straight line crossing a shelf."""
+    cells = np.flatnonzero(free.ravel())
+    xy = np.stack([X0 + (cells % W) * CELL, Y0 + (cells // W) * CELL], 1)
+    starts, goals = [], []
+    while len(starts) < B:
+        i, j = rng.integers(0, len(cells), 2)
+        d = np.linalg.norm(xy[i] - xy[j])
+        if not 10.0 <= d <= 20.0:
+            continue
+        t = np.linspace(0.0, 1.0, 200)[:, None]
+        seg = xy[i] + t * (xy[j] - xy[i])
+        cc = np.rint((seg - [X0, Y0]) / CELL).astype(int)
+        if not raw[cc[:, 1], cc[:, 0]].any():
+            continue
+        starts.append(cells[i]); goals.append(cells[j])
+    return np.array(starts, np.int32), np.array(goals, np.int32)
+
+
+def run(B=256, steps=1200, seed=0, dev="cuda:0", aisle=4, gap=3, size_robot=SIZE_ROBOT, threshold=1.3, shelf=2):
+    import torch
+    from robot_mpcs_amd import _lib
+    from robot_mpcs_amd.fleet import MixedFleetShard
+    from robot_mpcs_amd.global_planner import RouteFollower, plan_batch, png_values, shelf_map
+    from robot_mpcs_amd.scenarios import POINT_LIMITS, POINT_LIMITS_U, make_scenario
+
+    rng = np.random.default_rng(seed)
+    raw = shelf_map(H, W, seed=seed, aisle=aisle, gap=gap, shelf=shelf)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    g_raw = t(png_values(raw))
+    g_inf = torch.empty_like(g_raw)
+    _lib.grid_inflate_device(g_raw, g_inf, CELL, size_robot, 0.29)
+    free = g_inf.cpu().numpy() < 0.8
+    starts, goals = pick_routes(raw > 0.5, free, B, rng)
+
+    sc = make_scenario("cfg2", B=B, seed=seed)
+    s = _lib.Solver(sc.desc, max_batch=B)
+    N, nv, nob = sc.desc["N"], s.nvar, sc.desc["nobst"]
+    xinit = np.zeros((B, sc.desc["nx"]))
+    xinit[:, 0] = X0 + (starts % W) * CELL
+    xinit[:, 1] = Y0 + (starts // W) * CELL
+    x0 = np.zeros((B, N, nv))
+    x0[:, :, :sc.desc["nx"]] = xinit[:, None, :]
+    # the scenario's round obstacles are moved out of the store: the shelves are the obstacles here
+    obst = np.zeros((B, nob, 4))
+    obst[:, :, 0] = 50.0 + 5.0 * np.arange(nob)
+    obst[:, :, 1] = 50.0
+    obst[:, :, 3] = 0.1
+    goal = t(np.concatenate([xinit[:, :2], np.zeros((B, 1))], 1))
+    scene = s.make_scene(sc.setup["mpc"]["weights"], goal=goal, r_body=t(np.full(B, 0.3)), obst=t(obst),
+                         lower_limits=t(np.tile(POINT_LIMITS[0], (B, 1))), upper_limits=t(np.tile(POINT_LIMITS[1], (B, 1))),
+                         lower_limits_u=t(np.tile(POINT_LIMITS_U[0], (B, 1))),
+                         upper_limits_u=t(np.tile(POINT_LIMITS_U[1], (B, 1))))
+    tx, t0 = t(xinit), t(x0)
+    z = torch.empty((B, N, nv), dtype=torch.float64, device=dev)
+    ef = torch.empty(B, dtype=torch.int32, device=dev); it = torch.empty(B, dtype=torch.int32, device=dev)
+    kkt = torch.empty(B, dtype=torch.float64, device=dev); obj = torch.empty(B, dtype=torch.float64, device=dev)
+
+    torch.cuda.synchronize()
+    tp = time.perf_counter()
+    paths, lens = plan_batch(g_inf, torch.from_numpy(starts).to(dev), torch.from_numpy(goals).to(dev))
+    torch.cuda.synchronize()
+    plan_ms = 1e3 * (time.perf_counter() - tp)
+    follower = RouteFollower(paths, lens, W, X0, Y0, CELL, threshold=threshold)
+    final = follower.final_goals()
+
+    occ = np.flatnonzero(raw.ravel() > 0.5)
+    occ_xy = t(np.stack([X0 + (occ % W) * CELL, Y0 + (occ // W) * CELL], 1))
+    tol = MixedFleetShard.ARRIVE_TOL["cfg2"]
+    fails = torch.zeros((), dtype=torch.int64, device=dev)
+    clear = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
+    arrived = torch.full((B,), -1, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    t_loop = time.perf_counter()
+    for step in range(steps):
+        follower.step(tx, goal)
+        s.solve_scene_device(B, scene, tx, t0, z, ef, it, kkt, obj)
+        s.advance_device(B, z, tx, t0, previous_plan=False)
+        fails += (ef < 0).sum()
+        # distance from the robot's centre to the nearest raw-occupied cell (a square of side CELL)
+        d = ((tx[:, None, :2] - occ_xy[None]).abs() - 0.5 * CELL).clamp(min=0.0).norm(dim=2).min(dim=1).values
+        clear = torch.minimum(clear, d)
+        at = (tx[:, :2] - final).norm(dim=1) < tol
+        arrived = torch.where(at & (arrived < 0), torch.full_like(arrived, step + 1), arrived)
+    torch.cuda.synchronize()
+    ms = 1e3 * (time.perf_counter() - t_loop) / steps
+    a = arrived.cpu().numpy()
+    done = np.sort(a[a > 0])
+    q = lambda p: int(done[min(len(done) - 1, int(np.ceil(p * len(done))) - 1)]) if len(done) else None
+    s.close()
+    return dict(robots=B, steps=steps, routes=int((lens > 0).sum().item()), route_len_max=int(lens.max().item()),
+                plan_ms=round(plan_ms, 3), arrivals=int(len(done)), arrival_share=len(done) / B,
+                arrival_step_p50=q(0.5), arrival_step_p90=q(0.9), arrival_step_max=q(1.0),
+                failed_solves=int(fails.item()), min_clearance_m=float(clear.min().item()),
+                touching=int((clear <= 0).sum().item()), clearance_p10=float(clear.quantile(0.1).item()),
+                ms_per_step=round(ms, 3), arrive_tol_m=tol)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--robots", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=1200)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--aisle", type=int, default=4)
+    ap.add_argument("--gap", type=int, default=3)
+    ap.add_argument("--size-robot", type=float, default=SIZE_ROBOT)
+    ap.add_argument("--threshold", type=float, default=1.3)
+    ap.add_argument("--shelf", type=int, default=2)
+    a = ap.parse_args()
+    import __graft_entry__ as g
+    g.build()
+    print(json.dumps(run(a.robots, a.steps, a.seed, aisle=a.aisle, gap=a.gap, size_robot=a.size_robot,
+                         threshold=a.threshold, shelf=a.shelf)))
+
+
+if __name__ == "__main__":
+    main()

@@ -47,7 +47,10 @@ extern "C" {
  *              64-bit counters: NOT source compatible with 0.1.5), rmpc_advance_obstacles_device; rmpc_is_fused is 1
  *              for the arms with 5 .. 7 joints as well (k_fused_arm).
  * 0.2.1 (201): RMPC_MOD_ROWS -- constraint modules given as row descriptions (rmpc_desc grows by the xrow_* arrays at
- *              its end; a descriptor of the 0.2.0 size is still accepted and has no such rows). */
+ *              its end; a descriptor of the 0.2.0 size is still accepted and has no such rows).
+ *              Added without a change of the macro (source and binary compatible): the global planner,
+ *              RMPC_GRID_MAX_CELLS, rmpc_grid_inflate_device, rmpc_grid_fields_device, rmpc_grid_paths_device,
+ *              rmpc_grid_cells_device, rmpc_follow_path_device. */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -326,6 +329,55 @@ int rmpc_advance_obstacles_device(int B, int nobst, double dt, double arena, dou
  * examples/boxer_example.py:193-203).  Needs no handle. */
 int rmpc_free_space_device(int B, int N, int P, int K, double max_radius, const double *d_points,
                            const double *d_seeds, double *d_planes, void *stream);
+
+/* Global planner on the device (robotmpcs/global_planner/: globalPlanner.py, a_star.py, gridmap.py).  Needs no handle;
+ * every pointer is a device pointer, each call runs on the device of its first pointer.  A grid is d_grid [H][W]
+ * doubles, row-major, cell c = row * W + col; in the plain frame the centre of (row, col) is (x0 + col cell,
+ * y0 + row cell) (gridmap.py:get_coordinates_from_index with an origin).  A cell is occupied when data >= occ_threshold
+ * (OccupancyGridMap, 0.8); entering cell v costs delta + cost_factor data[v], delta = 1 axial, sqrt(2) diagonal
+ * (a_star.py:99-116, occupancy_cost_factor 3); movement 8 or 4 takes the reference's move order
+ * (_get_movements_8n / _get_movements_4n; diagonal steps between two occupied cells are allowed, as there). */
+#define RMPC_GRID_MAX_CELLS 16384       /* one cost-to-go field per workgroup, held in LDS: 128 x 128 */
+#define RMPC_GRID_OK 0
+#define RMPC_GRID_START_OCCUPIED (-1)   /* a_star.py:55-56 raises */
+#define RMPC_GRID_GOAL_OCCUPIED (-2)    /* a_star.py:58-59 raises */
+#define RMPC_GRID_OUTSIDE (-3)          /* gridmap.py:is_occupied_idx raises; also a goal index outside [0, G) */
+#define RMPC_GRID_TOO_LONG (-4)         /* the path has more than max_len cells */
+#define RMPC_GRID_BAD_MAP (-5)          /* a free cell (data < occ_threshold) holds a negative value */
+#define RMPC_GRID_NO_FIXED_POINT (-6)   /* no fixed point after H W + 1 sweeps (not reached with prices >= 0) */
+
+/* get_enlarged_obstacles (globalPlanner.py:39-70): box mean over (2k+1)^2 cells, k = ceil(size_robot / cell), on the
+ * cells at least k from the border (convolution_size_robot; the others keep their raw value), then 1 where the value is
+ * above threshold (0.29 in the reference) and 0 elsewhere.  d_out [H][W] may not alias d_grid. */
+int rmpc_grid_inflate_device(int H, int W, double cell, double size_robot, double threshold, const double *d_grid,
+                             double *d_out, void *stream);
+/* One cost-to-go field per goal cell d_goal_cells [G]: d_fields [G][H][W], D(goal) = 0,
+ * D(u) = min_v (delta(u,v) + cost_factor data[v] + D(v)), +inf on occupied and unreachable cells -- the exact fixed
+ * point, bitwise the same on every run.  d_status [G]: RMPC_GRID_OK, _GOAL_OCCUPIED, _OUTSIDE, _BAD_MAP or
+ * _NO_FIXED_POINT (field all +inf).  cost_factor must be finite and >= 0 (prices may not be negative: refused).
+ * d_sweeps [G] (may be NULL): the sweeps the field took.  H W <= RMPC_GRID_MAX_CELLS, larger maps are refused. */
+int rmpc_grid_fields_device(int H, int W, const double *d_grid, int G, const int32_t *d_goal_cells, int movement,
+                            double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status,
+                            int32_t *d_sweeps, void *stream);
+/* One path per query: from d_start_cell [b] down field d_goal_index [b] (neighbour with the least delta +
+ * cost_factor data[v] + D(v), the first in move order on ties) to its goal.  d_path [B][max_len] int32 cells with start
+ * and goal; d_len [B] > 0 the path's cell count, 0 the goal is unreachable (a_star.py:119-133 returns empty lists),
+ * or RMPC_GRID_START_OCCUPIED, _GOAL_OCCUPIED, _OUTSIDE, _TOO_LONG.  Cells past d_len [b] are not written. */
+int rmpc_grid_paths_device(int H, int W, const double *d_grid, int G, const double *d_fields, const int32_t *d_goal_cells,
+                           int B, const int32_t *d_start_cell, const int32_t *d_goal_index, int movement,
+                           double occ_threshold, double cost_factor, int max_len, int32_t *d_path, int32_t *d_len,
+                           void *stream);
+/* World positions d_pos [b * stride + 0 .. 1] (e.g. xinit [B][nx], stride nx) to cells d_cells [B] of the plain frame,
+ * rint((p - origin) / cell) (round half to even, gridmap.py:get_index_from_coordinates); -1 outside the map. */
+int rmpc_grid_cells_device(int B, const double *d_pos, int stride, int H, int W, double x0, double y0, double cell,
+                           int32_t *d_cells, void *stream);
+/* get_local_goal (globalPlanner.py:174-189) for B robots in one control step: when d_idx [b] < d_len [b] - 1 and the
+ * distance from d_pos [b * stride + 0 .. 1] to the centre of d_path [b][d_idx [b]] is <= threshold (1.3 m in the
+ * reference), d_idx [b] advances by one; then d_goal [b] = (centre of d_path [b][d_idx [b]], 0) -- the goal [B][3] the
+ * scene points at (rmpc_scene.goal, rmpc_retarget.goal).  Robots with d_len [b] <= 0 keep their goal. */
+int rmpc_follow_path_device(int B, const int32_t *d_path, const int32_t *d_len, int max_len, int32_t *d_idx,
+                            const double *d_pos, int stride, int W, double x0, double y0, double cell, double threshold,
+                            double *d_goal, void *stream);
 
 /* Debug / parity hooks (used by tests through the same ABI): evaluate one
  * stage-parallel sweep at z = x0 (first-pass semantics) and return the

@@ -89,6 +89,8 @@ EXPORTED_SYMBOLS = [
     "rmpc_solve_batch_device", "rmpc_workspace_bytes", "rmpc_set_warm_start", "rmpc_set_pass_budget", "rmpc_is_fused", "rmpc_fused_kernel_name", "rmpc_is_async", "rmpc_set_profiling", "rmpc_get_profile",
     "rmpc_kernel_name", "rmpc_last_passes", "rmpc_debug_sweep", "rmpc_spec_source", "rmpc_spec_name", "rmpc_spec_for", "rmpc_debug_poison_lds",
     "rmpc_debug_fused_stamps", "rmpc_pack_scene_device", "rmpc_solve_batch_scene_device", "rmpc_pack_scene_workspace", "rmpc_solve_batch_packed_device", "rmpc_advance_device", "rmpc_advance_device_flags", "rmpc_retarget_device", "rmpc_advance_obstacles_device", "rmpc_free_space_device",
+    "rmpc_grid_inflate_device", "rmpc_grid_fields_device", "rmpc_grid_paths_device", "rmpc_grid_cells_device",
+    "rmpc_follow_path_device",
 ]
 
 _lib = None
@@ -221,6 +223,17 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_advance_obstacles_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
     L.rmpc_free_space_device.restype = C.c_int
     L.rmpc_free_space_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    vp, i, d = C.c_void_p, C.c_int, C.c_double
+    L.rmpc_grid_inflate_device.restype = C.c_int
+    L.rmpc_grid_inflate_device.argtypes = [i, i, d, d, d, vp, vp, vp]
+    L.rmpc_grid_fields_device.restype = C.c_int
+    L.rmpc_grid_fields_device.argtypes = [i, i, vp, i, vp, i, d, d, vp, vp, vp, vp]
+    L.rmpc_grid_paths_device.restype = C.c_int
+    L.rmpc_grid_paths_device.argtypes = [i, i, vp, i, vp, vp, i, vp, vp, i, d, d, i, vp, vp, vp]
+    L.rmpc_grid_cells_device.restype = C.c_int
+    L.rmpc_grid_cells_device.argtypes = [i, vp, i, i, i, d, d, d, vp, vp]
+    L.rmpc_follow_path_device.restype = C.c_int
+    L.rmpc_follow_path_device.argtypes = [i, vp, vp, i, vp, vp, i, i, d, d, d, d, vp, vp]
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
         raise RmpcError("rmpc_desc layout mismatch between _lib.py and librmpc_hip.so")
     want = _source_hash()
@@ -320,6 +333,66 @@ def free_space_decomposition_device(points, seeds, planes_out, max_radius: float
                                   C.c_void_p(seeds.data_ptr()), C.c_void_p(planes_out.data_ptr()), st)
     if rc != 0:
         raise RmpcError("rmpc_free_space_device failed: " + L.rmpc_last_error().decode())
+
+
+# status codes of the global planner (include/rmpc.h)
+GRID_MAX_CELLS = 16384
+GRID_OK, GRID_START_OCCUPIED, GRID_GOAL_OCCUPIED, GRID_OUTSIDE, GRID_TOO_LONG = 0, -1, -2, -3, -4
+GRID_BAD_MAP, GRID_NO_FIXED_POINT = -5, -6
+
+
+def _grid_call(name, *args):
+    L = load_library()
+    rc = getattr(L, name)(*args)
+    if rc != 0:
+        raise RmpcError(name + " failed: " + L.rmpc_last_error().decode())
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def grid_inflate_device(grid, out, cell: float, size_robot: float, threshold: float = 0.29, stream=None):
+    """grid, out (H, W) contiguous fp64 device tensors: ``GlobalPlanner.get_enlarged_obstacles`` of the reference
+    (globalPlanner.py:39-70) on the device."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    _grid_call("rmpc_grid_inflate_device", H, W, float(cell), float(size_robot), float(threshold), _ptr(grid), _ptr(out),
+               _stream_arg(stream))
+
+
+def grid_fields_device(grid, goal_cells, fields, status, movement: int = 8, occ_threshold: float = 0.8,
+                       cost_factor: float = 3.0, sweeps=None, stream=None):
+    """grid (H, W) fp64, goal_cells (G,) int32, fields (G, H, W) fp64, status (G,) int32, sweeps (G,) int32 or None:
+    one cost-to-go field per goal (``rmpc_grid_fields_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    _grid_call("rmpc_grid_fields_device", H, W, _ptr(grid), int(goal_cells.shape[0]), _ptr(goal_cells), int(movement),
+               float(occ_threshold), float(cost_factor), _ptr(fields), _ptr(status),
+               None if sweeps is None else _ptr(sweeps), _stream_arg(stream))
+
+
+def grid_paths_device(grid, fields, goal_cells, start_cell, goal_index, path, length, movement: int = 8,
+                      occ_threshold: float = 0.8, cost_factor: float = 3.0, stream=None):
+    """start_cell, goal_index (B,) int32, path (B, max_len) int32, length (B,) int32: descent of the fields
+    (``rmpc_grid_paths_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    _grid_call("rmpc_grid_paths_device", H, W, _ptr(grid), int(fields.shape[0]), _ptr(fields), _ptr(goal_cells),
+               int(start_cell.shape[0]), _ptr(start_cell), _ptr(goal_index), int(movement), float(occ_threshold),
+               float(cost_factor), int(path.shape[1]), _ptr(path), _ptr(length), _stream_arg(stream))
+
+
+def grid_cells_device(pos, cells, H: int, W: int, x0: float, y0: float, cell: float, stream=None):
+    """pos (B, stride >= 2) fp64 (e.g. xinit), cells (B,) int32: world positions to cells of the plain frame."""
+    _grid_call("rmpc_grid_cells_device", int(pos.shape[0]), _ptr(pos), int(pos.stride(0)), int(H), int(W), float(x0),
+               float(y0), float(cell), _ptr(cells), _stream_arg(stream))
+
+
+def follow_path_device(path, length, idx, pos, goal, W: int, x0: float, y0: float, cell: float, threshold: float = 1.3,
+                       stream=None):
+    """path (B, max_len), length (B,), idx (B,) int32; pos (B, stride >= 2) fp64; goal (B, 3) fp64: one control step
+    of ``GlobalPlanner.get_local_goal`` for every robot (``rmpc_follow_path_device``)."""
+    _grid_call("rmpc_follow_path_device", int(path.shape[0]), _ptr(path), _ptr(length), int(path.shape[1]), _ptr(idx),
+               _ptr(pos), int(pos.stride(0)), int(W), float(x0), float(y0), float(cell), float(threshold), _ptr(goal),
+               _stream_arg(stream))
 
 
 class Solver:

@@ -468,6 +468,8 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 
 }  // namespace rmpc
 
+#include "rmpc_grid.hpp"
+
 // ===========================================================================
 // host side: handle, workspace, launch loop, C ABI
 // ===========================================================================
@@ -1510,6 +1512,94 @@ int rmpc_free_space_device(int B, int N, int P, int K, double max_radius, const 
   if (B < 1 || N < 1 || K < 1 || P < 1 || P > 64) return fail("free space decomposition: need 1 <= P <= 64 points, K >= 1");
   hipLaunchKernelGGL(k_fsd, dim3((B * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_points, d_seeds, d_planes,
                      B, N, P, K, max_radius);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+/* the global planner (rmpc_grid.hpp): no handle; each call runs on the device its first pointer lives on */
+static int grid_device(const void *p) {
+  hipPointerAttribute_t a;
+  HIPCHK(hipPointerGetAttributes(&a, p));
+  if (a.device < 0) return fail("not a device pointer");
+  HIPCHK(hipSetDevice(a.device));
+  return 0;
+}
+static bool grid_fits(long long a, long long b) { return a >= 0 && b >= 0 && (b == 0 || a <= INT_MAX / b); }
+static int grid_check(int H, int W, int movement) {
+  if (H < 1 || W < 1 || !grid_fits(H, W)) return fail("grid: need H, W >= 1");
+  if (movement != 4 && movement != 8) return fail("grid: movement must be 4 or 8");
+  return 0;
+}
+
+int rmpc_grid_inflate_device(int H, int W, double cell, double size_robot, double threshold, const double *d_grid,
+                             double *d_out, void *stream) {
+  if (!d_grid || !d_out) return fail("null argument");
+  if (grid_check(H, W, 8) || grid_device(d_grid)) return -1;
+  if (!(cell > 0.0) || !(size_robot >= 0.0)) return fail("grid inflate: need cell > 0, size_robot >= 0");
+  const double kd = ceil(size_robot / cell);
+  if (kd > (double)(H + W)) return fail("grid inflate: window larger than the map");
+  hipLaunchKernelGGL(k_grid_inflate, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, d_out, H, W,
+                     (int)kd, threshold);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int rmpc_grid_fields_device(int H, int W, const double *d_grid, int G, const int32_t *d_goal_cells, int movement,
+                            double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status,
+                            int32_t *d_sweeps, void *stream) {
+  if (!d_grid || !d_goal_cells || !d_fields || !d_status) return fail("null argument");
+  if (grid_check(H, W, movement)) return -1;
+  if (H * W > RMPC_GRID_MAX_CELLS)
+    return fail("grid fields: " + std::to_string(H) + "x" + std::to_string(W) + " map exceeds RMPC_GRID_MAX_CELLS = " +
+                std::to_string(RMPC_GRID_MAX_CELLS) + " cells (one field must fit in the LDS of a workgroup)");
+  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid fields: need 1 <= G and G*H*W <= INT_MAX");
+  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid fields: cost_factor must be finite and >= 0");
+  if (grid_device(d_grid)) return -1;
+  hipLaunchKernelGGL(k_grid_fields, dim3(G), dim3(kGridThreads), 0, (hipStream_t)stream, d_grid, H, W,
+                     (const int *)d_goal_cells, movement, occ_threshold, cost_factor, d_fields, (int *)d_status,
+                     (int *)d_sweeps);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int rmpc_grid_paths_device(int H, int W, const double *d_grid, int G, const double *d_fields, const int32_t *d_goal_cells,
+                           int B, const int32_t *d_start_cell, const int32_t *d_goal_index, int movement,
+                           double occ_threshold, double cost_factor, int max_len, int32_t *d_path, int32_t *d_len,
+                           void *stream) {
+  if (!d_grid || !d_fields || !d_goal_cells || !d_start_cell || !d_goal_index || !d_path || !d_len) return fail("null argument");
+  if (grid_check(H, W, movement)) return -1;
+  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid paths: need 1 <= G and G*H*W <= INT_MAX");
+  if (B < 1 || max_len < 1 || !grid_fits(B, max_len)) return fail("grid paths: need B, max_len >= 1 and B*max_len <= INT_MAX");
+  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid paths: cost_factor must be finite and >= 0");
+  if (grid_device(d_grid)) return -1;
+  hipLaunchKernelGGL(k_grid_paths, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, d_fields,
+                     (const int *)d_goal_cells, G, (const int *)d_start_cell, (const int *)d_goal_index, B, movement,
+                     occ_threshold, cost_factor, max_len, (int *)d_path, (int *)d_len);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int rmpc_grid_cells_device(int B, const double *d_pos, int stride, int H, int W, double x0, double y0, double cell,
+                           int32_t *d_cells, void *stream) {
+  if (!d_pos || !d_cells) return fail("null argument");
+  if (B < 1 || stride < 2 || !grid_fits(B, stride)) return fail("grid cells: need B >= 1, stride >= 2, B*stride <= INT_MAX");
+  if (grid_check(H, W, 8) || grid_device(d_pos)) return -1;
+  if (!(cell > 0.0)) return fail("grid cells: need cell > 0");
+  hipLaunchKernelGGL(k_grid_cells, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_pos, stride, B, H, W, x0,
+                     y0, cell, (int *)d_cells);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int rmpc_follow_path_device(int B, const int32_t *d_path, const int32_t *d_len, int max_len, int32_t *d_idx,
+                            const double *d_pos, int stride, int W, double x0, double y0, double cell, double threshold,
+                            double *d_goal, void *stream) {
+  if (!d_path || !d_len || !d_idx || !d_pos || !d_goal) return fail("null argument");
+  if (B < 1 || max_len < 1 || !grid_fits(B, max_len)) return fail("follow path: need B, max_len >= 1 and B*max_len <= INT_MAX");
+  if (stride < 2 || !grid_fits(B, stride) || W < 1) return fail("follow path: need stride >= 2, W >= 1");
+  if (grid_device(d_path)) return -1;
+  hipLaunchKernelGGL(k_follow_path, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int *)d_path,
+                     (const int *)d_len, max_len, (int *)d_idx, d_pos, stride, B, W, x0, y0, cell, threshold, d_goal);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -1,0 +1,15 @@
+"""Global planner: occupancy map -> enlarged obstacles -> shortest 8-connected path -> waypoint follower.
+
+Mirrors ``robotmpcs.global_planner`` (``gridmap.OccupancyGridMap``, ``a_star.a_star``, ``globalPlanner.GlobalPlanner``:
+same module, class and method names, so that a port of ``examples/boxer_example_global.py`` changes only its imports)
+and adds the batched, device-resident fleet API (``plan_batch``, ``RouteFollower``, ``shelf_map``).  The work is done
+by the ``rmpc_grid_*_device`` / ``rmpc_follow_path_device`` kernels (include/rmpc.h); there is no CPU path.  Importing
+the package needs no GPU.
+"""
+from .gridmap import OccupancyGridMap
+from .a_star import a_star
+from .globalPlanner import GlobalPlanner, png_values
+from .batch import RouteFollower, cells_from_positions, plan_batch, shelf_map
+
+__all__ = ["OccupancyGridMap", "a_star", "GlobalPlanner", "RouteFollower", "cells_from_positions", "plan_batch",
+           "png_values", "shelf_map"]
