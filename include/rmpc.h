@@ -50,7 +50,8 @@ extern "C" {
  *              its end; a descriptor of the 0.2.0 size is still accepted and has no such rows).
  *              Added without a change of the macro (source and binary compatible): the global planner,
  *              RMPC_GRID_MAX_CELLS, rmpc_grid_inflate_device, rmpc_grid_fields_device, rmpc_grid_paths_device,
- *              rmpc_grid_cells_device, rmpc_follow_path_device. */
+ *              rmpc_grid_cells_device, rmpc_follow_path_device; the lidar, rmpc_lidar, rmpc_lidar_scan_device,
+ *              rmpc_plan_points_device (rmpc_free_space_device now runs on the device of d_points). */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -326,7 +327,7 @@ int rmpc_advance_obstacles_device(int B, int nobst, double dt, double arena, dou
  * planes of robotmpcs/utils/free_space_decomposition.py:79-116.  d_points [B][P][3],
  * d_seeds [B][N][3], d_planes [B][N][K][4] = the lin_constrs field of rmpc_scene
  * (setLinearConstraints, mpcPlanner.py:135-141; called N times per control step by
- * examples/boxer_example.py:193-203).  Needs no handle. */
+ * examples/boxer_example.py:193-203).  Needs no handle; runs on the device of d_points. */
 int rmpc_free_space_device(int B, int N, int P, int K, double max_radius, const double *d_points,
                            const double *d_seeds, double *d_planes, void *stream);
 
@@ -378,6 +379,44 @@ int rmpc_grid_cells_device(int B, const double *d_pos, int stride, int H, int W,
 int rmpc_follow_path_device(int B, const int32_t *d_path, const int32_t *d_len, int max_len, int32_t *d_idx,
                             const double *d_pos, int stride, int W, double x0, double y0, double cell, double threshold,
                             double *d_goal, void *stream);
+
+/* Lidar on the device (the Lidar sensor and compute_point_cloud of examples/boxer_example_supermarket.py).  Needs no
+ * handle; every pointer is a device pointer, each call runs on the device of its first pointer.  B robots scan one
+ * world of axis-aligned boxes [nbox][4] = (cx, cy, lx, ly) (BoxObstacle position, length along x, width along y) and
+ * circles [ncircle][3] = (cx, cy, r).  Robot b has the pose (x, y, th) = pose [b * pose_stride + 0 .. 2]; its sensor
+ * sits at o = (x + offset_x cos th - offset_y sin th, y + offset_x sin th + offset_y cos th) (the boxer: (0.4, 0)).
+ * Ray i of R has the angle th + angle_min + i (angle_max - angle_min) / R (half-open: [-pi, pi) is a full circle)
+ * and the direction d = (cos, sin).  A box is hit at its entering distance 0 < t_enter <= t_exit (slab test; a
+ * direction component of exactly 0 is inside its slab iff the origin coordinate lies in the closed interval), a circle
+ * at t = -b - sqrt(b^2 - c), b = d.(o - c), c = |o - c|^2 - r^2, when c > 0, b^2 - c >= 0 and t > 0.  A shape that
+ * contains the origin is ignored by that ray.  t is the least hit distance, range when nothing is hit within range.
+ * points [B][R][3] = (o + t d, height): the absolute cloud of compute_point_cloud, laid out as the d_points of
+ * rmpc_free_space_device; ranges [B][R] = t (may be NULL).  The convention is the project's own.
+ * struct_size must equal sizeof(rmpc_lidar); refused (-1, rmpc_last_error): NULL pointers where a count is
+ * positive, B < 1, rays < 1, pose_stride < 3, a negative shape count, a range that is not positive and finite, and
+ * B*rays, nbox*4 or ncircle*3 beyond INT_MAX. */
+typedef struct rmpc_lidar {
+  int32_t struct_size;                 /* sizeof(rmpc_lidar) */
+  int32_t rays;                        /* R >= 1 */
+  double angle_min, angle_max, range;  /* body frame; range > 0 */
+  double offset_x, offset_y, height;
+  const double *pose; int32_t pose_stride;     /* [B][stride]: x, y, heading at 0, 1, 2 (xinit: stride nx) */
+  int32_t nbox; const double *boxes;           /* [nbox][4] */
+  int32_t ncircle; const double *circles;      /* [ncircle][3] */
+  double *points;                              /* [B][R][3] out */
+  double *ranges;                              /* [B][R] out, may be NULL */
+} rmpc_lidar;
+int rmpc_lidar_scan_device(int B, const rmpc_lidar *l, void *stream);
+/* The seeds of the free-space decomposition (examples/boxer_example_supermarket.py, "Preprocessing for planner"):
+ * d_points [B][N][3] = (sensor origin of q, height) with q = d_z_prev [b][k][0 .. 2] (stage k of the previous plan,
+ * [B][N][nvar] with z_k = [x_k; s_k; u_k]), or q = the current pose d_pose [b * pose_stride + 0 .. 2] when d_z_prev is
+ * NULL (first control step) or d_exitflag [b] < 0 (d_exitflag may be NULL).  The same offset and height as the scan;
+ * the seeds are not shifted (the reference's lag of one control step).  Runs on the device of d_z_prev, of d_pose when
+ * d_z_prev is NULL.  Refused: NULL d_pose or d_points, B < 1, N < 1, pose_stride < 3, nvar < 3, and B*N,
+ * B*pose_stride or B*N*nvar beyond INT_MAX. */
+int rmpc_plan_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
+                            const double *d_pose, int pose_stride, double offset_x, double offset_y, double height,
+                            double *d_points, void *stream);
 
 /* Debug / parity hooks (used by tests through the same ABI): evaluate one
  * stage-parallel sweep at z = x0 (first-pass semantics) and return the

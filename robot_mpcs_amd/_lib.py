@@ -83,6 +83,19 @@ class RetargetArgs(C.Structure):
     ]
 
 
+class LidarArgs(C.Structure):
+    """Mirror of ``rmpc_lidar`` (include/rmpc.h): one scan of B robots in a shared world, device pointers."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("rays", C.c_int32),
+        ("angle_min", C.c_double), ("angle_max", C.c_double), ("range", C.c_double),
+        ("offset_x", C.c_double), ("offset_y", C.c_double), ("height", C.c_double),
+        ("pose", C.c_void_p), ("pose_stride", C.c_int32),
+        ("nbox", C.c_int32), ("boxes", C.c_void_p),
+        ("ncircle", C.c_int32), ("circles", C.c_void_p),
+        ("points", C.c_void_p), ("ranges", C.c_void_p),
+    ]
+
+
 # every symbol include/rmpc.h declares
 EXPORTED_SYMBOLS = [
     "rmpc_version", "rmpc_source_hash", "rmpc_last_error", "rmpc_desc_size", "rmpc_create", "rmpc_destroy", "rmpc_solve_batch",
@@ -90,7 +103,7 @@ EXPORTED_SYMBOLS = [
     "rmpc_kernel_name", "rmpc_last_passes", "rmpc_debug_sweep", "rmpc_spec_source", "rmpc_spec_name", "rmpc_spec_for", "rmpc_debug_poison_lds",
     "rmpc_debug_fused_stamps", "rmpc_pack_scene_device", "rmpc_solve_batch_scene_device", "rmpc_pack_scene_workspace", "rmpc_solve_batch_packed_device", "rmpc_advance_device", "rmpc_advance_device_flags", "rmpc_retarget_device", "rmpc_advance_obstacles_device", "rmpc_free_space_device",
     "rmpc_grid_inflate_device", "rmpc_grid_fields_device", "rmpc_grid_paths_device", "rmpc_grid_cells_device",
-    "rmpc_follow_path_device",
+    "rmpc_follow_path_device", "rmpc_lidar_scan_device", "rmpc_plan_points_device",
 ]
 
 _lib = None
@@ -234,6 +247,10 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_grid_cells_device.argtypes = [i, vp, i, i, i, d, d, d, vp, vp]
     L.rmpc_follow_path_device.restype = C.c_int
     L.rmpc_follow_path_device.argtypes = [i, vp, vp, i, vp, vp, i, i, d, d, d, d, vp, vp]
+    L.rmpc_lidar_scan_device.restype = C.c_int
+    L.rmpc_lidar_scan_device.argtypes = [i, C.POINTER(LidarArgs), vp]
+    L.rmpc_plan_points_device.restype = C.c_int
+    L.rmpc_plan_points_device.argtypes = [i, i, vp, i, vp, vp, i, d, d, d, vp, vp]
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
         raise RmpcError("rmpc_desc layout mismatch between _lib.py and librmpc_hip.so")
     want = _source_hash()
@@ -393,6 +410,45 @@ def follow_path_device(path, length, idx, pos, goal, W: int, x0: float, y0: floa
     _grid_call("rmpc_follow_path_device", int(path.shape[0]), _ptr(path), _ptr(length), int(path.shape[1]), _ptr(idx),
                _ptr(pos), int(pos.stride(0)), int(W), float(x0), float(y0), float(cell), float(threshold), _ptr(goal),
                _stream_arg(stream))
+
+
+def lidar_args(pose, points, boxes=None, circles=None, angle_min: float = -np.pi, angle_max: float = np.pi,
+               max_range: float = 10.0, offset=(0.4, 0.0), height: float = 0.02, ranges=None) -> LidarArgs:
+    """The ``rmpc_lidar`` of one scan: pose (B, stride >= 3) fp64 (e.g. xinit), points (B, R, 3) fp64, boxes (nbox, 4)
+    and circles (ncircle, 3) fp64 or None, ranges (B, R) fp64 or None -- contiguous device tensors."""
+    a = LidarArgs()
+    a.struct_size = C.sizeof(LidarArgs)
+    a.rays = int(points.shape[1])
+    a.angle_min, a.angle_max, a.range = float(angle_min), float(angle_max), float(max_range)
+    a.offset_x, a.offset_y, a.height = float(offset[0]), float(offset[1]), float(height)
+    a.pose, a.pose_stride = pose.data_ptr(), int(pose.stride(0))
+    a.nbox = 0 if boxes is None else int(boxes.shape[0])
+    a.boxes = None if boxes is None or a.nbox == 0 else boxes.data_ptr()
+    a.ncircle = 0 if circles is None else int(circles.shape[0])
+    a.circles = None if circles is None or a.ncircle == 0 else circles.data_ptr()
+    a.points = points.data_ptr()
+    a.ranges = None if ranges is None else ranges.data_ptr()
+    return a
+
+
+def lidar_scan_device(pose, points, boxes=None, circles=None, angle_min: float = -np.pi, angle_max: float = np.pi,
+                      max_range: float = 10.0, offset=(0.4, 0.0), height: float = 0.02, ranges=None, stream=None):
+    """One lidar scan of B robots (``rmpc_lidar_scan_device``): R = points.shape[1] rays per robot into the shared
+    world of boxes (cx, cy, lx, ly) and circles (cx, cy, r); points (B, R, 3) = the absolute cloud of the reference's
+    ``compute_point_cloud``, ranges (B, R) the hit distances (max_range on a miss)."""
+    a = lidar_args(pose, points, boxes, circles, angle_min, angle_max, max_range, offset, height, ranges)
+    _grid_call("rmpc_lidar_scan_device", int(points.shape[0]), C.byref(a), _stream_arg(stream))
+
+
+def plan_points_device(pose, points, z_prev=None, exitflag=None, offset=(0.4, 0.0), height: float = 0.02, stream=None):
+    """Seeds of the free-space decomposition (``rmpc_plan_points_device``): points (B, N, 3) = the sensor origin of
+    stage k of the previous plan z_prev (B, N, nvar), or of the current pose (B, stride >= 3) when z_prev is None or
+    exitflag (B,) int32 [b] < 0."""
+    B, N = int(points.shape[0]), int(points.shape[1])
+    nvar = 3 if z_prev is None else int(z_prev.shape[2])
+    _grid_call("rmpc_plan_points_device", B, N, None if z_prev is None else _ptr(z_prev), nvar,
+               None if exitflag is None else _ptr(exitflag), _ptr(pose), int(pose.stride(0)), float(offset[0]),
+               float(offset[1]), float(height), _ptr(points), _stream_arg(stream))
 
 
 class Solver:

@@ -469,6 +469,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 }  // namespace rmpc
 
 #include "rmpc_grid.hpp"
+#include "rmpc_sense.hpp"
 
 // ===========================================================================
 // host side: handle, workspace, launch loop, C ABI
@@ -1506,10 +1507,13 @@ int rmpc_advance_obstacles_device(int B, int nobst, double dt, double arena, dou
   return 0;
 }
 
+static int grid_device(const void *p);
+
 int rmpc_free_space_device(int B, int N, int P, int K, double max_radius, const double *d_points,
                            const double *d_seeds, double *d_planes, void *stream) {
   if (!d_points || !d_seeds || !d_planes) return fail("null argument");
   if (B < 1 || N < 1 || K < 1 || P < 1 || P > 64) return fail("free space decomposition: need 1 <= P <= 64 points, K >= 1");
+  if (grid_device(d_points)) return -1;
   hipLaunchKernelGGL(k_fsd, dim3((B * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_points, d_seeds, d_planes,
                      B, N, P, K, max_radius);
   HIPCHK(hipGetLastError());
@@ -1600,6 +1604,43 @@ int rmpc_follow_path_device(int B, const int32_t *d_path, const int32_t *d_len, 
   if (grid_device(d_path)) return -1;
   hipLaunchKernelGGL(k_follow_path, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int *)d_path,
                      (const int *)d_len, max_len, (int *)d_idx, d_pos, stride, B, W, x0, y0, cell, threshold, d_goal);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+/* the lidar (rmpc_sense.hpp): no handle; each call runs on the device its first pointer lives on */
+int rmpc_lidar_scan_device(int B, const rmpc_lidar *l, void *stream) {
+  if (!l) return fail("null argument");
+  if (l->struct_size != (int)sizeof(rmpc_lidar)) return fail("rmpc_lidar.struct_size mismatch");
+  if (B < 1 || l->rays < 1) return fail("lidar: need B >= 1 and rays >= 1");
+  if (l->pose_stride < 3) return fail("lidar: pose_stride must be >= 3 (x, y, heading)");
+  if (l->nbox < 0 || l->ncircle < 0) return fail("lidar: negative shape count");
+  if (!grid_fits(B, l->rays) || !grid_fits(B, l->pose_stride) || !grid_fits(l->nbox, 4) || !grid_fits(l->ncircle, 3))
+    return fail("lidar: B*rays, B*pose_stride, nbox*4 and ncircle*3 must not exceed INT_MAX");
+  if (!(l->range > 0.0) || std::isinf(l->range)) return fail("lidar: range must be positive and finite");
+  if (!l->pose || !l->points || (l->nbox > 0 && !l->boxes) || (l->ncircle > 0 && !l->circles)) return fail("null argument");
+  if (grid_device(l->pose)) return -1;
+  const int n = B * l->rays;
+  const double step = (l->angle_max - l->angle_min) / (double)l->rays;
+  hipLaunchKernelGGL(k_lidar, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, l->pose, l->pose_stride, B,
+                     l->rays, l->angle_min, step, l->range, l->offset_x, l->offset_y, l->height, l->boxes, l->nbox,
+                     l->circles, l->ncircle, l->points, l->ranges);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int rmpc_plan_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
+                            const double *d_pose, int pose_stride, double offset_x, double offset_y, double height,
+                            double *d_points, void *stream) {
+  if (!d_pose || !d_points) return fail("null argument");
+  if (B < 1 || N < 1) return fail("plan points: need B, N >= 1");
+  if (pose_stride < 3) return fail("plan points: pose_stride must be >= 3 (x, y, heading)");
+  if (nvar < 3) return fail("plan points: nvar must be >= 3 (x, y, heading first)");
+  if (!grid_fits(B, N) || !grid_fits(B, pose_stride) || !grid_fits((long long)B * N, nvar))
+    return fail("plan points: B*N, B*pose_stride and B*N*nvar must not exceed INT_MAX");
+  if (grid_device(d_z_prev ? (const void *)d_z_prev : (const void *)d_pose)) return -1;
+  hipLaunchKernelGGL(k_plan_points, dim3((B * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_z_prev, nvar,
+                     (const int *)d_exitflag, d_pose, pose_stride, B, N, offset_x, offset_y, height, d_points);
   HIPCHK(hipGetLastError());
   return 0;
 }
