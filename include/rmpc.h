@@ -51,7 +51,8 @@ extern "C" {
  *              Added without a change of the macro (source and binary compatible): the global planner,
  *              RMPC_GRID_MAX_CELLS, rmpc_grid_inflate_device, rmpc_grid_fields_device, rmpc_grid_paths_device,
  *              rmpc_grid_cells_device, rmpc_follow_path_device; the lidar, rmpc_lidar, rmpc_lidar_scan_device,
- *              rmpc_plan_points_device (rmpc_free_space_device now runs on the device of d_points). */
+ *              rmpc_plan_points_device (rmpc_free_space_device now runs on the device of d_points); fleet
+ *              separation, rmpc_fleet_points_device, rmpc_fleet_planes_device. */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -417,6 +418,31 @@ int rmpc_lidar_scan_device(int B, const rmpc_lidar *l, void *stream);
 int rmpc_plan_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
                             const double *d_pose, int pose_stride, double offset_x, double offset_y, double height,
                             double *d_points, void *stream);
+
+/* Fleet separation: a separating plane per neighbour pair and stage, in the style of buffered Voronoi
+ * cells, written into the lin_constrs slots of an rmpc_scene: the LinearConstraints row |a.p + d| / |a| - r_body >= 0
+ * keeps the collision link clear of each.
+ * Needs no handle; every pointer is a device pointer, each call runs on the device of its first pointer.
+ * rmpc_fleet_points_device: the predicted collision points d_points [B][N][3] of the coming solve.  Stage k reads
+ * q = d_z_prev [b][min(k + 1, N - 1)][0 .. 2] (the previous plan shifted by the applied u_0, its last stage held), or
+ * q = d_pose [b * pose_stride + 0 .. 2] when d_z_prev is NULL or d_exitflag [b] < 0 (d_exitflag may be NULL).
+ * heading = 1 (the boxer): the point is (x + offset_x cos q2 - offset_y sin q2, y + offset_x sin q2 + offset_y cos q2,
+ * height) as in rmpc_plan_points_device; heading = 0 (the point robot): (q0, q1, height).  Refused: NULL d_pose or
+ * d_points, B < 1, N < 1, heading other than 0 or 1, pose_stride < 3, nvar < 3, and B*N, B*pose_stride or B*N*nvar
+ * beyond INT_MAX.
+ * rmpc_fleet_planes_device: for robot b at stage k, q_j = d_points [j][k] and s_j = |q_j - q_b|^2, the candidates are
+ * the robots j != b with s_j < range^2 (range = 0 admits nobody, +inf everyone); the K of least s_j (ties to the lower
+ * j) write slots slot0 .. slot0 + K - 1 of d_planes [B][N][nobst][4].  With lo = min(b, j), hi = max(b, j):
+ * u = q_lo - q_hi, d = |u|, n = u / d ((1, 0, 0) when d = 0), g = d - r_lo - r_hi, m = q_hi + (r_hi + g / 2) n,
+ * c = -n.m; robot lo gets (n, c), robot hi (-n, -c), so both predicted points lie r_own + g / 2 from the plane.  Slots
+ * without a candidate get the dummy plane of rmpc_free_space_device around q_b; the other slots are left untouched.
+ * d_radius [B] = r_body.  Refused: NULL pointers, B < 1, N < 1, K < 1, K > 8, slot0 < 0, slot0 + K > nobst, a
+ * negative or NaN range, and B*N*nobst*4 beyond INT_MAX. */
+int rmpc_fleet_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
+                             const double *d_pose, int pose_stride, int heading, double offset_x, double offset_y,
+                             double height, double *d_points, void *stream);
+int rmpc_fleet_planes_device(int B, int N, const double *d_points, const double *d_radius, int K, double range,
+                             int nobst, int slot0, double *d_planes, void *stream);
 
 /* Debug / parity hooks (used by tests through the same ABI): evaluate one
  * stage-parallel sweep at z = x0 (first-pass semantics) and return the

@@ -103,7 +103,8 @@ EXPORTED_SYMBOLS = [
     "rmpc_kernel_name", "rmpc_last_passes", "rmpc_debug_sweep", "rmpc_spec_source", "rmpc_spec_name", "rmpc_spec_for", "rmpc_debug_poison_lds",
     "rmpc_debug_fused_stamps", "rmpc_pack_scene_device", "rmpc_solve_batch_scene_device", "rmpc_pack_scene_workspace", "rmpc_solve_batch_packed_device", "rmpc_advance_device", "rmpc_advance_device_flags", "rmpc_retarget_device", "rmpc_advance_obstacles_device", "rmpc_free_space_device",
     "rmpc_grid_inflate_device", "rmpc_grid_fields_device", "rmpc_grid_paths_device", "rmpc_grid_cells_device",
-    "rmpc_follow_path_device", "rmpc_lidar_scan_device", "rmpc_plan_points_device",
+    "rmpc_follow_path_device", "rmpc_lidar_scan_device", "rmpc_plan_points_device", "rmpc_fleet_points_device",
+    "rmpc_fleet_planes_device",
 ]
 
 _lib = None
@@ -251,6 +252,10 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_lidar_scan_device.argtypes = [i, C.POINTER(LidarArgs), vp]
     L.rmpc_plan_points_device.restype = C.c_int
     L.rmpc_plan_points_device.argtypes = [i, i, vp, i, vp, vp, i, d, d, d, vp, vp]
+    L.rmpc_fleet_points_device.restype = C.c_int
+    L.rmpc_fleet_points_device.argtypes = [i, i, vp, i, vp, vp, i, i, d, d, d, vp, vp]
+    L.rmpc_fleet_planes_device.restype = C.c_int
+    L.rmpc_fleet_planes_device.argtypes = [i, i, vp, vp, i, d, i, i, vp, vp]
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
         raise RmpcError("rmpc_desc layout mismatch between _lib.py and librmpc_hip.so")
     want = _source_hash()
@@ -449,6 +454,26 @@ def plan_points_device(pose, points, z_prev=None, exitflag=None, offset=(0.4, 0.
     _grid_call("rmpc_plan_points_device", B, N, None if z_prev is None else _ptr(z_prev), nvar,
                None if exitflag is None else _ptr(exitflag), _ptr(pose), int(pose.stride(0)), float(offset[0]),
                float(offset[1]), float(height), _ptr(points), _stream_arg(stream))
+
+
+def fleet_points_device(pose, points, z_prev=None, exitflag=None, heading: int = 1, offset=(0.4, 0.0),
+                        height: float = 0.0, stream=None):
+    """Predicted collision points of the coming solve (``rmpc_fleet_points_device``): points (B, N, 3) from stage
+    min(k + 1, N - 1) of the previous plan z_prev (B, N, nvar), or from the current pose (B, stride >= 3) when z_prev is
+    None or exitflag (B,) int32 [b] < 0; heading 1 = the boxer's end link at ``offset``, 0 = (q0, q1, height)."""
+    B, N = int(points.shape[0]), int(points.shape[1])
+    nvar = 3 if z_prev is None else int(z_prev.shape[2])
+    _grid_call("rmpc_fleet_points_device", B, N, None if z_prev is None else _ptr(z_prev), nvar,
+               None if exitflag is None else _ptr(exitflag), _ptr(pose), int(pose.stride(0)), int(heading),
+               float(offset[0]), float(offset[1]), float(height), _ptr(points), _stream_arg(stream))
+
+
+def fleet_planes_device(points, radius, planes, K: int, max_range: float = float("inf"), slot0: int = 0, stream=None):
+    """Separating planes against the K nearest neighbours (``rmpc_fleet_planes_device``): points (B, N, 3), radius (B,)
+    fp64, planes (B, N, nobst, 4) fp64 whose slots slot0 .. slot0 + K - 1 are written."""
+    B, N, nobst = int(points.shape[0]), int(points.shape[1]), int(planes.shape[2])
+    _grid_call("rmpc_fleet_planes_device", B, N, _ptr(points), _ptr(radius), int(K), float(max_range), nobst, int(slot0),
+               _ptr(planes), _stream_arg(stream))
 
 
 class Solver:

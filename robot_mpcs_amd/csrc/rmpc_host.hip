@@ -1629,18 +1629,52 @@ int rmpc_lidar_scan_device(int B, const rmpc_lidar *l, void *stream) {
   return 0;
 }
 
-int rmpc_plan_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
-                            const double *d_pose, int pose_stride, double offset_x, double offset_y, double height,
-                            double *d_points, void *stream) {
+static int plan_points(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag, const double *d_pose,
+                       int pose_stride, int shift, int heading, double offset_x, double offset_y, double height,
+                       double *d_points, void *stream) {
   if (!d_pose || !d_points) return fail("null argument");
   if (B < 1 || N < 1) return fail("plan points: need B, N >= 1");
+  if (heading != 0 && heading != 1) return fail("plan points: heading must be 0 or 1");
   if (pose_stride < 3) return fail("plan points: pose_stride must be >= 3 (x, y, heading)");
   if (nvar < 3) return fail("plan points: nvar must be >= 3 (x, y, heading first)");
   if (!grid_fits(B, N) || !grid_fits(B, pose_stride) || !grid_fits((long long)B * N, nvar))
     return fail("plan points: B*N, B*pose_stride and B*N*nvar must not exceed INT_MAX");
   if (grid_device(d_z_prev ? (const void *)d_z_prev : (const void *)d_pose)) return -1;
   hipLaunchKernelGGL(k_plan_points, dim3((B * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_z_prev, nvar,
-                     (const int *)d_exitflag, d_pose, pose_stride, B, N, offset_x, offset_y, height, d_points);
+                     (const int *)d_exitflag, d_pose, pose_stride, B, N, shift, heading, offset_x, offset_y, height,
+                     d_points);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int rmpc_plan_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
+                            const double *d_pose, int pose_stride, double offset_x, double offset_y, double height,
+                            double *d_points, void *stream) {
+  return plan_points(B, N, d_z_prev, nvar, d_exitflag, d_pose, pose_stride, 0, 1, offset_x, offset_y, height, d_points,
+                     stream);
+}
+
+/* fleet separation (rmpc_sense.hpp): no handle; each call runs on the device its first pointer lives on */
+int rmpc_fleet_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
+                             const double *d_pose, int pose_stride, int heading, double offset_x, double offset_y,
+                             double height, double *d_points, void *stream) {
+  return plan_points(B, N, d_z_prev, nvar, d_exitflag, d_pose, pose_stride, 1, heading, offset_x, offset_y, height,
+                     d_points, stream);
+}
+
+int rmpc_fleet_planes_device(int B, int N, const double *d_points, const double *d_radius, int K, double range,
+                             int nobst, int slot0, double *d_planes, void *stream) {
+  if (!d_points || !d_radius || !d_planes) return fail("null argument");
+  if (B < 1 || N < 1) return fail("fleet planes: need B, N >= 1");
+  if (K < 1 || K > rmpc::kFleetKMax) return fail("fleet planes: need 1 <= K <= 8");
+  if (slot0 < 0 || nobst < 1 || slot0 > nobst - K) return fail("fleet planes: need 0 <= slot0 and slot0 + K <= nobst");
+  if (!(range >= 0.0)) return fail("fleet planes: range must be >= 0 (+inf admits every robot)");
+  if (!grid_fits(B, N) || !grid_fits((long long)B * N, nobst) || !grid_fits((long long)B * N * nobst, 4))
+    return fail("fleet planes: B*N*nobst*4 must not exceed INT_MAX");
+  if (grid_device(d_points)) return -1;
+  const int nbt = (B + 255) / 256;
+  hipLaunchKernelGGL(k_fleet_planes, dim3(nbt * N), dim3(256), 0, (hipStream_t)stream, d_points, d_radius, B, N, K,
+                     range * range, nobst, slot0, d_planes);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -12,6 +12,7 @@
 //   at its own seed, a plane with normal 0;
 //   t              the least hit distance, range when nothing is hit within range.
 // Contraction is off: the kernels evaluate the restatement's expressions (tests/test_lidar_cpu.py).
+// The fleet's separating planes (k_fleet_planes, below) live here too: their points come from k_plan_points.
 
 namespace rmpc {
 
@@ -78,23 +79,139 @@ __global__ __launch_bounds__(256) void k_lidar(const double *__restrict__ pose, 
 
 // One lane per (robot, stage): the sensor origin of q = z_prev [b][k][0 .. 2] (x_{k+1} of the previous plan, the
 // reference's "Preprocessing for planner"), of the robot's current pose when there is no plan or its solve failed.
+// shift = 1 reads stage min(k + 1, N - 1) instead (the coming solve's stage k, the last stage held: the fleet's
+// predicted collision points); heading = 0 writes (q0, q1, height) without the sensor offset (the point robot).
 __global__ __launch_bounds__(256) void k_plan_points(const double *__restrict__ z_prev, int nvar,
                                                      const int *__restrict__ exitflag, const double *__restrict__ pose,
-                                                     int stride, int B, int N, double offx, double offy, double height,
-                                                     double *__restrict__ points) {
+                                                     int stride, int B, int N, int shift, int heading, double offx,
+                                                     double offy, double height, double *__restrict__ points) {
 #pragma clang fp contract(off)
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= B * N) return;
   const int b = g / N;
+  const int k = g - b * N;
+  const int kk = shift ? min(k + 1, N - 1) : k;
   const bool plan = z_prev && !(exitflag && exitflag[b] < 0);
-  const double *const q = plan ? z_prev + (size_t)g * nvar : pose + (size_t)b * stride;
-  const double th = q[2];
-  double ox, oy;
-  sense_origin(q[0], q[1], cos(th), sin(th), offx, offy, ox, oy);
+  const double *const q = plan ? z_prev + ((size_t)b * N + kk) * nvar : pose + (size_t)b * stride;
   double *const o = points + (size_t)g * 3;
-  o[0] = ox;
-  o[1] = oy;
+  if (heading) {
+    const double th = q[2];
+    double ox, oy;
+    sense_origin(q[0], q[1], cos(th), sin(th), offx, offy, ox, oy);
+    o[0] = ox;
+    o[1] = oy;
+  } else {
+    o[0] = q[0];
+    o[1] = q[1];
+  }
   o[2] = height;
+}
+
+// ---- fleet separation: one separating plane per neighbour pair and stage ------------------------
+// Robot b at stage k with q_j = points [j][k]: the candidates are j != b with s_j = (u0^2 + u1^2) + u2^2 < range^2,
+// u = q_j - q_b; the K of least s_j (ties to the lower j) go to slots slot0 .. slot0 + K - 1 of planes [b][k][nobst].
+// The plane of a pair is computed from the lower index lo and the higher hi, so both robots hold bitwise-negated
+// copies of it: u = q_lo - q_hi, d = |u|, n = u / d ((1, 0, 0) when d = 0), g = d - r_lo - r_hi (the free gap),
+// m = q_hi + (r_hi + g / 2) n, c = -n.m; robot lo gets (n, c), robot hi (-n, -c).  Slots without a candidate get
+// k_fsd's dummy plane around q_b.
+constexpr int kFleetKMax = 8;
+
+// All-pairs scan in the shape of an N-body tiling: one block = 256 robots at one stage; tiles of 256 candidates pass
+// through LDS and every lane reads the same LDS word at the same time (a broadcast).  The sorted top-K list stays in
+// registers (kFleetKMax slots, fully unrolled; slots >= K hold -inf so that nothing enters them), the robot's own entry
+// gets s = +inf instead of a branch.  `worst` = the K-th least s so far (range^2 while the list is not full): a
+// candidate enters iff s < worst, which also keeps equal s in the order of j.
+__global__ __launch_bounds__(256) void k_fleet_planes(const double *__restrict__ points,
+                                                      const double *__restrict__ radius, int B, int N, int K,
+                                                      double r2, int nobst, int slot0, double *__restrict__ planes) {
+#pragma clang fp contract(off)
+  __shared__ double tx[256], ty[256], tz[256];
+  const int nbt = (B + 255) / 256;
+  const int k = blockIdx.x / nbt;
+  const int b = (blockIdx.x - k * nbt) * 256 + threadIdx.x;
+  const bool live = b < B;
+  const double *const qb = points + ((size_t)(live ? b : B - 1) * N + k) * 3;
+  const double x = qb[0], y = qb[1], z = qb[2];
+  const double inf = __builtin_inf();
+  double ts[kFleetKMax];
+  int tj[kFleetKMax];
+#pragma unroll
+  for (int i = 0; i < kFleetKMax; i++) {
+    ts[i] = i < K ? r2 : -inf;
+    tj[i] = -1;
+  }
+  double worst = r2;
+  for (int j0 = 0; j0 < B; j0 += 256) {
+    __syncthreads();
+    {
+      // a tile holds 256 candidates; the entries past B sit at +inf, where s = +inf never enters the list
+      const bool in = j0 + (int)threadIdx.x < B;
+      const double *const q = points + ((size_t)(in ? j0 + threadIdx.x : 0) * N + k) * 3;
+      tx[threadIdx.x] = in ? q[0] : inf;
+      ty[threadIdx.x] = in ? q[1] : inf;
+      tz[threadIdx.x] = in ? q[2] : inf;
+    }
+    __syncthreads();
+    for (int t = 0; t < 256; t++) {
+      const double u0 = tx[t] - x, u1 = ty[t] - y, u2 = tz[t] - z;
+      const double s = j0 + t == b ? inf : (u0 * u0 + u1 * u1) + u2 * u2;
+      if (s < worst) {
+        // sorted insert by (s, j): the new candidate has the largest j so far and goes behind equal s; an entry it
+        // displaces keeps its place before the equal s behind it
+        double cs = s;
+        int cj = j0 + t;
+#pragma unroll
+        for (int i = 0; i < kFleetKMax; i++) {
+          const bool lt = cs < ts[i] || (cs == ts[i] && cj < tj[i]);
+          const double os = ts[i];
+          const int oj = tj[i];
+          ts[i] = lt ? cs : os;
+          tj[i] = lt ? cj : oj;
+          cs = lt ? os : cs;
+          cj = lt ? oj : cj;
+        }
+        worst = ts[0];
+#pragma unroll
+        for (int i = 1; i < kFleetKMax; i++) worst = fmax(worst, ts[i]);
+      }
+    }
+  }
+  if (!live) return;
+  const double rb = radius[b];
+  double *const o = planes + (((size_t)b * N + k) * nobst + slot0) * 4;
+#pragma unroll
+  for (int i = 0; i < kFleetKMax; i++) {
+    if (i >= K) break;
+    const int j = tj[i];
+    double n0, n1, n2, c;
+    if (j < 0) {
+      // HalfPlane(seed + (20, 20, 0), seed) of k_fsd: normal = seed - point
+      const double p0 = x + 20.0, p1 = y + 20.0, p2 = z + 0.0;
+      n0 = x - p0; n1 = y - p1; n2 = z - p2;
+      c = -((n0 * p0 + n1 * p1) + n2 * p2);
+    } else {
+      const double *const qj = points + ((size_t)j * N + k) * 3;
+      const double rj = radius[j];
+      const bool lo = b < j;
+      const double l0 = lo ? x : qj[0], l1 = lo ? y : qj[1], l2 = lo ? z : qj[2], rl = lo ? rb : rj;
+      const double h0 = lo ? qj[0] : x, h1 = lo ? qj[1] : y, h2 = lo ? qj[2] : z, rh = lo ? rj : rb;
+      const double u0 = l0 - h0, u1 = l1 - h1, u2 = l2 - h2;
+      const double d = sqrt((u0 * u0 + u1 * u1) + u2 * u2);
+      const bool z0 = d == 0.0;
+      n0 = z0 ? 1.0 : u0 / d;
+      n1 = z0 ? 0.0 : u1 / d;
+      n2 = z0 ? 0.0 : u2 / d;
+      const double g = (d - rl) - rh;
+      const double w = rh + 0.5 * g;
+      const double m0 = h0 + w * n0, m1 = h1 + w * n1, m2 = h2 + w * n2;
+      c = -((n0 * m0 + n1 * m1) + n2 * m2);
+      if (!lo) { n0 = -n0; n1 = -n1; n2 = -n2; c = -c; }
+    }
+    o[4 * i] = n0;
+    o[4 * i + 1] = n1;
+    o[4 * i + 2] = n2;
+    o[4 * i + 3] = c;
+  }
 }
 
 }  // namespace rmpc
