@@ -104,7 +104,7 @@ def mutual_at(points, K, max_range):
 
 def run(robot="boxer", B=None, K=4, steps=None, seed=0, neighbours=True, max_range=3.0, dev="cuda:0", lookahead=None):
     import torch
-    from robot_mpcs_amd import _lib
+    from robot_mpcs_amd.fleet import Arrivals, dev_f64, event_ms, limit_tensors, make_block, step_block
     from robot_mpcs_amd.utils.separation import NeighbourPlanes
 
     cfg = ROBOTS[robot]
@@ -114,28 +114,20 @@ def run(robot="boxer", B=None, K=4, steps=None, seed=0, neighbours=True, max_ran
     rng = np.random.default_rng(seed)
     base, th, goals = pick(B, r, rng, cfg["heading"], cfg["offset"])
     desc, setup, lim, limu = model(robot, B, K, seed)
-    s = _lib.Solver(desc, max_batch=B)
-    N, nv, nx = desc["N"], s.nvar, desc["nx"]
-    xinit = np.zeros((B, nx))
+    N = desc["N"]
+    xinit = np.zeros((B, desc["nx"]))
     xinit[:, :2] = base
     xinit[:, 2] = th
-    x0 = np.zeros((B, N, nv))
-    x0[:, :, :nx] = xinit[:, None, :]
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-    rad = t(np.full(B, r))
+    rad = dev_f64(np.full(B, r), dev)
     npl = NeighbourPlanes(B, N, K, range=max_range if neighbours else 0.0, heading=cfg["heading"], offset=cfg["offset"],
                           height=cfg["height"], device=dev)
-    goal = t(np.concatenate([goals, np.zeros((B, 1))], 1))
-    scene = s.make_scene(setup["mpc"]["weights"], goal=goal, r_body=rad, lin_constrs=npl.planes,
-                         lower_limits=t(np.tile(lim[0], (B, 1))), upper_limits=t(np.tile(lim[1], (B, 1))),
-                         lower_limits_u=t(np.tile(limu[0], (B, 1))), upper_limits_u=t(np.tile(limu[1], (B, 1))))
+    goal = dev_f64(np.concatenate([goals, np.zeros((B, 1))], 1), dev)
+    f = make_block(desc, setup["mpc"]["weights"], B, xinit, dev, goal=goal, r_body=rad, lin_constrs=npl.planes,
+                   **limit_tensors(lim, limu, B, dev))
     previous_plan = setup["mpc"].get("initialization", "previous_plan") == "previous_plan"
     lookahead = float(cfg["lookahead"] if lookahead is None else lookahead)
     final = goal.clone()
-    tx, t0 = t(xinit), t(x0)
-    z = torch.zeros((B, N, nv), dtype=torch.float64, device=dev)
-    ef = torch.zeros(B, dtype=torch.int32, device=dev); it = torch.empty(B, dtype=torch.int32, device=dev)
-    kkt = torch.empty(B, dtype=torch.float64, device=dev); obj = torch.empty(B, dtype=torch.float64, device=dev)
+    tx, z, ef = f["x"], f["z"], f["ef"]
 
     def cpoint(x):
         if cfg["heading"]:
@@ -151,7 +143,7 @@ def run(robot="boxer", B=None, K=4, steps=None, seed=0, neighbours=True, max_ran
     below = torch.zeros(4, **i64)          # [both ok & mutual, both ok & not mutual, a failure & mutual, a failure & not]
     min_gap = torch.full((), float("inf"), dtype=torch.float64, device=dev)
     min_ratio = torch.full((), float("inf"), dtype=torch.float64, device=dev)
-    arrived = torch.full((B,), -1, **i64)
+    arrivals = Arrivals(B, dev)
     k1 = min(1, N - 1)
 
     failed_overlap = torch.zeros((), **i64)
@@ -168,8 +160,7 @@ def run(robot="boxer", B=None, K=4, steps=None, seed=0, neighbours=True, max_ran
         overlap = (d0 < -BELOW).any(dim=1)
         npl.step(tx, rad, z if step > 0 else None, ef if step > 0 else None)
         mutual = mutual_at(npl.points[:, k1], K, max_range if neighbours else 0.0)
-        s.solve_scene_device(B, scene, tx, t0, z, ef, it, kkt, obj)
-        s.advance_device(B, z, tx, t0, previous_plan=previous_plan, exitflag=ef)
+        step_block(f, previous_plan)
         fails += (ef < 0).sum()
         failed_overlap += ((ef < 0) & overlap).sum()
         ever_failed |= ef < 0
@@ -185,30 +176,20 @@ def run(robot="boxer", B=None, K=4, steps=None, seed=0, neighbours=True, max_ran
         both = ok[:, None] & ok[None, :]
         below += torch.stack([(close & both & mutual).sum(), (close & both & ~mutual).sum(),
                               (close & ~both & mutual).sum(), (close & ~both & ~mutual).sum()])
-        at = (p[:, :2] - final[:, :2]).norm(dim=1) < cfg["tol"]
-        arrived = torch.where(at & (arrived < 0), torch.full_like(arrived, step + 1), arrived)
+        arrivals.update((p[:, :2] - final[:, :2]).norm(dim=1) < cfg["tol"], step)
     torch.cuda.synchronize()
     ms = 1e3 * (time.perf_counter() - t_loop) / steps
 
-    step_ms = []
-    for _ in range(21):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); npl.step(tx, rad, z, ef); b.record()
-        b.synchronize()
-        step_ms.append(a.elapsed_time(b))
-    a = arrived.cpu().numpy()
-    done = np.sort(a[a > 0])
-    q = lambda f: int(done[min(len(done) - 1, int(np.ceil(f * len(done))) - 1)]) if len(done) else None
+    step_ms = event_ms(lambda: npl.step(tx, rad, z, ef), 20)
     bl = below.cpu().numpy().tolist()
     out = dict(robot=robot, robots=B, steps=steps, K=K, range=max_range if neighbours else 0.0, neighbours=bool(neighbours),
-               seed=seed, N=N, r_body=r, lookahead=lookahead, fused=s.is_fused(), arrivals=int(len(done)), arrival_share=len(done) / B,
-               arrival_step_p50=q(0.5), arrival_step_p90=q(0.9), arrival_step_max=q(1.0),
+               seed=seed, N=N, r_body=r, lookahead=lookahead, fused=f["s"].is_fused(), **arrivals.summary(),
                failed_solves=int(fails.item()), failed_share=int(fails.item()) / (B * steps), flag0_solves=int(flag0.item()),
                min_gap_m=float(min_gap.item()), min_ratio=float(min_ratio.item()),
                below_ok_mutual=bl[0], below_ok_not_mutual=bl[1], below_failed_mutual=bl[2], below_failed_not_mutual=bl[3],
                failed_overlapping=int(failed_overlap.item()), failed_robots=int(ever_failed.sum().item()),
-               max_speed=float(vmax.item()), ms_per_step=round(ms, 3), neighbour_step_ms=round(float(np.median(step_ms[1:])), 4), arrive_tol_m=cfg["tol"])
-    s.close()
+               max_speed=float(vmax.item()), ms_per_step=round(ms, 3), neighbour_step_ms=round(step_ms, 4), arrive_tol_m=cfg["tol"])
+    f["s"].close()
     return out
 
 

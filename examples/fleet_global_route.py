@@ -37,63 +37,29 @@ X0 = Y0 = -9.0
 SIZE_ROBOT = 0.45     # k = 1: every cell that touches a shelf is blocked
 
 
-def pick_routes(raw, free, B, rng):
-    """B (start, goal) cell pairs: both free on the enlarged map, 10 .. 20 m apart, the straight line crossing a shelf."""
-    cells = np.flatnonzero(free.ravel())
-    xy = np.stack([X0 + (cells % W) * CELL, Y0 + (cells // W) * CELL], 1)
-    starts, goals = [], []
-    while len(starts) < B:
-        i, j = rng.integers(0, len(cells), 2)
-        d = np.linalg.norm(xy[i] - xy[j])
-        if not 10.0 <= d <= 20.0:
-            continue
-        t = np.linspace(0.0, 1.0, 200)[:, None]
-        seg = xy[i] + t * (xy[j] - xy[i])
-        cc = np.rint((seg - [X0, Y0]) / CELL).astype(int)
-        if not raw[cc[:, 1], cc[:, 0]].any():
-            continue
-        starts.append(cells[i]); goals.append(cells[j])
-    return np.array(starts, np.int32), np.array(goals, np.int32)
-
-
 def run(B=256, steps=1200, seed=0, dev="cuda:0", aisle=4, gap=3, size_robot=SIZE_ROBOT, threshold=1.3, shelf=2):
     import torch
-    from robot_mpcs_amd import _lib
-    from robot_mpcs_amd.fleet import MixedFleetShard
-    from robot_mpcs_amd.global_planner import RouteFollower, plan_batch, png_values, shelf_map
-    from robot_mpcs_amd.scenarios import POINT_LIMITS, POINT_LIMITS_U, make_scenario
+    from robot_mpcs_amd.fleet import Arrivals, MixedFleetShard, dev_f64, limit_tensors, make_block, step_block
+    from robot_mpcs_amd.global_planner import RouteFollower, cell_xy, plan_batch, shelf_map, store_routes
+    from robot_mpcs_amd.scenarios import LIMITS, make_scenario
 
     rng = np.random.default_rng(seed)
     raw = shelf_map(H, W, seed=seed, aisle=aisle, gap=gap, shelf=shelf)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-    g_raw = t(png_values(raw))
-    g_inf = torch.empty_like(g_raw)
-    _lib.grid_inflate_device(g_raw, g_inf, CELL, size_robot, 0.29)
-    free = g_inf.cpu().numpy() < 0.8
-    starts, goals = pick_routes(raw > 0.5, free, B, rng)
+    g_inf, starts, goals = store_routes(raw, B, rng, X0, Y0, CELL, size_robot, dev)
 
     sc = make_scenario("cfg2", B=B, seed=seed)
-    s = _lib.Solver(sc.desc, max_batch=B)
-    N, nv, nob = sc.desc["N"], s.nvar, sc.desc["nobst"]
+    nob = sc.desc["nobst"]
     xinit = np.zeros((B, sc.desc["nx"]))
-    xinit[:, 0] = X0 + (starts % W) * CELL
-    xinit[:, 1] = Y0 + (starts // W) * CELL
-    x0 = np.zeros((B, N, nv))
-    x0[:, :, :sc.desc["nx"]] = xinit[:, None, :]
+    xinit[:, :2] = cell_xy(starts, W, X0, Y0, CELL)
     # the scenario's round obstacles are moved out of the store: the shelves are the obstacles here
     obst = np.zeros((B, nob, 4))
     obst[:, :, 0] = 50.0 + 5.0 * np.arange(nob)
     obst[:, :, 1] = 50.0
     obst[:, :, 3] = 0.1
-    goal = t(np.concatenate([xinit[:, :2], np.zeros((B, 1))], 1))
-    scene = s.make_scene(sc.setup["mpc"]["weights"], goal=goal, r_body=t(np.full(B, 0.3)), obst=t(obst),
-                         lower_limits=t(np.tile(POINT_LIMITS[0], (B, 1))), upper_limits=t(np.tile(POINT_LIMITS[1], (B, 1))),
-                         lower_limits_u=t(np.tile(POINT_LIMITS_U[0], (B, 1))),
-                         upper_limits_u=t(np.tile(POINT_LIMITS_U[1], (B, 1))))
-    tx, t0 = t(xinit), t(x0)
-    z = torch.empty((B, N, nv), dtype=torch.float64, device=dev)
-    ef = torch.empty(B, dtype=torch.int32, device=dev); it = torch.empty(B, dtype=torch.int32, device=dev)
-    kkt = torch.empty(B, dtype=torch.float64, device=dev); obj = torch.empty(B, dtype=torch.float64, device=dev)
+    goal = dev_f64(np.concatenate([xinit[:, :2], np.zeros((B, 1))], 1), dev)
+    f = make_block(sc.desc, sc.setup["mpc"]["weights"], B, xinit, dev, goal=goal, r_body=dev_f64(np.full(B, 0.3), dev),
+                   obst=dev_f64(obst, dev), **limit_tensors(*LIMITS["cfg2"], B, dev))
+    tx, ef = f["x"], f["ef"]
 
     torch.cuda.synchronize()
     tp = time.perf_counter()
@@ -103,33 +69,26 @@ def run(B=256, steps=1200, seed=0, dev="cuda:0", aisle=4, gap=3, size_robot=SIZE
     follower = RouteFollower(paths, lens, W, X0, Y0, CELL, threshold=threshold)
     final = follower.final_goals()
 
-    occ = np.flatnonzero(raw.ravel() > 0.5)
-    occ_xy = t(np.stack([X0 + (occ % W) * CELL, Y0 + (occ // W) * CELL], 1))
+    occ_xy = dev_f64(cell_xy(np.flatnonzero(raw.ravel() > 0.5), W, X0, Y0, CELL), dev)
     tol = MixedFleetShard.ARRIVE_TOL["cfg2"]
     fails = torch.zeros((), dtype=torch.int64, device=dev)
     clear = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
-    arrived = torch.full((B,), -1, dtype=torch.int64, device=dev)
+    arrivals = Arrivals(B, dev)
     torch.cuda.synchronize()
     t_loop = time.perf_counter()
     for step in range(steps):
         follower.step(tx, goal)
-        s.solve_scene_device(B, scene, tx, t0, z, ef, it, kkt, obj)
-        s.advance_device(B, z, tx, t0, previous_plan=False)
+        step_block(f, previous_plan=False, flags=False)
         fails += (ef < 0).sum()
         # distance from the robot's centre to the nearest raw-occupied cell (a square of side CELL)
         d = ((tx[:, None, :2] - occ_xy[None]).abs() - 0.5 * CELL).clamp(min=0.0).norm(dim=2).min(dim=1).values
         clear = torch.minimum(clear, d)
-        at = (tx[:, :2] - final).norm(dim=1) < tol
-        arrived = torch.where(at & (arrived < 0), torch.full_like(arrived, step + 1), arrived)
+        arrivals.update((tx[:, :2] - final).norm(dim=1) < tol, step)
     torch.cuda.synchronize()
     ms = 1e3 * (time.perf_counter() - t_loop) / steps
-    a = arrived.cpu().numpy()
-    done = np.sort(a[a > 0])
-    q = lambda p: int(done[min(len(done) - 1, int(np.ceil(p * len(done))) - 1)]) if len(done) else None
-    s.close()
+    f["s"].close()
     return dict(robots=B, steps=steps, routes=int((lens > 0).sum().item()), route_len_max=int(lens.max().item()),
-                plan_ms=round(plan_ms, 3), arrivals=int(len(done)), arrival_share=len(done) / B,
-                arrival_step_p50=q(0.5), arrival_step_p90=q(0.9), arrival_step_max=q(1.0),
+                plan_ms=round(plan_ms, 3), **arrivals.summary(),
                 failed_solves=int(fails.item()), min_clearance_m=float(clear.min().item()),
                 touching=int((clear <= 0).sum().item()), clearance_p10=float(clear.quantile(0.1).item()),
                 ms_per_step=round(ms, 3), arrive_tol_m=tol)

@@ -59,25 +59,6 @@ def clear_cells(raw, k):
     return ~near
 
 
-def pick_routes(raw, ok, B, rng):
-    """B (start, goal) cell pairs among the `ok` cells, 10 .. 20 m apart, the straight line crossing a shelf."""
-    cells = np.flatnonzero(ok.ravel())
-    xy = np.stack([X0 + (cells % W) * CELL, Y0 + (cells // W) * CELL], 1)
-    starts, goals = [], []
-    while len(starts) < B:
-        i, j = rng.integers(0, len(cells), 2)
-        d = np.linalg.norm(xy[i] - xy[j])
-        if not 10.0 <= d <= 20.0:
-            continue
-        t = np.linspace(0.0, 1.0, 200)[:, None]
-        seg = xy[i] + t * (xy[j] - xy[i])
-        cc = np.rint((seg - [X0, Y0]) / CELL).astype(int)
-        if not raw[cc[:, 1], cc[:, 0]].any():
-            continue
-        starts.append(cells[i]); goals.append(cells[j])
-    return np.array(starts, np.int32), np.array(goals, np.int32)
-
-
 def box_distance(p, boxes):
     """(B,) least distance from the points p (B, 2) to the boxes (nbox, 4) = (cx, cy, lx, ly); 0 inside"""
     return ((p[:, None, :] - boxes[None, :, :2]).abs() - 0.5 * boxes[None, :, 2:]).clamp(min=0.0).norm(dim=2).min(dim=1).values
@@ -85,42 +66,27 @@ def box_distance(p, boxes):
 
 def run(B=256, steps=1200, seed=0, dev="cuda:0", K=4, rays=64, lidar=True, threshold=1.3):
     import torch
-    from robot_mpcs_amd import _lib
-    from robot_mpcs_amd.fleet import MixedFleetShard
-    from robot_mpcs_amd.global_planner import RouteFollower, plan_batch, png_values, shelf_map
-    from robot_mpcs_amd.scenarios import BOXER_LIMITS, BOXER_LIMITS_U, make_scenario
+    from robot_mpcs_amd.fleet import (Arrivals, MixedFleetShard, dev_f64, event_ms, limit_tensors, make_block,
+                                      step_block)
+    from robot_mpcs_amd.global_planner import RouteFollower, cell_xy, plan_batch, shelf_map, store_routes
+    from robot_mpcs_amd.scenarios import LIMITS, make_scenario
     from robot_mpcs_amd.utils.lidar import LidarPlanes, boxes_from_grid
 
     rng = np.random.default_rng(seed)
     raw = shelf_map(H, W, seed=seed, aisle=AISLE, gap=GAP, shelf=SHELF)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-    g_raw = t(png_values(raw))
-    g_inf = torch.empty_like(g_raw)
-    _lib.grid_inflate_device(g_raw, g_inf, CELL, SIZE_ROBOT, 0.29)
-    free = g_inf.cpu().numpy() < 0.8
-    starts, goals = pick_routes(raw > 0.5, clear_cells(raw, CLEAR_CELLS) & free, B, rng)
+    g_inf, starts, goals = store_routes(raw, B, rng, X0, Y0, CELL, SIZE_ROBOT, dev, ok=clear_cells(raw, CLEAR_CELLS))
     boxes_np = boxes_from_grid(raw, X0, Y0, CELL)
-    boxes = t(boxes_np)
+    boxes = dev_f64(boxes_np, dev)
 
     sc = make_scenario("boxer", B=B, seed=seed, number_obstacles=K)
-    s = _lib.Solver(sc.desc, max_batch=B)
-    N, nv, nx = sc.desc["N"], s.nvar, sc.desc["nx"]
-    xinit = np.zeros((B, nx))
-    xinit[:, 0] = X0 + (starts % W) * CELL
-    xinit[:, 1] = Y0 + (starts // W) * CELL
+    xinit = np.zeros((B, sc.desc["nx"]))
+    xinit[:, :2] = cell_xy(starts, W, X0, Y0, CELL)
     xinit[:, 2] = rng.uniform(-math.pi, math.pi, B)
-    x0 = np.zeros((B, N, nv))
-    x0[:, :, :nx] = xinit[:, None, :]
-    lp = LidarPlanes(B, N, K, boxes=boxes_np if lidar else None, rays=rays, offset=(EE_OFFSET, 0.0), device=dev)
-    goal = t(np.concatenate([xinit[:, :2], np.zeros((B, 1))], 1))
-    scene = s.make_scene(sc.setup["mpc"]["weights"], goal=goal, r_body=t(np.full(B, R_BODY)), lin_constrs=lp.planes,
-                         lower_limits=t(np.tile(BOXER_LIMITS[0], (B, 1))), upper_limits=t(np.tile(BOXER_LIMITS[1], (B, 1))),
-                         lower_limits_u=t(np.tile(BOXER_LIMITS_U[0], (B, 1))),
-                         upper_limits_u=t(np.tile(BOXER_LIMITS_U[1], (B, 1))))
-    tx, t0 = t(xinit), t(x0)
-    z = torch.zeros((B, N, nv), dtype=torch.float64, device=dev)
-    ef = torch.zeros(B, dtype=torch.int32, device=dev); it = torch.empty(B, dtype=torch.int32, device=dev)
-    kkt = torch.empty(B, dtype=torch.float64, device=dev); obj = torch.empty(B, dtype=torch.float64, device=dev)
+    lp = LidarPlanes(B, sc.desc["N"], K, boxes=boxes_np if lidar else None, rays=rays, offset=(EE_OFFSET, 0.0), device=dev)
+    goal = dev_f64(np.concatenate([xinit[:, :2], np.zeros((B, 1))], 1), dev)
+    f = make_block(sc.desc, sc.setup["mpc"]["weights"], B, xinit, dev, goal=goal, r_body=dev_f64(np.full(B, R_BODY), dev),
+                   lin_constrs=lp.planes, **limit_tensors(*LIMITS["boxer"], B, dev))
+    tx, z, ef = f["x"], f["z"], f["ef"]
 
     paths, lens = plan_batch(g_inf, torch.from_numpy(starts).to(dev), torch.from_numpy(goals).to(dev))
     follower = RouteFollower(paths, lens, W, X0, Y0, CELL, threshold=threshold)
@@ -130,7 +96,7 @@ def run(B=256, steps=1200, seed=0, dev="cuda:0", K=4, rays=64, lidar=True, thres
     fails = torch.zeros((), dtype=torch.int64, device=dev)
     ee_clear = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
     base_clear = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
-    arrived = torch.full((B,), -1, dtype=torch.int64, device=dev)
+    arrivals = Arrivals(B, dev)
 
     def ee_of(x):
         return x[:, :2] + EE_OFFSET * torch.stack([torch.cos(x[:, 2]), torch.sin(x[:, 2])], 1)
@@ -140,36 +106,24 @@ def run(B=256, steps=1200, seed=0, dev="cuda:0", K=4, rays=64, lidar=True, thres
     for step in range(steps):
         follower.step(tx, goal)
         lp.step(tx, z if step > 0 else None, ef if step > 0 else None)
-        s.solve_scene_device(B, scene, tx, t0, z, ef, it, kkt, obj)
-        s.advance_device(B, z, tx, t0, previous_plan=True, exitflag=ef)
+        step_block(f, previous_plan=True)
         fails += (ef < 0).sum()
         ee = ee_of(tx)
         ee_clear = torch.minimum(ee_clear, box_distance(ee, boxes))
         base_clear = torch.minimum(base_clear, box_distance(tx[:, :2], boxes))
-        at = (ee - final).norm(dim=1) < tol
-        arrived = torch.where(at & (arrived < 0), torch.full_like(arrived, step + 1), arrived)
+        arrivals.update((ee - final).norm(dim=1) < tol, step)
     torch.cuda.synchronize()
     ms = 1e3 * (time.perf_counter() - t_loop) / steps
 
-    lidar_ms = []
-    for _ in range(21):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); lp.step(tx, z, ef); b.record()
-        b.synchronize()
-        lidar_ms.append(a.elapsed_time(b))
-    a = arrived.cpu().numpy()
-    done = np.sort(a[a > 0])
-    q = lambda p: int(done[min(len(done) - 1, int(np.ceil(p * len(done))) - 1)]) if len(done) else None
-    out = dict(robots=B, steps=steps, K=K, rays=rays, lidar=bool(lidar), fused=s.is_fused(), nbox=int(len(boxes_np)),
-               routes=int((lens > 0).sum().item()), arrivals=int(len(done)), arrival_share=len(done) / B,
-               arrival_step_p50=q(0.5), arrival_step_p90=q(0.9), arrival_step_max=q(1.0),
+    lidar_ms = event_ms(lambda: lp.step(tx, z, ef), 20)
+    out = dict(robots=B, steps=steps, K=K, rays=rays, lidar=bool(lidar), fused=f["s"].is_fused(), nbox=int(len(boxes_np)),
+               routes=int((lens > 0).sum().item()), **arrivals.summary(),
                failed_solves=int(fails.item()), failed_share=int(fails.item()) / (B * steps),
                min_ee_clearance_m=float(ee_clear.min().item()), ee_clearance_p10=float(ee_clear.quantile(0.1).item()),
                ee_below_half_r_body=int((ee_clear < 0.5 * R_BODY).sum().item()),
                min_base_clearance_m=float(base_clear.min().item()), base_inside=int((base_clear <= 0).sum().item()),
-               ms_per_step=round(ms, 3), lidar_step_ms=round(float(np.median(lidar_ms[1:])), 4), arrive_tol_m=tol,
-               r_body=R_BODY)
-    s.close()
+               ms_per_step=round(ms, 3), lidar_step_ms=round(lidar_ms, 4), arrive_tol_m=tol, r_body=R_BODY)
+    f["s"].close()
     return out
 
 

@@ -87,6 +87,92 @@ def summarize(allstats, instances_per_rank: int):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# One block of a device-resident closed loop: a solver handle, its scene and the arrays of one control step, as a
+# dict record.  A loop is written as  make_block(...)  once, then per control step whatever fills the scene
+# (RouteFollower.step, LidarPlanes.step, NeighbourPlanes.step, in the loop's own order) and  step_block(f, ...).
+# ---------------------------------------------------------------------------------------------------------
+def dev_f64(a, device):
+    """host array -> contiguous fp64 tensor on ``device``"""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+
+
+def limit_tensors(lim, limu, B, device):
+    """The (2, n) position and input limits (scenarios.LIMITS) tiled to the four (B, n) arrays of ``make_scene``."""
+    return dict(lower_limits=dev_f64(np.tile(lim[0], (B, 1)), device), upper_limits=dev_f64(np.tile(lim[1], (B, 1)), device),
+                lower_limits_u=dev_f64(np.tile(limu[0], (B, 1)), device), upper_limits_u=dev_f64(np.tile(limu[1], (B, 1)), device))
+
+
+def make_block(desc, weights, B, xinit, device, x0=None, name=None, stream=None, **scene_tensors):
+    """Solver handle ``s``, ``scene`` (``make_scene(weights, **scene_tensors)``), state ``x`` (B, nx), initial guess
+    ``x0`` (B, N, nvar; ``xinit`` repeated over the horizon when none is given) and the zero-filled outputs of a solve
+    ``z, ef, it, kkt, obj``, all on ``device``; ``goal`` is the scene's goal tensor and ``stream`` the stream
+    ``step_block`` enqueues on (a ``torch.cuda.Stream``, or None = the current one)."""
+    import torch
+    from robot_mpcs_amd._lib import Solver
+    s = Solver(desc, max_batch=B, device=torch.device(device).index or 0)
+    if x0 is None:
+        x0 = np.zeros((B, desc["N"], s.nvar))
+        x0[:, :, :desc["nx"]] = np.asarray(xinit)[:, None, :]
+    i32, f64 = dict(dtype=torch.int32, device=device), dict(dtype=torch.float64, device=device)
+    return dict(name=name, B=B, s=s, scene=s.make_scene(weights, **scene_tensors), x=dev_f64(xinit, device),
+                x0=dev_f64(x0, device), z=torch.zeros((B, desc["N"], s.nvar), **f64), ef=torch.zeros(B, **i32),
+                it=torch.zeros(B, **i32), kkt=torch.zeros(B, **f64), obj=torch.zeros(B, **f64),
+                goal=scene_tensors.get("goal"), stream=stream)
+
+
+def step_block(f, previous_plan, flags=True, stream=None):
+    """One control step of a block: ``solve_scene_device``, then ``advance_device`` (plant step and the next solve's
+    initial guess), on ``stream`` (a raw handle), else on the block's own, else on the current one.  ``flags``: hand the
+    exit flags to the advance, so that an instance whose solve failed restarts from its state.  ``flags=False`` exists only
+    because examples/fleet_global_route.py and test_device_closed_loop_reaches_goal have always called the flag-less
+    entry and their results must not move; a new loop leaves it on."""
+    s, B = f["s"], f["B"]
+    if stream is None and f["stream"] is not None:
+        stream = f["stream"].cuda_stream
+    s.solve_scene_device(B, f["scene"], f["x"], f["x0"], f["z"], f["ef"], f["it"], f["kkt"], f["obj"], stream=stream)
+    s.advance_device(B, f["z"], f["x"], f["x0"], previous_plan=previous_plan, stream=stream,
+                     exitflag=f["ef"] if flags else None)
+
+
+class Arrivals:
+    """``step`` (B,) int64 on the device: the control step (counted from 1) at which a robot was first seen at its
+    goal, -1 until then; read once, by ``summary()``."""
+
+    def __init__(self, B, device):
+        import torch
+        self.step = torch.full((B,), -1, dtype=torch.int64, device=device)
+
+    def update(self, at, step):
+        """``at`` (B,) bool: at the goal after control step ``step`` (counted from 0)"""
+        import torch
+        self.step = torch.where(at & (self.step < 0), torch.full_like(self.step, step + 1), self.step)
+
+    def summary(self):
+        """arrivals, their share of the fleet, and the step by which 50 / 90 / 100 % of them had happened (None: none)"""
+        a = self.step.cpu().numpy()
+        done = np.sort(a[a > 0])
+        q = lambda p: int(done[min(len(done) - 1, int(np.ceil(p * len(done))) - 1)]) if len(done) else None
+        return dict(arrivals=int(len(done)), arrival_share=len(done) / len(a), arrival_step_p50=q(0.5),
+                    arrival_step_p90=q(0.9), arrival_step_max=q(1.0))
+
+
+def event_ms(fn, reps):
+    """Median over ``reps`` calls of ``fn`` of the time between two events around it [ms], each call synchronised,
+    after one warm call."""
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); fn(); b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return float(np.median(out))
+
+
+# ---------------------------------------------------------------------------------------------------------
 # One GPU's shard of the mixed fleet as a device-resident closed loop (BASELINE configs[4])
 # ---------------------------------------------------------------------------------------------------------
 class MixedFleetShard:
@@ -120,7 +206,6 @@ class MixedFleetShard:
                  options: dict | None = None, pass_budget=0, steady: bool = False, max_dwell: int = 150,
                  mu_regoal: dict | None = None):
         import torch
-        from robot_mpcs_amd._lib import Solver
         from robot_mpcs_amd import scenarios as sn
         self.torch, self.dev = torch, device
         self.previous_plan = bool(previous_plan)
@@ -130,33 +215,22 @@ class MixedFleetShard:
         self.steady = bool(steady)
         self.max_dwell = int(max_dwell)
         self.mu_regoal = dict(self.MU_REGOAL, **(mu_regoal or {}))
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
-        limits = {"cfg2": (sn.POINT_LIMITS, sn.POINT_LIMITS_U), "cfg3": (sn.BOXER_LIMITS, sn.BOXER_LIMITS_U),
-                  "cfg4": (sn.PANDA_LIMITS, sn.PANDA_LIMITS_U)}
+        t = lambda a: dev_f64(a, device)
         self.fleets = []
-        dev_index = device.index if device.index is not None else 0
         for name, B in counts.items():
             if B <= 0:
                 continue
-            lim, limu = limits[name]
             sc = sn.make_scenario(name, B=B, seed=seed)
             d = dict(sc.desc)
             if options:
                 d["options"] = dict(d["options"], **options)
-            s = Solver(d, max_batch=B, device=dev_index)
-            s.set_warm_start(bool(warm_duals and previous_plan))
-            pb = pass_budget.get(name, 0) if isinstance(pass_budget, dict) else int(pass_budget)
-            if pb > 0:
-                s.set_pass_budget(pb)   # real-time deadline of a control step (rmpc_set_pass_budget)
-            ten = dict(goal=t(sc.extra["goal"]), r_body=t(np.full(B, sc.extra["r_body"])),
-                       lower_limits=t(np.tile(lim[0], (B, 1))), upper_limits=t(np.tile(lim[1], (B, 1))),
-                       lower_limits_u=t(np.tile(limu[0], (B, 1))), upper_limits_u=t(np.tile(limu[1], (B, 1))))
+            ten = dict(limit_tensors(*sn.LIMITS[name], B, device), goal=t(sc.extra["goal"]),
+                       r_body=t(np.full(B, sc.extra["r_body"])))
             if "obst_dyn" in sc.extra:
                 ten["obst_dyn"] = t(sc.extra["obst_dyn"])
             else:
                 rad = sc.extra.get("obst_radius", np.full(sc.extra["obst_pos"].shape[:2], 0.1))
                 ten["obst"] = t(np.concatenate([sc.extra["obst_pos"], rad[:, :, None]], axis=2))
-            N, nv = d["N"], s.nvar
             extra = {}
             if self.steady:
                 pool = goal_pool(name, sc, self.POOL, seed + 1000)
@@ -166,15 +240,16 @@ class MixedFleetShard:
                              failrun=torch.zeros(B, dtype=torch.int32, device=device),
                              # rmpc_retarget_device's counters (include/rmpc.h), summed over the control steps on the device
                              counts=torch.zeros(16, dtype=torch.int64, device=device))
-            self.fleets.append(dict(extra, 
-                name=name, B=B, s=s, sc=sc, scene=s.make_scene(sc.setup["mpc"]["weights"], **ten),
-                x=t(sc.xinit), x0=t(sc.x0), x_start=t(sc.xinit), x0_start=t(sc.x0),
-                z=torch.empty((B, N, nv), dtype=torch.float64, device=device),
-                ef=torch.empty(B, dtype=torch.int32, device=device), it=torch.empty(B, dtype=torch.int32, device=device),
-                kkt=torch.empty(B, dtype=torch.float64, device=device), obj=torch.empty(B, dtype=torch.float64, device=device),
-                goal=ten["goal"], obst_dyn=ten.get("obst_dyn"), dt=float(d["dt"]),
-                lim_lo=ten["lower_limits"], lim_hi=ten["upper_limits"],
-                stream=torch.cuda.Stream(device=device)))   # (a higher dispatch priority for the arm's stream: no effect, measured twice)
+            # (a higher dispatch priority for the arm's stream: no effect, measured twice)
+            f = make_block(d, sc.setup["mpc"]["weights"], B, sc.xinit, device, x0=sc.x0, name=name,
+                           stream=torch.cuda.Stream(device=device), **ten)
+            f["s"].set_warm_start(self.warm_duals)
+            pb = pass_budget.get(name, 0) if isinstance(pass_budget, dict) else int(pass_budget)
+            if pb > 0:
+                f["s"].set_pass_budget(pb)   # real-time deadline of a control step (rmpc_set_pass_budget)
+            f.update(extra, sc=sc, x_start=t(sc.xinit), x0_start=t(sc.x0), obst_dyn=ten.get("obst_dyn"), dt=float(d["dt"]),
+                     lim_lo=ten["lower_limits"], lim_hi=ten["upper_limits"])
+            self.fleets.append(f)
         torch.cuda.synchronize(device)
 
     @property

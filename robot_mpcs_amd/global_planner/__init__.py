@@ -9,7 +9,7 @@ the package needs no GPU.
 from .gridmap import OccupancyGridMap
 from .a_star import a_star
 from .globalPlanner import GlobalPlanner, png_values
-from .batch import RouteFollower, cells_from_positions, plan_batch, shelf_map
+from .batch import RouteFollower, cell_xy, cells_from_positions, pick_routes, plan_batch, shelf_map, store_routes
 
-__all__ = ["OccupancyGridMap", "a_star", "GlobalPlanner", "RouteFollower", "cells_from_positions", "plan_batch",
-           "png_values", "shelf_map"]
+__all__ = ["OccupancyGridMap", "a_star", "GlobalPlanner", "RouteFollower", "cell_xy", "cells_from_positions",
+           "pick_routes", "plan_batch", "png_values", "shelf_map", "store_routes"]

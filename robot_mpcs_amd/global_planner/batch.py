@@ -1,8 +1,8 @@
 """The fleet side of the global planner, in the plain frame (cell (row, col) centred at (x0 + col cell, y0 + row cell)):
 ``plan_batch`` computes one cost-to-go field per distinct goal and one path per query on the device, ``RouteFollower``
 keeps the routes on the device and hands every robot its next waypoint once per control step (``get_local_goal`` of
-the reference for B robots in one launch), ``shelf_map`` draws a seeded procedural store for tests, the example and
-the benchmark."""
+the reference for B robots in one launch), ``shelf_map`` draws a seeded procedural store for tests, the examples and
+the benchmark, ``store_routes`` enlarges such a map and draws the fleet's (start, goal) cells on it (``pick_routes``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -103,3 +103,42 @@ def shelf_map(H=41, W=41, seed=0, aisle=4, shelf=2, gap=3, gaps_per_shelf=2):
                 g[row:row + shelf, c:c + gap] = 0.0
         row += shelf + aisle
     return g
+
+
+def cell_xy(cells, W, x0, y0, cell):
+    """(n, 2) centres of the cells (indices row * W + col) in the plain frame"""
+    return np.stack([x0 + (cells % W) * cell, y0 + (cells // W) * cell], 1)
+
+
+def pick_routes(raw, ok, B, rng, x0, y0, cell):
+    """B (start, goal) cell pairs among the `ok` cells of the map `raw` (bool, occupied), 10 .. 20 m apart, the straight
+    line between them crossing an occupied cell."""
+    cells = np.flatnonzero(ok.ravel())
+    xy = cell_xy(cells, raw.shape[1], x0, y0, cell)
+    starts, goals = [], []
+    while len(starts) < B:
+        i, j = rng.integers(0, len(cells), 2)
+        d = np.linalg.norm(xy[i] - xy[j])
+        if not 10.0 <= d <= 20.0:
+            continue
+        t = np.linspace(0.0, 1.0, 200)[:, None]
+        seg = xy[i] + t * (xy[j] - xy[i])
+        cc = np.rint((seg - [x0, y0]) / cell).astype(int)
+        if not raw[cc[:, 1], cc[:, 0]].any():
+            continue
+        starts.append(cells[i]); goals.append(cells[j])
+    return np.array(starts, np.int32), np.array(goals, np.int32)
+
+
+def store_routes(raw, B, rng, x0, y0, cell, size_robot, device, ok=None):
+    """The prologue of a store example: the map enlarged as the reference does it (``png_values`` through
+    ``grid_inflate_device``, box mean > 0.29), then ``pick_routes`` among the cells free on it (below the planner's
+    occupancy threshold 0.8) and, if given, in the mask ``ok``.  Returns (g_inf (H, W) on the device, starts, goals);
+    ``plan_batch(g_inf, starts, goals)`` and ``RouteFollower`` take it from there."""
+    import torch
+    from .globalPlanner import png_values   # (globalPlanner imports a_star, which imports this module)
+    g_raw = _dev_tensor(png_values(raw), torch.float64, device)
+    g_inf = torch.empty_like(g_raw)
+    _lib.grid_inflate_device(g_raw, g_inf, cell, size_robot, 0.29)
+    free = g_inf.cpu().numpy() < 0.8
+    return (g_inf,) + pick_routes(raw > 0.5, free if ok is None else ok & free, B, rng, x0, y0, cell)

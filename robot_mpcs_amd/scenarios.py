@@ -109,6 +109,9 @@ PANDA_LIMITS_U = np.array([
     [-1.0, -1.0, -15.0, -15.0, -7.5, -10.0, -12.5],
     [1.0, 1.0, 15.0, 15.0, 7.5, 10.0, 12.5],
 ])
+# (position limits, input limits) by config and by model name: what a scene's limit rows are tiled from (fleet.limit_tensors)
+LIMITS = {"cfg2": (POINT_LIMITS, POINT_LIMITS_U), "cfg3": (BOXER_LIMITS, BOXER_LIMITS_U), "cfg4": (PANDA_LIMITS, PANDA_LIMITS_U)}
+LIMITS.update(pointRobot=LIMITS["cfg2"], boxer=LIMITS["cfg3"], panda=LIMITS["cfg4"])
 # (the extra joint of the test asset panda_tool8.urdf, configuration chain8: position and input limits)
 TOOL8_LIMITS = np.array([[-2.0, -12.5], [2.0, 12.5]])
 

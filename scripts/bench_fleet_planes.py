@@ -24,19 +24,6 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def timed(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b))
-    return float(np.median(out))
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -45,6 +32,7 @@ def main():
     g.build()
     import torch
     from robot_mpcs_amd import _lib
+    from robot_mpcs_amd.fleet import event_ms
 
     dev = "cuda:0"
     rng = np.random.default_rng(0)
@@ -61,11 +49,11 @@ def main():
         ef = torch.ones(B, dtype=torch.int32, device=dev)
         rad = torch.full((B,), 0.6, dtype=torch.float64, device=dev)
         pts = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
-        pts_ms = timed(lambda: _lib.fleet_points_device(tp, pts, tz, ef, 1, (0.4, 0.0), 0.0), a.reps)
+        pts_ms = event_ms(lambda: _lib.fleet_points_device(tp, pts, tz, ef, 1, (0.4, 0.0), 0.0), a.reps)
         r = dict(points_ms=round(pts_ms, 4))
         for K in (4, 8):
             planes = torch.empty((B, N, K, 4), dtype=torch.float64, device=dev)
-            ms = timed(lambda: _lib.fleet_planes_device(pts, rad, planes, K), a.reps)
+            ms = event_ms(lambda: _lib.fleet_planes_device(pts, rad, planes, K), a.reps)
             r[f"K{K}_planes_ms"] = round(ms, 4)
             r[f"K{K}_pair_tests_per_s"] = float(f"{1e3 * B * B * N / ms:.3e}")
             r[f"K{K}_step_ms"] = round(pts_ms + ms, 4)

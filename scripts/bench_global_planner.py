@@ -25,19 +25,6 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def timed(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b))
-    return float(np.median(out))
-
-
 def cpu_astar_ms(grid, pairs):
     """Median ms per query of a heap A* with the reference's priority (g + h + potential twice)."""
     import heapq
@@ -76,6 +63,7 @@ def main():
     g.build()
     import torch
     from robot_mpcs_amd import _lib
+    from robot_mpcs_amd.fleet import event_ms
     from robot_mpcs_amd.global_planner import RouteFollower, shelf_map
 
     dev = "cuda:0"
@@ -93,7 +81,7 @@ def main():
             fields = torch.empty((G, H, H), dtype=torch.float64, device=dev)
             status = torch.empty(G, dtype=torch.int32, device=dev)
             sweeps = torch.empty(G, dtype=torch.int32, device=dev)
-            ms = timed(lambda: _lib.grid_fields_device(grid, goals, fields, status, sweeps=sweeps), a.reps)
+            ms = event_ms(lambda: _lib.grid_fields_device(grid, goals, fields, status, sweeps=sweeps), a.reps)
             r[f"fields_G{G}_ms"] = round(ms, 4)
             r[f"fields_G{G}_per_s"] = round(1e3 * G / ms, 1)
             r[f"sweeps_G{G}_max"] = int(sweeps.max().item())
@@ -105,13 +93,13 @@ def main():
         max_len = 4 * (2 * H)
         path = torch.empty((Bq, max_len), dtype=torch.int32, device=dev)
         lens = torch.empty(Bq, dtype=torch.int32, device=dev)
-        r["paths_4096_ms"] = round(timed(lambda: _lib.grid_paths_device(grid, fields16, goals16, starts, gi, path, lens),
+        r["paths_4096_ms"] = round(event_ms(lambda: _lib.grid_paths_device(grid, fields16, goals16, starts, gi, path, lens),
                                          a.reps), 4)
         r["path_len_max"] = int(lens.max().item())
         f = RouteFollower(path, lens, H, -1.0, -1.0, cell)
         xinit = torch.zeros((Bq, 6), dtype=torch.float64, device=dev)
         goal = torch.zeros((Bq, 3), dtype=torch.float64, device=dev)
-        r["follow_4096_us"] = round(1e3 * timed(lambda: f.step(xinit, goal), a.reps * 5), 2)
+        r["follow_4096_us"] = round(1e3 * event_ms(lambda: f.step(xinit, goal), a.reps * 5), 2)
         pairs = [(int(s), int(goals16[int(k)].item())) for s, k in zip(starts[:32].cpu().numpy(), gi[:32].cpu().numpy())]
         r["cpu_astar_ms_per_query"] = round(cpu_astar_ms(grid.cpu().numpy(), pairs), 3)
         res[f"{H}x{H}"] = r

@@ -28,19 +28,6 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 
-def timed(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b))
-    return float(np.median(out))
-
-
 def cpu_ms_per_robot(pose, boxes, N, K, robots=8):
     """Median ms of the numpy restatement for one robot: scan, seeds, N decompositions."""
     from oracle.fsd_numpy import free_space_decomposition
@@ -64,6 +51,7 @@ def main():
     g.build()
     import torch
     from robot_mpcs_amd import _lib
+    from robot_mpcs_amd.fleet import event_ms
     from robot_mpcs_amd.global_planner import shelf_map
     from robot_mpcs_amd.utils.lidar import boxes_from_grid
 
@@ -88,15 +76,15 @@ def main():
             ef = torch.zeros(B, dtype=torch.int32, device=dev)
             pts = torch.empty((B, R, 3), dtype=torch.float64, device=dev)
             seeds = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
-            scan_ms = timed(lambda: _lib.lidar_scan_device(pose, pts, boxes), a.reps)
-            plan_ms = timed(lambda: _lib.plan_points_device(pose, seeds, z, ef), a.reps)
+            scan_ms = event_ms(lambda: _lib.lidar_scan_device(pose, pts, boxes), a.reps)
+            plan_ms = event_ms(lambda: _lib.plan_points_device(pose, seeds, z, ef), a.reps)
             r[f"B{B}_scan_ms"] = round(scan_ms, 4)
             r[f"B{B}_rays_per_s"] = round(1e3 * B * R / scan_ms)
             r[f"B{B}_box_tests_per_s"] = round(1e3 * B * R * len(boxes_np) / scan_ms)
             r[f"B{B}_plan_points_ms"] = round(plan_ms, 4)
             for K in (1, 4):
                 planes = torch.empty((B, N, K, 4), dtype=torch.float64, device=dev)
-                fsd_ms = timed(lambda: _lib.free_space_decomposition_device(pts, seeds, planes, 5.0), a.reps)
+                fsd_ms = event_ms(lambda: _lib.free_space_decomposition_device(pts, seeds, planes, 5.0), a.reps)
                 r[f"B{B}_K{K}_fsd_ms"] = round(fsd_ms, 4)
                 r[f"B{B}_K{K}_chain_ms"] = round(scan_ms + plan_ms + fsd_ms, 4)
         for K in (1, 4):

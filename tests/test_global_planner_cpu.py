@@ -276,6 +276,26 @@ def test_shelf_map_is_seeded_and_walled():
     assert np.isfinite(D[a < 0.8]).all()
 
 
+def test_pick_routes_is_seeded_and_every_line_crosses_a_shelf():
+    from robot_mpcs_amd.global_planner import cell_xy, pick_routes, png_values, shelf_map
+    raw = shelf_map(41, 41, seed=0)
+    ok = inflate_ref(png_values(raw), 0.45, 0.45)[0] < 0.8
+    starts, goals = pick_routes(raw > 0.5, ok, 256, np.random.default_rng(0), -9.0, -9.0, 0.45)
+    again = pick_routes(raw > 0.5, ok, 256, np.random.default_rng(0), -9.0, -9.0, 0.45)
+    assert np.array_equal(starts, again[0]) and np.array_equal(goals, again[1])
+    assert starts.dtype == goals.dtype == np.int32 and starts.shape == goals.shape == (256,)
+    # the fleet of seed 0 on the default store, as the store examples drew it before the function moved here
+    assert starts[:5].tolist() == [1468, 360, 1317, 1086, 1465] and goals[:5].tolist() == [1191, 1439, 86, 110, 360]
+    assert ok.ravel()[starts].all() and ok.ravel()[goals].all()
+    a, b = cell_xy(starts, 41, -9.0, -9.0, 0.45), cell_xy(goals, 41, -9.0, -9.0, 0.45)
+    assert np.array_equal(a[:, 0], -9.0 + (starts % 41) * 0.45) and np.array_equal(a[:, 1], -9.0 + (starts // 41) * 0.45)
+    d = np.linalg.norm(a - b, axis=1)
+    assert d.min() >= 10.0 and d.max() <= 20.0
+    for p, q in zip(a, b):
+        cc = np.rint((p + np.linspace(0.0, 1.0, 200)[:, None] * (q - p) + 9.0) / 0.45).astype(int)
+        assert (raw[cc[:, 1], cc[:, 0]] > 0.5).any()
+
+
 def test_png_values_reproduce_the_reference_png_round_trip(tmp_path):
     """plt.imsave -> OccupancyGridMap.from_png (what get_occupancy_map / get_enlarged_obstacles of the reference go
     through) yields png_values with the rows reversed; free cells 68/256, occupied 253/256."""

@@ -185,8 +185,7 @@ def test_mid_loop_planes_hip_vs_oracle(rt, robot):
     """Run the crossing loop 40 control steps, then solve the last state with its planes on the device and in the CPU
     oracle (parameters packed from the same scene): |du_1| <= 1e-6 and consistent exit flags."""
     from oracle.oracle import Oracle
-    from robot_mpcs_amd import _lib
-    from robot_mpcs_amd.fleet import flags_consistent
+    from robot_mpcs_amd.fleet import flags_consistent, limit_tensors, make_block, step_block
     from robot_mpcs_amd.utils.separation import NeighbourPlanes
     torch = rt["torch"]
     ex = _example()
@@ -195,26 +194,18 @@ def test_mid_loop_planes_hip_vs_oracle(rt, robot):
     rng = np.random.default_rng(1)
     base, th, goals = ex.pick(B, cfg["r_body"], rng, cfg["heading"], cfg["offset"])
     desc, setup, lim, limu = ex.model(robot, B, K, 1)
-    s = _lib.Solver(desc, max_batch=B)
-    N, nv, nx = desc["N"], s.nvar, desc["nx"]
-    xinit = np.zeros((B, nx)); xinit[:, :2] = base; xinit[:, 2] = th
-    x0 = np.repeat(np.pad(xinit, ((0, 0), (0, nv - nx)))[:, None, :], N, axis=1)
+    N = desc["N"]
+    xinit = np.zeros((B, desc["nx"])); xinit[:, :2] = base; xinit[:, 2] = th
     rad = _t(torch, np.full(B, cfg["r_body"]))
     npl = NeighbourPlanes(B, N, K, range=3.0, heading=cfg["heading"], offset=cfg["offset"], height=cfg["height"],
                           device=DEV)
-    scene = s.make_scene(setup["mpc"]["weights"], goal=_t(torch, np.pad(goals, ((0, 0), (0, 1)))), r_body=rad,
-                         lin_constrs=npl.planes, lower_limits=_t(torch, np.tile(lim[0], (B, 1))),
-                         upper_limits=_t(torch, np.tile(lim[1], (B, 1))), lower_limits_u=_t(torch, np.tile(limu[0], (B, 1))),
-                         upper_limits_u=_t(torch, np.tile(limu[1], (B, 1))))
+    f = make_block(desc, setup["mpc"]["weights"], B, xinit, DEV, goal=_t(torch, np.pad(goals, ((0, 0), (0, 1)))),
+                   r_body=rad, lin_constrs=npl.planes, **limit_tensors(lim, limu, B, DEV))
     prev = setup["mpc"]["initialization"] == "previous_plan"
-    tx, t0 = _t(torch, xinit), _t(torch, x0)
-    z = torch.zeros((B, N, nv), dtype=torch.float64, device=DEV)
-    ef = torch.zeros(B, dtype=torch.int32, device=DEV); it = torch.empty_like(ef)
-    kkt = torch.empty(B, dtype=torch.float64, device=DEV); obj = torch.empty_like(kkt)
+    s, scene, tx, t0, z, ef = f["s"], f["scene"], f["x"], f["x0"], f["z"], f["ef"]
     for step in range(40):
         npl.step(tx, rad, z if step else None, ef if step else None)
-        s.solve_scene_device(B, scene, tx, t0, z, ef, it, kkt, obj)
-        s.advance_device(B, z, tx, t0, previous_plan=prev, exitflag=ef)
+        step_block(f, prev)
     npl.step(tx, rad, z, ef)
     params = torch.empty((B, N * desc["npar"]), dtype=torch.float64, device=DEV)
     s.pack_scene_device(B, scene, params)

@@ -15,11 +15,8 @@ def rt():
     g.build()
     from oracle.oracle import Oracle
     from robot_mpcs_amd._lib import Solver
-    from robot_mpcs_amd.scenarios import (BOXER_LIMITS, BOXER_LIMITS_U, PANDA_LIMITS, PANDA_LIMITS_U, POINT_LIMITS,
-                                          POINT_LIMITS_U, make_scenario)
-    return dict(torch=torch, Oracle=Oracle, Solver=Solver, make_scenario=make_scenario,
-                limits=dict(pointRobot=(POINT_LIMITS, POINT_LIMITS_U), boxer=(BOXER_LIMITS, BOXER_LIMITS_U),
-                            panda=(PANDA_LIMITS, PANDA_LIMITS_U)))
+    from robot_mpcs_amd.scenarios import LIMITS, make_scenario
+    return dict(torch=torch, Oracle=Oracle, Solver=Solver, make_scenario=make_scenario, limits=LIMITS)
 
 
 def _scene_tensors(rt, sc):
@@ -140,26 +137,19 @@ def test_device_closed_loop_reaches_goal(rt):
     rng = np.random.default_rng(3)
     sc.xinit[:, 0:2] += rng.uniform(-0.5, 0.5, size=(B, 2))
     sc.x0[:, :, 0:6] = sc.xinit[:, None, :]
-    s = rt["Solver"](sc.desc, max_batch=B)
+    from robot_mpcs_amd.fleet import dev_f64, limit_tensors, make_block, step_block
     dev = "cuda:0"
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-    lim, limu = rt["limits"]["pointRobot"]
     obst = np.tile(np.array([[[4.0, -0.5, 0.0, 1.0]]]), (B, 1, 1))
-    scene = s.make_scene(sc.setup["mpc"]["weights"], goal=t(sc.extra["goal"]), r_body=t(np.full(B, 0.3)), obst=t(obst),
-                         lower_limits=t(np.tile(lim[0], (B, 1))), upper_limits=t(np.tile(lim[1], (B, 1))),
-                         lower_limits_u=t(np.tile(limu[0], (B, 1))), upper_limits_u=t(np.tile(limu[1], (B, 1))))
-    N, nv = sc.desc["N"], s.nvar
-    tx = t(sc.xinit); t0 = t(sc.x0)
-    z = torch.empty((B, N, nv), dtype=torch.float64, device=dev)
-    ef = torch.empty(B, dtype=torch.int32, device=dev); it = torch.empty(B, dtype=torch.int32, device=dev)
-    kkt = torch.empty(B, dtype=torch.float64, device=dev); obj = torch.empty(B, dtype=torch.float64, device=dev)
+    f = make_block(sc.desc, sc.setup["mpc"]["weights"], B, sc.xinit, dev, x0=sc.x0, goal=dev_f64(sc.extra["goal"], dev),
+                   r_body=dev_f64(np.full(B, 0.3), dev), obst=dev_f64(obst, dev),
+                   **limit_tensors(*rt["limits"]["pointRobot"], B, dev))
+    tx, ef = f["x"], f["ef"]
     goal = sc.extra["goal"][:, :2]
     d0 = np.linalg.norm(sc.xinit[:, :2] - goal, axis=1)
     min_clear = np.full(B, np.inf)
     for step in range(60):
-        s.solve_scene_device(B, scene, tx, t0, z, ef, it, kkt, obj)
-        assert int((ef < 0).sum().item()) == 0, (step, ef.cpu().numpy())
-        s.advance_device(B, z, tx, t0, previous_plan=False)
+        step_block(f, previous_plan=False, flags=False)
+        assert int((ef < 0).sum().item()) == 0, (step, ef.cpu().numpy())   # (the advance does not write the flags)
         if step % 4 == 0:
             x = tx.cpu().numpy()
             c = np.linalg.norm(np.stack([x[:, 0] - 4.0, x[:, 1] + 0.5, np.full(B, 0.05)], 1), axis=1) - 1.0 - 0.3
@@ -168,7 +158,7 @@ def test_device_closed_loop_reaches_goal(rt):
     x = tx.cpu().numpy()
     d1 = np.linalg.norm(x[:, :2] - goal, axis=1)
     assert np.all(d1 < d0 - 3.0) and min_clear.min() > -1e-6
-    s.close()
+    f["s"].close()
 
 
 def test_free_space_decomposition_matches_reference_restatement(rt):

@@ -192,6 +192,31 @@ def test_closed_loop_golden_trace_reproduces_from_oracle(oracle_lib):
 # ---------------------------------------------------------------------------------------------------
 # tooling parity: makeSolver argv contract, ROS-style YAML, set_mpc_parameter dispatcher
 # ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [0, 1, 256])
+def test_arrivals_summary_gives_the_examples_quantiles(n):
+    """fleet.Arrivals against the expression the closed-loop examples carried, on hand-made first-arrival steps; a robot
+    counts at the first control step it is seen at its goal and keeps that step while it stays there."""
+    import torch
+    from robot_mpcs_amd.fleet import Arrivals
+    B = 300
+    rng = np.random.default_rng(n)
+    arrived = np.full(B, -1, dtype=np.int64)
+    arrived[rng.permutation(B)[:n]] = rng.integers(1, 1201, n)
+    arr = Arrivals(B, "cpu")
+    for k in np.unique(arrived[arrived > 0]):
+        arr.update(torch.from_numpy((arrived > 0) & (arrived <= k)), int(k) - 1)
+    assert np.array_equal(arr.step.numpy(), arrived)
+    done = np.sort(arrived[arrived > 0])
+    q = lambda p: int(done[min(len(done) - 1, int(np.ceil(p * len(done))) - 1)]) if len(done) else None
+    assert arr.summary() == dict(arrivals=n, arrival_share=n / B, arrival_step_p50=q(0.5), arrival_step_p90=q(0.9),
+                                 arrival_step_max=q(1.0))
+    assert list(arr.summary()) == ["arrivals", "arrival_share", "arrival_step_p50", "arrival_step_p90", "arrival_step_max"]
+    if n == 0:
+        assert arr.summary()["arrival_step_p50"] is None
+    if n == 256:
+        assert arr.summary()["arrival_step_max"] == arrived.max() and arr.summary()["arrival_step_p50"] == done[127]
+
+
 def _load_make_solver():
     import importlib.util
     path = os.path.join(os.path.dirname(CONFIG_DIR), "makeSolver.py")
