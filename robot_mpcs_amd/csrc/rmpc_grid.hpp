@@ -1,5 +1,5 @@
 // rmpc_grid.hpp -- the global planner on the device (robotmpcs/global_planner/: occupancy map -> enlarged obstacles
-// -> 8-connected shortest path -> waypoint follower), included by rmpc_host.hip.  Grids are [H][W] doubles, row-major,
+// -> 8-connected shortest path -> waypoint follower), included by rmpc_world.hip.  Grids are [H][W] doubles, row-major,
 // cell c = row * W + col; the plain frame puts the centre of (row, col) at (x0 + col * cell, y0 + row * cell).
 //
 // The field kernel builds one cost-to-go field per goal, D(goal) = 0, D(u) = min_v (delta(u, v) + E(v)) with

@@ -1,475 +1,14 @@
-// rmpc_host.hip -- the host side of the library (handle, descriptor checks, row tables, generated-view matching,
-// workspace carving, the launch loop, the C ABI) and the kernels that do not depend on a kernel variant.  It reaches
-// the kernels of a variant through the handle's entry of the variant table (VariantOps, rmpc_host.hpp), which the
-// units built from rmpc_variants.hip fill while the library loads.
+// rmpc_host.hip -- the host unit: the handle and everything that takes one (variant lookup, generated-view
+// matching, workspace carving, profiling, the launch loop, the solver entries of the C ABI, setters, debug and test
+// aids).  The descriptor checks and row tables are in rmpc_desc.hpp, the kernels that do not depend on a kernel
+// variant in rmpc_batch.hpp, the entries without a handle (planner, lidar, fleet planes, ...) in rmpc_world.hip.  It
+// reaches the kernels of a variant through the handle's entry of the variant table (VariantOps, rmpc_host.hpp), which
+// the units built from rmpc_variants.hip fill while the library loads.
 #include "rmpc_host.hpp"
+#include "rmpc_desc.hpp"
+#include "rmpc_batch.hpp"
 
-namespace rmpc {
-
-// ===========================================================================
-// pack / unpack: instance-major ABI layout <-> batch-minor SoA (LDS transpose)
-// ===========================================================================
-// in[b][c], c = k*inner + j  ->  out[(j*N + k)*Bp + b]
-__global__ __launch_bounds__(256) void k_pack(const double *__restrict__ in, double *__restrict__ out, int B,
-                                              int C, int inner, int N, int Bp) {
-  __shared__ double tile[64][65];
-  const int b0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  // unconditional requests with clamped indices, all issued before the first LDS store (a branch around a
-  // load makes the compiler wait for each element separately)
-  double v[16];
-#pragma unroll
-  for (int u = 0; u < 16; u++) {
-    const int r = ty + 4 * u;
-    const int b = b0 + r < B ? b0 + r : B - 1, c = c0 + tx < C ? c0 + tx : C - 1;
-    v[u] = in[(size_t)b * C + c];
-  }
-#pragma unroll
-  for (int u = 0; u < 16; u++) tile[ty + 4 * u][tx] = v[u];
-  __syncthreads();
-  for (int r = ty; r < 64; r += 4) {
-    int c = c0 + r, b = b0 + tx;
-    if (c < C && b < B) {
-      int k = c / inner, j = c - k * inner;
-      out[((size_t)j * N + k) * Bp + b] = tile[tx][r];
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void k_init(Ws W, const double *__restrict__ xinit, int B, int nx, double mu0, int warm) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  for (int j = 0; j < nx; j++) W.z[0][IDX(j, 0, b)] = xinit[(size_t)b * nx + j];
-  W.status[b] = ST_ACTIVE;
-  W.act_idx[b] = b;
-  if (b == 0) *W.n_act = B;
-  W.iters[b] = 0;
-  W.ls[b] = 0;
-  W.cur[b] = 0;
-  W.newstep[b] = 0;
-  W.amin_p[b] = (unsigned long long)__double_as_longlong(1.0);
-  W.amin_d[b] = (unsigned long long)__double_as_longlong(1.0);
-  W.redo[b] = 0; W.force_gn[b] = 0; W.gn_sticky[b] = 0; W.curv_fail[b] = 0; W.usedc[b] = 0; W.stall[b] = 0;
-  W.curv_skip[b] = 0; W.curv_back[b] = 0;
-  W.small_steps[b] = 0; W.mu_hold[b] = 0.0;
-  W.theta_mem[b] = 1.0; W.theta_c[b] = 1.0; W.theta_clean[b] = 0; W.theta_retry[b] = 0;
-  W.ls0[b] = 0; W.lsst[b] = 0;
-  W.mu[b] = warm ? warm_mu(W.wmu[b], mu0) : mu0;
-  W.rho[b] = 0.0;
-  W.phi0[b] = 0.0;
-  W.Dd[b] = 0.0;
-  W.fcur[b] = 0.0;
-  W.thcur[b] = 0.0;
-  W.logcur[b] = 0.0;
-  W.res_stat[b] = 0.0; W.res_eq[b] = 0.0; W.res_ineq[b] = 0.0; W.res_comp[b] = 0.0; W.obj[b] = 0.0;
-}
-
-// z (current buffer of each instance) -> z_out[b][k][v]; stats
-__global__ __launch_bounds__(256) void k_unpack(Ws W, double *__restrict__ zout, int *__restrict__ exitflag,
-                                                int *__restrict__ iters, double *__restrict__ kkt,
-                                                double *__restrict__ obj, int B, int nv,
-                                                const int *__restrict__ orig) {
-  // orig != nullptr: W is the compact workspace, column b belongs to instance orig[b] of the batch
-  __shared__ double tile[64][65];
-  const int N = W.N;
-  const int C = N * nv;
-  const int b0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  {
-    const int b = b0 + tx < B ? b0 + tx : B - 1;   // clamped: the requests stay unconditional
-    const double *__restrict__ zb = W.z[W.cur[b]];
-    double v[16];
-#pragma unroll
-    for (int u = 0; u < 16; u++) {
-      const int c = c0 + ty + 4 * u < C ? c0 + ty + 4 * u : C - 1;
-      const int k = c / nv, j = c - k * nv;
-      v[u] = zb[IDX(j, k, b)];
-    }
-#pragma unroll
-    for (int u = 0; u < 16; u++) tile[ty + 4 * u][tx] = v[u];
-  }
-  __syncthreads();
-  for (int r = ty; r < 64; r += 4) {
-    int b = b0 + r, c = c0 + tx;
-    if (b < B && c < C) zout[(size_t)(orig ? orig[b] : b) * C + c] = tile[tx][r];
-  }
-  if (blockIdx.y == 0 && threadIdx.x < 64) {
-    int b = b0 + threadIdx.x;
-    if (b < B) {
-      const int ob = orig ? orig[b] : b;
-      int st = W.status[b];
-      exitflag[ob] = (st == ST_ACTIVE) ? 0 : st;
-      iters[ob] = W.iters[b];
-      double r = fmax(fmax(W.res_stat[b], W.res_eq[b]), fmax(W.res_ineq[b], W.res_comp[b]));
-      kkt[ob] = r;
-      obj[ob] = W.obj[b];
-    }
-  }
-}
-
-// Multipliers of the finished solve -> the warm-start arrays of the batch's workspace D (W may be the compact
-// workspace: column b then belongs to instance orig[b]).  One lane per (column, stage).
-// d[j * ds] = s[j * ss], j < cnt, eight requests in flight (source and destination never alias: the copies below are
-// chains of dependent latencies otherwise -- 50 us for the arm's multipliers, 105 us for a migration of 128 instances)
-__device__ __forceinline__ void copy_strided(double *__restrict__ d, const double *__restrict__ s, const int cnt, const size_t ds,
-                                             const size_t ss) {
-  int j = 0;
-  for (; j + 8 <= cnt; j += 8) {
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) v[u] = s[(size_t)(j + u) * ss];
-#pragma unroll
-    for (int u = 0; u < 8; u++) d[(size_t)(j + u) * ds] = v[u];
-  }
-  for (; j < cnt; j++) d[(size_t)j * ds] = s[(size_t)j * ss];
-}
-__device__ __forceinline__ void fill_strided(double *__restrict__ d, const double val, const int cnt, const size_t ds) {
-  for (int j = 0; j < cnt; j++) d[(size_t)j * ds] = val;
-}
-
-__global__ __launch_bounds__(256) void k_save_duals(const Ws W, const Ws D, int B, int m, int nx, const int *__restrict__ orig,
-                                                    double mu0) {
-  const int gid = blockIdx.x * 256 + threadIdx.x;
-  const int b = gid % W.Bp, k = gid / W.Bp;
-  if (b >= B || k >= W.N) return;
-  const int cur = W.cur[b];
-  const int ob = orig ? orig[b] : b;
-  // a failed solve leaves nothing to start from: zero multipliers and mu0 (the warm start then degenerates to
-  // lambda = mu0 / t, nu = 0)
-  const int st = W.status[b];
-  const double mu = W.mu[b];
-  const bool ok = (st == ST_ACTIVE || st >= 0) && isfinite(mu) && mu > 0.0;
-  double *const dl = D.wlam + (size_t)k * D.Bp + ob, *const dn = D.wnu + (size_t)k * D.Bp + ob;
-  const size_t ds = (size_t)D.N * D.Bp, ss = (size_t)W.N * W.Bp;
-  if (ok) {
-    copy_strided(dl, W.lam[cur] + (size_t)k * W.Bp + b, m, ds, ss);
-    copy_strided(dn, W.nu[cur] + (size_t)k * W.Bp + b, nx, ds, ss);
-  } else {
-    fill_strided(dl, 0.0, m, ds);
-    fill_strided(dn, 0.0, nx, ds);
-  }
-  if (k == 0) D.wmu[ob] = ok ? mu : mu0;
-}
-
-// ===========================================================================
-// k_compact: ordered list of the instances that are still iterating.  All pass
-// kernels index their lanes through it, so wavefronts beyond the list exit at
-// once and the passes of the iteration tail touch a few wavefronts only.
-// ===========================================================================
-__global__ __launch_bounds__(1024) void k_compact(Ws W, int B, int pass) {
-  __shared__ int sums[1024];
-  const int tid = threadIdx.x;
-  // (passes enqueued without a host look, rmpc_set_pass_budget: once nothing iterates any more the remaining passes
-  //  are empty launches -- this one too; active_hist was zeroed before the solve)
-  if (pass > 0 && *W.n_act == 0) return;
-  const int per = (B + 1023) / 1024;
-  const int lo = tid * per, hi = (lo + per < B) ? lo + per : B;
-  int cnt = 0;
-  for (int b = lo; b < hi; b++) cnt += (W.status[b] == ST_ACTIVE);
-  sums[tid] = cnt;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int v = (tid >= off) ? sums[tid - off] : 0;
-    __syncthreads();
-    sums[tid] += v;
-    __syncthreads();
-  }
-  const int total = sums[1023];
-  // while most instances are still iterating the identity list keeps every access coalesced
-  const bool dense = (total * kDenseDiv > B);
-  int base = dense ? lo : sums[tid] - cnt;
-  for (int b = lo; b < hi; b++)
-    if (dense || W.status[b] == ST_ACTIVE) W.act_idx[base++] = b;
-  if (tid == 1023) {
-    *W.n_act = dense ? B : total;
-    W.active_hist[pass] = total;
-  }
-}
-
-// The same list from ONE wavefront (batches up to kCompactWaveMax instances).  With other handles' kernels on the chip
-// every SIMD holds a long-lived 512-register wavefront, and the 16-wavefront block above waits until a whole compute
-// unit has drained: in a trace of four arm batches in flight k_compact took 25 us on average (p90 93 us) for 5 us of
-// work -- once per pass, on the critical path of its stream.  A single wavefront takes the first SIMD that frees.
-// 64 instances per round (one coalesced request, ballot + popcount instead of a scan), eight rounds in flight.
-constexpr int kCompactWaveMax = 8192;
-__global__ __launch_bounds__(64) void k_compact_wave(Ws W, int B, int pass) {
-  const int lane = threadIdx.x;
-  if (pass > 0 && *W.n_act == 0) return;
-  const int rounds = (B + 63) / 64;
-  int total = 0;
-  for (int r0 = 0; r0 < rounds; r0 += 8) {
-    int st[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      const int b = (r0 + u) * 64 + lane;
-      st[u] = W.status[b < B ? b : B - 1];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      const int b = (r0 + u) * 64 + lane;
-      total += __popcll(__ballot(b < B && st[u] == ST_ACTIVE));
-    }
-  }
-  const bool dense = (total * kDenseDiv > B);
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int base = 0;
-  for (int r0 = 0; r0 < rounds; r0 += 8) {
-    int st[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      const int b = (r0 + u) * 64 + lane;
-      st[u] = W.status[b < B ? b : B - 1];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      const int b = (r0 + u) * 64 + lane;
-      const bool on = b < B && (dense || st[u] == ST_ACTIVE);
-      const unsigned long long mk = __ballot(on);
-      if (on) W.act_idx[base + __popcll(mk & below)] = b;
-      base += __popcll(mk);
-    }
-  }
-  if (lane == 0) {
-    *W.n_act = dense ? B : total;
-    W.active_hist[pass] = total;
-  }
-}
-
-// ===========================================================================
-// k_migrate: once few instances are left their whole iteration state moves to the
-// dense columns 0..n-1 of a small second workspace.  Indexing scattered survivors
-// through the list costs a 64-byte sector per 8-byte element (every pass then moves
-// as many bytes as a full batch); one gather of that kind pays for itself in the
-// next pass.  Runs between k_step and the next k_sweep: what crosses that boundary
-// is the current iterate, the step, the parameters and the per-instance words.
-// ===========================================================================
-__global__ __launch_bounds__(64) void k_migrate(const Ws S, const Ws D, int n, int nv, int m, int nx, int npar, int nh,
-                                                int njq) {
-  const int li = blockIdx.x * 64 + threadIdx.x, k = blockIdx.y;
-  if (li >= n) return;
-  const int b = S.act_idx[li];
-  const int cur = S.cur[b];
-  auto si = [&](int slot) { return ((size_t)slot * S.N + k) * S.Bp + b; };
-  auto di = [&](int slot) { return ((size_t)slot * D.N + k) * D.Bp + li; };
-  {
-    const size_t ds = (size_t)D.N * D.Bp, ss = (size_t)S.N * S.Bp, d0 = di(0), s0 = si(0);
-    copy_strided(D.z[0] + d0, S.z[cur] + s0, nv, ds, ss);
-    copy_strided(D.dz + d0, S.dz + s0, nv, ds, ss);
-    copy_strided(D.t[0] + d0, S.t[cur] + s0, m, ds, ss);
-    copy_strided(D.lam[0] + d0, S.lam[cur] + s0, m, ds, ss);
-    copy_strided(D.grow[0] + d0, S.grow[cur] + s0, nh, ds, ss);
-    copy_strided(D.Jq[0] + d0, S.Jq[cur] + s0, njq, ds, ss);
-    copy_strided(D.nu[0] + d0, S.nu[cur] + s0, nx, ds, ss);
-    copy_strided(D.nunew + d0, S.nunew + s0, nx, ds, ss);
-    copy_strided(D.p + d0, S.p + s0, npar, ds, ss);
-  }
-  D.gphi[di(0)] = S.gphi[si(0)];
-  if (k == 0) {
-    D.amin_p[li] = S.amin_p[b]; D.amin_d[li] = S.amin_d[b];
-    D.mu[li] = S.mu[b]; D.rho[li] = S.rho[b]; D.phi0[li] = S.phi0[b]; D.Dd[li] = S.Dd[b];
-    D.fcur[li] = S.fcur[b]; D.thcur[li] = S.thcur[b]; D.logcur[li] = S.logcur[b];
-    D.res_stat[li] = S.res_stat[b]; D.res_eq[li] = S.res_eq[b]; D.res_ineq[li] = S.res_ineq[b];
-    D.res_comp[li] = S.res_comp[b]; D.obj[li] = S.obj[b];
-    D.status[li] = S.status[b]; D.iters[li] = S.iters[b]; D.ls[li] = S.ls[b]; D.newstep[li] = S.newstep[b];
-    D.redo[li] = S.redo[b]; D.force_gn[li] = S.force_gn[b]; D.gn_sticky[li] = S.gn_sticky[b];
-    D.curv_fail[li] = S.curv_fail[b]; D.usedc[li] = S.usedc[b]; D.stall[li] = S.stall[b];
-    D.curv_skip[li] = S.curv_skip[b]; D.curv_back[li] = S.curv_back[b];
-    D.small_steps[li] = S.small_steps[b]; D.mu_hold[li] = S.mu_hold[b];
-    D.theta_mem[li] = S.theta_mem[b]; D.theta_c[li] = S.theta_c[b]; D.theta_clean[li] = S.theta_clean[b]; D.theta_retry[li] = S.theta_retry[b];
-    D.ls0[li] = S.ls0[b]; D.lsst[li] = S.lsst[b];
-    D.cur[li] = 0;
-    D.orig[li] = b;
-    D.act_idx[li] = li;
-    if (li == 0) *D.n_act = n;
-  }
-}
-
-// Launch order of a fused launch: the instances sorted by a key (the passes of their previous solve for a warm start,
-// k_difficulty's estimate for a cold one), largest first (counting sort, one block; the order inside a bucket is
-// whatever the atomics give -- it changes which instances share a wavefront, never what an instance computes).
-// (NT = 64 for the order of a cold launch, which runs IN FRONT of the fused launch: with other handles' fused launches
-//  on the chip every SIMD is held by one long-lived 512-register wavefront, and a block of several wavefronts would
-//  wait until a whole compute unit has drained; a single wavefront takes the first SIMD that frees)
-template <int NT>
-static __global__ __launch_bounds__(NT) void k_order_t(const int *__restrict__ key, int *__restrict__ order, int B) {
-  __shared__ int cnt[256];
-  const int tid = threadIdx.x;
-  for (int i = tid; i < 256; i += NT) cnt[i] = 0;
-  __syncthreads();
-  // (eight keys per lane and round: the requests of a round are in flight together -- one by one the single
-  //  wavefront of the cold order spent 33 us on 4096 keys, most of it waiting for one key at a time)
-  constexpr int U = 8;
-  for (int b0 = tid; b0 < B; b0 += NT * U) {
-    int kq[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) { const int b = b0 + u * NT; kq[u] = key[b < B ? b : B - 1]; }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int kk = kq[u] < 0 ? 0 : (kq[u] > 255 ? 255 : kq[u]);
-      if (b0 + u * NT < B) atomicAdd(&cnt[255 - kk], 1);
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int i = 0; i < 256; i++) { const int c = cnt[i]; cnt[i] = run; run += c; }
-  }
-  __syncthreads();
-  for (int b0 = tid; b0 < B; b0 += NT * U) {
-    int kq[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) { const int b = b0 + u * NT; kq[u] = key[b < B ? b : B - 1]; }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int kk = kq[u] < 0 ? 0 : (kq[u] > 255 ? 255 : kq[u]);
-      if (b0 + u * NT < B) order[atomicAdd(&cnt[255 - kk], 1)] = b0 + u * NT;
-    }
-  }
-}
-
-struct SceneDev {
-  const double *goal, *r_body, *obst, *obst_dyn, *lower, *upper, *lower_u, *upper_u, *lower_vel, *upper_vel, *lin;
-  double dyn_radius, w, wu, ws;
-  double wconstr[RMPC_MAX_MODULES];
-};
-struct SceneOff {
-  int r_body, obst, lin, lower, upper, lower_u, upper_u, lower_vel, upper_vel, wu, goal, wgoal, wconstr, ws;
-  int n, nu, nobst, n_modules, npar, N;
-  double dt;
-};
-
-// One lane per (instance, stage).  SOA = 0: ABI layout params[b][k][npar] (what
-// MPCPlanner.reset() + set*() + updateDynamicObstacles() produce, mpcPlanner.py:83-210);
-// SOA = 1: straight into the pass kernels' batch-minor parameter array; SOA = 2: into the fused kernel's
-// per-instance layout.
-template <int SOA>
-__global__ __launch_bounds__(256) void k_scene(const SceneDev S, const SceneOff O, double *__restrict__ out, int B, int Bp) {
-#pragma clang fp contract(off)
-  const int gid = blockIdx.x * 256 + threadIdx.x;
-  int b, k;
-  if (SOA == 1) { b = gid % Bp; k = gid / Bp; } else { k = gid % O.N; b = gid / O.N; }
-  if (b >= B || k >= O.N) return;
-  auto put = [&](int off, double v) __attribute__((always_inline)) {
-    if (SOA == 1) out[((size_t)off * O.N + k) * Bp + b] = v;
-    else if (SOA == 2) out[((size_t)b * O.npar + off) * kFusedStages + k] = v;   // fused kernel: [instance][slot][32 stages]
-    else out[((size_t)b * O.N + k) * O.npar + off] = v;
-  };
-  // reset(): zeros, then the broadcast weights (mpcPlanner.py:91-104)
-  for (int j = 0; j < O.npar; j++) put(j, 0.0);
-  if (O.wgoal >= 0) for (int j = 0; j < 3; j++) put(O.wgoal + j, S.w);
-  for (int j = 0; j < O.nu; j++) put(O.wu + j, S.wu);
-  if (O.ws >= 0) put(O.ws, S.ws);
-  if (O.wconstr >= 0) for (int j = 0; j < O.n_modules; j++) put(O.wconstr + j, S.wconstr[j]);
-  if (O.goal >= 0 && S.goal) for (int j = 0; j < 3; j++) put(O.goal + j, S.goal[(size_t)b * 3 + j]);
-  if (O.r_body >= 0 && S.r_body) put(O.r_body, S.r_body[b]);
-  if (O.obst >= 0) {
-    if (S.obst_dyn) {
-      // updateDynamicObstacles (mpcPlanner.py:144-161): c = pos + (vel*dt)*k + (0.5*(dt*k)^2)*acc
-      const double kk = (double)k;
-      for (int j = 0; j < O.nobst; j++) {
-        const double *o = S.obst_dyn + ((size_t)b * O.nobst + j) * 9;
-        for (int c = 0; c < 3; c++) {
-          // every product and sum rounded separately (fp contraction is switched off for this
-          // kernel): bit-identical to the reference's numpy expression pos + vel*dt*i + 0.5*(dt*i)**2*acc
-          const double tk = O.dt * kk;
-          const double lin = (o[3 + c] * O.dt) * kk;
-          const double quad = (0.5 * (tk * tk)) * o[6 + c];
-          put(O.obst + 4 * j + c, (o[c] + lin) + quad);
-        }
-        put(O.obst + 4 * j + 3, S.dyn_radius);
-      }
-    } else if (S.obst) {
-      for (int j = 0; j < 4 * O.nobst; j++) put(O.obst + j, S.obst[(size_t)b * 4 * O.nobst + j]);
-    } else {
-      // no obstacles given: every slot is the reference's EmptyObstacle (position -100, radius -100;
-      // mpcPlanner.py:18-26,127-133), as the host packer writes
-      for (int j = 0; j < 4 * O.nobst; j++) put(O.obst + j, -100.0);
-    }
-  }
-  if (O.lin >= 0 && S.lin)
-    for (int j = 0; j < 4 * O.nobst; j++) put(O.lin + j, S.lin[((size_t)b * O.N + k) * 4 * O.nobst + j]);
-  if (O.lower >= 0 && S.lower) for (int j = 0; j < O.n; j++) put(O.lower + j, S.lower[(size_t)b * O.n + j]);
-  if (O.upper >= 0 && S.upper) for (int j = 0; j < O.n; j++) put(O.upper + j, S.upper[(size_t)b * O.n + j]);
-  if (O.lower_u >= 0 && S.lower_u) for (int j = 0; j < O.nu; j++) put(O.lower_u + j, S.lower_u[(size_t)b * O.nu + j]);
-  if (O.upper_u >= 0 && S.upper_u) for (int j = 0; j < O.nu; j++) put(O.upper_u + j, S.upper_u[(size_t)b * O.nu + j]);
-  if (O.lower_vel >= 0 && S.lower_vel) for (int j = 0; j < 2; j++) put(O.lower_vel + j, S.lower_vel[(size_t)b * 2 + j]);
-  if (O.upper_vel >= 0 && S.upper_vel) for (int j = 0; j < 2; j++) put(O.upper_vel + j, S.upper_vel[(size_t)b * 2 + j]);
-}
-
-// The environment of the moving obstacles between two control steps (what the examples' simulator does before the driver
-// hands the planner ob[nx:], mpcPlanner.py:243-244): pos += vel dt + acc dt^2 / 2, vel += acc dt, one lane per
-// (instance, obstacle); arena > 0: an obstacle that leaves [-arena, arena] in x or y comes back (velocity component
-// mirrored), so that a loop that runs for hours keeps its obstacles.
-static __global__ __launch_bounds__(256) void k_obst_advance(double *__restrict__ od, int n, double dt, double arena) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  double *o = od + (size_t)i * 9;
-  for (int c = 0; c < 3; c++) {
-    double pos = o[c] + o[3 + c] * dt + 0.5 * o[6 + c] * dt * dt;
-    double vel = o[3 + c] + o[6 + c] * dt;
-    if (arena > 0.0 && c < 2) {
-      if (pos > arena) { pos = 2.0 * arena - pos; vel = -vel; }
-      else if (pos < -arena) { pos = -2.0 * arena - pos; vel = -vel; }
-    }
-    o[c] = pos; o[3 + c] = vel;
-  }
-}
-
-// ===========================================================================
-// Free-space decomposition: lidar point cloud -> at most K half-planes
-// around a seed point, one lane per (instance, stage) seed.  Greedy rule of the reference
-// (robotmpcs/utils/free_space_decomposition.py:79-97): the closest remaining point inside
-// max_radius defines the plane through it with normal (seed - point); points on or behind the
-// plane are discarded; unused slots get the dummy plane of asdict() (:110-114).  The sort of
-// the reference is replaced by K arg-min sweeps over a keep-mask (P <= 64 points).
-// ===========================================================================
-__global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, const double *__restrict__ seeds,
-                                             double *__restrict__ out, int B, int N, int P, int K, double max_radius) {
-#pragma clang fp contract(off)
-  const int gid = blockIdx.x * 256 + threadIdx.x;
-  if (gid >= B * N) return;
-  const int b = gid / N;
-  const double *pc = points + (size_t)b * P * 3;
-  const double s0 = seeds[(size_t)gid * 3], s1 = seeds[(size_t)gid * 3 + 1], s2 = seeds[(size_t)gid * 3 + 2];
-  double *o = out + (size_t)gid * K * 4;
-  unsigned long long keep = 0ull;
-  for (int i = 0; i < P; i++) {
-    const double d0 = pc[3 * i] - s0, d1 = pc[3 * i + 1] - s1, d2 = pc[3 * i + 2] - s2;
-    if (sqrt(d0 * d0 + d1 * d1 + d2 * d2) < max_radius) keep |= (1ull << i);
-  }
-  int nc = 0;
-  while (keep && nc < K) {
-    int best = -1;
-    double bd = 0.0;
-    for (int i = 0; i < P; i++)
-      if (keep & (1ull << i)) {
-        const double d0 = pc[3 * i] - s0, d1 = pc[3 * i + 1] - s1, d2 = pc[3 * i + 2] - s2;
-        const double dd = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-        if (best < 0 || dd < bd) { best = i; bd = dd; }
-      }
-    const double p0 = pc[3 * best], p1 = pc[3 * best + 1], p2 = pc[3 * best + 2];
-    const double n0 = s0 - p0, n1 = s1 - p1, n2 = s2 - p2;
-    const double c = -((n0 * p0 + n1 * p1) + n2 * p2);
-    o[4 * nc] = n0; o[4 * nc + 1] = n1; o[4 * nc + 2] = n2; o[4 * nc + 3] = c;
-    nc++;
-    for (int i = 0; i < P; i++)
-      if (keep & (1ull << i)) {
-        const double v = ((n0 * pc[3 * i] + n1 * pc[3 * i + 1]) + n2 * pc[3 * i + 2]) + c;
-        if (v <= 0.0) keep &= ~(1ull << i);
-      }
-  }
-  for (; nc < K; nc++) {
-    // HalfPlane(seed + (20, 20, 0), seed): normal = seed - point
-    const double p0 = s0 + 20.0, p1 = s1 + 20.0, p2 = s2 + 0.0;
-    const double n0 = s0 - p0, n1 = s1 - p1, n2 = s2 - p2;
-    o[4 * nc] = n0; o[4 * nc + 1] = n1; o[4 * nc + 2] = n2; o[4 * nc + 3] = -((n0 * p0 + n1 * p1) + n2 * p2);
-  }
-}
-
-}  // namespace rmpc
-
-#include "rmpc_grid.hpp"
-#include "rmpc_sense.hpp"
+static_assert(kDescLsMax == kLsMax, "rmpc_desc.hpp: the default of rmpc_desc.ls_max is the solver's kLsMax");
 
 // ===========================================================================
 // host side: handle, workspace, launch loop, C ABI
@@ -504,346 +43,6 @@ static std::string variant_list() {
       s += (s.empty() ? "" : ", ") + (v.robot == RMPC_ROBOT_CHAIN ? "holonomic chain n = " + std::to_string(v.nq) : std::string("diff-drive base")) +
            (v.ns ? " with the slack variable" : "");
   return s;
-}
-
-// Row tables in device memory (DevTables): kinematic slots with their FK rows, and the
-// single-variable rows grouped by variable.
-static int build_tables(const rmpc_desc &d, const DevModel &M, DevTables &T, std::string &err) {
-  memset(&T, 0, sizeof T);
-  for (int s = 0; s < kMaxSlots; s++) { T.slot_fa[s] = -1; T.slot_fb[s] = -1; }
-  for (int j = 0; j < RMPC_NV_MAX; j++)
-    for (int u = 0; u < kVarRows; u++) { T.v_row[j][u] = -1; T.v_poff[j][u] = -1; T.v_mod[j][u] = -1; }
-  auto slot_of = [&](int fa, int fb) -> int {
-    for (int s = 0; s < T.nslots; s++)
-      if (T.slot_fa[s] == fa && T.slot_fb[s] == fb) return s;
-    if (T.nslots >= kMaxSlots) return -1;
-    T.slot_fa[T.nslots] = fa; T.slot_fb[T.nslots] = fb;
-    return T.nslots++;
-  };
-  if (d.has_goal && slot_of(d.end_frame, -1) != 0) { err = "slot table"; return -1; }
-  // FK rows with their slots, then sorted by slot
-  struct FkRow { int row, kind, obst, mod, first, idx, slot; };
-  std::vector<FkRow> rows;
-  for (int i = 0; i < M.nh; i++) {
-    if (M.row_kind[i] == ROW_SINGLE) continue;
-    const int fb = (M.row_kind[i] == ROW_SELF) ? M.row_b[i] : -1;
-    const int s = slot_of(M.row_a[i], fb);
-    if (s < 0) { err = "more than 4 distinct collision points (links / link pairs / end link)"; return -1; }
-    rows.push_back({i, M.row_kind[i], M.row_kind[i] == ROW_SELF ? 0 : M.row_b[i], M.row_mod[i],
-                    i == M.mod_row0[M.row_mod[i]] ? 1 : 0, M.row_fk[i], s});
-  }
-  if ((int)rows.size() > kMaxFkRows) { err = "too many distance rows"; return -1; }
-  int r = 0;
-  for (int s = 0; s < kMaxSlots; s++) {
-    T.slot_row_begin[s] = r;
-    for (const FkRow &fr : rows)
-      if (fr.slot == s) {
-        T.fk_row[r] = fr.row; T.fk_kind[r] = fr.kind; T.fk_obst[r] = fr.obst;
-        T.fk_mod[r] = fr.mod; T.fk_first[r] = fr.first; T.fk_idx[r] = fr.idx;
-        r++;
-      }
-  }
-  T.slot_row_begin[kMaxSlots] = r;
-  T.nfkrows = r;
-  // single-variable rows
-  auto add_var_row = [&](int var, int row, int sgn, int poff, double val, int soft, int mod, int firstrow) -> bool {
-    for (int u = 0; u < kVarRows; u++)
-      if (T.v_row[var][u] < 0) {
-        T.v_row[var][u] = row; T.v_sgn[var][u] = sgn; T.v_poff[var][u] = poff;
-        T.v_val[var][u] = val; T.v_soft[var][u] = soft; T.v_mod[var][u] = mod;
-        T.v_first[var][u] = firstrow;
-        return true;
-      }
-    return false;
-  };
-  bool ok = true;
-  for (int i = 0; i < M.nh && ok; i++)
-    if (M.row_kind[i] == ROW_SINGLE)
-      ok = add_var_row(M.row_a[i], i, M.row_b[i], M.row_poff[i], 0.0, 1, M.row_mod[i], i == M.mod_row0[M.row_mod[i]] ? 1 : 0);
-  int i = M.nh;
-  for (int q = 0; q < M.nlb && ok; q++, i++) ok = add_var_row(M.lb_var[q], i, +1, -1, M.lb_val[q], 0, -1, 0);
-  for (int q = 0; q < M.nub && ok; q++, i++) ok = add_var_row(M.ub_var[q], i, -1, -1, M.ub_val[q], 0, -1, 0);
-  if (!ok) { err = "more than 4 limit / bound rows on one variable"; return -1; }
-  // packed copies (fused arm kernel)
-  for (int j = 0; j < RMPC_NV_MAX; j++)
-    for (int u = 0; u < kVarRows; u++) {
-      int w = 0;
-      if (T.v_row[j][u] >= 0 && T.v_row[j][u] < 256 && T.v_poff[j][u] < 65536) {
-        w = T.v_row[j][u] | (1 << 8) | ((T.v_sgn[j][u] < 0 ? 1 : 0) << 9) | ((T.v_first[j][u] ? 1 : 0) << 10) |
-            ((T.v_poff[j][u] >= 0 ? 1 : 0) << 11) | ((T.v_mod[j][u] >= 0 ? T.v_mod[j][u] & 7 : 0) << 12) |
-            ((T.v_poff[j][u] >= 0 ? T.v_poff[j][u] : 0) << 16);
-      }
-      T.v_desc[j][u] = w;
-    }
-  for (int q = 0; q < T.nfkrows; q++)
-    T.fk_desc[q] = (T.fk_row[q] & 255) | ((T.fk_kind[q] & 3) << 8) | ((T.fk_obst[q] & 63) << 10) | ((T.fk_mod[q] & 7) << 16) |
-                   ((T.fk_first[q] ? 1 : 0) << 19) | ((T.fk_idx[q] & 63) << 20);
-  T.slot_rows_max = 0;
-  for (int s = 0; s < kMaxSlots; s++)
-    if (T.slot_row_begin[s + 1] - T.slot_row_begin[s] > T.slot_rows_max) T.slot_rows_max = T.slot_row_begin[s + 1] - T.slot_row_begin[s];
-  return 0;
-}
-
-static int build_model(const rmpc_desc &d, DevModel &M, std::string &err) {
-  memset(&M, 0, sizeof M);
-  M.robot = d.robot; M.N = d.N; M.n = d.n; M.nx = d.nx; M.nu = d.nu; M.ns = d.ns;
-  M.nv = d.nx + d.ns + d.nu; M.nw = d.ns + d.nu; M.npar = d.npar; M.dt = d.dt;
-  if (d.N < 1 || d.N > 1000) { err = "horizon out of range"; return -1; }
-  if (d.n_joints < 1 || d.n_joints > RMPC_MAX_JOINTS) { err = "n_joints out of range"; return -1; }
-  if (d.ns != 0 && d.ns != 1) { err = "ns must be 0 or 1"; return -1; }
-  if (d.robot == RMPC_ROBOT_CHAIN) {
-    if (d.nx != 2 * d.n || d.nu != d.n) { err = "holonomic chain needs nx = 2n, nu = n"; return -1; }
-    if (d.n_joints != d.n) { err = "chain with fixed joints between root and end link is not supported"; return -1; }
-    for (int j = 0; j < d.n_joints; j++)
-      if (d.joint_type[j] == RMPC_JOINT_FIXED || d.joint_dof[j] != j) { err = "chain joints must all be actuated, in order"; return -1; }
-  } else if (d.robot == RMPC_ROBOT_DIFFDRIVE) {
-    if (d.n != 3 || d.nx != 8 || d.nu != 2) { err = "diff-drive needs n = 3, nx = 8, nu = 2 (fk.n() == 0)"; return -1; }
-    for (int j = 0; j < d.n_joints; j++)
-      if (d.joint_type[j] != RMPC_JOINT_FIXED) { err = "diff-drive chain must consist of fixed joints"; return -1; }
-  } else { err = "unknown robot kind"; return -1; }
-  if (d.n_joints < 1 || d.n_joints > RMPC_MAX_JOINTS) { err = "n_joints out of range"; return -1; }
-  if (M.nv > RMPC_NV_MAX) { err = "nvar too large"; return -1; }
-  M.n_modules = d.n_modules; M.nobst = d.nobst; M.end_frame = d.end_frame; M.n_joints = d.n_joints;
-  if (d.n_modules < 0 || d.n_modules > RMPC_MAX_MODULES) { err = "n_modules out of range"; return -1; }
-  if (d.n_xrows < 0 || d.n_xrows > RMPC_MAX_XROWS) { err = "n_xrows out of range"; return -1; }
-  for (int r = 0; r < d.n_xrows; r++)
-    if (d.xrow_mod[r] < 0 || d.xrow_mod[r] >= d.n_modules || d.module_kind[d.xrow_mod[r]] != RMPC_MOD_ROWS) { err = "row description: xrow_mod must name a module of kind RMPC_MOD_ROWS"; return -1; }
-  if (d.n_links < 0 || d.n_links > RMPC_MAX_LINKS || d.n_pairs < 0 || d.n_pairs > RMPC_MAX_PAIRS) { err = "links/pairs out of range"; return -1; }
-  auto frame_ok = [&](int f) { return f >= 0 && f < d.n_joints; };
-  if (!frame_ok(d.end_frame)) { err = "end_frame out of range"; return -1; }
-  for (int j = 0; j < d.n_joints; j++) {
-    M.joint_type[j] = d.joint_type[j];
-    for (int c = 0; c < 3; c++) { M.joint_xyz[j][c] = d.joint_xyz[j][c]; M.joint_axis[j][c] = d.joint_axis[j][c]; }
-    for (int c = 0; c < 9; c++) M.joint_rot[j][c] = d.joint_rot[j][c];
-  }
-  if (d.robot == RMPC_ROBOT_DIFFDRIVE) {
-    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};
-    for (int j = 0; j < d.n_joints; j++) {
-      const double *t = d.joint_xyz[j];
-      for (int r = 0; r < 3; r++) o[r] += R[3 * r] * t[0] + R[3 * r + 1] * t[1] + R[3 * r + 2] * t[2];
-      double Rn[9];
-      for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++)
-          Rn[3 * r + c] = R[3 * r] * d.joint_rot[j][c] + R[3 * r + 1] * d.joint_rot[j][3 + c] + R[3 * r + 2] * d.joint_rot[j][6 + c];
-      memcpy(R, Rn, sizeof R);
-      for (int c = 0; c < 3; c++) M.dd_off[j][c] = o[c];
-    }
-  }
-  M.off_r_body = d.off_r_body; M.off_obst = d.off_obst; M.off_lin = d.off_lin; M.off_wu = d.off_wu;
-  M.off_goal = d.off_goal; M.off_wgoal = d.off_wgoal; M.off_wconstr = d.off_wconstr; M.off_ws = d.off_ws;
-  M.has_goal = d.has_goal; M.has_avoid = d.has_avoid;
-  auto off_ok = [&](int off, int len) { return off >= 0 && off + len <= d.npar; };
-  if (!off_ok(d.off_wu, d.nu)) { err = "off_wu"; return -1; }
-  if (d.ns && !off_ok(d.off_ws, 1)) { err = "off_ws"; return -1; }
-  if (d.has_goal && (!off_ok(d.off_goal, 3) || !off_ok(d.off_wgoal, 3))) { err = "goal offsets"; return -1; }
-  if (d.has_avoid && !off_ok(d.off_wconstr, d.n_modules)) { err = "off_wconstr"; return -1; }
-  // general rows in module order
-  int row = 0, nfk = 0;
-  for (int mi = 0; mi < d.n_modules; mi++) {
-    M.mod_kind[mi] = d.module_kind[mi];
-    M.mod_row0[mi] = row;
-    auto push = [&](int kind, int a, int bb, int poff, bool fk) -> bool {
-      if (row >= kMaxRows) return false;
-      M.row_kind[row] = (int8_t)kind; M.row_a[row] = (int8_t)a; M.row_b[row] = (int8_t)bb;
-      M.row_poff[row] = poff; M.row_fk[row] = fk ? (int8_t)nfk++ : (int8_t)-1; M.row_mod[row] = (int8_t)mi;
-      row++;
-      return true;
-    };
-    bool ok = true;
-    switch (d.module_kind[mi]) {
-      case RMPC_MOD_RADIAL:
-        if (!off_ok(d.off_r_body, 1) || !off_ok(d.off_obst, 4 * d.nobst)) { err = "radial offsets"; return -1; }
-        for (int l = 0; l < d.n_links && ok; l++) {
-          if (!frame_ok(d.link_frame[l])) { err = "link frame"; return -1; }
-          for (int i = 0; i < d.nobst && ok; i++) ok = push(ROW_RADIAL, d.link_frame[l], i, 0, true);
-        }
-        break;
-      case RMPC_MOD_LINEAR:
-        if (!off_ok(d.off_r_body, 1) || !off_ok(d.off_lin, 4 * d.nobst)) { err = "linear offsets"; return -1; }
-        for (int l = 0; l < d.n_links && ok; l++) {
-          if (!frame_ok(d.link_frame[l])) { err = "link frame"; return -1; }
-          for (int i = 0; i < d.nobst && ok; i++) ok = push(ROW_LINEAR, d.link_frame[l], i, 0, true);
-        }
-        break;
-      case RMPC_MOD_SELFCOLLISION:
-        if (d.n_pairs > 0 && !off_ok(d.off_r_body, 1)) { err = "self collision offsets"; return -1; }
-        for (int pi = 0; pi < d.n_pairs && ok; pi++) {
-          if (!frame_ok(d.pair_frame[pi][0]) || !frame_ok(d.pair_frame[pi][1])) { err = "pair frame"; return -1; }
-          ok = push(ROW_SELF, d.pair_frame[pi][0], d.pair_frame[pi][1], 0, true);
-        }
-        break;
-      case RMPC_MOD_JOINTLIMIT:
-        if (!off_ok(d.off_lower, d.n) || !off_ok(d.off_upper, d.n)) { err = "joint limit offsets"; return -1; }
-        for (int j = 0; j < d.n && ok; j++) {
-          ok = push(ROW_SINGLE, j, +1, d.off_lower + j, false);
-          ok = ok && push(ROW_SINGLE, j, -1, d.off_upper + j, false);
-        }
-        break;
-      case RMPC_MOD_VELLIMIT:
-        if (!off_ok(d.off_lower_vel, 2) || !off_ok(d.off_upper_vel, 2)) { err = "velocity limit offsets"; return -1; }
-        for (int j = 0; j < 2 && ok; j++) {
-          ok = push(ROW_SINGLE, d.nx - 2 + j, +1, d.off_lower_vel + j, false);
-          ok = ok && push(ROW_SINGLE, d.nx - 2 + j, -1, d.off_upper_vel + j, false);
-        }
-        break;
-      case RMPC_MOD_INPUTLIMIT:
-        if (!off_ok(d.off_lower_u, d.nu) || !off_ok(d.off_upper_u, d.nu)) { err = "input limit offsets"; return -1; }
-        for (int j = 0; j < d.nu && ok; j++) {
-          ok = push(ROW_SINGLE, d.nx + d.ns + j, +1, d.off_lower_u + j, false);
-          ok = ok && push(ROW_SINGLE, d.nx + d.ns + j, -1, d.off_upper_u + j, false);
-        }
-        break;
-      case RMPC_MOD_ROWS: {
-        // a module given as row descriptions (rmpc.h): variants of the six kinds through the same row tables
-        int on_x = 0, on_u = 0;
-        for (int r = 0; r < d.n_xrows && ok; r++) {
-          if (d.xrow_mod[r] != mi) continue;
-          const int a = d.xrow_a[r], b = d.xrow_b[r], po = d.xrow_poff[r];
-          switch (d.xrow_kind[r]) {
-            case RMPC_ROW_RADIAL:
-            case RMPC_ROW_LINEAR: {
-              const bool radial = d.xrow_kind[r] == RMPC_ROW_RADIAL;
-              int &base = radial ? M.off_obst : M.off_lin;
-              if (!frame_ok(a)) { err = "row description: frame"; return -1; }
-              if (!off_ok(d.off_r_body, 1) || !off_ok(po, 4)) { err = "row description: parameter offsets"; return -1; }
-              if (base < 0) base = po;   // (no module of the kind: the list starts at the first described row)
-              if (po < base || (po - base) % 4 != 0 || (po - base) / 4 > 63) {
-                err = "row description: a sphere / plane must lie a multiple of 4 (at most 252) parameters behind the obstacle / plane list";
-                return -1;
-              }
-              ok = push(radial ? ROW_RADIAL : ROW_LINEAR, a, (po - base) / 4, 0, true);
-              on_x++;
-              break;
-            }
-            case RMPC_ROW_SELF:
-              if (!frame_ok(a) || !frame_ok(b) || a == b) { err = "row description: pair frames"; return -1; }
-              if (!off_ok(d.off_r_body, 1)) { err = "row description: r_body"; return -1; }
-              ok = push(ROW_SELF, a, b, 0, true);
-              on_x++;
-              break;
-            case RMPC_ROW_VAR:
-              if (a < 0 || a >= M.nv || (d.ns && a == d.nx)) { err = "row description: variable"; return -1; }
-              if (b != 1 && b != -1) { err = "row description: sign must be +1 or -1"; return -1; }
-              if (!off_ok(po, 1)) { err = "row description: limit offset"; return -1; }
-              ok = push(ROW_SINGLE, a, b, po, false);
-              (a < d.nx ? on_x : on_u)++;
-              break;
-            default:
-              err = "row description: unknown row kind";
-              return -1;
-          }
-        }
-        if (on_x && on_u) { err = "row description: the rows of a module must all be on states or all on inputs"; return -1; }
-        break;
-      }
-      default:
-        err = "unknown constraint module";
-        return -1;
-    }
-    if (!ok) { err = "too many inequality rows"; return -1; }
-    M.mod_rows[mi] = row - M.mod_row0[mi];
-  }
-  M.nh = row; M.nfk = nfk;
-  for (int j = 0; j < M.nv; j++)
-    if (std::isfinite(d.lb[j])) { M.lb_var[M.nlb] = (int8_t)j; M.lb_val[M.nlb] = d.lb[j]; M.nlb++; }
-  for (int j = 0; j < M.nv; j++)
-    if (std::isfinite(d.ub[j])) { M.ub_var[M.nub] = (int8_t)j; M.ub_val[M.nub] = d.ub[j]; M.nub++; }
-  M.m = M.nh + M.nlb + M.nub;
-  M.max_iter = d.max_iter > 0 ? d.max_iter : 200;
-  M.tol_stat = d.tol_stat > 0 ? d.tol_stat : 1e-6;
-  M.tol_eq = d.tol_eq > 0 ? d.tol_eq : 1e-8;
-  M.tol_ineq = d.tol_ineq > 0 ? d.tol_ineq : 1e-8;
-  M.tol_comp = d.tol_comp > 0 ? d.tol_comp : 1e-6;
-  M.mu0 = d.mu0 > 0 ? d.mu0 : 1.0;
-  M.acc_iters = d.acc_iters < 0 ? 0 : d.acc_iters;
-  M.acc_obj_tol = d.acc_obj_tol > 0 ? d.acc_obj_tol : 1e-8;
-  M.ls_max = d.ls_max > 0 ? d.ls_max : kLsMax;
-  // exact curvature of the distance rows: holonomic chain, no slack, and for n <= 3 every frame a
-  // distance row refers to moves affinely with q (prismatic joints, or revolute at the frame itself)
-  auto affine = [&](int f) {
-    for (int j = 0; j <= f; j++)
-      if (d.joint_type[j] == RMPC_JOINT_REVOLUTE && j != f) return false;
-    return true;
-  };
-  bool curv = d.robot == RMPC_ROBOT_CHAIN && d.ns == 0;
-  // (the arms carry the kinematics' own second derivatives: Cfg::FKCURV)
-  // (by row: the sphere and pair rows of the built-in modules and of the row-described ones alike)
-  for (int r = 0; r < M.nh && curv && d.n <= 3; r++) {
-    if (M.row_kind[r] == ROW_RADIAL) curv = curv && affine(M.row_a[r]);
-    if (M.row_kind[r] == ROW_SELF) curv = curv && affine(M.row_a[r]) && affine(M.row_b[r]);
-  }
-  if (d.robot == RMPC_ROBOT_DIFFDRIVE) curv = true;   // exact second-order terms of the unicycle (Cfg::DDCURV)
-  M.use_curv = curv ? 1 : 0;
-  return 0;
-}
-
-// ---- generated views (rmpc_spec_gen.hpp) --------------------------------------------------
-// Source text of the view of one descriptor: the accessors of RtView as constexpr functions over literal tables
-// (doubles as hex floats: exact).  scripts/gen_specs.py writes rmpc_spec_gen.hpp from it for the shipped
-// configurations; the library is then built with those views next to the runtime one.
-static std::string spec_source(const rmpc_desc &d, const DevModel &M, const DevTables &T, const std::string &name) {
-  std::string o;
-  char buf[128];
-  auto fi = [&](int v) { snprintf(buf, sizeof buf, "%d", v); return std::string(buf); };
-  auto fd = [&](double v) { snprintf(buf, sizeof buf, "%a", v); return std::string(buf); };
-  auto scalar = [&](const char *nm, int v) {
-    o += "  __host__ __device__ static constexpr int " + std::string(nm) + "() { return " + fi(v) + "; }\n";
-  };
-  auto arr1 = [&](const char *nm, const int *p, int n) {
-    o += "  __host__ __device__ static constexpr int " + std::string(nm) + "(int i) { constexpr int t[" + fi(n) + "] = {";
-    for (int i = 0; i < n; i++) o += (i ? ", " : "") + fi(p[i]);
-    o += "}; return t[i]; }\n";
-  };
-  auto arr2i = [&](const char *nm, const int *p, int n0, int n1) {
-    o += "  __host__ __device__ static constexpr int " + std::string(nm) + "(int i, int j) { constexpr int t[" + fi(n0) + "][" + fi(n1) + "] = {";
-    for (int i = 0; i < n0; i++) {
-      o += (i ? ", {" : "{");
-      for (int j = 0; j < n1; j++) o += (j ? ", " : "") + fi(p[i * n1 + j]);
-      o += "}";
-    }
-    o += "}; return t[i][j]; }\n";
-  };
-  auto arr2d = [&](const char *nm, const double *p, int n0, int n1) {
-    o += "  __host__ __device__ static constexpr double " + std::string(nm) + "(int i, int j) { constexpr double t[" + fi(n0) + "][" + fi(n1) + "] = {";
-    for (int i = 0; i < n0; i++) {
-      o += (i ? ", {" : "{");
-      for (int j = 0; j < n1; j++) o += (j ? ", " : "") + fd(p[i * n1 + j]);
-      o += "}";
-    }
-    o += "}; return t[i][j]; }\n";
-  };
-  o += "struct " + name + " {\n  static constexpr bool SPEC = true;\n";
-  o += "  static constexpr int ROBOT = " + fi(d.robot) + ", NQ = " + fi(d.n) + ", NS = " + fi(d.ns) + ";\n";
-  o += "  __host__ __device__ " + name + "() {}\n  __host__ __device__ " + name + "(const DevModel &, const DevTables &) {}\n";
-  scalar("nslots", T.nslots);
-  arr1("slot_fa", T.slot_fa, kMaxSlots);
-  arr1("slot_fb", T.slot_fb, kMaxSlots);
-  arr1("slot_row_begin", T.slot_row_begin, kMaxSlots + 1);
-  scalar("nfkrows", T.nfkrows);
-  arr1("fk_row", T.fk_row, kMaxFkRows);
-  arr1("fk_kind", T.fk_kind, kMaxFkRows);
-  arr1("fk_obst", T.fk_obst, kMaxFkRows);
-  arr1("fk_mod", T.fk_mod, kMaxFkRows);
-  arr1("fk_first", T.fk_first, kMaxFkRows);
-  arr1("fk_idx", T.fk_idx, kMaxFkRows);
-  arr2i("v_row", &T.v_row[0][0], RMPC_NV_MAX, kVarRows);
-  arr2i("v_sgn", &T.v_sgn[0][0], RMPC_NV_MAX, kVarRows);
-  arr2i("v_poff", &T.v_poff[0][0], RMPC_NV_MAX, kVarRows);
-  arr2i("v_soft", &T.v_soft[0][0], RMPC_NV_MAX, kVarRows);
-  arr2i("v_mod", &T.v_mod[0][0], RMPC_NV_MAX, kVarRows);
-  arr2i("v_first", &T.v_first[0][0], RMPC_NV_MAX, kVarRows);
-  arr2d("v_val", &T.v_val[0][0], RMPC_NV_MAX, kVarRows);
-  scalar("off_r_body", M.off_r_body); scalar("off_obst", M.off_obst); scalar("off_lin", M.off_lin);
-  scalar("off_wu", M.off_wu); scalar("off_goal", M.off_goal); scalar("off_wgoal", M.off_wgoal);
-  scalar("off_wconstr", M.off_wconstr); scalar("off_ws", M.off_ws);
-  scalar("has_goal", M.has_goal); scalar("has_avoid", M.has_avoid);
-  arr1("joint_type", M.joint_type, RMPC_MAX_JOINTS);
-  arr2d("joint_xyz", &M.joint_xyz[0][0], RMPC_MAX_JOINTS, 3);
-  arr2d("joint_rot", &M.joint_rot[0][0], RMPC_MAX_JOINTS, 9);
-  arr2d("joint_axis", &M.joint_axis[0][0], RMPC_MAX_JOINTS, 3);
-  arr2d("dd_off", &M.dd_off[0][0], RMPC_MAX_JOINTS, 3);
-  o += "};\n";
-  return o;
 }
 
 // ---- workspace carving ---------------------------------------------------------------
@@ -1032,6 +231,14 @@ static bool fused_supported(const VariantOps *v, const DevModel &M, const DevTab
   return v && v->fused && (!v->arm_fused || arm_rows_uniform(M, T)) && M.N <= kFusedStages;
 }
 
+// What every entry that works on B instances of a handle begins with, behind its own argument checks: B is one the
+// handle was created for, and the calls that follow go to the handle's device.
+static int enter_batch(rmpc_handle *h, int B) {
+  if (B < 1 || B > h->max_batch) return fail("batch size out of range for this handle");
+  HIPCHK(hipSetDevice(h->device));
+  return 0;
+}
+
 static void launch_fused(rmpc_handle *h, int B, const double *d_xinit, const double *d_x0, const double *d_params,
                          double *d_zout, int *d_exit, int *d_iters, double *d_kkt, double *d_obj, hipStream_t st, int cap) {
   const VariantOps &v = *h->ops;
@@ -1059,9 +266,8 @@ static void launch_fused(rmpc_handle *h, int B, const double *d_xinit, const dou
 static int solve_device(rmpc_handle *h, int B, const double *d_xinit, const double *d_x0, const double *d_params,
                         double *d_zout, int *d_exit, int *d_iters, double *d_kkt, double *d_obj, hipStream_t st,
                         int max_passes_override) {
-  if (B < 1 || B > h->max_batch) return fail("batch size out of range for this handle");
+  if (enter_batch(h, B)) return -1;
   const DevModel &M = h->M;
-  HIPCHK(hipSetDevice(h->device));
   fill_lane_bytes(h, B);
   if (h->have_duals && h->duals_B != B) h->have_duals = false;   // multipliers of another batch: cold start
   if (d_params) h->packed_B = 0;   // (the workspace parameters are about to be overwritten)
@@ -1205,16 +411,6 @@ int rmpc_version(void) { return RMPC_VERSION; }
 #endif
 const char *rmpc_source_hash(void) { return RMPC_SOURCE_HASH; }
 const char *rmpc_last_error(void) { return g_err.c_str(); }
-/* a descriptor of this version, or of 0.2.0 (the struct without the xrow_* arrays at its end: no row-described modules) */
-static bool take_desc(const rmpc_desc *in, rmpc_desc &full) {
-  if (!in) return false;
-  const int old_size = (int)offsetof(rmpc_desc, n_xrows);
-  if (in->struct_size != (int)sizeof(rmpc_desc) && in->struct_size != old_size) return false;
-  memset(&full, 0, sizeof full);
-  memcpy(&full, in, (size_t)in->struct_size);
-  full.struct_size = (int)sizeof(rmpc_desc);
-  return true;
-}
 /* generated views: source text for one descriptor, and which view a handle runs (see rmpc.h) */
 int64_t rmpc_spec_source(const rmpc_desc *desc_in, const char *name, char *out, int64_t cap) {
   rmpc_desc dfull;
@@ -1368,8 +564,7 @@ static int ensure_staging(rmpc_handle *h) {
 int rmpc_solve_batch(rmpc_handle *h, int B, const double *xinit, const double *x0, const double *params,
                      double *z_out, int32_t *exitflag, int32_t *iters, double *kkt_res, double *obj) {
   if (!h || !xinit || !x0 || !params || !z_out || !exitflag) return fail("null argument");
-  if (B < 1 || B > h->max_batch) return fail("batch size out of range for this handle");
-  HIPCHK(hipSetDevice(h->device));
+  if (enter_batch(h, B)) return -1;
   if (ensure_staging(h) != 0) return -1;
   const DevModel &M = h->M;
   hipStream_t st = h->stream;
@@ -1413,8 +608,7 @@ static void scene_args(const rmpc_handle *h, const rmpc_scene *s, SceneDev &S, S
 int rmpc_pack_scene_device(rmpc_handle *h, int B, const rmpc_scene *scene, double *d_params, void *stream) {
   if (!h || !scene || !d_params) return fail("null argument");
   if (scene->struct_size != (int)sizeof(rmpc_scene)) return fail("rmpc_scene size mismatch");
-  if (B < 1 || B > h->max_batch) return fail("batch size out of range for this handle");
-  HIPCHK(hipSetDevice(h->device));
+  if (enter_batch(h, B)) return -1;
   hipStream_t st = (hipStream_t)stream;   // NULL: the legacy null stream, ordered with the caller's default-stream work
   SceneDev S; SceneOff O;
   scene_args(h, scene, S, O);
@@ -1427,8 +621,7 @@ int rmpc_pack_scene_device(rmpc_handle *h, int B, const rmpc_scene *scene, doubl
 int rmpc_pack_scene_workspace(rmpc_handle *h, int B, const rmpc_scene *scene, void *stream) {
   if (!h || !scene) return fail("null argument");
   if (scene->struct_size != (int)sizeof(rmpc_scene)) return fail("rmpc_scene size mismatch");
-  if (B < 1 || B > h->max_batch) return fail("batch size out of range for this handle");
-  HIPCHK(hipSetDevice(h->device));
+  if (enter_batch(h, B)) return -1;
   hipStream_t st = (hipStream_t)stream;   // NULL: the legacy null stream, ordered with the caller's default-stream work
   SceneDev S; SceneOff O;
   scene_args(h, scene, S, O);
@@ -1463,8 +656,7 @@ int rmpc_solve_batch_scene_device(rmpc_handle *h, int B, const rmpc_scene *scene
 int rmpc_advance_device_flags(rmpc_handle *h, int B, const double *d_z_prev, const int32_t *d_exitflag, double *d_xinit,
                               double *d_x0, int previous_plan, void *stream) {
   if (!h || !d_z_prev || !d_xinit || !d_x0) return fail("null argument");
-  if (B < 1 || B > h->max_batch) return fail("batch size out of range for this handle");
-  HIPCHK(hipSetDevice(h->device));
+  if (enter_batch(h, B)) return -1;
   hipStream_t st = (hipStream_t)stream;   // NULL: the legacy null stream, ordered with the caller's default-stream work
   const int *ef = (const int *)d_exitflag;
   h->ops->advance(h, B, d_z_prev, ef, d_xinit, d_x0, previous_plan, st);
@@ -1481,10 +673,9 @@ int rmpc_retarget_device(rmpc_handle *h, int B, const rmpc_retarget *r, void *st
   if (!h || !r) return fail("null argument");
   if (r->struct_size != (int)sizeof(rmpc_retarget)) return fail("rmpc_retarget.struct_size mismatch");
   if (!r->xinit || !r->x0 || !r->goal || !r->goal_pool || !r->cursor || !r->dwell || !r->x_start) return fail("null argument");
-  if (B < 1 || B > h->max_batch) return fail("batch size out of range for this handle");
+  if (enter_batch(h, B)) return -1;
   if (r->pool_len < 1) return fail("goal pool must hold at least one goal per instance");
   if (!h->desc.has_goal) return fail("the model has no GoalReaching objective");
-  HIPCHK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   RetargetDev R;
   R.xinit = r->xinit; R.x0 = r->x0; R.goal = r->goal; R.exitflag = (const int *)r->exitflag; R.iters = (const int *)r->iters;
@@ -1495,186 +686,6 @@ int rmpc_retarget_device(rmpc_handle *h, int B, const rmpc_retarget *r, void *st
   R.wmu = h->warm_mode ? (h->fused ? h->F.wmu : h->W.wmu) : nullptr;
   R.wmu_regoal = r->mu_regoal > 0.0 ? r->mu_regoal / kWarmKappa : 0.0;
   h->ops->retarget(h, B, R, st);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int rmpc_advance_obstacles_device(int B, int nobst, double dt, double arena, double *d_obst_dyn, void *stream) {
-  if (B < 1 || nobst < 1 || !d_obst_dyn) return fail("bad argument");
-  const int n = B * nobst;
-  hipLaunchKernelGGL(k_obst_advance, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_obst_dyn, n, dt, arena);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-static int grid_device(const void *p);
-
-int rmpc_free_space_device(int B, int N, int P, int K, double max_radius, const double *d_points,
-                           const double *d_seeds, double *d_planes, void *stream) {
-  if (!d_points || !d_seeds || !d_planes) return fail("null argument");
-  if (B < 1 || N < 1 || K < 1 || P < 1 || P > 64) return fail("free space decomposition: need 1 <= P <= 64 points, K >= 1");
-  if (grid_device(d_points)) return -1;
-  hipLaunchKernelGGL(k_fsd, dim3((B * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_points, d_seeds, d_planes,
-                     B, N, P, K, max_radius);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-/* the global planner (rmpc_grid.hpp): no handle; each call runs on the device its first pointer lives on */
-static int grid_device(const void *p) {
-  hipPointerAttribute_t a;
-  HIPCHK(hipPointerGetAttributes(&a, p));
-  if (a.device < 0) return fail("not a device pointer");
-  HIPCHK(hipSetDevice(a.device));
-  return 0;
-}
-static bool grid_fits(long long a, long long b) { return a >= 0 && b >= 0 && (b == 0 || a <= INT_MAX / b); }
-static int grid_check(int H, int W, int movement) {
-  if (H < 1 || W < 1 || !grid_fits(H, W)) return fail("grid: need H, W >= 1");
-  if (movement != 4 && movement != 8) return fail("grid: movement must be 4 or 8");
-  return 0;
-}
-
-int rmpc_grid_inflate_device(int H, int W, double cell, double size_robot, double threshold, const double *d_grid,
-                             double *d_out, void *stream) {
-  if (!d_grid || !d_out) return fail("null argument");
-  if (grid_check(H, W, 8) || grid_device(d_grid)) return -1;
-  if (!(cell > 0.0) || !(size_robot >= 0.0)) return fail("grid inflate: need cell > 0, size_robot >= 0");
-  const double kd = ceil(size_robot / cell);
-  if (kd > (double)(H + W)) return fail("grid inflate: window larger than the map");
-  hipLaunchKernelGGL(k_grid_inflate, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, d_out, H, W,
-                     (int)kd, threshold);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int rmpc_grid_fields_device(int H, int W, const double *d_grid, int G, const int32_t *d_goal_cells, int movement,
-                            double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status,
-                            int32_t *d_sweeps, void *stream) {
-  if (!d_grid || !d_goal_cells || !d_fields || !d_status) return fail("null argument");
-  if (grid_check(H, W, movement)) return -1;
-  if (H * W > RMPC_GRID_MAX_CELLS)
-    return fail("grid fields: " + std::to_string(H) + "x" + std::to_string(W) + " map exceeds RMPC_GRID_MAX_CELLS = " +
-                std::to_string(RMPC_GRID_MAX_CELLS) + " cells (one field must fit in the LDS of a workgroup)");
-  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid fields: need 1 <= G and G*H*W <= INT_MAX");
-  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid fields: cost_factor must be finite and >= 0");
-  if (grid_device(d_grid)) return -1;
-  hipLaunchKernelGGL(k_grid_fields, dim3(G), dim3(kGridThreads), 0, (hipStream_t)stream, d_grid, H, W,
-                     (const int *)d_goal_cells, movement, occ_threshold, cost_factor, d_fields, (int *)d_status,
-                     (int *)d_sweeps);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int rmpc_grid_paths_device(int H, int W, const double *d_grid, int G, const double *d_fields, const int32_t *d_goal_cells,
-                           int B, const int32_t *d_start_cell, const int32_t *d_goal_index, int movement,
-                           double occ_threshold, double cost_factor, int max_len, int32_t *d_path, int32_t *d_len,
-                           void *stream) {
-  if (!d_grid || !d_fields || !d_goal_cells || !d_start_cell || !d_goal_index || !d_path || !d_len) return fail("null argument");
-  if (grid_check(H, W, movement)) return -1;
-  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid paths: need 1 <= G and G*H*W <= INT_MAX");
-  if (B < 1 || max_len < 1 || !grid_fits(B, max_len)) return fail("grid paths: need B, max_len >= 1 and B*max_len <= INT_MAX");
-  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid paths: cost_factor must be finite and >= 0");
-  if (grid_device(d_grid)) return -1;
-  hipLaunchKernelGGL(k_grid_paths, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, d_fields,
-                     (const int *)d_goal_cells, G, (const int *)d_start_cell, (const int *)d_goal_index, B, movement,
-                     occ_threshold, cost_factor, max_len, (int *)d_path, (int *)d_len);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int rmpc_grid_cells_device(int B, const double *d_pos, int stride, int H, int W, double x0, double y0, double cell,
-                           int32_t *d_cells, void *stream) {
-  if (!d_pos || !d_cells) return fail("null argument");
-  if (B < 1 || stride < 2 || !grid_fits(B, stride)) return fail("grid cells: need B >= 1, stride >= 2, B*stride <= INT_MAX");
-  if (grid_check(H, W, 8) || grid_device(d_pos)) return -1;
-  if (!(cell > 0.0)) return fail("grid cells: need cell > 0");
-  hipLaunchKernelGGL(k_grid_cells, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_pos, stride, B, H, W, x0,
-                     y0, cell, (int *)d_cells);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int rmpc_follow_path_device(int B, const int32_t *d_path, const int32_t *d_len, int max_len, int32_t *d_idx,
-                            const double *d_pos, int stride, int W, double x0, double y0, double cell, double threshold,
-                            double *d_goal, void *stream) {
-  if (!d_path || !d_len || !d_idx || !d_pos || !d_goal) return fail("null argument");
-  if (B < 1 || max_len < 1 || !grid_fits(B, max_len)) return fail("follow path: need B, max_len >= 1 and B*max_len <= INT_MAX");
-  if (stride < 2 || !grid_fits(B, stride) || W < 1) return fail("follow path: need stride >= 2, W >= 1");
-  if (grid_device(d_path)) return -1;
-  hipLaunchKernelGGL(k_follow_path, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int *)d_path,
-                     (const int *)d_len, max_len, (int *)d_idx, d_pos, stride, B, W, x0, y0, cell, threshold, d_goal);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-/* the lidar (rmpc_sense.hpp): no handle; each call runs on the device its first pointer lives on */
-int rmpc_lidar_scan_device(int B, const rmpc_lidar *l, void *stream) {
-  if (!l) return fail("null argument");
-  if (l->struct_size != (int)sizeof(rmpc_lidar)) return fail("rmpc_lidar.struct_size mismatch");
-  if (B < 1 || l->rays < 1) return fail("lidar: need B >= 1 and rays >= 1");
-  if (l->pose_stride < 3) return fail("lidar: pose_stride must be >= 3 (x, y, heading)");
-  if (l->nbox < 0 || l->ncircle < 0) return fail("lidar: negative shape count");
-  if (!grid_fits(B, l->rays) || !grid_fits(B, l->pose_stride) || !grid_fits(l->nbox, 4) || !grid_fits(l->ncircle, 3))
-    return fail("lidar: B*rays, B*pose_stride, nbox*4 and ncircle*3 must not exceed INT_MAX");
-  if (!(l->range > 0.0) || std::isinf(l->range)) return fail("lidar: range must be positive and finite");
-  if (!l->pose || !l->points || (l->nbox > 0 && !l->boxes) || (l->ncircle > 0 && !l->circles)) return fail("null argument");
-  if (grid_device(l->pose)) return -1;
-  const int n = B * l->rays;
-  const double step = (l->angle_max - l->angle_min) / (double)l->rays;
-  hipLaunchKernelGGL(k_lidar, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, l->pose, l->pose_stride, B,
-                     l->rays, l->angle_min, step, l->range, l->offset_x, l->offset_y, l->height, l->boxes, l->nbox,
-                     l->circles, l->ncircle, l->points, l->ranges);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-static int plan_points(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag, const double *d_pose,
-                       int pose_stride, int shift, int heading, double offset_x, double offset_y, double height,
-                       double *d_points, void *stream) {
-  if (!d_pose || !d_points) return fail("null argument");
-  if (B < 1 || N < 1) return fail("plan points: need B, N >= 1");
-  if (heading != 0 && heading != 1) return fail("plan points: heading must be 0 or 1");
-  if (pose_stride < 3) return fail("plan points: pose_stride must be >= 3 (x, y, heading)");
-  if (nvar < 3) return fail("plan points: nvar must be >= 3 (x, y, heading first)");
-  if (!grid_fits(B, N) || !grid_fits(B, pose_stride) || !grid_fits((long long)B * N, nvar))
-    return fail("plan points: B*N, B*pose_stride and B*N*nvar must not exceed INT_MAX");
-  if (grid_device(d_z_prev ? (const void *)d_z_prev : (const void *)d_pose)) return -1;
-  hipLaunchKernelGGL(k_plan_points, dim3((B * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_z_prev, nvar,
-                     (const int *)d_exitflag, d_pose, pose_stride, B, N, shift, heading, offset_x, offset_y, height,
-                     d_points);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-int rmpc_plan_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
-                            const double *d_pose, int pose_stride, double offset_x, double offset_y, double height,
-                            double *d_points, void *stream) {
-  return plan_points(B, N, d_z_prev, nvar, d_exitflag, d_pose, pose_stride, 0, 1, offset_x, offset_y, height, d_points,
-                     stream);
-}
-
-/* fleet separation (rmpc_sense.hpp): no handle; each call runs on the device its first pointer lives on */
-int rmpc_fleet_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
-                             const double *d_pose, int pose_stride, int heading, double offset_x, double offset_y,
-                             double height, double *d_points, void *stream) {
-  return plan_points(B, N, d_z_prev, nvar, d_exitflag, d_pose, pose_stride, 1, heading, offset_x, offset_y, height,
-                     d_points, stream);
-}
-
-int rmpc_fleet_planes_device(int B, int N, const double *d_points, const double *d_radius, int K, double range,
-                             int nobst, int slot0, double *d_planes, void *stream) {
-  if (!d_points || !d_radius || !d_planes) return fail("null argument");
-  if (B < 1 || N < 1) return fail("fleet planes: need B, N >= 1");
-  if (K < 1 || K > rmpc::kFleetKMax) return fail("fleet planes: need 1 <= K <= 8");
-  if (slot0 < 0 || nobst < 1 || slot0 > nobst - K) return fail("fleet planes: need 0 <= slot0 and slot0 + K <= nobst");
-  if (!(range >= 0.0)) return fail("fleet planes: range must be >= 0 (+inf admits every robot)");
-  if (!grid_fits(B, N) || !grid_fits((long long)B * N, nobst) || !grid_fits((long long)B * N * nobst, 4))
-    return fail("fleet planes: B*N*nobst*4 must not exceed INT_MAX");
-  if (grid_device(d_points)) return -1;
-  const int nbt = (B + 255) / 256;
-  hipLaunchKernelGGL(k_fleet_planes, dim3(nbt * N), dim3(256), 0, (hipStream_t)stream, d_points, d_radius, B, N, K,
-                     range * range, nobst, slot0, d_planes);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1803,8 +814,7 @@ int rmpc_debug_poison_lds(rmpc_handle *h) {
 int rmpc_debug_sweep(rmpc_handle *h, int B, const double *xinit, const double *x0, const double *params,
                      double *out_Q, double *out_q0, double *out_q1, double *out_rc, double *out_g, double *out_f) {
   if (!h) return fail("null handle");
-  if (B < 1 || B > h->max_batch) return fail("batch size out of range for this handle");
-  HIPCHK(hipSetDevice(h->device));
+  if (enter_batch(h, B)) return -1;
   if (ensure_staging(h) != 0) return -1;
   const DevModel &M = h->M;
   hipStream_t st = h->stream;

@@ -1,21 +1,10 @@
 // rmpc_host.hpp -- what the host unit (rmpc_host.hip) and the variant units (rmpc_variants.hip) share: the handle,
-// the error channel and the table through which the host reaches the kernels of a variant.
+// the error channel (rmpc_err.hpp) and the table through which the host reaches the kernels of a variant.
 #pragma once
 #include "rmpc_kernels.hip"
+#include "rmpc_err.hpp"
 
 using namespace rmpc;
-
-inline thread_local std::string g_err;   // (one object for all translation units of the library)
-inline int fail(const std::string &m) {
-  g_err = m;
-  return -1;
-}
-#define HIPCHK(x)                                                                         \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess)                                                                 \
-      return fail(std::string(#x) + ": " + hipGetErrorString(e_));                        \
-  } while (0)
 
 enum KernelId { K_PACK = 0, K_SWEEP, K_RICCATI, K_STEP, K_UNPACK, K_FUSED };
 

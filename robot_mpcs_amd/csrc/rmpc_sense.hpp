@@ -1,6 +1,6 @@
 // rmpc_sense.hpp -- the lidar on the device (the reference's boxer examples: a Lidar sensor on the robot, then
 // compute_point_cloud, then one free-space decomposition per stage around the previous plan), included by
-// rmpc_host.hip.  The world is shared by all B robots: axis-aligned boxes [nbox][4] = (cx, cy, lx, ly) and circles
+// rmpc_world.hip.  The world is shared by all B robots: axis-aligned boxes [nbox][4] = (cx, cy, lx, ly) and circles
 // [ncircle][3] = (cx, cy, r).  The ray convention is the project's own ("Lidar"):
 //   sensor origin  o = (x + ox cos th - oy sin th, y + ox sin th + oy cos th), (ox, oy) in the body frame;
 //   ray i of R     angle th + a_min + i (a_max - a_min) / R (half-open sweep), direction d = (cos, sin);

@@ -1,6 +1,6 @@
 // rmpc_variants.hip -- the kernels of some kernel variants and their entries in the host's variant table
 // (VariantOps, rmpc_host.hpp).  __graft_entry__.compile_library compiles this file once per group of variants
-// (__graft_entry__.TU_MASKS), in parallel with each other and with the host unit rmpc_host.hip: RMPC_UNIT_VARIANTS is
+// (__graft_entry__.TU_MASKS), in parallel with each other, the host unit rmpc_host.hip and rmpc_world.hip: RMPC_UNIT_VARIANTS is
 // the bit mask of the rows of RMPC_VARIANTS this unit builds (bit i = id i; default: all of them).
 #include "rmpc_host.hpp"
 

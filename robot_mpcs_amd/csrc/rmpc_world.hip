@@ -1,0 +1,271 @@
+// rmpc_world.hip -- the world around the solver, on the device: the moving obstacles between two control steps, the
+// free-space decomposition, the global planner (rmpc_grid.hpp), the lidar and the fleet's separating planes
+// (rmpc_sense.hpp), with their entries of the C ABI.  None of them takes a handle: each call runs on the device its
+// first pointer lives on, on the stream it is given.  A translation unit of its own, which needs rmpc.h, the HIP
+// runtime and the error channel only -- nothing of the solver.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <string>
+
+#include "../../include/rmpc.h"
+#include "rmpc_err.hpp"
+
+namespace rmpc {
+
+// The environment of the moving obstacles between two control steps (what the examples' simulator does before the driver
+// hands the planner ob[nx:], mpcPlanner.py:243-244): pos += vel dt + acc dt^2 / 2, vel += acc dt, one lane per
+// (instance, obstacle); arena > 0: an obstacle that leaves [-arena, arena] in x or y comes back (velocity component
+// mirrored), so that a loop that runs for hours keeps its obstacles.
+static __global__ __launch_bounds__(256) void k_obst_advance(double *__restrict__ od, int n, double dt, double arena) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double *o = od + (size_t)i * 9;
+  for (int c = 0; c < 3; c++) {
+    double pos = o[c] + o[3 + c] * dt + 0.5 * o[6 + c] * dt * dt;
+    double vel = o[3 + c] + o[6 + c] * dt;
+    if (arena > 0.0 && c < 2) {
+      if (pos > arena) { pos = 2.0 * arena - pos; vel = -vel; }
+      else if (pos < -arena) { pos = -2.0 * arena - pos; vel = -vel; }
+    }
+    o[c] = pos; o[3 + c] = vel;
+  }
+}
+
+// ===========================================================================
+// Free-space decomposition: lidar point cloud -> at most K half-planes
+// around a seed point, one lane per (instance, stage) seed.  Greedy rule of the reference
+// (robotmpcs/utils/free_space_decomposition.py:79-97): the closest remaining point inside
+// max_radius defines the plane through it with normal (seed - point); points on or behind the
+// plane are discarded; unused slots get the dummy plane of asdict() (:110-114).  The sort of
+// the reference is replaced by K arg-min sweeps over a keep-mask (P <= 64 points).
+// ===========================================================================
+__global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, const double *__restrict__ seeds,
+                                             double *__restrict__ out, int B, int N, int P, int K, double max_radius) {
+#pragma clang fp contract(off)
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  if (gid >= B * N) return;
+  const int b = gid / N;
+  const double *pc = points + (size_t)b * P * 3;
+  const double s0 = seeds[(size_t)gid * 3], s1 = seeds[(size_t)gid * 3 + 1], s2 = seeds[(size_t)gid * 3 + 2];
+  double *o = out + (size_t)gid * K * 4;
+  unsigned long long keep = 0ull;
+  for (int i = 0; i < P; i++) {
+    const double d0 = pc[3 * i] - s0, d1 = pc[3 * i + 1] - s1, d2 = pc[3 * i + 2] - s2;
+    if (sqrt(d0 * d0 + d1 * d1 + d2 * d2) < max_radius) keep |= (1ull << i);
+  }
+  int nc = 0;
+  while (keep && nc < K) {
+    int best = -1;
+    double bd = 0.0;
+    for (int i = 0; i < P; i++)
+      if (keep & (1ull << i)) {
+        const double d0 = pc[3 * i] - s0, d1 = pc[3 * i + 1] - s1, d2 = pc[3 * i + 2] - s2;
+        const double dd = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+        if (best < 0 || dd < bd) { best = i; bd = dd; }
+      }
+    const double p0 = pc[3 * best], p1 = pc[3 * best + 1], p2 = pc[3 * best + 2];
+    const double n0 = s0 - p0, n1 = s1 - p1, n2 = s2 - p2;
+    const double c = -((n0 * p0 + n1 * p1) + n2 * p2);
+    o[4 * nc] = n0; o[4 * nc + 1] = n1; o[4 * nc + 2] = n2; o[4 * nc + 3] = c;
+    nc++;
+    for (int i = 0; i < P; i++)
+      if (keep & (1ull << i)) {
+        const double v = ((n0 * pc[3 * i] + n1 * pc[3 * i + 1]) + n2 * pc[3 * i + 2]) + c;
+        if (v <= 0.0) keep &= ~(1ull << i);
+      }
+  }
+  for (; nc < K; nc++) {
+    // HalfPlane(seed + (20, 20, 0), seed): normal = seed - point
+    const double p0 = s0 + 20.0, p1 = s1 + 20.0, p2 = s2 + 0.0;
+    const double n0 = s0 - p0, n1 = s1 - p1, n2 = s2 - p2;
+    o[4 * nc] = n0; o[4 * nc + 1] = n1; o[4 * nc + 2] = n2; o[4 * nc + 3] = -((n0 * p0 + n1 * p1) + n2 * p2);
+  }
+}
+
+}  // namespace rmpc
+
+#include "rmpc_grid.hpp"
+#include "rmpc_sense.hpp"
+
+using namespace rmpc;
+
+// no handle names the device: a call runs on the one this pointer lives on
+static int use_device_of(const void *p) {
+  hipPointerAttribute_t a;
+  HIPCHK(hipPointerGetAttributes(&a, p));
+  if (a.device < 0) return fail("not a device pointer");
+  HIPCHK(hipSetDevice(a.device));
+  return 0;
+}
+// what every entry ends with, behind its launch
+static int launch_status() {
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" {
+
+int rmpc_advance_obstacles_device(int B, int nobst, double dt, double arena, double *d_obst_dyn, void *stream) {
+  if (B < 1 || nobst < 1 || !d_obst_dyn) return fail("bad argument");
+  const int n = B * nobst;
+  hipLaunchKernelGGL(k_obst_advance, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_obst_dyn, n, dt, arena);
+  return launch_status();
+}
+
+int rmpc_free_space_device(int B, int N, int P, int K, double max_radius, const double *d_points,
+                           const double *d_seeds, double *d_planes, void *stream) {
+  if (!d_points || !d_seeds || !d_planes) return fail("null argument");
+  if (B < 1 || N < 1 || K < 1 || P < 1 || P > 64) return fail("free space decomposition: need 1 <= P <= 64 points, K >= 1");
+  if (use_device_of(d_points)) return -1;
+  hipLaunchKernelGGL(k_fsd, dim3((B * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_points, d_seeds, d_planes,
+                     B, N, P, K, max_radius);
+  return launch_status();
+}
+
+/* the global planner (rmpc_grid.hpp): no handle; each call runs on the device its first pointer lives on */
+static bool grid_fits(long long a, long long b) { return a >= 0 && b >= 0 && (b == 0 || a <= INT_MAX / b); }
+static int grid_check(int H, int W, int movement) {
+  if (H < 1 || W < 1 || !grid_fits(H, W)) return fail("grid: need H, W >= 1");
+  if (movement != 4 && movement != 8) return fail("grid: movement must be 4 or 8");
+  return 0;
+}
+
+int rmpc_grid_inflate_device(int H, int W, double cell, double size_robot, double threshold, const double *d_grid,
+                             double *d_out, void *stream) {
+  if (!d_grid || !d_out) return fail("null argument");
+  if (grid_check(H, W, 8) || use_device_of(d_grid)) return -1;
+  if (!(cell > 0.0) || !(size_robot >= 0.0)) return fail("grid inflate: need cell > 0, size_robot >= 0");
+  const double kd = ceil(size_robot / cell);
+  if (kd > (double)(H + W)) return fail("grid inflate: window larger than the map");
+  hipLaunchKernelGGL(k_grid_inflate, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, d_out, H, W,
+                     (int)kd, threshold);
+  return launch_status();
+}
+
+int rmpc_grid_fields_device(int H, int W, const double *d_grid, int G, const int32_t *d_goal_cells, int movement,
+                            double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status,
+                            int32_t *d_sweeps, void *stream) {
+  if (!d_grid || !d_goal_cells || !d_fields || !d_status) return fail("null argument");
+  if (grid_check(H, W, movement)) return -1;
+  if (H * W > RMPC_GRID_MAX_CELLS)
+    return fail("grid fields: " + std::to_string(H) + "x" + std::to_string(W) + " map exceeds RMPC_GRID_MAX_CELLS = " +
+                std::to_string(RMPC_GRID_MAX_CELLS) + " cells (one field must fit in the LDS of a workgroup)");
+  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid fields: need 1 <= G and G*H*W <= INT_MAX");
+  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid fields: cost_factor must be finite and >= 0");
+  if (use_device_of(d_grid)) return -1;
+  hipLaunchKernelGGL(k_grid_fields, dim3(G), dim3(kGridThreads), 0, (hipStream_t)stream, d_grid, H, W,
+                     (const int *)d_goal_cells, movement, occ_threshold, cost_factor, d_fields, (int *)d_status,
+                     (int *)d_sweeps);
+  return launch_status();
+}
+
+int rmpc_grid_paths_device(int H, int W, const double *d_grid, int G, const double *d_fields, const int32_t *d_goal_cells,
+                           int B, const int32_t *d_start_cell, const int32_t *d_goal_index, int movement,
+                           double occ_threshold, double cost_factor, int max_len, int32_t *d_path, int32_t *d_len,
+                           void *stream) {
+  if (!d_grid || !d_fields || !d_goal_cells || !d_start_cell || !d_goal_index || !d_path || !d_len) return fail("null argument");
+  if (grid_check(H, W, movement)) return -1;
+  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid paths: need 1 <= G and G*H*W <= INT_MAX");
+  if (B < 1 || max_len < 1 || !grid_fits(B, max_len)) return fail("grid paths: need B, max_len >= 1 and B*max_len <= INT_MAX");
+  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid paths: cost_factor must be finite and >= 0");
+  if (use_device_of(d_grid)) return -1;
+  hipLaunchKernelGGL(k_grid_paths, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, d_fields,
+                     (const int *)d_goal_cells, G, (const int *)d_start_cell, (const int *)d_goal_index, B, movement,
+                     occ_threshold, cost_factor, max_len, (int *)d_path, (int *)d_len);
+  return launch_status();
+}
+
+int rmpc_grid_cells_device(int B, const double *d_pos, int stride, int H, int W, double x0, double y0, double cell,
+                           int32_t *d_cells, void *stream) {
+  if (!d_pos || !d_cells) return fail("null argument");
+  if (B < 1 || stride < 2 || !grid_fits(B, stride)) return fail("grid cells: need B >= 1, stride >= 2, B*stride <= INT_MAX");
+  if (grid_check(H, W, 8) || use_device_of(d_pos)) return -1;
+  if (!(cell > 0.0)) return fail("grid cells: need cell > 0");
+  hipLaunchKernelGGL(k_grid_cells, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_pos, stride, B, H, W, x0,
+                     y0, cell, (int *)d_cells);
+  return launch_status();
+}
+
+int rmpc_follow_path_device(int B, const int32_t *d_path, const int32_t *d_len, int max_len, int32_t *d_idx,
+                            const double *d_pos, int stride, int W, double x0, double y0, double cell, double threshold,
+                            double *d_goal, void *stream) {
+  if (!d_path || !d_len || !d_idx || !d_pos || !d_goal) return fail("null argument");
+  if (B < 1 || max_len < 1 || !grid_fits(B, max_len)) return fail("follow path: need B, max_len >= 1 and B*max_len <= INT_MAX");
+  if (stride < 2 || !grid_fits(B, stride) || W < 1) return fail("follow path: need stride >= 2, W >= 1");
+  if (use_device_of(d_path)) return -1;
+  hipLaunchKernelGGL(k_follow_path, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int *)d_path,
+                     (const int *)d_len, max_len, (int *)d_idx, d_pos, stride, B, W, x0, y0, cell, threshold, d_goal);
+  return launch_status();
+}
+
+/* the lidar (rmpc_sense.hpp): no handle; each call runs on the device its first pointer lives on */
+int rmpc_lidar_scan_device(int B, const rmpc_lidar *l, void *stream) {
+  if (!l) return fail("null argument");
+  if (l->struct_size != (int)sizeof(rmpc_lidar)) return fail("rmpc_lidar.struct_size mismatch");
+  if (B < 1 || l->rays < 1) return fail("lidar: need B >= 1 and rays >= 1");
+  if (l->pose_stride < 3) return fail("lidar: pose_stride must be >= 3 (x, y, heading)");
+  if (l->nbox < 0 || l->ncircle < 0) return fail("lidar: negative shape count");
+  if (!grid_fits(B, l->rays) || !grid_fits(B, l->pose_stride) || !grid_fits(l->nbox, 4) || !grid_fits(l->ncircle, 3))
+    return fail("lidar: B*rays, B*pose_stride, nbox*4 and ncircle*3 must not exceed INT_MAX");
+  if (!(l->range > 0.0) || std::isinf(l->range)) return fail("lidar: range must be positive and finite");
+  if (!l->pose || !l->points || (l->nbox > 0 && !l->boxes) || (l->ncircle > 0 && !l->circles)) return fail("null argument");
+  if (use_device_of(l->pose)) return -1;
+  const int n = B * l->rays;
+  const double step = (l->angle_max - l->angle_min) / (double)l->rays;
+  hipLaunchKernelGGL(k_lidar, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, l->pose, l->pose_stride, B,
+                     l->rays, l->angle_min, step, l->range, l->offset_x, l->offset_y, l->height, l->boxes, l->nbox,
+                     l->circles, l->ncircle, l->points, l->ranges);
+  return launch_status();
+}
+
+static int plan_points(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag, const double *d_pose,
+                       int pose_stride, int shift, int heading, double offset_x, double offset_y, double height,
+                       double *d_points, void *stream) {
+  if (!d_pose || !d_points) return fail("null argument");
+  if (B < 1 || N < 1) return fail("plan points: need B, N >= 1");
+  if (heading != 0 && heading != 1) return fail("plan points: heading must be 0 or 1");
+  if (pose_stride < 3) return fail("plan points: pose_stride must be >= 3 (x, y, heading)");
+  if (nvar < 3) return fail("plan points: nvar must be >= 3 (x, y, heading first)");
+  if (!grid_fits(B, N) || !grid_fits(B, pose_stride) || !grid_fits((long long)B * N, nvar))
+    return fail("plan points: B*N, B*pose_stride and B*N*nvar must not exceed INT_MAX");
+  if (use_device_of(d_z_prev ? (const void *)d_z_prev : (const void *)d_pose)) return -1;
+  hipLaunchKernelGGL(k_plan_points, dim3((B * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_z_prev, nvar,
+                     (const int *)d_exitflag, d_pose, pose_stride, B, N, shift, heading, offset_x, offset_y, height,
+                     d_points);
+  return launch_status();
+}
+
+int rmpc_plan_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
+                            const double *d_pose, int pose_stride, double offset_x, double offset_y, double height,
+                            double *d_points, void *stream) {
+  return plan_points(B, N, d_z_prev, nvar, d_exitflag, d_pose, pose_stride, 0, 1, offset_x, offset_y, height, d_points,
+                     stream);
+}
+
+/* fleet separation (rmpc_sense.hpp): no handle; each call runs on the device its first pointer lives on */
+int rmpc_fleet_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
+                             const double *d_pose, int pose_stride, int heading, double offset_x, double offset_y,
+                             double height, double *d_points, void *stream) {
+  return plan_points(B, N, d_z_prev, nvar, d_exitflag, d_pose, pose_stride, 1, heading, offset_x, offset_y, height,
+                     d_points, stream);
+}
+
+int rmpc_fleet_planes_device(int B, int N, const double *d_points, const double *d_radius, int K, double range,
+                             int nobst, int slot0, double *d_planes, void *stream) {
+  if (!d_points || !d_radius || !d_planes) return fail("null argument");
+  if (B < 1 || N < 1) return fail("fleet planes: need B, N >= 1");
+  if (K < 1 || K > rmpc::kFleetKMax) return fail("fleet planes: need 1 <= K <= 8");
+  if (slot0 < 0 || nobst < 1 || slot0 > nobst - K) return fail("fleet planes: need 0 <= slot0 and slot0 + K <= nobst");
+  if (!(range >= 0.0)) return fail("fleet planes: range must be >= 0 (+inf admits every robot)");
+  if (!grid_fits(B, N) || !grid_fits((long long)B * N, nobst) || !grid_fits((long long)B * N * nobst, 4))
+    return fail("fleet planes: B*N*nobst*4 must not exceed INT_MAX");
+  if (use_device_of(d_points)) return -1;
+  const int nbt = (B + 255) / 256;
+  hipLaunchKernelGGL(k_fleet_planes, dim3(nbt * N), dim3(256), 0, (hipStream_t)stream, d_points, d_radius, B, N, K,
+                     range * range, nobst, slot0, d_planes);
+  return launch_status();
+}
+
+}  // extern "C"

@@ -4,7 +4,8 @@
 // UBSan any undefined operation in the row, kinematics and dynamics code.  Test infrastructure only: nothing in the
 // product includes or links this file.  Build and run: tests/host/run_asan.sh.
 #include "host_prelude.h"
-#include "../../robot_mpcs_amd/csrc/rmpc_host.hip"   // (the device code and build_model / build_tables)
+#include "../../robot_mpcs_amd/csrc/rmpc_kernels.hip"   // (the device code)
+#include "../../robot_mpcs_amd/csrc/rmpc_desc.hpp"      // (build_model / build_tables)
 
 #include <vector>
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds tests/host/host_sweep.cpp for x86 with AddressSanitizer + UBSan and runs tests/host/check_host_sweeps.py under it
-# (the host unit rmpc_host.hip, with the device code it includes, compiled for the host; the harness instantiates the
-#  sweeps of three variants).
+# (the device code of rmpc_kernels.hip and the descriptor code of rmpc_desc.hpp, compiled for the host; the harness
+#  instantiates the sweeps of three variants).
 #   bash tests/host/run_asan.sh > profiles/rNN_host_device_functions_asan_ubsan.log 2>&1
 set -e
 cd "$(dirname "$0")/../.."
@@ -14,7 +14,7 @@ for f in tests/host/host_sweep.cpp tests/host/host_prelude.h $(grep -v '^#' robo
 done
 if [ $stale = 1 ]; then
   /opt/rocm/bin/hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -fno-omit-frame-pointer $SAN -ferror-limit=0 -fPIC \
-    -DRMPC_SOURCE_HASH='"host"' -Irobot_mpcs_amd/csrc -Iinclude -c tests/host/host_sweep.cpp -o $OBJ
+    -Irobot_mpcs_amd/csrc -Iinclude -c tests/host/host_sweep.cpp -o $OBJ
 fi
 # (the symbol the registration code refers to: the device code bundle of this file -- there is none)
 FAT=$(nm -u $OBJ | awk '/__hip_fatbin_/{print $2}' | head -1)
