@@ -166,6 +166,68 @@ __device__ __forceinline__ void for_range(F &&fn) {
 //   * single-variable rows (limits and simple bounds), grouped by variable (static
 //     loops; absent entries load row 0 and are masked -- a branch around a load,
 //     even a wave-uniform one, makes hipcc wait for every element separately).
+
+// Step lengths of one stage (k_step's arithmetic): the fraction-to-the-boundary minima over the rows and the merit
+// slope partial.  One copy of the row code for step_body and for the merged form inside sweep_body (PHASE 1): the
+// callers differ in where the inputs come from, not in what is done with them.
+template <class C>
+struct StepRow {
+  double ap = 1.0, ad = 1.0, gphi = 0.0;
+  template <int NV_>
+  __device__ __forceinline__ void slope(const double (&gfv)[NV_], const double (&dz)[NV_]) {
+#pragma unroll
+    for (int j = 0; j < NV_; j++) gphi += gfv[j] * dz[j];
+  }
+  __device__ __forceinline__ void row(const double mu, const double gdz, const double g, const double tv, const double lv) {
+    const double dt = gdz + (g - tv);
+    const double itv = frcp(tv);
+    const double dl = (mu - tv * lv - lv * dt) * itv;   // (same expression as in sweep_body's row_core)
+    // the steps themselves are not kept: the sweep recomputes them from the same inputs
+    // ratio tests with Newton reciprocals (the quotient of a non-negative step is discarded by the select)
+    const double rp = -C::TAU * tv * frcp(dt), rd = -C::TAU * lv * frcp(dl);
+    // (bitwise and: no short-circuit branch -- the rows of a stage stay one basic block)
+    ap = ((dt < 0) & (rp < ap)) ? rp : ap;
+    ad = ((dl < 0) & (rd < ad)) ? rd : ad;
+    gphi -= mu * dt * itv;
+  }
+  // distance row r: jq = its gradient at the current iterate
+  template <class V, int NV_>
+  __device__ __forceinline__ void fk_row(const double mu, const double (&dz)[NV_], const double g, const double tv, const double lv,
+                                         const double (&jq)[C::NQ]) {
+    double gdz = 0.0;
+#pragma unroll
+    for (int a = 0; a < C::NQ; a++) gdz += jq[a] * dz[a];
+    if constexpr (C::NS > 0) gdz += dz[C::NX];
+    row(mu, gdz, g, tv, lv);
+  }
+  // single-variable row (j, u) (present: v_row(j, u) >= 0); gl: its stored value (general rows only)
+  template <class V, int NV_>
+  __device__ __forceinline__ void var_row(const V &v, const int k, const double mu, const int j, const int u, const double (&z)[NV_],
+                                          const double (&dz)[NV_], const double gl, const double tv, const double lv) {
+    const bool general = v.v_poff(j, u) >= 0;
+    const double gvv = general ? gl : ((k == 0 && j < C::NX) ? 1.0 : (double)v.v_sgn(j, u) * (z[j] - v.v_val(j, u)));
+    double gdz = (double)v.v_sgn(j, u) * dz[j];
+    if constexpr (C::NS > 0) { if (v.v_soft(j, u)) gdz += dz[C::NX]; }
+    row(mu, gdz, gvv, tv, lv);
+  }
+};
+
+// inputs of a distance row of the sweep: slack, multiplier, value and gradient at the current iterate, obstacle, weight
+template <int NQ_>
+struct SweepFkBuf { double tcv, lcv, gold, jo[NQ_], op[4], wi; };
+// What sweep_body requests at its top, before the trial point can be formed.  A local of the body; the merged call of
+// the fused kernel (PHASE 1 / 2) keeps it in registers across the reduction of the step lengths, together with the
+// slacks and multipliers of the single-variable rows (vt, vl: otherwise requested two variables ahead of their rows).
+template <class C, class V>
+struct SweepTop {
+  static constexpr int NFKC = []() { if constexpr (V::SPEC) return V::nfkrows() > 0 ? V::nfkrows() : 1; else return 1; }();
+  double zo[C::NV], dzo[C::NV];   // current iterate and step of this stage (the row steps are recomputed from them)
+  double x1[C::NX], dx1[C::NX], n0[C::NX], n0n[C::NX], n1[C::NX], n1n[C::NX];
+  double wuv[C::NU], wsv, rbody, goalv[3], wgoalv[3];
+  SweepFkBuf<C::NQ> fkb[NFKC];
+  double vt[C::NV][kVarRows], vl[C::NV][kVarRows];
+};
+
 // What one lane -- one (instance, stage) pair -- of the stage-parallel sweep addresses.  Element `slot` of an
 // array is ptr[slot * SS + loff]: the batch-minor SoA of the pass kernels (SS = N * Bp, loff = k * Bp + b,
 // next stage kstride = Bp) and the per-instance layout of the fused kernel ([instance][slot][32 stages]:
@@ -230,10 +292,17 @@ struct SweepK { int N; double dt; int use_curv; };
 // FIRSTC: 1 / 0 = the first pass of a solve (or not) known at compile time, -1 = taken from first_rt.  The rows
 // branch on it; callers that can afford two copies of the body (every kernel here) pass it as a constant so that
 // the rows of a stage form one basic block and their requests are issued together.
-template <class C, int EARLY_MODE = -1, class RP = gdouble, class V = RtView, int FIRSTC = -1>
+// PHASE: 0 = the whole body.  1 / 2 = the merged form of the fused kernel, for passes that are not the first of a solve:
+// 1 issues every request of the stage once -- what the body needs at its top and the slacks and multipliers of all the
+// single-variable rows (top) -- and forms the step lengths of the stage from the loaded values (slen: what step_body
+// computes, same rows in the same order); 2 continues from the registers of `top` with the step lengths the caller
+// reduced over the stages in between, and requests none of tc, lc, gro, jqo, zc, dzp again.
+template <class C, int EARLY_MODE = -1, class RP = gdouble, class V = RtView, int FIRSTC = -1, int PHASE = 0>
 __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const SweepIO<RP> &io, const int k,
                                            const bool first_rt, const bool nostep, const double alpha, const double adual,
-                                           const double mu, Partials &out, ldouble *const qacc = nullptr) {
+                                           const double mu, Partials &out, ldouble *const qacc = nullptr,
+                                           SweepTop<C, V> *const top = nullptr, StepRow<C> *const slen = nullptr) {
+  static_assert(PHASE == 0 || (FIRSTC == 0 && V::SPEC), "the merged form: static rows, not the first pass of a solve");
   const bool first = FIRSTC < 0 ? first_rt : (FIRSTC != 0);
   // (FKCURV, k_sweep) the two 7 x 7 blocks of the q variables are accumulated in LDS, one column of 2 x 28 doubles per
   // lane (qacc, lane stride kSweepBlock): they are touched once per FK point and by the joint-limit rows only, and the
@@ -267,15 +336,17 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
 
   // ---- trial stage vector, costates, next stage's state ------------------------
   double z[NV], xk1[NX], nuk[NX], nun[NX];
-  double zo[NV], dzo[NV];   // current iterate and step of this stage (the row steps are recomputed from them)
+  SweepTop<C, V> top_local;
+  SweepTop<C, V> &T = PHASE == 0 ? top_local : *top;
+  auto &zo = T.zo; auto &dzo = T.dzo;
   const unsigned loff1 = loff + (k < N - 1 ? io.kstride : 0u);  // next stage, clamped: loads stay unconditional
   const bool warm = first && (io.warm != 0);
   // multipliers the rows start from: the current buffer, or (warm first pass) the previous solve's, one stage on
   const gdouble *__restrict__ lsrc = warm ? io.wl : lc;
   const unsigned loffl = warm ? loff1 : loff;
 #define IDXLL(slot) ((size_t)(slot) * SS + loffl)
-  double x1[NX], dx1[NX], n0[NX], n0n[NX], n1[NX], n1n[NX];
-  {
+  auto &x1 = T.x1; auto &dx1 = T.dx1; auto &n0 = T.n0; auto &n0n = T.n0n; auto &n1 = T.n1; auto &n1n = T.n1n;
+  if constexpr (PHASE != 2) {
     const size_t SSd = io.SSd;
     const unsigned loffd = io.loffd, loffd1 = io.loffd + (k < N - 1 ? io.kstrided : 0u);
 #pragma unroll
@@ -294,17 +365,22 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
   // tables the requests stay where the arithmetic is, as before.
   // (the arms too, over the runtime tables: their sweep waits on memory for 63 % of its cycles -- 114 -> 110 us)
   constexpr bool PIPE = V::SPEC || C::FKCURV || std::is_same<V, GView>::value;
-  double wuv[NU], wsv = 0.0, goalv[3] = {0, 0, 0}, wgoalv[3] = {0, 0, 0};
+  auto &wuv = T.wuv; auto &wsv = T.wsv; auto &goalv = T.goalv; auto &wgoalv = T.wgoalv;
+  if constexpr (PHASE != 2) {
+    wsv = 0.0;
 #pragma unroll
-  for (int j = 0; j < NU; j++) wuv[j] = P(v.off_wu() + j);
-  if constexpr (NS > 0) wsv = P(v.off_ws());
-  const double rbody = (v.off_r_body() >= 0) ? P(v.off_r_body()) : 0.0;
-  if (v.has_goal()) {
+    for (int c = 0; c < 3; c++) { goalv[c] = 0.0; wgoalv[c] = 0.0; }
 #pragma unroll
-    for (int c = 0; c < 3; c++) { goalv[c] = P(v.off_goal() + c); wgoalv[c] = P(v.off_wgoal() + c); }
+    for (int j = 0; j < NU; j++) wuv[j] = P(v.off_wu() + j);
+    if constexpr (NS > 0) wsv = P(v.off_ws());
+    T.rbody = (v.off_r_body() >= 0) ? P(v.off_r_body()) : 0.0;
+    if (v.has_goal()) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) { goalv[c] = P(v.off_goal() + c); wgoalv[c] = P(v.off_wgoal() + c); }
+    }
   }
-  // inputs of a distance row: slack, multiplier, value and gradient at the current iterate, obstacle, weight
-  struct FkBuf { double tcv, lcv, gold, jo[NQ], op[4], wi; };
+  const double rbody = T.rbody;
+  using FkBuf = SweepFkBuf<NQ>;
   auto fk_load = [&](const int r, FkBuf &Bf) __attribute__((always_inline)) {
     const int i = v.fk_row(r), kind = v.fk_kind(r), ob = v.fk_obst(r), fi = v.fk_idx(r);
     Bf.tcv = tc[IDXL(i)]; Bf.lcv = lsrc[IDXLL(i)]; Bf.gold = gro[IDXL(i)];
@@ -322,9 +398,9 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
     Bf.wi = 0.0;
     if (v.has_avoid() && v.fk_first(r)) Bf.wi = P(v.off_wconstr() + v.fk_mod(r));
   };
-  constexpr int NFKC = []() { if constexpr (V::SPEC) return V::nfkrows() > 0 ? V::nfkrows() : 1; else return 1; }();
-  FkBuf fkb[NFKC];
-  if constexpr (V::SPEC) {   // (the rows of a generated view are static: their inputs are requested here, all at once)
+  constexpr int NFKC = SweepTop<C, V>::NFKC;
+  auto &fkb = T.fkb;
+  if constexpr (V::SPEC && PHASE != 2) {   // (the rows of a generated view are static: their inputs are requested here, all at once)
     for_range<0, NFKC>([&](auto rc) __attribute__((always_inline)) {
       constexpr int r = decltype(rc)::value;
       if constexpr (r < V::nfkrows()) fk_load(r, fkb[r]);
@@ -340,14 +416,51 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
       const int i = v.v_row(j, u);
       const int ii = i >= 0 ? i : 0;
       const int po = v.v_poff(j, u);
-      Bv.tcv[u] = tc[IDXL(ii)];
-      Bv.lcv[u] = lsrc[IDXLL(ii)];
+      if constexpr (PHASE == 0) {   // (merged form: requested once, at the top of the call -- T.vt / T.vl)
+        Bv.tcv[u] = tc[IDXL(ii)];
+        Bv.lcv[u] = lsrc[IDXLL(ii)];
+      }
       const double pl = pp[IDXL(po >= 0 ? po : 0)];
       Bv.lim[u] = po >= 0 ? pl : v.v_val(j, u);
       Bv.wi[u] = 0.0;
       if (i >= 0 && v.has_avoid() && v.v_first(j, u)) Bv.wi[u] = P(v.off_wconstr() + v.v_mod(j, u));
     }
   };
+  if constexpr (PHASE == 1) {
+    // ---- merged form: the rest of the stage's requests, then the step lengths from the loaded values -------------
+    // (what step_body does, on the words the sweep holds anyway; only the cost gradient and the stored values of the
+    //  general rows are requested for the step lengths alone)
+    double gfv[NV], gl[NV][kVarRows];
+#pragma unroll
+    for (int j = 0; j < NV; j++) {
+      gfv[j] = gfa[IDXL(j)];
+#pragma unroll
+      for (int u = 0; u < kVarRows; u++) {
+        const int i = v.v_row(j, u);
+        gl[j][u] = 0.0;
+        if (i < 0) continue;   // (static rows)
+        T.vt[j][u] = tc[IDXL(i)];
+        T.vl[j][u] = lc[IDXL(i)];
+        if (v.v_poff(j, u) >= 0) gl[j][u] = gro[IDXL(i)];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    StepRow<C> &sr = *slen;
+    sr.slope(gfv, dzo);
+    for_range<0, V::nfkrows()>([&](auto rc) __attribute__((always_inline)) {
+      constexpr int r = decltype(rc)::value;
+      sr.template fk_row<V>(mu, dzo, fkb[r].gold, fkb[r].tcv, fkb[r].lcv, fkb[r].jo);
+    });
+#pragma unroll
+    for (int j = 0; j < NV; j++) {
+#pragma unroll
+      for (int u = 0; u < kVarRows; u++) {
+        if (v.v_row(j, u) < 0) continue;
+        sr.template var_row<V>(v, k, mu, j, u, zo, dzo, gl[j][u], T.vt[j][u], T.vl[j][u]);
+      }
+    }
+    return;
+  }
   const double al = alpha, adl = adual;
   // ---- trial point -----------------------------------------------------------------------------------
   {
@@ -492,7 +605,10 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
       double gold = neutral ? 1.0 : sg * (zo[j] - Bv.lim[u]);
       double gdz = sg * dzo[j];
       if constexpr (NS > 0) { if (soft) { gold += zo[NX]; gdz += dzo[NX]; } }
-      const RowW rw = row_core(i, g, Bv.tcv[u], Bv.lcv[u], gold, gdz);
+      double tcv, lcv;
+      if constexpr (PHASE == 0) { tcv = Bv.tcv[u]; lcv = Bv.lcv[u]; }
+      else { tcv = T.vt[j][u]; lcv = T.vl[j][u]; }
+      const RowW rw = row_core(i, g, tcv, lcv, gold, gdz);
       // (a neutralised row contributes nothing; by selection, not by a branch: in the fused kernel the stage differs
       //  from lane to lane and a divergent `continue` cuts the rows of a variable into exec-masked blocks)
       q0[j] = neutral ? q0[j] : q0[j] + sg * rw.ca;
@@ -1785,22 +1901,8 @@ __device__ __forceinline__ void step_body(const V &v, const StepIO<RP> &io, cons
     z[j] = zc[IDXL(j)];
     gfv[j] = io.gfa[IDXL(j)];
   }
-  double gphi = 0.0;
-#pragma unroll
-  for (int j = 0; j < NV; j++) gphi += gfv[j] * dz[j];
-  double ap = 1.0, ad = 1.0;
-  auto row = [&](int i, double gdz, double g, double tv, double lv) __attribute__((always_inline)) {
-    const double dt = gdz + (g - tv);
-    const double itv = frcp(tv);
-    const double dl = (mu - tv * lv - lv * dt) * itv;   // (same expression as in sweep_body's row_core)
-    (void)i;  // the steps themselves are not stored: the sweep recomputes them from the same inputs
-    // ratio tests with Newton reciprocals (the quotient of a non-negative step is discarded by the select)
-    const double rp = -C::TAU * tv * frcp(dt), rd = -C::TAU * lv * frcp(dl);
-    // (bitwise and: no short-circuit branch -- the rows of a stage stay one basic block)
-    ap = ((dt < 0) & (rp < ap)) ? rp : ap;
-    ad = ((dl < 0) & (rd < ad)) ? rd : ad;
-    gphi -= mu * dt * itv;
-  };
+  StepRow<C> sr;   // (the row arithmetic: shared with the merged form in sweep_body)
+  sr.slope(gfv, dz);
   // Every request of the phase leaves before the first row is evaluated (one wavefront per SIMD hides no latency by
   // itself; left where the arithmetic is, the compiler waits for each small group of loads in turn: a dozen round
   // trips to L2 per call instead of one).  The rows are then evaluated in the old order (the merit slope is a sum).
@@ -1812,11 +1914,8 @@ __device__ __forceinline__ void step_body(const V &v, const StepIO<RP> &io, cons
     for (int a = 0; a < NQ; a++) f.jq[a] = Jq[IDXL(fi * NQ + a)];
   };
   auto fk_row_body = [&](const int r, const FkIn &f) __attribute__((always_inline)) {
-    double gdz = 0.0;
-#pragma unroll
-    for (int a = 0; a < NQ; a++) gdz += f.jq[a] * dz[a];
-    if constexpr (NS > 0) gdz += dz[NX];
-    row(v.fk_row(r), gdz, f.g, f.tv, f.lv);
+    (void)r;
+    sr.template fk_row<V>(mu, dz, f.g, f.tv, f.lv, f.jq);
   };
   constexpr int NFKC = []() { if constexpr (V::SPEC) return V::nfkrows() > 0 ? V::nfkrows() : 1; else return 1; }();
   FkIn fkin[NFKC];
@@ -1854,11 +1953,7 @@ __device__ __forceinline__ void step_body(const V &v, const StepIO<RP> &io, cons
       for (int u = 0; u < kVarRows; u++) {
         const int i = v.v_row(j, u);
         if (i < 0) continue;
-        const bool general = v.v_poff(j, u) >= 0;
-        const double gvv = general ? glv[jj][u] : ((k == 0 && j < NX) ? 1.0 : (double)v.v_sgn(j, u) * (z[j] - v.v_val(j, u)));
-        double gdz = (double)v.v_sgn(j, u) * dz[j];
-        if constexpr (NS > 0) { if (v.v_soft(j, u)) gdz += dz[NX]; }
-        row(i, gdz, gvv, tvv[jj][u], lvv[jj][u]);
+        sr.template var_row<V>(v, k, mu, j, u, z, dz, glv[jj][u], tvv[jj][u], lvv[jj][u]);
       }
     }
   };
@@ -1887,7 +1982,7 @@ __device__ __forceinline__ void step_body(const V &v, const StepIO<RP> &io, cons
     __builtin_amdgcn_sched_barrier(0);
     chunk_rows(std::integral_constant<int, c0>{});
   });
-  ap_out = ap; ad_out = ad; gphi_out = gphi;
+  ap_out = sr.ap; ad_out = sr.ad; gphi_out = sr.gphi;
 }
 
 template <class C, class V>
@@ -2122,9 +2217,10 @@ __device__ __noinline__ RMPC_ONE_WAVE StepRes fused_step_call(const FusedWs *Fp,
 
 // Generated views, records in LDS: the step lengths of a fresh step are formed at the beginning of the sweep call
 // instead of after the recursion -- the whole wavefront calls (the reductions over the 32
-// lanes of the instance run inside), lanes without work skip the bodies.  The slacks and multipliers the step phase
-// reads are then read again by the sweep a few thousand cycles later (L2) instead of a whole recursion later (fabric),
-// and a pass is two calls: this one and the recursion (1.90-1.94 -> 1.97-2.03 M solves/s, same results).
+// lanes of the instance run inside), lanes without work skip the bodies.  A pass is two calls: this one and the
+// recursion (1.90-1.94 -> 1.97-2.03 M solves/s, same results).  The step lengths and the sweep share one set of
+// requests: what both read (slacks, multipliers, row values and gradients, iterate, step) is requested once, at the
+// top of the call, and the sweep continues from registers (sweep_body, PHASE 1 / 2).
 // What the call hands back, per instance (identical in the 32 lanes of a half: the reductions over the stages run
 // inside the call): the reduced partials of the sweep and the step lengths.  Through LDS, not by value -- an
 // aggregate of this size is returned in memory, i.e. through scratch: a store, a full wait before the return, and a
@@ -2148,49 +2244,54 @@ __device__ __noinline__ RMPC_ONE_WAVE void fused_sweep_step_call(__attribute__((
   const size_t S = kFusedStages;
   const FusedCur Pw = fused_cur(F, b, cur);
   const V v{};
-  double ap = 1.0, ad = 1.0, gp = 0.0;
-#ifdef RMPC_STAMPS
-  const long long ss_t0 = __builtin_amdgcn_s_memtime();
-#endif
-  if (fresh && live) {
-    StepIO<ldouble> io;
-    io.zc = Pw.zc; io.tc = Pw.tc; io.lc = Pw.lc; io.grow = Pw.gc; io.Jq = Pw.jc;
-    io.gfa = Pw.pgf;
-    io.SS = S; io.loff = (unsigned)k;
-    io.dz = slots + DZ_OFF; io.SSd = 1; io.loffd = (unsigned)(k * GS);
-    step_body<C, ldouble, V>(v, io, k, mu, ap, ad, gp);
-  }
-#ifdef RMPC_STAMPS
-  const long long ss_t1 = __builtin_amdgcn_s_memtime();
-#endif
-  {
-    double rs1[1] = {gp}, rm0[1] = {0.0}, rn2[2] = {ap, ad};
-    wave_reduce_many<kFusedStages>(rs1, rm0, rn2);
-    gp = rs1[0]; ap = rn2[0]; ad = rn2[1];
-  }
-#ifdef RMPC_STAMPS
-  const long long ss_t2 = __builtin_amdgcn_s_memtime();
-#endif
+  SweepIO<ldouble> io;
+  io.zc = Pw.zc; io.tc = Pw.tc; io.lc = Pw.lc; io.nc = Pw.nc;
+  io.zn = Pw.zn; io.tn = Pw.tn; io.ln = Pw.ln; io.nn = Pw.nn;
+  io.pp = Pw.pp; io.gro = Pw.gc; io.jqo = Pw.jc; io.grn = Pw.gn; io.jqn = Pw.jn;
+  io.gfa = Pw.pgf;
+  io.SS = S; io.loff = (unsigned)k; io.kstride = 1u;
+  io.rec = slots + k * GS;
+  io.dzp = slots + DZ_OFF; io.nup = slots + DZ_OFF + NV;
+  io.SSd = 1; io.loffd = (unsigned)(k * GS); io.kstrided = (unsigned)GS;
+  io.wl = Pw.pwl; io.wn = Pw.pwn; io.warm = warm;
+  const SweepK sk = {N, dt, use_curv};
   SweepStepRes r;
-  r.amin_p = fresh ? fmin(amin_p_in, ap) : amin_p_in;
-  r.amin_d = fresh ? fmin(amin_d_in, ad) : amin_d_in;
-  r.gphi = fresh ? gp : gphi_in;
-  const double alpha = nostep ? 0.0 : ldexp(r.amin_p, -ls), adual = nostep ? 0.0 : r.amin_d;
   const Partials qn = {0, 0, 0, 0, 0, 0, 0, 0, 1e300, 0};
   r.q = qn;
-  if (live) {
-    SweepIO<ldouble> io;
-    io.zc = Pw.zc; io.tc = Pw.tc; io.lc = Pw.lc; io.nc = Pw.nc;
-    io.zn = Pw.zn; io.tn = Pw.tn; io.ln = Pw.ln; io.nn = Pw.nn;
-    io.pp = Pw.pp; io.gro = Pw.gc; io.jqo = Pw.jc; io.grn = Pw.gn; io.jqn = Pw.jn;
-    io.gfa = Pw.pgf;
-    io.SS = S; io.loff = (unsigned)k; io.kstride = 1u;
-    io.rec = slots + k * GS;
-    io.dzp = slots + DZ_OFF; io.nup = slots + DZ_OFF + NV;
-    io.SSd = 1; io.loffd = (unsigned)(k * GS); io.kstrided = (unsigned)GS;
-    io.wl = Pw.pwl; io.wn = Pw.pwn; io.warm = warm;
-    const SweepK sk = {N, dt, use_curv};
-    sweep_body<C, -1, ldouble, V, FIRSTC>(sk, v, io, k, FIRSTC != 0, nostep, alpha, adual, mu, r.q);
+#ifdef RMPC_STAMPS
+  const long long ss_t0 = __builtin_amdgcn_s_memtime();
+  long long ss_t1 = ss_t0, ss_t2 = ss_t0;
+#endif
+  if constexpr (FIRSTC != 0) {
+    // the first pass of a solve takes no step: nothing to merge
+    r.amin_p = amin_p_in; r.amin_d = amin_d_in; r.gphi = gphi_in;
+    if (live) sweep_body<C, -1, ldouble, V, FIRSTC>(sk, v, io, k, true, nostep, 0.0, 0.0, mu, r.q);
+  } else {
+    // One set of requests per pass: the top of the sweep (PHASE 1) asks for every word of the stage once and forms
+    // the step lengths from the loaded values while the words only the sweep needs are still on their way; the sweep
+    // (PHASE 2) continues from the registers.  Every live lane forms the step lengths -- on a pass that is not fresh
+    // (line-search retry, null pass) from a step that may be stale -- and `fresh` selects: the two halves of the
+    // wavefront may differ in it, and a divergent branch around the requests would serialise them.
+    SweepTop<C, V> top;
+    StepRow<C> sl;
+    if (live) sweep_body<C, -1, ldouble, V, 0, 1>(sk, v, io, k, false, nostep, 0.0, 0.0, mu, r.q, nullptr, &top, &sl);
+    double ap = (fresh && live) ? sl.ap : 1.0, ad = (fresh && live) ? sl.ad : 1.0, gp = (fresh && live) ? sl.gphi : 0.0;
+#ifdef RMPC_STAMPS
+    ss_t1 = __builtin_amdgcn_s_memtime();
+#endif
+    {
+      double rs1[1] = {gp}, rm0[1] = {0.0}, rn2[2] = {ap, ad};
+      wave_reduce_many<kFusedStages>(rs1, rm0, rn2);
+      gp = rs1[0]; ap = rn2[0]; ad = rn2[1];
+    }
+#ifdef RMPC_STAMPS
+    ss_t2 = __builtin_amdgcn_s_memtime();
+#endif
+    r.amin_p = fresh ? fmin(amin_p_in, ap) : amin_p_in;
+    r.amin_d = fresh ? fmin(amin_d_in, ad) : amin_d_in;
+    r.gphi = fresh ? gp : gphi_in;
+    const double alpha = nostep ? 0.0 : ldexp(r.amin_p, -ls), adual = nostep ? 0.0 : r.amin_d;
+    if (live) sweep_body<C, -1, ldouble, V, 0, 2>(sk, v, io, k, false, nostep, alpha, adual, mu, r.q, nullptr, &top);
   }
 #ifdef RMPC_STAMPS
   r.q.tk[4] = ss_t1 - ss_t0; r.q.tk[5] = ss_t2 - ss_t1;
@@ -2276,6 +2377,7 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
   long long st_sweep = 0, st_dec = 0, st_ric = 0, st_step = 0, st_t0 = __builtin_amdgcn_s_memtime(), st_a, st_b;
   long long st_sw[6] = {0, 0, 0, 0, 0, 0}, st_sw2[2] = {0, 0};
   int st_ipass = 0;   // instance passes of this wavefront (both halves)
+  int st_both = 0;    // wavefront passes in which both copies of the sweep call ran (the halves differed in `first`)
 #define STAMP_A() st_a = __builtin_amdgcn_s_memtime()
 #define STAMP_B(acc) do { st_b = __builtin_amdgcn_s_memtime(); acc += st_b - st_a; st_a = st_b; } while (0)
 #else
@@ -2387,6 +2489,9 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
     // which copy of the sweep the lane runs this pass (first pass of its instance or not): the two halves of the
     // wavefront may differ (both copies then run, one after the other); an idle half follows its partner
     const bool v1 = act ? first : (__ballot(act && first) != 0ull);
+#ifdef RMPC_STAMPS
+    st_both += (__ballot(v1) != 0ull && __ballot(!v1) != 0ull) ? 1 : 0;
+#endif
     STAMP_A();
     // ---- sweep: trial point, model functions, condensing, stage partials -------------------------------
     Partials q = {0, 0, 0, 0, 0, 0, 0, 0, 1e300, 0};
@@ -2459,7 +2564,6 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
     const double mu_r = s.mu;
     const double cw_r = usec ? (C::CSCALE ? s.theta_c : 1.0) : 0.0;   // weight of the curvature terms in this recursion
     bool rec_ok = true;
-    double ap = 1.0, ad = 1.0, gp = 0.0;
     if (recurse) {
       bool ok;
       if constexpr (REC_LDS) {
@@ -2480,23 +2584,27 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
     GSYNC();   // dz, nunew
     STAMP_B(st_ric);
     // ---- step lengths of the new step -----------------------------------------------------------------
-    const bool stepping = !MERGE2 && act && (s.status == ST_ACTIVE) && (s.newstep != 0);
-    park();
-    if (stepping && stage) {
-      const FusedWs *const Fp = (const FusedWs *)(Tp + 1);
-      const StepRes sr = fused_step_call<C, VC, REC_LDS>(Fp, b, s.cur, k, slots, s.mu);
-      ap = sr.ap; ad = sr.ad; gp = sr.gp;
-    }
-    unpark();
-    {
-      double rs1[1] = {gp}, rm0[1] = {0.0}, rn2[2] = {ap, ad};
-      wave_reduce_many<LPI>(rs1, rm0, rn2);
-      gp = rs1[0]; ap = rn2[0]; ad = rn2[1];
-    }
-    if (stepping) {
-      s.amin_p = fmin(s.amin_p, ap);
-      s.amin_d = fmin(s.amin_d, ad);
-      gphi_sum = gp;
+    // (MERGE2: formed inside the next sweep call -- nothing to park, call or reduce here)
+    if constexpr (!MERGE2) {
+      double ap = 1.0, ad = 1.0, gp = 0.0;
+      const bool stepping = act && (s.status == ST_ACTIVE) && (s.newstep != 0);
+      park();
+      if (stepping && stage) {
+        const FusedWs *const Fp = (const FusedWs *)(Tp + 1);
+        const StepRes sr = fused_step_call<C, VC, REC_LDS>(Fp, b, s.cur, k, slots, s.mu);
+        ap = sr.ap; ad = sr.ad; gp = sr.gp;
+      }
+      unpark();
+      {
+        double rs1[1] = {gp}, rm0[1] = {0.0}, rn2[2] = {ap, ad};
+        wave_reduce_many<LPI>(rs1, rm0, rn2);
+        gp = rs1[0]; ap = rn2[0]; ad = rn2[1];
+      }
+      if (stepping) {
+        s.amin_p = fmin(s.amin_p, ap);
+        s.amin_d = fmin(s.amin_d, ad);
+        gphi_sum = gp;
+      }
     }
     STAMP_B(st_step);
   }
@@ -2508,7 +2616,8 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
       for (int i = 0; i < 6; i++) o2[i] = st_sw[i];
       o2[6] = st_sw2[0]; o2[7] = st_sw2[1];
     }
-    o[0] = st_sweep; o[1] = st_dec; o[2] = st_ric; o[3] = st_step; o[4] = __builtin_amdgcn_s_memtime() - st_t0; o[5] = pass;
+    o[0] = st_sweep; o[1] = st_dec; o[2] = st_ric; o[3] = st_step; o[4] = __builtin_amdgcn_s_memtime() - st_t0;
+    o[5] = (long long)pass | ((long long)st_both << 32);   // (low word: passes of the wavefront; high word: those with both sweep copies)
     o[6] = st_t0; o[7] = st_ipass;
   }
 #endif

@@ -18,8 +18,13 @@ s.solve(sc.xinit, sc.x0, sc.params)
 r = s.solve(sc.xinit, sc.x0, sc.params)
 # the launch is a queue drained by at most one wavefront per SIMD (4 x compute units; RMPC_FUSED_GRID overrides)
 nb = min((B + 1) // 2, int(os.environ.get("RMPC_FUSED_GRID", "1024")))
-both = s.fused_stamps(2 * nb).astype(float)
-st, sec = both[:nb], both[nb:]
+both = s.fused_stamps(2 * nb)
+st, sec = both[:nb].astype(float), both[nb:].astype(float)
+# word 5 of a wavefront's record: its passes (low half) and how many of them ran both copies of the sweep call, the one
+# for an instance's first pass and the one for the others, because its two halves differed (high half)
+raw5 = both[:nb, 5].astype(np.int64)
+st[:, 5] = (raw5 & 0xffffffff).astype(float)
+double_sweeps = (raw5 >> 32).astype(float)
 tot = st[:, 4]
 print(f"{cfg} B={B}: wavefronts {len(st)}, passes per wavefront mean {st[:, 5].mean():.1f} max {st[:, 5].max():.0f}, "
       f"instance passes per wavefront pass {st[:, 7].sum() / st[:, 5].sum():.2f} (2 = both halves busy), "
@@ -27,7 +32,11 @@ print(f"{cfg} B={B}: wavefronts {len(st)}, passes per wavefront mean {st[:, 5].m
 for i, name in enumerate(["sweep", "decide", "riccati", "step"]):
     print(f"  {name:8s} {st[:, i].sum() / tot.sum() * 100:5.1f} %   cycles per pass {st[:, i].sum() / st[:, 5].sum():9.0f}")
 if sec[:, :6].sum() > 0:
-    for i, name in enumerate(["top loads + trial point", "objective, kinematics, distance rows", "single-variable rows", "dynamics, records, log",
-                              "step lengths (inside the sweep call)", "their reduction", "after the call: unpark + reductions", "ordering point (wait for the stores)"]):
-        print(f"     sweep / {name:38s} {sec[:, i].sum() / st[:, 5].sum():9.0f}")
+    # generated views (merged call): the stage's requests leave once, in section 5, which also forms the step lengths
+    # from them; section 1 is then the trial point alone.  Runtime tables: section 1 holds the top loads, 5 and 6 are empty.
+    for i, name in enumerate(["trial point (runtime tables: + top loads)", "objective, kinematics, distance rows", "single-variable rows", "dynamics, records, log",
+                              "top loads + step lengths (merged call)", "reduction of the step lengths", "after the call: unpark + reductions", "ordering point (wait for the stores)"]):
+        print(f"     sweep / {name:42s} {sec[:, i].sum() / st[:, 5].sum():9.0f}")
+    print(f"  wavefront passes with both copies of the sweep call: {double_sweeps.sum():.0f} of {st[:, 5].sum():.0f} "
+          f"({double_sweeps.sum() / st[:, 5].sum() * 100:.2f} %), per wavefront {double_sweeps.mean():.2f}")
 print(f"  total cycles per pass {tot.sum() / st[:, 5].sum():.0f}   (s_memtime: shader clock)")
