@@ -453,6 +453,26 @@ int rmpc_debug_sweep(rmpc_handle *h, int B, const double *xinit, const double *x
                      const double *params, double *out_Q, double *out_q0,
                      double *out_q1, double *out_rc, double *out_g, double *out_f);
 
+/* Debug / parity hook (tests only): ONE first sweep and ONE Riccati recursion of B instances on the path this handle
+ * runs in production -- the pass kernels (k_sweep, then k_riccati / k_riccati_lane as the batch size and the
+ * development switches select them) or, on a fused handle, the phase functions of k_fused / k_fused_arm -- and the
+ * Newton step that came out.  lam_w [B][N][m], nu_w [B][N][nx], mu_w [B]: multipliers, costates and final barrier
+ * parameter of a previous solve as a warm-started handle stores them (stage k starts from the values of stage k + 1);
+ * all three NULL: the cold first pass.  The recursion runs on the Gauss-Newton blocks (no curvature terms), so that
+ * the returned blocks are what it consumed.  Instance-major outputs: out_Q [B][N][nvar*nvar], out_q0 / out_q1
+ * [B][N][nvar] (q = q0 - mu q1), out_rc [B][N][nx] as rmpc_debug_sweep; out_t / out_lam [B][N][m] slacks and
+ * multipliers the blocks were built with, out_mu [B]; out_dz [B][N][nvar] the step, out_nu [B][N][nx] the new
+ * costates (stage 0, the multiplier of the fixed first state, is formed by no path and read by nothing: zeros),
+ * out_ok [B] the recursion's return value (1: every control block was positive definite).  Forgets the
+ * stored multipliers of a warm-started handle.  m_rows: the m the caller sized out_t / out_lam
+ * for (refused when it is not the model's).  out_path [4] (may be NULL): what the handle holds of the switches that
+ * select the path -- fused kernel (0 none, 1 k_fused, 2 k_fused_arm), the lane-per-instance setting (RMPC_RIC_LANE:
+ * 0 never, 1 large lists, 2 always), parts per stage of k_fused_arm (0: not that kernel), 1 when a generated view runs. */
+int rmpc_debug_step(rmpc_handle *h, int B, const double *xinit, const double *x0, const double *params,
+                    const double *lam_w, const double *nu_w, const double *mu_w, double *out_Q, double *out_q0,
+                    double *out_q1, double *out_rc, double *out_t, double *out_lam, double *out_mu, double *out_dz,
+                    double *out_nu, int32_t *out_ok, int m_rows, int32_t *out_path);
+
 /* Generated solvers.  The reference has FORCES Pro generate C code for ONE problem (mpcModel.py:139-160
  * generateSolver, examples/makeSolver.py); here the kernels exist in two forms: over runtime row tables (any
  * descriptor) and over "generated views" -- the same tables as compile-time constants, so that the row loops of

@@ -1076,6 +1076,102 @@ int orc_solve_warm(const orc_desc *d, const double *xinit, const double *x0, con
   return solve_impl(d, xinit, x0, params, zout, st, 0, lam_w, nu_w, mu_w, lam_out, nu_out);
 }
 
+/* First pass of a solve: slacks, multipliers and costates at w->z (eval_all done), cold (lam_w == 0) or from the
+ * multipliers of a previous solve; returns the barrier parameter the solve starts from. */
+static double first_duals(const orc_desc *d, orc_work *w, const double *lam_w, const double *nu_w, double mu_w) {
+  const int N = w->N, nx = w->nx, m = w->m;
+  double mu = d->mu0;
+  if (lam_w) {
+    mu = ORC_WARM_KAPPA * mu_w;
+    if (mu < ORC_WARM_MU_MIN) mu = ORC_WARM_MU_MIN;
+    if (mu > d->mu0) mu = d->mu0;
+  }
+  for (int k = 0; k < N; k++) {
+    const int ks = k < N - 1 ? k + 1 : k; /* shifted like the plan */
+    for (int i = 0; i < m; i++) {
+      double gv = w->g[(size_t)k * MRM + i];
+      if (lam_w) {
+        double tv = gv > ORC_WARM_TMIN ? gv : ORC_WARM_TMIN;
+        double lc = mu / tv, lw = lam_w[(size_t)ks * m + i];
+        w->t[(size_t)k * m + i] = tv;
+        w->lam[(size_t)k * m + i] = lw > lc ? lw : lc;
+      } else {
+        double tv = gv > ORC_TMIN ? gv : ORC_TMIN;
+        w->t[(size_t)k * m + i] = tv;
+        w->lam[(size_t)k * m + i] = mu / tv;
+      }
+    }
+    if (nu_w)
+      for (int i = 0; i < nx; i++) w->nu[(size_t)k * nx + i] = (k == 0) ? 0.0 : nu_w[(size_t)ks * nx + i];
+  }
+  return mu;
+}
+
+/* Condensed stage blocks w->Q, w->qv of the step computation at the current iterate (w->rc is set by the caller). */
+static void stage_blocks(const orc_desc *d, orc_work *w, int nh, double mu, int use_curv, double theta_c) {
+  const int N = w->N, nx = w->nx, nv = w->nv, m = w->m;
+  for (int k = 0; k < N; k++) {
+    const double *Jg = w->Jg + (size_t)k * MRM * nv;
+    double *Q = w->Q + (size_t)k * nv * nv, *qv = w->qv + (size_t)k * nv;
+    memcpy(Q, w->H + (size_t)k * nv * nv, sizeof(double) * nv * nv);
+    memcpy(qv, w->gf + (size_t)k * nv, sizeof(double) * nv);
+    for (int i = 0; i < m; i++) {
+      double tv = w->t[(size_t)k * m + i], lv = w->lam[(size_t)k * m + i];
+      double rg = w->g[(size_t)k * MRM + i] - tv;
+      double sig = lv / tv, cq = (mu - lv * rg) / tv;
+      const double *jr = Jg + i * nv;
+      for (int a2 = 0; a2 < nv; a2++) {
+        if (jr[a2] == 0.0) continue;
+        qv[a2] -= jr[a2] * cq;
+        for (int b2 = 0; b2 < nv; b2++) Q[a2 * nv + b2] += sig * jr[a2] * jr[b2];
+      }
+      if (use_curv && i < nh) {
+        /* - (lambda_i + cN/h^2) * grad^2 h_i, distance rows with affine kinematics */
+        const double *Cm = w->Cc + ((size_t)k * ORC_NH_MAX + i) * 64;
+        double wgt = lv + w->cw[(size_t)k * ORC_NH_MAX + i];
+        for (int a2 = 0; a2 < d->n; a2++)
+          for (int b2 = 0; b2 < d->n; b2++) Q[a2 * nv + b2] -= theta_c * (wgt * Cm[a2 * d->n + b2]);
+      }
+    }
+    if (use_curv && d->has_goal) {
+      const double *G = w->Gc + (size_t)k * 64;
+      for (int a2 = 0; a2 < d->n; a2++)
+        for (int b2 = 0; b2 < d->n; b2++) Q[a2 * nv + b2] += theta_c * G[a2 * d->n + b2];
+    }
+    if (use_curv && dd_curv(d) && k < N - 1) dd_dyn_curv(d, w->z + (size_t)k * nv, w->nu + (size_t)(k + 1) * nx, Q);
+  }
+}
+
+/* Test entry: the first pass of a solve (cold, or warm with lam_w / nu_w / mu_w as orc_solve_warm) and ONE step
+ * computation on the Gauss-Newton blocks.  Outputs, stage-major: Q [N][nv*nv], q [N][nv], A [N][nx*nx], B [N][nx*nw],
+ * rc [N][nx] (last stage zero), t / lam [N][m], *mu, dz [N][nv], nu [N][nx] the new costates, *ok = 1 when every
+ * control block was positive definite.  Returns 0, or < 0 when the start point cannot be evaluated. */
+int orc_debug_step(const orc_desc *d, const double *xinit, const double *x0, const double *params, const double *lam_w,
+                   const double *nu_w, double mu_w, double *Q, double *q, double *A, double *Bm, double *rc, double *t,
+                   double *lam, double *mu_out, double *dz, double *nu, int *ok) {
+  int nh, m;
+  if (orc_num_rows(d, &nh, &m) != 0) return -1;
+  const int N = d->N, nx = d->nx, nv = nvar_of(d), nw = d->ns + d->nu;
+  if (nx > NXM || nw > NWM || nv > NVM || N < 1) return -1;
+  orc_work *w = work_get(d, m);
+  memcpy(w->z, x0, sizeof(double) * N * nv);
+  memcpy(w->z, xinit, sizeof(double) * nx);
+  int ev = eval_all(d, w, params);
+  if (ev != 0) return ev;
+  const double mu = first_duals(d, w, lam_w, nu_w, mu_w);
+  for (int k = 0; k < N - 1; k++)
+    for (int i = 0; i < nx; i++) w->rc[(size_t)k * nx + i] = w->xn[(size_t)k * nx + i] - w->z[(size_t)(k + 1) * nv + i];
+  stage_blocks(d, w, nh, mu, 0, 1.0);
+  *ok = riccati(w) == 0;
+  *mu_out = mu;
+  memcpy(Q, w->Q, sizeof(double) * N * nv * nv); memcpy(q, w->qv, sizeof(double) * N * nv);
+  memcpy(A, w->A, sizeof(double) * N * nx * nx); memcpy(Bm, w->Bm, sizeof(double) * N * nx * nw);
+  memcpy(rc, w->rc, sizeof(double) * N * nx);
+  memcpy(t, w->t, sizeof(double) * N * m); memcpy(lam, w->lam, sizeof(double) * N * m);
+  memcpy(dz, w->dz, sizeof(double) * N * nv); memcpy(nu, w->nunew, sizeof(double) * N * nx);
+  return 0;
+}
+
 static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, const double *params,
                       double *zout, orc_stats *st, double *trace, const double *lam_w, const double *nu_w,
                       double mu_w, double *lam_out, double *nu_out) {
@@ -1108,29 +1204,7 @@ static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, 
   tl_passes = 1;
   int ev = eval_all(d, w, params);
   if (ev != 0) { exitflag = (ev == ORC_EVAL_BAD_AVOID) ? -7 : -10; goto done; }
-  if (lam_w) {
-    mu = ORC_WARM_KAPPA * mu_w;
-    if (mu < ORC_WARM_MU_MIN) mu = ORC_WARM_MU_MIN;
-    if (mu > d->mu0) mu = d->mu0;
-  }
-  for (int k = 0; k < N; k++) {
-    const int ks = k < N - 1 ? k + 1 : k; /* shifted like the plan */
-    for (int i = 0; i < m; i++) {
-      double gv = w->g[(size_t)k * MRM + i];
-      if (lam_w) {
-        double tv = gv > ORC_WARM_TMIN ? gv : ORC_WARM_TMIN;
-        double lc = mu / tv, lw = lam_w[(size_t)ks * m + i];
-        w->t[(size_t)k * m + i] = tv;
-        w->lam[(size_t)k * m + i] = lw > lc ? lw : lc;
-      } else {
-        double tv = gv > ORC_TMIN ? gv : ORC_TMIN;
-        w->t[(size_t)k * m + i] = tv;
-        w->lam[(size_t)k * m + i] = mu / tv;
-      }
-    }
-    if (nu_w)
-      for (int i = 0; i < nx; i++) w->nu[(size_t)k * nx + i] = (k == 0) ? 0.0 : nu_w[(size_t)ks * nx + i];
-  }
+  mu = first_duals(d, w, lam_w, nu_w, mu_w);
   for (it = 0;; it++) {
     /* ---- residuals at the current iterate ---- */
     double res_stat = 0, res_eq = 0, res_ineq = 0, res_comp = 0, obj = 0, theta = 0, logsum = 0;
@@ -1200,36 +1274,7 @@ static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, 
     double theta_c = cscale ? theta_mem : 1.0;
     int theta_retry = 0;
     for (;;) {
-      for (int k = 0; k < N; k++) {
-        const double *Jg = w->Jg + (size_t)k * MRM * nv;
-        double *Q = w->Q + (size_t)k * nv * nv, *qv = w->qv + (size_t)k * nv;
-        memcpy(Q, w->H + (size_t)k * nv * nv, sizeof(double) * nv * nv);
-        memcpy(qv, w->gf + (size_t)k * nv, sizeof(double) * nv);
-        for (int i = 0; i < m; i++) {
-          double tv = w->t[(size_t)k * m + i], lv = w->lam[(size_t)k * m + i];
-          double rg = w->g[(size_t)k * MRM + i] - tv;
-          double sig = lv / tv, cq = (mu - lv * rg) / tv;
-          const double *jr = Jg + i * nv;
-          for (int a2 = 0; a2 < nv; a2++) {
-            if (jr[a2] == 0.0) continue;
-            qv[a2] -= jr[a2] * cq;
-            for (int b2 = 0; b2 < nv; b2++) Q[a2 * nv + b2] += sig * jr[a2] * jr[b2];
-          }
-          if (use_curv && i < nh) {
-            /* - (lambda_i + cN/h^2) * grad^2 h_i, distance rows with affine kinematics */
-            const double *Cm = w->Cc + ((size_t)k * ORC_NH_MAX + i) * 64;
-            double wgt = lv + w->cw[(size_t)k * ORC_NH_MAX + i];
-            for (int a2 = 0; a2 < d->n; a2++)
-              for (int b2 = 0; b2 < d->n; b2++) Q[a2 * nv + b2] -= theta_c * (wgt * Cm[a2 * d->n + b2]);
-          }
-        }
-        if (use_curv && d->has_goal) {
-          const double *G = w->Gc + (size_t)k * 64;
-          for (int a2 = 0; a2 < d->n; a2++)
-            for (int b2 = 0; b2 < d->n; b2++) Q[a2 * nv + b2] += theta_c * G[a2 * d->n + b2];
-        }
-        if (use_curv && dd_curv(d) && k < N - 1) dd_dyn_curv(d, w->z + (size_t)k * nv, w->nu + (size_t)(k + 1) * nx, Q);
-      }
+      stage_blocks(d, w, nh, mu, use_curv, theta_c);
       if (riccati(w) != 0) {
         if (use_curv && cscale && theta_c > ORC_CS_MIN) { theta_c *= 0.5; theta_retry = 1; tl_passes++; continue; }
         if (use_curv) {

@@ -157,6 +157,13 @@ int orc_solve_batch(const orc_desc *d, int B, const double *xinit,
                     const double *x0, const double *params, double *zout,
                     orc_stats *st, int nthreads);
 
+/* Test entry: the first pass of a solve (cold: lam_w == nu_w == NULL; warm: as orc_solve_warm) and one step computation
+ * on the Gauss-Newton blocks.  Stage-major outputs: Q [N][nvar*nvar], q [N][nvar], A [N][nx*nx], B [N][nx*(ns+nu)],
+ * rc [N][nx], t / lam [N][m], *mu, dz [N][nvar], nu [N][nx] (new costates), *ok (1: step computed). */
+int orc_debug_step(const orc_desc *d, const double *xinit, const double *x0, const double *params, const double *lam_w,
+                   const double *nu_w, double mu_w, double *Q, double *q, double *A, double *B, double *rc, double *t,
+                   double *lam, double *mu, double *dz, double *nu, int *ok);
+
 /* discrete dynamics only (plant model for closed-loop tests) */
 int orc_dynamics(const orc_desc *d, const double *x, const double *u, double *xnext);
 

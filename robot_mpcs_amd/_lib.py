@@ -100,7 +100,7 @@ class LidarArgs(C.Structure):
 EXPORTED_SYMBOLS = [
     "rmpc_version", "rmpc_source_hash", "rmpc_last_error", "rmpc_desc_size", "rmpc_create", "rmpc_destroy", "rmpc_solve_batch",
     "rmpc_solve_batch_device", "rmpc_workspace_bytes", "rmpc_set_warm_start", "rmpc_set_pass_budget", "rmpc_is_fused", "rmpc_fused_kernel_name", "rmpc_is_async", "rmpc_set_profiling", "rmpc_get_profile",
-    "rmpc_kernel_name", "rmpc_last_passes", "rmpc_debug_sweep", "rmpc_spec_source", "rmpc_spec_name", "rmpc_spec_for", "rmpc_debug_poison_lds",
+    "rmpc_kernel_name", "rmpc_last_passes", "rmpc_debug_sweep", "rmpc_debug_step", "rmpc_spec_source", "rmpc_spec_name", "rmpc_spec_for", "rmpc_debug_poison_lds",
     "rmpc_debug_fused_stamps", "rmpc_pack_scene_device", "rmpc_solve_batch_scene_device", "rmpc_pack_scene_workspace", "rmpc_solve_batch_packed_device", "rmpc_advance_device", "rmpc_advance_device_flags", "rmpc_retarget_device", "rmpc_advance_obstacles_device", "rmpc_free_space_device",
     "rmpc_grid_inflate_device", "rmpc_grid_fields_device", "rmpc_grid_paths_device", "rmpc_grid_cells_device",
     "rmpc_follow_path_device", "rmpc_lidar_scan_device", "rmpc_plan_points_device", "rmpc_fleet_points_device",
@@ -209,6 +209,8 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_last_passes.argtypes = [C.c_void_p]
     L.rmpc_debug_sweep.restype = C.c_int
     L.rmpc_debug_sweep.argtypes = [C.c_void_p, C.c_int] + [dp] * 9
+    L.rmpc_debug_step.restype = C.c_int
+    L.rmpc_debug_step.argtypes = [C.c_void_p, C.c_int] + [dp] * 15 + [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]
     L.rmpc_spec_source.restype = C.c_int64
     L.rmpc_spec_source.argtypes = [C.POINTER(RmpcDesc), C.c_char_p, C.c_char_p, C.c_int64]
     L.rmpc_spec_name.restype = C.c_char_p
@@ -674,3 +676,35 @@ class Solver:
                                       _dp(rc_), _dp(g), _dp(f))
         self._check(rc, "rmpc_debug_sweep")
         return dict(Q=Q, q0=q0, q1=q1, rc=rc_, g=g[:, :, :nh], f=f)
+
+    def debug_step(self, xinit, x0, params, duals=None):
+        """``rmpc_debug_step``: one first sweep and one Riccati recursion on the path this handle runs in production.
+        ``duals`` = (lam [B, N, m], nu [B, N, nx], mu [B]) of a previous solve (the warm first pass) or None (cold).
+        Returns the blocks the recursion consumed (Q, q0, q1, rc), the slacks, multipliers and barrier parameter they
+        were built with (t, lam, mu), the step dz, the new costates nu, the recursion's return value ok and ``path``: what
+        the handle holds of the switches that select the path."""
+        xinit = np.ascontiguousarray(xinit, dtype=np.float64).reshape(-1, self.nx)
+        B = xinit.shape[0]
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(B, self.N * self.nvar)
+        params = np.ascontiguousarray(params, dtype=np.float64).reshape(B, self.N * self.npar)
+        nv, N, nx = self.nvar, self.N, self.nx
+        # rows of a stage: the general rows, then one per finite lower / upper bound (the library refuses another count)
+        m = int(self.desc["nh"]) + sum(int(np.isfinite(float(v))) for bd in ("lb", "ub") for v in self.desc[bd][:nv])
+        if duals is None:
+            lw = nw = mw = None
+        else:
+            lw = np.ascontiguousarray(duals[0], dtype=np.float64).reshape(B, N, m)
+            nw = np.ascontiguousarray(duals[1], dtype=np.float64).reshape(B, N, nx)
+            mw = np.ascontiguousarray(duals[2], dtype=np.float64).reshape(B)
+        p = lambda a: _dp(a) if a is not None else None
+        Q = np.zeros((B, N, nv, nv)); q0 = np.zeros((B, N, nv)); q1 = np.zeros((B, N, nv)); rc_ = np.zeros((B, N, nx))
+        t = np.zeros((B, N, m)); lam = np.zeros((B, N, m)); mu = np.zeros(B)
+        dz = np.zeros((B, N, nv)); nu = np.zeros((B, N, nx)); ok = np.zeros(B, dtype=np.int32)
+        path = np.zeros(4, dtype=np.int32)
+        rc = self._L.rmpc_debug_step(self._h, B, _dp(xinit), _dp(x0), _dp(params), p(lw), p(nw), p(mw), _dp(Q), _dp(q0),
+                                     _dp(q1), _dp(rc_), _dp(t), _dp(lam), _dp(mu), _dp(dz), _dp(nu),
+                                     ok.ctypes.data_as(C.POINTER(C.c_int32)), m, path.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._check(rc, "rmpc_debug_step")
+        return dict(Q=Q, q0=q0, q1=q1, rc=rc_, t=t, lam=lam, mu=mu, dz=dz, nu=nu, ok=ok.astype(bool),
+                    path=dict(fused=("", "k_fused", "k_fused_arm")[path[0]], ric_lane=int(path[1]), arm_parts=int(path[2]),
+                              generated_view=bool(path[3])))

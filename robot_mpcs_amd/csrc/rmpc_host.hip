@@ -403,6 +403,34 @@ static int sum_stamps(int (*VariantOps::*reader)(long long *), long long *out) {
 }
 #endif
 
+// stage records -> the dense blocks of rmpc_debug_sweep / rmpc_debug_step in instance-major order; rec(off, k, b): word
+// off of the record of stage k of instance b
+template <class RecFn>
+static void unpack_records(const DevModel &M, int B, RecFn rec, double *out_Q, double *out_q0, double *out_q1, double *out_rc) {
+  const int nq = M.n, nv = M.nv;
+  const RecLayout L = rec_layout(M);
+  for (int b = 0; b < B; b++)
+    for (int k = 0; k < M.N; k++) {
+      const size_t sb = (size_t)b * M.N + k;
+      if (out_Q) {
+        double *Q = out_Q + sb * nv * nv;
+        for (int i = 0; i < nv * nv; i++) Q[i] = 0.0;
+        int s = 0;
+        for (int a = 0; a < nq; a++)
+          for (int c = a; c < nq; c++) { double v = rec(L.q + s++, k, b); Q[a * nv + c] = v; Q[c * nv + a] = v; }
+        for (int j = nq; j < nv; j++) Q[j * nv + j] = rec(L.dg + j - nq, k, b);
+        if (M.ns)
+          for (int j = 0; j < nv; j++)
+            if (j != M.nx) { double v = rec(L.cs + j, k, b); Q[j * nv + M.nx] = v; Q[M.nx * nv + j] = v; }
+      }
+      for (int j = 0; j < nv; j++) {
+        if (out_q0) out_q0[sb * nv + j] = rec(L.q0 + j, k, b);
+        if (out_q1) out_q1[sb * nv + j] = rec(L.q1 + j, k, b);
+      }
+      if (out_rc) for (int j = 0; j < M.nx; j++) out_rc[sb * M.nx + j] = (k < M.N - 1) ? rec(L.rc + j, k, b) : 0.0;
+    }
+}
+
 extern "C" {
 
 int rmpc_version(void) { return RMPC_VERSION; }
@@ -843,35 +871,149 @@ int rmpc_debug_sweep(rmpc_handle *h, int B, const double *xinit, const double *x
     return 0;
   };
   std::vector<double> R, gr, part;
-  const int nq = M.n, nv = M.nv;
   const RecLayout L = rec_layout(M);
   if (fetch(h->W.R, L.rs, R) || fetch(h->W.grow[1], M.nh > 0 ? M.nh : 1, gr)  /* first pass: cur = 0, written to buffer 1 */ ||
       fetch(h->W.part, P_COUNT, part))
     return -1;
   auto at = [&](const std::vector<double> &v, int slot, int k, int b) { return v[((size_t)slot * M.N + k) * h->Bp + b]; };
   auto rec = [&](int off, int k, int b) { return R[((size_t)b * M.N + k) * L.rs + off]; };
+  unpack_records(M, B, rec, out_Q, out_q0, out_q1, out_rc);
   for (int b = 0; b < B; b++)
     for (int k = 0; k < M.N; k++) {
       const size_t sb = (size_t)b * M.N + k;
-      if (out_Q) {
-        double *Q = out_Q + sb * nv * nv;
-        for (int i = 0; i < nv * nv; i++) Q[i] = 0.0;
-        int s = 0;
-        for (int a = 0; a < nq; a++)
-          for (int c = a; c < nq; c++) { double v = rec(L.q + s++, k, b); Q[a * nv + c] = v; Q[c * nv + a] = v; }
-        for (int j = nq; j < nv; j++) Q[j * nv + j] = rec(L.dg + j - nq, k, b);
-        if (M.ns)
-          for (int j = 0; j < nv; j++)
-            if (j != M.nx) { double v = rec(L.cs + j, k, b); Q[j * nv + M.nx] = v; Q[M.nx * nv + j] = v; }
-      }
-      for (int j = 0; j < nv; j++) {
-        if (out_q0) out_q0[sb * nv + j] = rec(L.q0 + j, k, b);
-        if (out_q1) out_q1[sb * nv + j] = rec(L.q1 + j, k, b);
-      }
-      if (out_rc) for (int j = 0; j < M.nx; j++) out_rc[sb * M.nx + j] = (k < M.N - 1) ? rec(L.rc + j, k, b) : 0.0;
       if (out_g) for (int j = 0; j < M.nh; j++) out_g[sb * M.nh + j] = at(gr, j, k, b);
       if (out_f) out_f[sb] = at(part, P_F, k, b);
     }
+  return 0;
+}
+
+int rmpc_debug_step(rmpc_handle *h, int B, const double *xinit, const double *x0, const double *params,
+                    const double *lam_w, const double *nu_w, const double *mu_w, double *out_Q, double *out_q0,
+                    double *out_q1, double *out_rc, double *out_t, double *out_lam, double *out_mu, double *out_dz,
+                    double *out_nu, int32_t *out_ok, int m_rows, int32_t *out_path) {
+  if (!h || !xinit || !x0 || !params || !out_t || !out_lam || !out_mu || !out_dz || !out_nu || !out_ok) return fail("null argument");
+  if (m_rows != h->M.m) return fail("rmpc_debug_step: out_t / out_lam are sized for " + std::to_string(m_rows) + " rows, the model has " + std::to_string(h->M.m));
+  if (out_path) {
+    // what the handle holds of the switches that select the path (read once, at rmpc_create)
+    out_path[0] = h->fused ? (h->ops->arm_fused ? 2 : 1) : 0;
+    out_path[1] = h->ric_lane;
+    out_path[2] = (h->fused && h->ops->arm_fused) ? ((3 * h->M.N <= 64 && !h->env_arm_two_parts) ? 3 : 2) : 0;
+    out_path[3] = h->ops->matches ? 1 : 0;
+  }
+  const int warm = (lam_w || nu_w || mu_w) ? 1 : 0;
+  if (warm && !(lam_w && nu_w && mu_w)) return fail("rmpc_debug_step: lam_w, nu_w and mu_w come together");
+  if (enter_batch(h, B)) return -1;
+  if (ensure_staging(h) != 0) return -1;
+  const DevModel &M = h->M;
+  const int N = M.N, nv = M.nv, nx = M.nx, m = M.m;
+  hipStream_t st = h->stream;
+  HIPCHK(hipMemcpyAsync(h->d_xinit, xinit, sizeof(double) * B * nx, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(h->d_x0, x0, sizeof(double) * (size_t)B * N * nv, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(h->d_params, params, sizeof(double) * (size_t)B * N * M.npar, hipMemcpyHostToDevice, st));
+  h->have_duals = false;
+  h->packed_B = 0;
+  const int rs = h->ops->rs;
+  std::vector<double> R, tv, lv, dz, nn, mu((size_t)B);
+  std::vector<int> ok((size_t)B);
+  // word `slot` of stage k of instance b in an array of the workspace the handle's path runs in
+  const size_t S32 = kFusedStages;
+  const int fm = h->fused ? h->F.m : m;   // (the arms' fused workspace: one spare row behind the m rows)
+  auto widx = [&](int slots, int slot, int k, int b) -> size_t {
+    return h->fused ? ((size_t)b * slots + slot) * S32 + k : ((size_t)slot * N + k) * h->Bp + b;
+  };
+  if (warm) {
+    // the multipliers of the "previous solve", in the layout k_save_duals / the fused epilogue leave them in
+    const size_t cols = h->fused ? (size_t)fused_columns(h->max_batch) * S32 : (size_t)N * h->Bp;
+    std::vector<double> wl(cols * fm, 0.0), wn(cols * nx, 0.0);
+    for (int b = 0; b < B; b++)
+      for (int k = 0; k < N; k++) {
+        for (int i = 0; i < m; i++) wl[widx(fm, i, k, b)] = lam_w[((size_t)b * N + k) * m + i];
+        for (int j = 0; j < nx; j++) wn[widx(nx, j, k, b)] = nu_w[((size_t)b * N + k) * nx + j];
+      }
+    HIPCHK(hipMemcpy(h->fused ? h->F.wlam : h->W.wlam, wl.data(), sizeof(double) * wl.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->fused ? h->F.wnu : h->W.wnu, wn.data(), sizeof(double) * wn.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->fused ? h->F.wmu : h->W.wmu, mu_w, sizeof(double) * B, hipMemcpyHostToDevice));
+  }
+  auto fetch = [&](const double *dptr, size_t n, std::vector<double> &v) -> int {
+    v.resize(n);
+    HIPCHK(hipMemcpy(v.data(), dptr, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return 0;
+  };
+  if (h->fused) {
+    if (!h->ops->fused_step_debug) return fail("rmpc_debug_step: no debug kernel for this fused variant");
+    double *d_buf = nullptr;
+    int *d_ok = nullptr;
+    const size_t n_rec = (size_t)B * N * rs, n_dz = (size_t)B * N * nv, n_nu = (size_t)B * N * nx;
+    HIPCHK(hipMalloc((void **)&d_buf, sizeof(double) * (n_rec + n_dz + n_nu + B)));
+    if (hipMalloc((void **)&d_ok, sizeof(int) * B) != hipSuccess) { (void)hipFree(d_buf); return fail("hipMalloc"); }
+    double *const d_rec = d_buf, *const d_dz = d_rec + n_rec, *const d_nu = d_dz + n_dz, *const d_mu = d_nu + n_nu;
+    hipError_t e = hipMemsetAsync(d_buf, 0, sizeof(double) * (n_rec + n_dz + n_nu + B), st);
+    if (e == hipSuccess) {
+      h->ops->fused_step_debug(h, B, h->d_xinit, h->d_x0, h->d_params, warm, d_rec, d_dz, d_nu, d_mu, d_ok, st);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    R.resize(n_rec); dz.resize(n_dz); nn.resize(n_nu);
+    if (e == hipSuccess) e = hipMemcpy(R.data(), d_rec, sizeof(double) * n_rec, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(dz.data(), d_dz, sizeof(double) * n_dz, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(nn.data(), d_nu, sizeof(double) * n_nu, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(mu.data(), d_mu, sizeof(double) * B, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(ok.data(), d_ok, sizeof(int) * B, hipMemcpyDeviceToHost);
+    (void)hipFree(d_buf);
+    (void)hipFree(d_ok);
+    if (e != hipSuccess) return fail(std::string("rmpc_debug_step: ") + hipGetErrorString(e));
+    // the first sweep writes the trial point's slacks and multipliers to buffer 1 (cur = 0)
+    const size_t cols = (size_t)fused_columns(h->max_batch) * S32;
+    if (fetch(h->F.t[1], cols * fm, tv) || fetch(h->F.lam[1], cols * fm, lv)) return -1;
+    for (int b = 0; b < B; b++)
+      for (int k = 0; k < N; k++) {
+        const size_t sb = (size_t)b * N + k;
+        for (int j = 0; j < nv; j++) out_dz[sb * nv + j] = dz[sb * nv + j];
+        for (int j = 0; j < nx; j++) out_nu[sb * nx + j] = k ? nn[sb * nx + j] : 0.0;   // (no path forms the costate of the fixed first state)
+      }
+  } else {
+    dim3 g1((B + 63) / 64, (N * M.npar + 63) / 64);
+    hipLaunchKernelGGL(k_pack, g1, dim3(256), 0, st, h->d_params, h->W.p, B, N * M.npar, M.npar, N, h->Bp);
+    dim3 g2((B + 63) / 64, (N * nv + 63) / 64);
+    hipLaunchKernelGGL(k_pack, g2, dim3(256), 0, st, h->d_x0, h->W.z[0], B, N * nv, nv, N, h->Bp);
+    hipLaunchKernelGGL(k_init, dim3((B + 255) / 256), dim3(256), 0, st, h->W, h->d_xinit, B, nx, M.mu0, warm);
+    {
+      // the existing first pass, cold or warm, with the curvature terms off: k_sweep, then the recursion kernel
+      const int wm = h->warm_mode, uc = h->M.use_curv;
+      h->warm_mode = warm; h->have_duals = warm != 0; h->M.use_curv = 0;
+      h->ops->pass(h, Phase{h->W, B}, 1, 0, st, K_SWEEP);
+      h->ops->pass(h, Phase{h->W, B}, 1, 0, st, K_RICCATI);
+      h->warm_mode = wm; h->have_duals = false; h->M.use_curv = uc;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    const size_t S = (size_t)N * h->Bp;
+    std::vector<int> newstep((size_t)B), status((size_t)B);
+    if (fetch(h->W.R, S * rs, R) || fetch(h->W.t[1], S * m, tv) || fetch(h->W.lam[1], S * m, lv) || fetch(h->W.dz, S * nv, dz) ||
+        fetch(h->W.nunew, S * nx, nn) || fetch(h->W.mu, (size_t)B, mu))
+      return -1;
+    HIPCHK(hipMemcpy(newstep.data(), h->W.newstep, sizeof(int) * B, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(status.data(), h->W.status, sizeof(int) * B, hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; b++) {
+      ok[b] = (status[b] == ST_ACTIVE && newstep[b] == 1) ? 1 : 0;   // (what the kernel stores when the recursion returned true)
+      for (int k = 0; k < N; k++) {
+        const size_t sb = (size_t)b * N + k;
+        for (int j = 0; j < nv; j++) out_dz[sb * nv + j] = dz[widx(nv, j, k, b)];
+        for (int j = 0; j < nx; j++) out_nu[sb * nx + j] = k ? nn[widx(nx, j, k, b)] : 0.0;
+      }
+    }
+  }
+  auto rec = [&](int off, int k, int b) { return R[((size_t)b * N + k) * rs + off]; };
+  unpack_records(M, B, rec, out_Q, out_q0, out_q1, out_rc);
+  for (int b = 0; b < B; b++) {
+    out_mu[b] = mu[b];
+    out_ok[b] = ok[b];
+    for (int k = 0; k < N; k++)
+      for (int i = 0; i < m; i++) {
+        out_t[((size_t)b * N + k) * m + i] = tv[widx(fm, i, k, b)];
+        out_lam[((size_t)b * N + k) * m + i] = lv[widx(fm, i, k, b)];
+      }
+  }
   return 0;
 }
 

@@ -97,6 +97,10 @@ struct VariantOps {
   void (*fused_launch)(rmpc_handle *h, int B, const double *d_xinit, const double *d_x0, const double *d_params,
                        double *d_zout, int *d_exit, int *d_iters, double *d_kkt, double *d_obj, hipStream_t st, int cap,
                        int warm, int use_order);
+  // test aid (rmpc_debug_step, rmpc_step_debug.hpp): first sweep and recursion of the fused kernel, nullptr: none.
+  // d_rec [B][N][rs], d_dz [B][N][nv], d_nu [B][N][nx], d_mu [B], d_ok [B]
+  void (*fused_step_debug)(rmpc_handle *h, int B, const double *d_xinit, const double *d_x0, const double *d_params, int warm,
+                           double *d_rec, double *d_dz, double *d_nu, double *d_mu, int *d_ok, hipStream_t st);
   void (*advance)(rmpc_handle *h, int B, const double *d_z_prev, const int *ef, double *d_xinit, double *d_x0,
                   int previous_plan, hipStream_t st);
   void (*retarget)(rmpc_handle *h, int B, const RetargetDev &R, hipStream_t st);

@@ -3,6 +3,7 @@
 // (__graft_entry__.TU_MASKS), in parallel with each other, the host unit rmpc_host.hip and rmpc_world.hip: RMPC_UNIT_VARIANTS is
 // the bit mask of the rows of RMPC_VARIANTS this unit builds (bit i = id i; default: all of them).
 #include "rmpc_host.hpp"
+#include "rmpc_step_debug.hpp"
 
 // One kernel variant per robot family and size: X(id, robot kind, n, ns).  ids 0 .. 5 are the shipped configurations
 // (point robot, panda, boxer, each without / with the slack variable); 6 .. 10 further holonomic chains (mpcBase.py:52-55:
@@ -79,6 +80,31 @@ void launch_fused_arm(rmpc_handle *h, int B, const double *d_xinit, const double
                        d_params, d_zout, d_exit, d_iters, d_kkt, d_obj, cap, warm, use_order);
 }
 
+// rmpc_debug_step on a fused handle: the grid and the parts per stage of launch_fused / launch_fused_arm
+template <class C, class V>
+void launch_fused_step_debug(rmpc_handle *h, int B, const double *d_xinit, const double *d_x0, const double *d_params, int warm,
+                             double *d_rec, double *d_dz, double *d_nu, double *d_mu, int *d_ok, hipStream_t st) {
+  hipLaunchKernelGGL((k_fused_step_debug<C, C::FUSED_REC_LDS, V>), dim3((B + 1) / 2), dim3(64), 0, st, h->M, h->d_T, h->F, B,
+                     d_xinit, d_x0, d_params, warm, d_rec, d_dz, d_nu, d_mu, d_ok);
+}
+
+template <class C>
+void launch_fused_arm_step_debug(rmpc_handle *h, int B, const double *d_xinit, const double *d_x0, const double *d_params, int warm,
+                                 double *d_rec, double *d_dz, double *d_nu, double *d_mu, int *d_ok, hipStream_t st) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void *)k_fused_arm_step_debug<C, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, ArmLds<C>::TOTAL * 8);
+    (void)hipFuncSetAttribute((const void *)k_fused_arm_step_debug<C, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, ArmLds<C>::TOTAL * 8);
+    attr_set = true;
+  }
+  if (3 * h->M.N <= 64 && !h->env_arm_two_parts)
+    hipLaunchKernelGGL((k_fused_arm_step_debug<C, 3>), dim3(B), dim3(64), ArmLds<C>::TOTAL * 8, st, h->M, h->d_T, h->F, B, d_xinit,
+                       d_x0, d_params, warm, d_rec, d_dz, d_nu, d_mu, d_ok);
+  else
+    hipLaunchKernelGGL((k_fused_arm_step_debug<C, 2>), dim3(B), dim3(64), ArmLds<C>::TOTAL * 8, st, h->M, h->d_T, h->F, B, d_xinit,
+                       d_x0, d_params, warm, d_rec, d_dz, d_nu, d_mu, d_ok);
+}
+
 template <class C>
 void launch_advance(rmpc_handle *h, int B, const double *d_z_prev, const int *ef, double *d_xinit, double *d_x0, int previous_plan,
                     hipStream_t st) {
@@ -146,8 +172,10 @@ VariantOps ops(const char *spec, bool (*matches)(const rmpc_desc &, const DevMod
   if constexpr (C::FUSED_OK) {
     v.difficulty = launch_difficulty<C>;
     v.fused_launch = launch_fused<C, V>;
+    v.fused_step_debug = launch_fused_step_debug<C, V>;
   } else if constexpr (C::ARM_FUSED) {
     v.fused_launch = launch_fused_arm<C>;
+    v.fused_step_debug = launch_fused_arm_step_debug<C>;
   }
   v.advance = launch_advance<C>;
   v.retarget = launch_retarget<C>;
