@@ -281,7 +281,8 @@ static int solve_device(rmpc_handle *h, int B, const double *d_xinit, const doub
       launch_fused(h, B, d_xinit, d_x0, d_params, d_zout, d_exit, d_iters, d_kkt, d_obj, st, cap);
     }
     HIPCHK(hipGetLastError());
-    h->have_duals = true; h->duals_B = B;   // (the kernel has left the multipliers in the warm-start arrays)
+    // (k_fused leaves the multipliers in the warm-start arrays only for a handle in warm-start mode; k_fused_arm always)
+    h->have_duals = h->warm_mode || h->ops->arm_fused; h->duals_B = B;
     h->last_passes = -1;   // on the device (rmpc_last_passes fetches it)
     if (h->profiling) {
       HIPCHK(hipStreamSynchronize(st));

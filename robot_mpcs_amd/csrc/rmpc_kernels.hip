@@ -2142,6 +2142,12 @@ struct ArmBlock {
   FusedWs F;
   DevModel M;
 };
+typedef const __attribute__((address_space(4))) ArmBlock cArmBlock;
+// The words of a half-wavefront of k_fused that live across the phase calls, parked in LDS beside its solver words
+struct FusedHalf {
+  double gphi_sum;
+  int b, valid, retired, first, ipass, nextslot;
+};
 // The view a phase FUNCTION reads the problem's structure through: a generated view is a set of constants; the runtime
 // tables come through uniform pointers in the constant address space (GView: tables in front of the pointer block,
 // the model's copy behind it), i.e. by scalar loads -- round 4: with that the sweep and the step phase of the models
@@ -2324,12 +2330,20 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
                                               const double *__restrict__ params, double *__restrict__ zout,
                                               int *__restrict__ exitflag, int *__restrict__ iters_out,
                                               double *__restrict__ kkt, double *__restrict__ obj, const int max_passes,
-                                              const int warm_mode, const int use_order) {
+                                              const int warm_mode, const int use_order, const int save_duals) {
   constexpr int LPI = kFusedStages;
   constexpr int IPW = 2;   // instances per wavefront
   constexpr int NX = C::NX, NV = C::NV;
   using VC = typename std::conditional<V::SPEC, V, GView>::type;   // the view of the phase functions
-  const V v(M, *Tp);
+  // The model and the workspace block are NOT read from the kernel's arguments (M, F: some 90 scalar registers that
+  // would live across every phase call, i.e. in lanes of vector registers that go through scratch around the calls),
+  // but from their copies behind the row tables (ArmBlock, rmpc_create), through a uniform address in the constant
+  // address space: scalar loads at the point of use -- hand-over, the decision's tolerances, the caps.
+  auto blk = [&]() __attribute__((always_inline)) -> cArmBlock * {
+    unsigned long long a = (unsigned long long)(Tp + 1);
+    asm volatile("" : "+s"(a));   // opaque: the loads are not hoisted out of the pass loop
+    return (cArmBlock *)a;
+  };
   const int half = threadIdx.x / LPI;
   const int k = threadIdx.x & (LPI - 1);       // stage of this lane; also its lane index inside the instance
   // The launch is a queue of instances, not a grid of pairs: a half-wavefront takes instance after instance until the
@@ -2338,7 +2352,7 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
   // chip.  In a closed loop (use_order) the queue holds the instances in the order of their previous solve's passes,
   // longest first (k_order): longest-processing-time-first scheduling.  The arithmetic of an instance depends neither
   // on its position in the queue nor on its partner.
-  const int N = M.N;
+  const int N = blk()->M.N;
   const bool stage = k < N;
 
   // LDS of an instance: the work area of the recursion, and (REC_LDS) its 32 stage slots (FusedSlots)
@@ -2350,32 +2364,50 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
   ldouble *const work = (ldouble *)lds + half * (LW + RECW);
   ldouble *const slots = work + LW;
 
-  // ---- per-instance bases of the workspace: fused_ptrs(F, b) where a phase needs them ---------------------
+  // ---- per-instance bases of the workspace: computed from the instance index where a phase needs them --------
   const size_t S = kFusedStages;
   // the solver words of the two instances are parked here around the phase calls (the callees own the register file)
+  // and beside them the words of the half itself (FusedHalf): nothing of a half lives in registers across a call, where
+  // it would be saved to scratch and fetched back with a wait of its own in every pass
   __shared__ Inst sinst[IPW];
+  __shared__ FusedHalf shalf[IPW];
   __shared__ SweepStepOut sres[IPW];   // what the sweep call hands back (generated views with LDS records)
   Inst s;
   const bool warm = warm_mode != 0;
-  // (every lane of an instance holds the same words: its lane 0 parks them, all lanes take them back)
-  auto park = [&]() __attribute__((always_inline)) { if (k == 0) sinst[half] = s; };
-  // (lane 0's store and the other lanes' loads are ordered by the wavefront fence: without it the compiler may
-  //  keep a lane's copy from the previous unpark -- nothing in that lane's own program wrote the words since)
-  auto unpark = [&]() __attribute__((always_inline)) { WSYNC(); s = sinst[half]; };
-  inst_init(s, M.mu0);
+  inst_init(s, blk()->M.mu0);
   s.status = 0;                 // (no instance yet)
-  size_t b = (size_t)(B - 1);   // instance of this half (none: clamped -- addresses stay legal, nothing is written)
+  int bi = B - 1;               // instance of this half (none: clamped -- addresses stay legal, nothing is written)
   bool valid = false;           // the half holds an instance
   bool retired = false;         // the queue was empty when the half asked: it stays idle
   bool first = true;            // the instance's next pass is its first
   int ipass = 0;                // passes of the instance so far
   int nextslot = blockIdx.x * IPW + half;   // queue position of the half's first instance (-1: ask the counter)
-  int *const qhead = F.passes + 1;          // positions handed out beyond the grid's own (zeroed before the launch)
   double gphi_sum = 0.0;   // merit slope of the current step (sum over the stages; step phase)
+  // (every lane of an instance holds the same words: its lane 0 parks them, all lanes take them back)
+  auto park = [&]() __attribute__((always_inline)) {
+    if (k == 0) {
+      sinst[half] = s;
+      FusedHalf hw;
+      hw.gphi_sum = gphi_sum; hw.b = bi; hw.ipass = ipass; hw.nextslot = nextslot;
+      hw.valid = valid ? 1 : 0; hw.retired = retired ? 1 : 0; hw.first = first ? 1 : 0;
+      shalf[half] = hw;
+    }
+  };
+  // (lane 0's store and the other lanes' loads are ordered by the wavefront fence: without it the compiler may
+  //  keep a lane's copy from the previous unpark -- nothing in that lane's own program wrote the words since)
+  auto unpark = [&]() __attribute__((always_inline)) {
+    WSYNC();
+    s = sinst[half];
+    const FusedHalf hw = shalf[half];
+    gphi_sum = hw.gphi_sum; bi = hw.b; ipass = hw.ipass; nextslot = hw.nextslot;
+    valid = hw.valid != 0; retired = hw.retired != 0; first = hw.first != 0;
+  };
 
 #ifdef RMPC_STAMPS
   long long st_sweep = 0, st_dec = 0, st_ric = 0, st_step = 0, st_t0 = __builtin_amdgcn_s_memtime(), st_a, st_b;
   long long st_sw[6] = {0, 0, 0, 0, 0, 0}, st_sw2[2] = {0, 0};
+  long long st_hand = 0;   // cycles between the top of the pass loop and the test that ends it: epilogue, dequeue, prologue
+  int st_nhand = 0;        // hand-over events of this wavefront (epilogues + prologues, both halves)
   int st_ipass = 0;   // instance passes of this wavefront (both halves)
   int st_both = 0;    // wavefront passes in which both copies of the sweep call ran (the halves differed in `first`)
 #define STAMP_A() st_a = __builtin_amdgcn_s_memtime()
@@ -2387,100 +2419,171 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
   int pass = 0;   // passes of the wavefront
   for (;; pass++) {
     // ---- finished instances leave, idle halves take the next instance of the queue -----------------------------------
+#ifdef RMPC_STAMPS
+    const long long st_top = __builtin_amdgcn_s_memtime();
+#endif
     {
       const bool over = valid && (s.status == ST_ACTIVE) && ipass >= max_passes;   // deadline (rmpc_set_pass_budget) or cap
       const bool done = valid && (s.status != ST_ACTIVE || over);
       if (__ballot(done || (!valid && !retired)) != 0ull) {
+        cArmBlock *const A = blk();
+        // The half asks the queue FIRST: the counter's answer travels while the epilogue runs and is looked at behind
+        // the epilogue's stores (positions beyond the grid's own; the counter is zeroed before the launch).
+        const bool take = (done || !valid) && !retired;   // the half wants the next instance
+        bool took = false;
+        int qt = 0;
+        if (take && nextslot < 0 && k == 0) qt = atomicAdd(A->F.passes + 1, 1);
         if (done) {
           // epilogue: plan in the ABI layout, statistics (the trial point and the step were made visible to the whole
           // wavefront by the ordering points of the pass that ended the solve)
-          const FusedPtrs Pe = fused_ptrs(F, b);
+          const size_t b = (size_t)bi;
+          const bool c1 = s.cur != 0;
+          const bool okd = (s.status == ST_ACTIVE || s.status >= 0) && isfinite(s.mu) && s.mu > 0.0;
           if (stage) {
-            const gdouble *zf = Pe.pz[s.cur];
+            const gdouble *zf = (const gdouble *)(c1 ? A->F.z[1] : A->F.z[0]) + b * A->F.nv * S;
             double *zr = zout + (b * N + k) * NV;
+            double zv[NV];
 #pragma unroll
-            for (int j = 0; j < NV; j++) zr[j] = zf[j * S + k];
-            // multipliers for a warm start of the next solve of this instance (a failed solve leaves zeros and mu0)
-            const bool okd = (s.status == ST_ACTIVE || s.status >= 0) && isfinite(s.mu) && s.mu > 0.0;
-            const gdouble *lf = Pe.pl[s.cur], *nf = Pe.pn[s.cur];
-            {
-              int i = 0;
-              for (; i + 8 <= F.m; i += 8) {   // (eight requests in flight, as for the parameters)
-                double lv8[8];
+            for (int j = 0; j < NV; j++) zv[j] = zf[j * S + k];
+            if (save_duals) {
+              // multipliers for a warm start of the next solve of this instance (a failed solve leaves zeros and mu0):
+              // every word of the stage is requested before the first is stored (sets of kDualSet rows: the point
+              // robot's 33 rows and 6 costates are one set; slots beyond the last row repeat it -- same address, same
+              // value: no tail loop, no branch)
+              const int m = A->F.m;
+              const gdouble *lf = (const gdouble *)(c1 ? A->F.lam[1] : A->F.lam[0]) + b * m * S;
+              const gdouble *nf = (const gdouble *)(c1 ? A->F.nu[1] : A->F.nu[0]) + b * A->F.nx * S;
+              gdouble *wl = (gdouble *)A->F.wlam + b * m * S, *wn = (gdouble *)A->F.wnu + b * A->F.nx * S;
+              double nv6[NX];
 #pragma unroll
-                for (int u = 0; u < 8; u++) lv8[u] = lf[(i + u) * S + k];
+              for (int j = 0; j < NX; j++) nv6[j] = nf[j * S + k];
+              constexpr int kDualSet = 36;
+              for (int i0 = 0; i0 < m; i0 += kDualSet) {
+                double lv[kDualSet];
 #pragma unroll
-                for (int u = 0; u < 8; u++) Pe.pwl[(i + u) * S + k] = okd ? lv8[u] : 0.0;
+                for (int u = 0; u < kDualSet; u++) lv[u] = lf[min(i0 + u, m - 1) * S + k];
+                if (i0 == 0) {
+#pragma unroll
+                  for (int j = 0; j < NV; j++) zr[j] = zv[j];
+#pragma unroll
+                  for (int j = 0; j < NX; j++) wn[j * S + k] = okd ? nv6[j] : 0.0;
+                }
+#pragma unroll
+                for (int u = 0; u < kDualSet; u++) wl[min(i0 + u, m - 1) * S + k] = okd ? lv[u] : 0.0;
               }
-              for (; i < F.m; i++) Pe.pwl[i * S + k] = okd ? lf[i * S + k] : 0.0;
-            }
+              if (m <= 0) {
 #pragma unroll
-            for (int j = 0; j < NX; j++) Pe.pwn[j * S + k] = okd ? nf[j * S + k] : 0.0;
+                for (int j = 0; j < NV; j++) zr[j] = zv[j];
+#pragma unroll
+                for (int j = 0; j < NX; j++) wn[j * S + k] = okd ? nv6[j] : 0.0;
+              }
+            } else {
+#pragma unroll
+              for (int j = 0; j < NV; j++) zr[j] = zv[j];
+            }
           }
           if (k == 0) {
             exitflag[b] = (s.status == ST_ACTIVE) ? 0 : s.status;
             iters_out[b] = s.iters;
             kkt[b] = fmax(fmax(s.res_stat, s.res_eq), fmax(s.res_ineq, s.res_comp));
             obj[b] = s.obj;
-            F.wmu[b] = ((s.status == ST_ACTIVE || s.status >= 0) && isfinite(s.mu) && s.mu > 0.0) ? s.mu : M.mu0;
-            F.lastp[b] = ipass;
-            atomicMax(F.passes, ipass);
+            if (save_duals) {   // (read by a warm-started launch, k_order_t and rmpc_retarget_device only)
+              A->F.wmu[b] = okd ? s.mu : A->M.mu0;
+              A->F.lastp[b] = ipass;
+            }
+            atomicMax(A->F.passes, ipass);
           }
           valid = false;
           s.status = 0;
         }
-        if (!valid && !retired) {
+        if (take) {
           int pos = nextslot;
+          if (pos < 0) pos = (int)gridDim.x * IPW + __shfl(qt, half * LPI, 64);
           nextslot = -1;
-          if (pos < 0) {
-            int t = 0;
-            if (k == 0) t = atomicAdd(qhead, 1);
-            pos = (int)gridDim.x * IPW + __shfl(t, half * LPI, 64);
-          }
           if (pos < B) {
-            b = (size_t)(use_order ? F.order[pos] : pos);
+            bi = use_order ? A->F.order[pos] : pos;
+            const size_t b = (size_t)bi;
             valid = true;
-            // prologue: ABI rows of this stage -> the instance's block (x_1 := xinit, mpcModel.py:108)
-            const FusedPtrs P0 = fused_ptrs(F, b);
+            took = true;
+            // prologue: ABI rows of this stage -> the instance's block (x_1 := xinit, mpcModel.py:108).  One set of
+            // requests: the stage's row of x0, xinit (lane 0) and every parameter word, then the stores.
             if (stage) {
+              gdouble *const pz0 = (gdouble *)A->F.z[0] + b * A->F.nv * S;
               const double *zr = x0 + (b * N + k) * NV;
+              double zv[NV];
 #pragma unroll
-              for (int j = 0; j < NV; j++) {
-                double v = zr[j];
-                if (k == 0 && j < NX) v = xinit[b * NX + j];
-                P0.pz[0][j * S + k] = v;
+              for (int j = 0; j < NV; j++) zv[j] = zr[j];
+              if (k == 0) {
+#pragma unroll
+                for (int j = 0; j < NX; j++) zv[j] = xinit[b * NX + j];
+              }
+              if (params) {
+                // 16-byte requests from the first 16-byte boundary of the stage's row on (one word in front of it when
+                // the row starts between two: odd npar and odd stage index, or a caller's array at an odd word), a
+                // last single word when one is left.  Sets of kParSet pairs; slots beyond the row repeat its last pair
+                // (same address, same value: no tail loop, no branch).
+                const int npar = A->M.npar;
+                gdouble *const pp = (gdouble *)A->F.p + b * A->F.npar * S;
+                const double *pr = params + (b * N + k) * npar;
+                const int head = (int)(((unsigned long long)pr >> 3) & 1ull);
+                const int np2 = (npar - head) >> 1;           // whole pairs
+                const bool tail = ((npar - head) & 1) != 0;
+                const double h0 = head ? pr[0] : 0.0, t0 = tail ? pr[npar - 1] : 0.0;
+                const double2 *pq = (const double2 *)(pr + head);
+                constexpr int kParSet = 20;
+                for (int j0 = 0; j0 < np2; j0 += kParSet) {
+                  double2 pv[kParSet];
+#pragma unroll
+                  for (int u = 0; u < kParSet; u++) pv[u] = pq[min(j0 + u, np2 - 1)];
+                  if (j0 == 0) {
+#pragma unroll
+                    for (int j = 0; j < NV; j++) pz0[j * S + k] = zv[j];
+                  }
+#pragma unroll
+                  for (int u = 0; u < kParSet; u++) {
+                    const int j = head + 2 * min(j0 + u, np2 - 1);
+                    pp[j * S + k] = pv[u].x; pp[(j + 1) * S + k] = pv[u].y;
+                  }
+                }
+                if (np2 <= 0) {
+#pragma unroll
+                  for (int j = 0; j < NV; j++) pz0[j * S + k] = zv[j];
+                }
+                if (head) pp[k] = h0;
+                if (tail) pp[(npar - 1) * S + k] = t0;
+              } else {
+#pragma unroll
+                for (int j = 0; j < NV; j++) pz0[j * S + k] = zv[j];
               }
               if constexpr (REC_LDS) {   // the step slots are read (and discarded) by the first sweep: keep them finite
 #pragma unroll
                 for (int j = 0; j < NV + NX; j++) slots[k * GS + DZ_OFF + j] = 0.0;
               }
-              if (params) {
-                // (eight requests in flight: one by one the copy is npar dependent round trips to memory)
-                const double *pr = params + (b * N + k) * M.npar;
-                int j = 0;
-                for (; j + 8 <= M.npar; j += 8) {
-                  double pv8[8];
-#pragma unroll
-                  for (int u = 0; u < 8; u++) pv8[u] = pr[j + u];
-#pragma unroll
-                  for (int u = 0; u < 8; u++) P0.pp[(j + u) * S + k] = pv8[u];
-                }
-                for (; j < M.npar; j++) P0.pp[j * S + k] = pr[j];
-              }
             }
-            inst_init(s, warm ? warm_mu(F.wmu[b], M.mu0) : M.mu0);
+            {
+              const double mu0 = A->M.mu0;
+              inst_init(s, warm ? warm_mu(A->F.wmu[b], mu0) : mu0);
+            }
             first = true;
             ipass = 0;
             gphi_sum = 0.0;
           } else {
             retired = true;
-            b = (size_t)(B - 1);
+            bi = B - 1;
           }
         }
         GSYNC();   // the new instance's block is complete before any lane reads another lane's part
+#ifdef RMPC_STAMPS
+        st_nhand += __popcll(__ballot(done && k == 0)) + __popcll(__ballot(took && k == 0));   // epilogues + prologues
+#else
+        (void)took;
+#endif
       }
     }
     const bool act = valid && (s.status == ST_ACTIVE);
+#ifdef RMPC_STAMPS
+    st_hand += __builtin_amdgcn_s_memtime() - st_top;   // top of the pass loop .. here: the hand-over
+#endif
     if (__ballot(act) == 0ull) break;   // both halves are idle and the queue is empty
     if (act) ipass++;
 #ifdef RMPC_STAMPS
@@ -2508,8 +2611,11 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
       fresh = act && !nostep && (s.newstep != 0);
       const FusedWs *const Fp = (const FusedWs *)(Tp + 1);
       __attribute__((address_space(3))) SweepStepOut *const so = (__attribute__((address_space(3))) SweepStepOut *)&sres[half];
-      if (v1) fused_sweep_step_call<C, V, 1>(so, Fp, M.N, M.dt, M.use_curv, b, s.cur, k, slots, act && stage, nostep, fresh, s.ls, s.amin_p, s.amin_d, gphi_sum, s.mu, warm ? 1 : 0);
-      else fused_sweep_step_call<C, V, 0>(so, Fp, M.N, M.dt, M.use_curv, b, s.cur, k, slots, act && stage, nostep, fresh, s.ls, s.amin_p, s.amin_d, gphi_sum, s.mu, warm ? 1 : 0);
+      cArmBlock *const A = blk();
+      const double dt = A->M.dt;
+      const int use_curv = A->M.use_curv;
+      if (v1) fused_sweep_step_call<C, V, 1>(so, Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, act && stage, nostep, fresh, s.ls, s.amin_p, s.amin_d, gphi_sum, s.mu, warm ? 1 : 0);
+      else fused_sweep_step_call<C, V, 0>(so, Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, act && stage, nostep, fresh, s.ls, s.amin_p, s.amin_d, gphi_sum, s.mu, warm ? 1 : 0);
     } else {
       // the sweep is a call (scalars in, partials out): a generated view, or the runtime tables through GView
       if (act && stage) {
@@ -2520,8 +2626,11 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
           adual = s.amin_d;
         }
         const FusedWs *const Fp = (const FusedWs *)(Tp + 1);   // (the pointer block behind the row tables)
-        if (first) q = fused_sweep_call<C, VC, 1, REC_LDS>(Fp, M.N, M.dt, M.use_curv, b, s.cur, k, slots, nostep, alpha, adual, s.mu, warm ? 1 : 0);
-        else q = fused_sweep_call<C, VC, 0, REC_LDS>(Fp, M.N, M.dt, M.use_curv, b, s.cur, k, slots, nostep, alpha, adual, s.mu, warm ? 1 : 0);
+        cArmBlock *const A = blk();
+        const double dt = A->M.dt;
+        const int use_curv = A->M.use_curv;
+        if (first) q = fused_sweep_call<C, VC, 1, REC_LDS>(Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, nostep, alpha, adual, s.mu, warm ? 1 : 0);
+        else q = fused_sweep_call<C, VC, 0, REC_LDS>(Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, nostep, alpha, adual, s.mu, warm ? 1 : 0);
       }
     }
 #ifdef RMPC_STAMPS
@@ -2557,7 +2666,8 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
     // ---- decisions, then a new step when the trial was accepted --------------------------------------
     bool usec = false;
     bool recurse = false;
-    if (act) recurse = inst_decide<C>(M, s, r, first, usec);
+    // (the tolerances and caps of the decision: scalar loads from the model's copy behind the row tables)
+    if (act) recurse = inst_decide<C>(*(const DevModel *)&blk()->M, s, r, first, usec);
     if (act) first = false;
     STAMP_B(st_dec);
     park();
@@ -2569,13 +2679,15 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
       if constexpr (REC_LDS) {
         StepOut<ldouble> so;
         so.dz = slots + DZ_OFF; so.nunew = slots + DZ_OFF + NV; so.SS = 1; so.KS = GS;
-        ok = fused_recursion_lds<C>(M.N, M.dt, mu_r, cw_r, k, work, slots, so);
+        ok = fused_recursion_lds<C>(N, blk()->M.dt, mu_r, cw_r, k, work, slots, so);
       } else {
-        const FusedPtrs Pr = fused_ptrs(F, b);
+        cArmBlock *const A = blk();
+        const size_t b = (size_t)bi;
+        const int kps = A->F.kps;
         StepOut<gdouble> so;
-        so.dz = Pr.pdz; so.nunew = Pr.pnn; so.SS = S; so.KS = 1;
-        ok = fused_recursion_mem<C>(M.N, M.dt, mu_r, cw_r, k, work, (gdouble *)F.R + b * (size_t)N * C::RS,
-                                    (gdouble *)F.KP + b * (size_t)N * F.kps, F.kps, so);
+        so.dz = (gdouble *)A->F.dz + b * A->F.nv * S; so.nunew = (gdouble *)A->F.nunew + b * A->F.nx * S; so.SS = S; so.KS = 1;
+        ok = fused_recursion_mem<C>(N, A->M.dt, mu_r, cw_r, k, work, (gdouble *)A->F.R + b * (size_t)N * C::RS,
+                                    (gdouble *)A->F.KP + b * (size_t)N * kps, kps, so);
       }
       rec_ok = ok;
     }
@@ -2591,7 +2703,7 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
       park();
       if (stepping && stage) {
         const FusedWs *const Fp = (const FusedWs *)(Tp + 1);
-        const StepRes sr = fused_step_call<C, VC, REC_LDS>(Fp, b, s.cur, k, slots, s.mu);
+        const StepRes sr = fused_step_call<C, VC, REC_LDS>(Fp, (size_t)bi, s.cur, k, slots, s.mu);
         ap = sr.ap; ad = sr.ad; gp = sr.gp;
       }
       unpark();
@@ -2610,15 +2722,17 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
   }
 #ifdef RMPC_STAMPS
   if (threadIdx.x == 0) {
-    long long *o = F.stamps + (size_t)blockIdx.x * 8;
+    long long *const stamps = blk()->F.stamps;
+    long long *o = stamps + (size_t)blockIdx.x * 8;
     {
-      long long *o2 = F.stamps + (size_t)(gridDim.x + blockIdx.x) * 8;   // second half of the array: sweep sections
+      long long *o2 = stamps + (size_t)(gridDim.x + blockIdx.x) * 8;   // second half of the array: sweep sections
       for (int i = 0; i < 6; i++) o2[i] = st_sw[i];
       o2[6] = st_sw2[0]; o2[7] = st_sw2[1];
     }
     o[0] = st_sweep; o[1] = st_dec; o[2] = st_ric; o[3] = st_step; o[4] = __builtin_amdgcn_s_memtime() - st_t0;
     o[5] = (long long)pass | ((long long)st_both << 32);   // (low word: passes of the wavefront; high word: those with both sweep copies)
-    o[6] = st_t0; o[7] = st_ipass;
+    o[6] = st_hand;   // hand-over: top of the pass loop to the test that ends it
+    o[7] = (long long)st_ipass | ((long long)st_nhand << 32);   // (low word: instance passes; high word: hand-over events)
   }
 #endif
 }

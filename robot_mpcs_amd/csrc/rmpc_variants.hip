@@ -56,8 +56,9 @@ void launch_fused(rmpc_handle *h, int B, const double *d_xinit, const double *d_
   // the grid is the chip (one wavefront per SIMD: __launch_bounds__(64, 1)), the batch is a queue its halves drain
   const int pairs = (B + 1) / 2;
   const int grid = pairs < h->fused_grid ? pairs : h->fused_grid;
+  // (save_duals: only a handle in warm-start mode reads the multipliers, mu and the pass counts a solve leaves behind)
   hipLaunchKernelGGL((k_fused<C, C::FUSED_REC_LDS, V>), dim3(grid), dim3(64), 0, st, h->M, h->d_T, h->F, B, d_xinit, d_x0,
-                     d_params, d_zout, d_exit, d_iters, d_kkt, d_obj, cap, warm, use_order);
+                     d_params, d_zout, d_exit, d_iters, d_kkt, d_obj, cap, warm, use_order, h->warm_mode ? 1 : 0);
 }
 
 template <class C>

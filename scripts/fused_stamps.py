@@ -25,6 +25,11 @@ st, sec = both[:nb].astype(float), both[nb:].astype(float)
 raw5 = both[:nb, 5].astype(np.int64)
 st[:, 5] = (raw5 & 0xffffffff).astype(float)
 double_sweeps = (raw5 >> 32).astype(float)
+# word 7: instance passes of the wavefront (low half) and its hand-over events, epilogues + prologues (high half; a
+# library from before the hand-over stamp leaves it 0 and keeps a time stamp in word 6)
+raw7 = both[:nb, 7].astype(np.int64)
+st[:, 7] = (raw7 & 0xffffffff).astype(float)
+handovers = (raw7 >> 32).astype(float)
 tot = st[:, 4]
 print(f"{cfg} B={B}: wavefronts {len(st)}, passes per wavefront mean {st[:, 5].mean():.1f} max {st[:, 5].max():.0f}, "
       f"instance passes per wavefront pass {st[:, 7].sum() / st[:, 5].sum():.2f} (2 = both halves busy), "
@@ -39,4 +44,13 @@ if sec[:, :6].sum() > 0:
         print(f"     sweep / {name:42s} {sec[:, i].sum() / st[:, 5].sum():9.0f}")
     print(f"  wavefront passes with both copies of the sweep call: {double_sweeps.sum():.0f} of {st[:, 5].sum():.0f} "
           f"({double_sweeps.sum() / st[:, 5].sum() * 100:.2f} %), per wavefront {double_sweeps.mean():.2f}")
-print(f"  total cycles per pass {tot.sum() / st[:, 5].sum():.0f}   (s_memtime: shader clock)")
+passes = st[:, 5].sum()
+print(f"  outside the four phases (total minus their sum): cycles per pass {(tot.sum() - st[:, :4].sum()) / passes:.0f}")
+if handovers.sum() > 0:
+    # stamped: from the top of the pass loop to the test that ends it (epilogue, dequeue, prologue and its ordering point)
+    print(f"  hand-over: cycles per pass {st[:, 6].sum() / passes:.0f}, cycles per event {st[:, 6].sum() / handovers.sum():.0f} "
+          f"({handovers.sum():.0f} events, {handovers.mean():.1f} per wavefront)")
+if sec[:, :6].sum() == 0:
+    print(f"  wavefront passes with both copies of the sweep call: {double_sweeps.sum():.0f} of {passes:.0f} "
+          f"({double_sweeps.sum() / passes * 100:.2f} %)")
+print(f"  total cycles per pass {tot.sum() / passes:.0f}   (s_memtime: shader clock)")
