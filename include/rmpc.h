@@ -52,7 +52,8 @@ extern "C" {
  *              RMPC_GRID_MAX_CELLS, rmpc_grid_inflate_device, rmpc_grid_fields_device, rmpc_grid_paths_device,
  *              rmpc_grid_cells_device, rmpc_follow_path_device; the lidar, rmpc_lidar, rmpc_lidar_scan_device,
  *              rmpc_plan_points_device (rmpc_free_space_device now runs on the device of d_points); fleet
- *              separation, rmpc_fleet_points_device, rmpc_fleet_planes_device. */
+ *              separation, rmpc_fleet_points_device, rmpc_fleet_planes_device; the test hook rmpc_debug_step_curv
+ *              (rmpc_debug_step is that call at the weight 0 without out_C, results unchanged). */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -472,6 +473,24 @@ int rmpc_debug_step(rmpc_handle *h, int B, const double *xinit, const double *x0
                     const double *lam_w, const double *nu_w, const double *mu_w, double *out_Q, double *out_q0,
                     double *out_q1, double *out_rc, double *out_t, double *out_lam, double *out_mu, double *out_dz,
                     double *out_nu, int32_t *out_ok, int m_rows, int32_t *out_path);
+
+/* rmpc_debug_step with the curvature terms (tests only).  The sweep runs with the model's own curvature setting (the
+ * exact second-order terms of the distance rows and the inverse-barrier objective, the arms' second derivatives of the
+ * kinematics, the unicycle's frame rotation and nu . grad^2 Phi of its dynamics with the costates of the first pass) and
+ * the recursion on  H = out_Q - cw out_C:  out_Q the Gauss-Newton blocks as above, out_C [B][N][nvar*nvar] (may be NULL)
+ * the dense symmetric matrix the recursion subtracts per unit weight, unpacked from the stage records by the host: the
+ * q block, and for the unicycle the entries over (theta, omega, u1 | v, u0); zero where the model has no terms (all of
+ * it for a model that uses none, e.g. a holonomic chain with the slack variable).  cw in [0, 1]: 1 the exact Hessian,
+ * 1/2, 1/4 the scaled curvature of the small holonomic chains, 0 Gauss-Newton; k_fused_arm takes 0 or 1 only.  The
+ * pass kernels: k_riccati's recursion is called at cw as the fused kernels' is; k_riccati_lane decides its weight from
+ * the instance (the barrier parameter at or below 1e-2: the instance's scale, set to cw here; else 0) and the call
+ * fails when the first pass cannot run at cw.  out_ok: 0 where a control block was not positive definite (the return
+ * value that drives the Gauss-Newton fallback, the back-off and the half-weight retry); out_dz / out_nu are then
+ * unspecified.  cw = 0 and out_C = NULL is rmpc_debug_step, bit for bit. */
+int rmpc_debug_step_curv(rmpc_handle *h, int B, const double *xinit, const double *x0, const double *params,
+                         const double *lam_w, const double *nu_w, const double *mu_w, double *out_Q, double *out_q0,
+                         double *out_q1, double *out_rc, double *out_t, double *out_lam, double *out_mu, double *out_dz,
+                         double *out_nu, int32_t *out_ok, int m_rows, int32_t *out_path, double cw, double *out_C);
 
 /* Generated solvers.  The reference has FORCES Pro generate C code for ONE problem (mpcModel.py:139-160
  * generateSolver, examples/makeSolver.py); here the kernels exist in two forms: over runtime row tables (any

@@ -97,7 +97,7 @@ def lib():
         L.orc_solve_batch.restype = C.c_int
         L.orc_solve_batch.argtypes = [C.POINTER(OrcDesc), C.c_int, dp, dp, dp, dp, C.POINTER(OrcStats), C.c_int]
         L.orc_debug_step.restype = C.c_int
-        L.orc_debug_step.argtypes = [C.POINTER(OrcDesc), dp, dp, dp, dp, dp, C.c_double] + [dp] * 10 + [C.POINTER(C.c_int)]
+        L.orc_debug_step.argtypes = [C.POINTER(OrcDesc), dp, dp, dp, dp, dp, C.c_double] + [dp] * 10 + [C.POINTER(C.c_int), C.c_double, dp]
         L.orc_dynamics.restype = C.c_int
         L.orc_dynamics.argtypes = [C.POINTER(OrcDesc), dp, dp, dp]
         assert L.orc_desc_size() == C.sizeof(OrcDesc), "orc_desc layout mismatch"
@@ -251,10 +251,11 @@ class Oracle:
                     res_eq=st.res_eq, res_ineq=st.res_ineq, res_comp=st.res_comp, obj=st.obj, mu=st.mu,
                     duals=(lam_out, nu_out, st.mu))
 
-    def debug_step(self, xinit, x0, params, duals=None):
+    def debug_step(self, xinit, x0, params, duals=None, curv=0.0):
         """One instance: the first pass of a solve (``duals`` as in ``solve_warm``, None = cold) and one step computation
-        on the Gauss-Newton blocks.  Returns the blocks (Q, q, A, B, rc), what they were built with (t, lam, mu), the
-        step dz, the new costates nu and ok."""
+        on the blocks Q - curv * C (Q: Gauss-Newton, C: the model's curvature terms per unit weight, zeros for a model
+        without any).  Returns the blocks (Q, C, q, A, B, rc), what they were built with (t, lam, mu), the step dz, the
+        new costates nu and ok."""
         xinit = np.ascontiguousarray(xinit, dtype=np.float64)
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
         params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
@@ -268,11 +269,11 @@ class Oracle:
             lw, nw_, mw = _p(lam_w), _p(nu_w), float(duals[2])
         Q = np.zeros((N, nv, nv)); q = np.zeros((N, nv)); A = np.zeros((N, nx, nx)); Bm = np.zeros((N, nx, nw))
         rc_ = np.zeros((N, nx)); t = np.zeros((N, m)); lam = np.zeros((N, m)); mu = np.zeros(1)
-        dz = np.zeros((N, nv)); nu = np.zeros((N, nx)); ok = C.c_int(0)
+        dz = np.zeros((N, nv)); nu = np.zeros((N, nx)); ok = C.c_int(0); Cm = np.zeros((N, nv, nv))
         rc = lib().orc_debug_step(C.byref(self.cd), _p(xinit), _p(x0), _p(params), lw, nw_, mw, _p(Q), _p(q), _p(A), _p(Bm),
-                                  _p(rc_), _p(t), _p(lam), _p(mu), _p(dz), _p(nu), C.byref(ok))
+                                  _p(rc_), _p(t), _p(lam), _p(mu), _p(dz), _p(nu), C.byref(ok), float(curv), _p(Cm))
         assert rc == 0, rc
-        return dict(Q=Q, q=q, A=A, B=Bm, rc=rc_, t=t, lam=lam, mu=float(mu[0]), dz=dz, nu=nu, ok=bool(ok.value))
+        return dict(Q=Q, C=Cm, q=q, A=A, B=Bm, rc=rc_, t=t, lam=lam, mu=float(mu[0]), dz=dz, nu=nu, ok=bool(ok.value))
 
     def solve_batch(self, xinit, x0, params, nthreads=0):
         xinit = np.ascontiguousarray(xinit, dtype=np.float64)

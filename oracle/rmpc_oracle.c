@@ -1142,13 +1142,42 @@ static void stage_blocks(const orc_desc *d, orc_work *w, int nh, double mu, int 
   }
 }
 
+/* What stage_blocks subtracts from the Gauss-Newton block of stage k per unit weight when the model uses its curvature
+ * terms, as one dense symmetric matrix Cm [nv*nv] (zeroed here): the distance rows and the inverse-barrier objective
+ * over q, minus the goal cost's second-order term, minus dd_dyn_curv with the costates of the iterate (w->nu). */
+static void stage_curv_terms(const orc_desc *d, const orc_work *w, int nh, int k, double *Cm) {
+  const int N = w->N, nx = w->nx, nv = w->nv, m = w->m, n = d->n;
+  memset(Cm, 0, sizeof(double) * nv * nv);
+  for (int i = 0; i < nh && i < m; i++) {
+    const double *Ci = w->Cc + ((size_t)k * ORC_NH_MAX + i) * 64;
+    const double wgt = w->lam[(size_t)k * m + i] + w->cw[(size_t)k * ORC_NH_MAX + i];
+    for (int a = 0; a < n; a++)
+      for (int b = 0; b < n; b++) Cm[a * nv + b] += wgt * Ci[a * n + b];
+  }
+  if (d->has_goal) {
+    const double *G = w->Gc + (size_t)k * 64;
+    for (int a = 0; a < n; a++)
+      for (int b = 0; b < n; b++) Cm[a * nv + b] -= G[a * n + b];
+  }
+  if (dd_curv(d) && k < N - 1) {
+    double D[NVM * NVM];
+    memset(D, 0, sizeof(double) * nv * nv);
+    dd_dyn_curv(d, w->z + (size_t)k * nv, w->nu + (size_t)(k + 1) * nx, D);
+    for (int a = 0; a < nv * nv; a++) Cm[a] -= D[a];
+  }
+  for (int a = 0; a < nv; a++)   /* (the sums above are symmetric up to the order of their products) */
+    for (int b = a + 1; b < nv; b++) Cm[b * nv + a] = Cm[a * nv + b];
+}
+
 /* Test entry: the first pass of a solve (cold, or warm with lam_w / nu_w / mu_w as orc_solve_warm) and ONE step
- * computation on the Gauss-Newton blocks.  Outputs, stage-major: Q [N][nv*nv], q [N][nv], A [N][nx*nx], B [N][nx*nw],
+ * computation on the blocks Q = Gauss-Newton blocks - cw * C; C: the curvature terms of the model per unit weight
+ * (stage_curv_terms; zero for a model that uses none), cw = 0: the Gauss-Newton blocks.  Outputs, stage-major: Q
+ * [N][nv*nv] the GAUSS-NEWTON blocks, Cout [N][nv*nv] (may be NULL), q [N][nv], A [N][nx*nx], B [N][nx*nw],
  * rc [N][nx] (last stage zero), t / lam [N][m], *mu, dz [N][nv], nu [N][nx] the new costates, *ok = 1 when every
  * control block was positive definite.  Returns 0, or < 0 when the start point cannot be evaluated. */
 int orc_debug_step(const orc_desc *d, const double *xinit, const double *x0, const double *params, const double *lam_w,
                    const double *nu_w, double mu_w, double *Q, double *q, double *A, double *Bm, double *rc, double *t,
-                   double *lam, double *mu_out, double *dz, double *nu, int *ok) {
+                   double *lam, double *mu_out, double *dz, double *nu, int *ok, double cw, double *Cout) {
   int nh, m;
   if (orc_num_rows(d, &nh, &m) != 0) return -1;
   const int N = d->N, nx = d->nx, nv = nvar_of(d), nw = d->ns + d->nu;
@@ -1162,9 +1191,19 @@ int orc_debug_step(const orc_desc *d, const double *xinit, const double *x0, con
   for (int k = 0; k < N - 1; k++)
     for (int i = 0; i < nx; i++) w->rc[(size_t)k * nx + i] = w->xn[(size_t)k * nx + i] - w->z[(size_t)(k + 1) * nv + i];
   stage_blocks(d, w, nh, mu, 0, 1.0);
+  memcpy(Q, w->Q, sizeof(double) * N * nv * nv);
+  if (Cout) memset(Cout, 0, sizeof(double) * N * nv * nv);
+  if (model_uses_curvature(d) && (Cout || cw != 0.0))
+    for (int k = 0; k < N; k++) {
+      double Cm[NVM * NVM];
+      stage_curv_terms(d, w, nh, k, Cm);
+      if (Cout) memcpy(Cout + (size_t)k * nv * nv, Cm, sizeof(double) * nv * nv);
+      if (cw != 0.0)
+        for (int a = 0; a < nv * nv; a++) w->Q[(size_t)k * nv * nv + a] -= cw * Cm[a];
+    }
   *ok = riccati(w) == 0;
   *mu_out = mu;
-  memcpy(Q, w->Q, sizeof(double) * N * nv * nv); memcpy(q, w->qv, sizeof(double) * N * nv);
+  memcpy(q, w->qv, sizeof(double) * N * nv);
   memcpy(A, w->A, sizeof(double) * N * nx * nx); memcpy(Bm, w->Bm, sizeof(double) * N * nx * nw);
   memcpy(rc, w->rc, sizeof(double) * N * nx);
   memcpy(t, w->t, sizeof(double) * N * m); memcpy(lam, w->lam, sizeof(double) * N * m);

@@ -158,11 +158,14 @@ int orc_solve_batch(const orc_desc *d, int B, const double *xinit,
                     orc_stats *st, int nthreads);
 
 /* Test entry: the first pass of a solve (cold: lam_w == nu_w == NULL; warm: as orc_solve_warm) and one step computation
- * on the Gauss-Newton blocks.  Stage-major outputs: Q [N][nvar*nvar], q [N][nvar], A [N][nx*nx], B [N][nx*(ns+nu)],
- * rc [N][nx], t / lam [N][m], *mu, dz [N][nvar], nu [N][nx] (new costates), *ok (1: step computed). */
+ * on the blocks Q - cw C: Q the Gauss-Newton blocks, C [N][nvar*nvar] (may be NULL) the curvature terms the model's
+ * solves subtract per unit weight (distance rows, inverse-barrier objective and goal cost over q; the unicycle's
+ * nu . grad^2 Phi with the costates of the first pass; zero for a model without such terms), cw = 0: Gauss-Newton.
+ * Stage-major outputs: Q [N][nvar*nvar], q [N][nvar], A [N][nx*nx], B [N][nx*(ns+nu)], rc [N][nx], t / lam [N][m],
+ * *mu, dz [N][nvar], nu [N][nx] (new costates), *ok (1: every control block was positive definite). */
 int orc_debug_step(const orc_desc *d, const double *xinit, const double *x0, const double *params, const double *lam_w,
                    const double *nu_w, double mu_w, double *Q, double *q, double *A, double *B, double *rc, double *t,
-                   double *lam, double *mu, double *dz, double *nu, int *ok);
+                   double *lam, double *mu, double *dz, double *nu, int *ok, double cw, double *C);
 
 /* discrete dynamics only (plant model for closed-loop tests) */
 int orc_dynamics(const orc_desc *d, const double *x, const double *u, double *xnext);

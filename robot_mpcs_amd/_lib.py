@@ -100,7 +100,7 @@ class LidarArgs(C.Structure):
 EXPORTED_SYMBOLS = [
     "rmpc_version", "rmpc_source_hash", "rmpc_last_error", "rmpc_desc_size", "rmpc_create", "rmpc_destroy", "rmpc_solve_batch",
     "rmpc_solve_batch_device", "rmpc_workspace_bytes", "rmpc_set_warm_start", "rmpc_set_pass_budget", "rmpc_is_fused", "rmpc_fused_kernel_name", "rmpc_is_async", "rmpc_set_profiling", "rmpc_get_profile",
-    "rmpc_kernel_name", "rmpc_last_passes", "rmpc_debug_sweep", "rmpc_debug_step", "rmpc_spec_source", "rmpc_spec_name", "rmpc_spec_for", "rmpc_debug_poison_lds",
+    "rmpc_kernel_name", "rmpc_last_passes", "rmpc_debug_sweep", "rmpc_debug_step", "rmpc_debug_step_curv", "rmpc_spec_source", "rmpc_spec_name", "rmpc_spec_for", "rmpc_debug_poison_lds",
     "rmpc_debug_fused_stamps", "rmpc_pack_scene_device", "rmpc_solve_batch_scene_device", "rmpc_pack_scene_workspace", "rmpc_solve_batch_packed_device", "rmpc_advance_device", "rmpc_advance_device_flags", "rmpc_retarget_device", "rmpc_advance_obstacles_device", "rmpc_free_space_device",
     "rmpc_grid_inflate_device", "rmpc_grid_fields_device", "rmpc_grid_paths_device", "rmpc_grid_cells_device",
     "rmpc_follow_path_device", "rmpc_lidar_scan_device", "rmpc_plan_points_device", "rmpc_fleet_points_device",
@@ -211,6 +211,8 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_debug_sweep.argtypes = [C.c_void_p, C.c_int] + [dp] * 9
     L.rmpc_debug_step.restype = C.c_int
     L.rmpc_debug_step.argtypes = [C.c_void_p, C.c_int] + [dp] * 15 + [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]
+    L.rmpc_debug_step_curv.restype = C.c_int
+    L.rmpc_debug_step_curv.argtypes = L.rmpc_debug_step.argtypes + [C.c_double, dp]
     L.rmpc_spec_source.restype = C.c_int64
     L.rmpc_spec_source.argtypes = [C.POINTER(RmpcDesc), C.c_char_p, C.c_char_p, C.c_int64]
     L.rmpc_spec_name.restype = C.c_char_p
@@ -677,12 +679,14 @@ class Solver:
         self._check(rc, "rmpc_debug_sweep")
         return dict(Q=Q, q0=q0, q1=q1, rc=rc_, g=g[:, :, :nh], f=f)
 
-    def debug_step(self, xinit, x0, params, duals=None):
+    def debug_step(self, xinit, x0, params, duals=None, curv=None):
         """``rmpc_debug_step``: one first sweep and one Riccati recursion on the path this handle runs in production.
         ``duals`` = (lam [B, N, m], nu [B, N, nx], mu [B]) of a previous solve (the warm first pass) or None (cold).
         Returns the blocks the recursion consumed (Q, q0, q1, rc), the slacks, multipliers and barrier parameter they
         were built with (t, lam, mu), the step dz, the new costates nu, the recursion's return value ok and ``path``: what
-        the handle holds of the switches that select the path."""
+        the handle holds of the switches that select the path.  ``curv`` = cw (a number, 0.0 included):
+        ``rmpc_debug_step_curv`` -- the sweep with the model's curvature terms, the recursion on Q - cw C, and ``C``
+        [B, N, nvar, nvar] in the result."""
         xinit = np.ascontiguousarray(xinit, dtype=np.float64).reshape(-1, self.nx)
         B = xinit.shape[0]
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(B, self.N * self.nvar)
@@ -701,10 +705,16 @@ class Solver:
         t = np.zeros((B, N, m)); lam = np.zeros((B, N, m)); mu = np.zeros(B)
         dz = np.zeros((B, N, nv)); nu = np.zeros((B, N, nx)); ok = np.zeros(B, dtype=np.int32)
         path = np.zeros(4, dtype=np.int32)
-        rc = self._L.rmpc_debug_step(self._h, B, _dp(xinit), _dp(x0), _dp(params), p(lw), p(nw), p(mw), _dp(Q), _dp(q0),
-                                     _dp(q1), _dp(rc_), _dp(t), _dp(lam), _dp(mu), _dp(dz), _dp(nu),
-                                     ok.ctypes.data_as(C.POINTER(C.c_int32)), m, path.ctypes.data_as(C.POINTER(C.c_int32)))
+        args = (self._h, B, _dp(xinit), _dp(x0), _dp(params), p(lw), p(nw), p(mw), _dp(Q), _dp(q0),
+                _dp(q1), _dp(rc_), _dp(t), _dp(lam), _dp(mu), _dp(dz), _dp(nu),
+                ok.ctypes.data_as(C.POINTER(C.c_int32)), m, path.ctypes.data_as(C.POINTER(C.c_int32)))
+        extra = {}
+        if curv is None:
+            rc = self._L.rmpc_debug_step(*args)
+        else:
+            extra["C"] = np.zeros((B, N, nv, nv))
+            rc = self._L.rmpc_debug_step_curv(*args, float(curv), _dp(extra["C"]))
         self._check(rc, "rmpc_debug_step")
-        return dict(Q=Q, q0=q0, q1=q1, rc=rc_, t=t, lam=lam, mu=mu, dz=dz, nu=nu, ok=ok.astype(bool),
+        return dict(Q=Q, **extra, q0=q0, q1=q1, rc=rc_, t=t, lam=lam, mu=mu, dz=dz, nu=nu, ok=ok.astype(bool),
                     path=dict(fused=("", "k_fused", "k_fused_arm")[path[0]], ric_lane=int(path[1]), arm_parts=int(path[2]),
                               generated_view=bool(path[3])))

@@ -406,13 +406,33 @@ static int sum_stamps(int (*VariantOps::*reader)(long long *), long long *out) {
 
 // stage records -> the dense blocks of rmpc_debug_sweep / rmpc_debug_step in instance-major order; rec(off, k, b): word
 // off of the record of stage k of instance b
+// out_C (may be null): the curvature entries of the records as the dense symmetric matrix a recursion subtracts per
+// unit weight -- R_C over the q block; the unicycle's R_D entries over (theta, omega, u1 | v, u0) in the order
+// Cfg::ND lists them, placed here by variable index (not through RicCtx::cp).
 template <class RecFn>
-static void unpack_records(const DevModel &M, int B, RecFn rec, double *out_Q, double *out_q0, double *out_q1, double *out_rc) {
+static void unpack_records(const DevModel &M, int B, RecFn rec, double *out_Q, double *out_q0, double *out_q1, double *out_rc,
+                           double *out_C = nullptr) {
   const int nq = M.n, nv = M.nv;
   const RecLayout L = rec_layout(M);
   for (int b = 0; b < B; b++)
     for (int k = 0; k < M.N; k++) {
       const size_t sb = (size_t)b * M.N + k;
+      if (out_C) {
+        double *Cm = out_C + sb * nv * nv;
+        for (int i = 0; i < nv * nv; i++) Cm[i] = 0.0;
+        int s = 0;
+        for (int a = 0; a < nq; a++)
+          for (int c = a; c < nq; c++) { double v = rec(L.c + s++, k, b); Cm[a * nv + c] = v; Cm[c * nv + a] = v; }
+        if (M.robot == RMPC_ROBOT_DIFFDRIVE) {
+          const int th = 2, v_ = 6, om = 7, u0 = M.nx + M.ns, u1 = u0 + 1;
+          const int pr[11][2] = {{th, om}, {th, u1}, {om, om}, {om, u1}, {u1, u1},
+                                 {th, v_}, {th, u0}, {om, v_}, {om, u0}, {u1, v_}, {u1, u0}};
+          for (int i = 0; i < 11; i++) {
+            const double v = rec(L.d + i, k, b);
+            Cm[pr[i][0] * nv + pr[i][1]] = v; Cm[pr[i][1] * nv + pr[i][0]] = v;
+          }
+        }
+      }
       if (out_Q) {
         double *Q = out_Q + sb * nv * nv;
         for (int i = 0; i < nv * nv; i++) Q[i] = 0.0;
@@ -892,6 +912,14 @@ int rmpc_debug_step(rmpc_handle *h, int B, const double *xinit, const double *x0
                     const double *lam_w, const double *nu_w, const double *mu_w, double *out_Q, double *out_q0,
                     double *out_q1, double *out_rc, double *out_t, double *out_lam, double *out_mu, double *out_dz,
                     double *out_nu, int32_t *out_ok, int m_rows, int32_t *out_path) {
+  return rmpc_debug_step_curv(h, B, xinit, x0, params, lam_w, nu_w, mu_w, out_Q, out_q0, out_q1, out_rc, out_t, out_lam, out_mu,
+                              out_dz, out_nu, out_ok, m_rows, out_path, 0.0, nullptr);
+}
+
+int rmpc_debug_step_curv(rmpc_handle *h, int B, const double *xinit, const double *x0, const double *params,
+                         const double *lam_w, const double *nu_w, const double *mu_w, double *out_Q, double *out_q0,
+                         double *out_q1, double *out_rc, double *out_t, double *out_lam, double *out_mu, double *out_dz,
+                         double *out_nu, int32_t *out_ok, int m_rows, int32_t *out_path, double cw, double *out_C) {
   if (!h || !xinit || !x0 || !params || !out_t || !out_lam || !out_mu || !out_dz || !out_nu || !out_ok) return fail("null argument");
   if (m_rows != h->M.m) return fail("rmpc_debug_step: out_t / out_lam are sized for " + std::to_string(m_rows) + " rows, the model has " + std::to_string(h->M.m));
   if (out_path) {
@@ -903,6 +931,12 @@ int rmpc_debug_step(rmpc_handle *h, int B, const double *xinit, const double *x0
   }
   const int warm = (lam_w || nu_w || mu_w) ? 1 : 0;
   if (warm && !(lam_w && nu_w && mu_w)) return fail("rmpc_debug_step: lam_w, nu_w and mu_w come together");
+  // the plain hook (cw = 0, no out_C) sweeps without the curvature terms, as it always has; the other sweeps with the model's
+  const bool curv = cw != 0.0 || out_C != nullptr;
+  const int sweep_curv = curv ? h->M.use_curv : 0;
+  if (!(cw >= 0.0 && cw <= 1.0)) return fail("rmpc_debug_step_curv: the curvature weight is in [0, 1]");
+  if (h->fused && h->ops->arm_fused && cw != 0.0 && cw != 1.0)
+    return fail("rmpc_debug_step_curv: k_fused_arm runs its recursion at the weight 0 or 1");
   if (enter_batch(h, B)) return -1;
   if (ensure_staging(h) != 0) return -1;
   const DevModel &M = h->M;
@@ -950,7 +984,7 @@ int rmpc_debug_step(rmpc_handle *h, int B, const double *xinit, const double *x0
     double *const d_rec = d_buf, *const d_dz = d_rec + n_rec, *const d_nu = d_dz + n_dz, *const d_mu = d_nu + n_nu;
     hipError_t e = hipMemsetAsync(d_buf, 0, sizeof(double) * (n_rec + n_dz + n_nu + B), st);
     if (e == hipSuccess) {
-      h->ops->fused_step_debug(h, B, h->d_xinit, h->d_x0, h->d_params, warm, d_rec, d_dz, d_nu, d_mu, d_ok, st);
+      h->ops->fused_step_debug(h, B, h->d_xinit, h->d_x0, h->d_params, warm, sweep_curv, cw, d_rec, d_dz, d_nu, d_mu, d_ok, st);
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -978,16 +1012,32 @@ int rmpc_debug_step(rmpc_handle *h, int B, const double *xinit, const double *x0
     dim3 g2((B + 63) / 64, (N * nv + 63) / 64);
     hipLaunchKernelGGL(k_pack, g2, dim3(256), 0, st, h->d_x0, h->W.z[0], B, N * nv, nv, N, h->Bp);
     hipLaunchKernelGGL(k_init, dim3((B + 255) / 256), dim3(256), 0, st, h->W, h->d_xinit, B, nx, M.mu0, warm);
+    int *d_okp = nullptr;   // (rmpc_debug_step_curv) the recursion's return value / lane path: the weight cannot be taken
+    int lane_path = 0;
+    if (curv) HIPCHK(hipMalloc((void **)&d_okp, sizeof(int) * B));
     {
-      // the existing first pass, cold or warm, with the curvature terms off: k_sweep, then the recursion kernel
+      // the existing first pass, cold or warm: k_sweep (plain hook: with the curvature terms off), then the recursion
+      // kernel, or the recursion at the weight cw
       const int wm = h->warm_mode, uc = h->M.use_curv;
-      h->warm_mode = warm; h->have_duals = warm != 0; h->M.use_curv = 0;
+      h->warm_mode = warm; h->have_duals = warm != 0; h->M.use_curv = sweep_curv;
       h->ops->pass(h, Phase{h->W, B}, 1, 0, st, K_SWEEP);
-      h->ops->pass(h, Phase{h->W, B}, 1, 0, st, K_RICCATI);
+      if (curv) lane_path = h->ops->pass_step_debug(h, Phase{h->W, B}, cw, d_okp, st);
+      else h->ops->pass(h, Phase{h->W, B}, 1, 0, st, K_RICCATI);
       h->warm_mode = wm; h->have_duals = false; h->M.use_curv = uc;
     }
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipGetLastError());
+    std::vector<int> okp((size_t)(curv ? B : 0));
+    {
+      hipError_t e = hipStreamSynchronize(st);
+      if (e == hipSuccess) e = hipGetLastError();
+      if (e == hipSuccess && curv) e = hipMemcpy(okp.data(), d_okp, sizeof(int) * B, hipMemcpyDeviceToHost);
+      if (d_okp) (void)hipFree(d_okp);
+      if (e != hipSuccess) return fail(std::string("rmpc_debug_step: ") + hipGetErrorString(e));
+    }
+    if (lane_path)
+      for (int b = 0; b < B; b++)
+        if (okp[b])
+          return fail("rmpc_debug_step_curv: k_riccati_lane takes its curvature weight from the instance (mu <= 1e-2: the scale, "
+                      "else 0); this first pass cannot run at the weight asked for");
     const size_t S = (size_t)N * h->Bp;
     std::vector<int> newstep((size_t)B), status((size_t)B);
     if (fetch(h->W.R, S * rs, R) || fetch(h->W.t[1], S * m, tv) || fetch(h->W.lam[1], S * m, lv) || fetch(h->W.dz, S * nv, dz) ||
@@ -996,7 +1046,8 @@ int rmpc_debug_step(rmpc_handle *h, int B, const double *xinit, const double *x0
     HIPCHK(hipMemcpy(newstep.data(), h->W.newstep, sizeof(int) * B, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(status.data(), h->W.status, sizeof(int) * B, hipMemcpyDeviceToHost));
     for (int b = 0; b < B; b++) {
-      ok[b] = (status[b] == ST_ACTIVE && newstep[b] == 1) ? 1 : 0;   // (what the kernel stores when the recursion returned true)
+      if (curv && !lane_path) ok[b] = okp[b];
+      else ok[b] = (status[b] == ST_ACTIVE && newstep[b] == 1) ? 1 : 0;   // (what the kernel stores when the recursion returned true)
       for (int k = 0; k < N; k++) {
         const size_t sb = (size_t)b * N + k;
         for (int j = 0; j < nv; j++) out_dz[sb * nv + j] = dz[widx(nv, j, k, b)];
@@ -1005,7 +1056,7 @@ int rmpc_debug_step(rmpc_handle *h, int B, const double *xinit, const double *x0
     }
   }
   auto rec = [&](int off, int k, int b) { return R[((size_t)b * N + k) * rs + off]; };
-  unpack_records(M, B, rec, out_Q, out_q0, out_q1, out_rc);
+  unpack_records(M, B, rec, out_Q, out_q0, out_q1, out_rc, out_C);
   for (int b = 0; b < B; b++) {
     out_mu[b] = mu[b];
     out_ok[b] = ok[b];

@@ -66,13 +66,13 @@ struct Phase {
 
 // Host view of the stage-record layout, for the host code that sizes or reads records without a variant at hand
 // (rmpc_workspace_bytes, rmpc_debug_sweep).  rmpc_variants.hip checks it against Cfg::R_* of every variant it builds.
-struct RecLayout { int q, c, dg, cs, q0, q1, rc, a5, b5, rw, rs; };
+struct RecLayout { int q, c, dg, cs, q0, q1, rc, a5, b5, d, rw, rs; };
 constexpr RecLayout rec_layout(int robot, int n, int nv, int ns, int nx) {
   RecLayout L{};
   const int nq2 = n * (n + 1) / 2;
   L.q = 0; L.c = nq2; L.dg = 2 * nq2; L.cs = L.dg + (nv - n);
   L.q0 = L.cs + (ns > 0 ? nv : 0); L.q1 = L.q0 + nv; L.rc = L.q1 + nv;
-  L.a5 = L.rc + nx; L.b5 = L.a5 + 25;
+  L.a5 = L.rc + nx; L.b5 = L.a5 + 25; L.d = L.b5 + 10;
   L.rw = L.a5 + (robot == RMPC_ROBOT_DIFFDRIVE ? 35 + 11 : 0);   // (+ Cfg::ND curvature entries)
   L.rs = (L.rw + 1 + 7) / 8 * 8;
   return L;
@@ -97,10 +97,16 @@ struct VariantOps {
   void (*fused_launch)(rmpc_handle *h, int B, const double *d_xinit, const double *d_x0, const double *d_params,
                        double *d_zout, int *d_exit, int *d_iters, double *d_kkt, double *d_obj, hipStream_t st, int cap,
                        int warm, int use_order);
-  // test aid (rmpc_debug_step, rmpc_step_debug.hpp): first sweep and recursion of the fused kernel, nullptr: none.
+  // test aid (rmpc_debug_step[_curv], rmpc_step_debug.hpp): first sweep and recursion of the fused kernel, nullptr: none.
+  // use_curv: DevModel::use_curv of the sweep; cw: curvature weight of the recursion (the arms: 0 or 1).
   // d_rec [B][N][rs], d_dz [B][N][nv], d_nu [B][N][nx], d_mu [B], d_ok [B]
   void (*fused_step_debug)(rmpc_handle *h, int B, const double *d_xinit, const double *d_x0, const double *d_params, int warm,
-                           double *d_rec, double *d_dz, double *d_nu, double *d_mu, int *d_ok, hipStream_t st);
+                           int use_curv, double cw, double *d_rec, double *d_dz, double *d_nu, double *d_mu, int *d_ok,
+                           hipStream_t st);
+  // test aid (rmpc_debug_step_curv): the recursion of the pass kernels at the weight cw on the records of the first
+  // sweep.  k_riccati's path: d_ok [B] the recursion's return value, returns 0.  k_riccati_lane's (ric_lane as
+  // launch_pass reads it): runs the kernel itself, d_ok [B] is 1 where the first pass cannot take that weight, returns 1.
+  int (*pass_step_debug)(rmpc_handle *h, const Phase &ph, double cw, int *d_ok, hipStream_t st);
   void (*advance)(rmpc_handle *h, int B, const double *d_z_prev, const int *ef, double *d_xinit, double *d_x0,
                   int previous_plan, hipStream_t st);
   void (*retarget)(rmpc_handle *h, int B, const RetargetDev &R, hipStream_t st);

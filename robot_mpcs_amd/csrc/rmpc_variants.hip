@@ -84,14 +84,18 @@ void launch_fused_arm(rmpc_handle *h, int B, const double *d_xinit, const double
 // rmpc_debug_step on a fused handle: the grid and the parts per stage of launch_fused / launch_fused_arm
 template <class C, class V>
 void launch_fused_step_debug(rmpc_handle *h, int B, const double *d_xinit, const double *d_x0, const double *d_params, int warm,
-                             double *d_rec, double *d_dz, double *d_nu, double *d_mu, int *d_ok, hipStream_t st) {
+                             int use_curv, double cw, double *d_rec, double *d_dz, double *d_nu, double *d_mu, int *d_ok,
+                             hipStream_t st) {
   hipLaunchKernelGGL((k_fused_step_debug<C, C::FUSED_REC_LDS, V>), dim3((B + 1) / 2), dim3(64), 0, st, h->M, h->d_T, h->F, B,
-                     d_xinit, d_x0, d_params, warm, d_rec, d_dz, d_nu, d_mu, d_ok);
+                     d_xinit, d_x0, d_params, warm, use_curv, cw, d_rec, d_dz, d_nu, d_mu, d_ok);
 }
 
 template <class C>
 void launch_fused_arm_step_debug(rmpc_handle *h, int B, const double *d_xinit, const double *d_x0, const double *d_params, int warm,
-                                 double *d_rec, double *d_dz, double *d_nu, double *d_mu, int *d_ok, hipStream_t st) {
+                                 int use_curv, double cw, double *d_rec, double *d_dz, double *d_nu, double *d_mu, int *d_ok,
+                                 hipStream_t st) {
+  (void)use_curv;   // (arm_sweep_call reads it from the instance block)
+  const bool usec = cw != 0.0;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void *)k_fused_arm_step_debug<C, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, ArmLds<C>::TOTAL * 8);
@@ -100,10 +104,25 @@ void launch_fused_arm_step_debug(rmpc_handle *h, int B, const double *d_xinit, c
   }
   if (3 * h->M.N <= 64 && !h->env_arm_two_parts)
     hipLaunchKernelGGL((k_fused_arm_step_debug<C, 3>), dim3(B), dim3(64), ArmLds<C>::TOTAL * 8, st, h->M, h->d_T, h->F, B, d_xinit,
-                       d_x0, d_params, warm, d_rec, d_dz, d_nu, d_mu, d_ok);
+                       d_x0, d_params, warm, usec, d_rec, d_dz, d_nu, d_mu, d_ok);
   else
     hipLaunchKernelGGL((k_fused_arm_step_debug<C, 2>), dim3(B), dim3(64), ArmLds<C>::TOTAL * 8, st, h->M, h->d_T, h->F, B, d_xinit,
-                       d_x0, d_params, warm, d_rec, d_dz, d_nu, d_mu, d_ok);
+                       d_x0, d_params, warm, usec, d_rec, d_dz, d_nu, d_mu, d_ok);
+}
+
+// rmpc_debug_step_curv on the pass kernels: see VariantOps::pass_step_debug
+template <class C, class V>
+int launch_pass_step_debug(rmpc_handle *h, const Phase &ph, double cw, int *d_ok, hipStream_t st) {
+  const int B = ph.B;
+  if constexpr (C::ROBOT == RMPC_ROBOT_CHAIN && C::NQ <= 3) {
+    if (h->ric_lane == 2 || (h->ric_lane == 1 && B >= kLaneMin)) {
+      hipLaunchKernelGGL((k_lane_weight<C>), dim3((B + 63) / 64), dim3(64), 0, st, h->M, ph.W, B, cw, d_ok);
+      launch_pass<C, V>(h, ph, 1, 0, st, K_RICCATI);
+      return 1;
+    }
+  }
+  hipLaunchKernelGGL((k_riccati_step_debug<C>), dim3(B), dim3(64), 0, st, h->M, ph.W, B, cw, d_ok);
+  return 0;
 }
 
 template <class C>
@@ -170,6 +189,7 @@ VariantOps ops(const char *spec, bool (*matches)(const rmpc_desc &, const DevMod
   v.arm_fused = C::ARM_FUSED;
   v.rs = C::RS;
   v.pass = launch_pass<C, V>;
+  v.pass_step_debug = launch_pass_step_debug<C, V>;
   if constexpr (C::FUSED_OK) {
     v.difficulty = launch_difficulty<C>;
     v.fused_launch = launch_fused<C, V>;
@@ -195,7 +215,7 @@ bool add_variant() {
   if constexpr (BUILD) {
     constexpr RecLayout L = rec_layout(C::ROBOT, C::NQ, C::NV, C::NS, C::NX);
     static_assert(L.q == C::R_Q && L.c == C::R_C && L.dg == C::R_DG && L.cs == C::R_CS && L.q0 == C::R_Q0 && L.q1 == C::R_Q1 &&
-                  L.rc == C::R_RC && L.a5 == C::R_A5 && L.b5 == C::R_B5 && L.rw == C::RW && L.rs == C::RS,
+                  L.rc == C::R_RC && L.a5 == C::R_A5 && L.b5 == C::R_B5 && L.d == C::R_D && L.rw == C::RW && L.rs == C::RS,
                   "rec_layout out of step with Cfg::R_*");
     add_variant_ops(ops<C, RtView>("", nullptr));
 #define RMPC_S(ID, S, ROBOT_, NQ_, NS_) \

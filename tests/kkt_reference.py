@@ -93,6 +93,41 @@ def textbook_riccati(Q, q, A, B, rc):
     return dz, nu
 
 
+def verdict(Q, A, B, gn_diag=None):
+    """Is the condensed QP's reduced Hessian positive definite, and by what margin?  The textbook recursion on the
+    cost-to-go alone, never raising: per stage (last to first) the smallest eigenvalue of the control block
+    Quu = Q_uu + B^T P B over its largest diagonal entry, the block first scaled to a unit diagonal, S Quu S with
+    S = diag(d)^-1/2 (what a Cholesky pivot is measured against is its own diagonal entry, and without the scaling the
+    slack's weight, 2e10 beside input weights of 1e-2, would make the ratio 1e-12 for every block of a model with a
+    slack, definite or not; with equal diagonal entries the two ratios are the same number).  d_i = |Quu_ii|, and no
+    less than gn_diag[k, i] where that is given -- the diagonal of the Gauss-Newton control block Q is made from, so
+    that an entry the curvature terms have cancelled or turned negative is measured against what it was made of.
+    Returns (pd, ratio): all stages positive -> (True, the smallest ratio); else (False, the ratio of the first stage
+    met that is not positive -- the recursion below it is undefined)."""
+    N = Q.shape[0]
+    nx = A.shape[1]
+    P = np.zeros((nx, nx))
+    worst = np.inf
+    for k in range(N - 1, -1, -1):
+        Qk = np.array(Q[k], dtype=np.float64)
+        if k < N - 1:
+            AB = np.hstack([A[k], B[k]])
+            Qk = Qk + AB.T @ P @ AB
+        Qxx, Qxu, Quu = Qk[:nx, :nx], Qk[:nx, nx:], Qk[nx:, nx:]
+        Quu = 0.5 * (Quu + Quu.T)
+        d = np.abs(np.diag(Quu))
+        if gn_diag is not None:
+            d = np.maximum(d, gn_diag[k])
+        s = 1.0 / np.sqrt(np.where(d > 0.0, d, 1.0))
+        ratio = float(np.linalg.eigvalsh(Quu * s[:, None] * s[None, :])[0])
+        if not ratio > 0.0:
+            return False, ratio
+        worst = min(worst, ratio)
+        P = Qxx - Qxu @ np.linalg.solve(Quu, Qxu.T)
+        P = 0.5 * (P + P.T)
+    return True, worst
+
+
 def block_errors(dz, nu, dz_ref, nu_ref, nx, nu_from=0):
     """Worst error over the stages and the three blocks of a stage (dx, the controls with the slack, nu+): max-norm of
     the difference over the max-norm of that block of the reference.  A block of zeros is compared absolutely; the

@@ -7,6 +7,9 @@ Modes
         rows at the warm-start clamp (t = 1e-4) and of a random third of the others set to 10^U(0, 4), and the stored
         barrier parameter (1e-10) makes the warm start begin at its floor 1e-6: the blocks of a late iteration
         (lam / t up to 1e8) through the existing warm first pass.
+  conv  (the exact-Hessian tests only: not in MODES) x0 is the oracle's converged plan and the duals are that solve's
+        own, unmodified, with a stored barrier parameter of 1e-10: the blocks a late iteration really sees.  The random
+        multipliers of `late` on convex distance rows make the exact Hessian indefinite by construction.
 
 Tolerance: errors are measured per stage and block against the refined dense solution (kkt_reference.block_errors);
 the textbook fp64 Riccati recursion's worst error over the instances of the class is the unit, and a solver path may
@@ -29,9 +32,11 @@ def case_seed(*key):
     return zlib.crc32(repr(key).encode()) % 100000
 
 
-def make_inputs(make_scenario, Oracle, name, mode, B, **kw):
-    """Scenario, oracle and the inputs of the step hooks: xinit, x0, params, duals (None in the cold mode)."""
-    seed = case_seed(name, sorted(kw.items()))
+def make_inputs(make_scenario, Oracle, name, mode, B, salt=0, **kw):
+    """Scenario, oracle and the inputs of the step hooks: xinit, x0, params, duals (None in the cold mode).  salt: another
+    draw of the same class."""
+    assert mode in ("cold", "late", "conv"), mode
+    seed = case_seed(name, sorted(kw.items())) + salt
     sc = make_scenario(name, B=B, seed=seed, **kw)
     o = Oracle(sc.desc)
     if mode == "cold":
@@ -45,6 +50,8 @@ def make_inputs(make_scenario, Oracle, name, mode, B, **kw):
         assert r["exitflag"] in (1, 2), (name, b, r["exitflag"])
         x0[b] = r["z"]
         lam[b], nu[b] = r["duals"][0], r["duals"][1]
+        if mode == "conv":
+            continue
         P = sc.params[b].reshape(N, o.npar)
         for k in range(N):
             g = o.eval_stage(x0[b, k], P[k], derivs=False, dynamics=False, fixed_state=(k == 0))["g"]
@@ -53,7 +60,7 @@ def make_inputs(make_scenario, Oracle, name, mode, B, **kw):
             clamped += int((g < WARM_TMIN).sum())
             lam[b, ks] = np.where(big, 10.0 ** rng.uniform(0.0, 4.0, m), lam[b, ks])
     # (one or two stages with the first state fixed: the converged plan of the point robots touches no row)
-    assert clamped > 0 or N <= 2, "no row of the class sits at the warm-start clamp"
+    assert mode == "conv" or clamped > 0 or N <= 2, "no row of the class sits at the warm-start clamp"
     return sc, o, sc.xinit, x0, sc.params, (lam, nu, np.full(B, 1e-10))
 
 

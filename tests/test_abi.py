@@ -38,6 +38,19 @@ def test_descriptor_layout_and_version(lib):
     assert [L.rmpc_kernel_name(i).decode() for i in range(5)] == ["k_pack", "k_sweep", "k_riccati", "k_step", "k_unpack"]
 
 
+def test_debug_step_hooks_are_exported_and_refuse_a_null_handle(lib):
+    """rmpc_debug_step and rmpc_debug_step_curv (the same hook with the curvature weight and out_C) are part of the
+    exported set and fail cleanly without a handle."""
+    L = lib.load_library()
+    assert {"rmpc_debug_step", "rmpc_debug_step_curv"} <= set(lib.EXPORTED_SYMBOLS)
+    assert len(L.rmpc_debug_step_curv.argtypes) == len(L.rmpc_debug_step.argtypes) + 2
+    none = [None] * 15
+    i32 = C.POINTER(C.c_int32)()
+    assert L.rmpc_debug_step(None, 1, *none, i32, 0, i32) != 0
+    assert L.rmpc_debug_step_curv(None, 1, *none, i32, 0, i32, 1.0, None) != 0
+    assert b"null" in L.rmpc_last_error()
+
+
 def test_workspace_bytes_is_host_only_and_scales(lib):
     from robot_mpcs_amd.scenarios import make_scenario
     L = lib.load_library()
