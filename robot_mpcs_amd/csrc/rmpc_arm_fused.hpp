@@ -20,14 +20,9 @@
 #pragma once
 // (included inside namespace rmpc)
 
-#ifdef RMPC_STAMPS
-// development aid: cycles per section of the part-wise sweep, summed over the calls of all wavefronts into g_sst
-// ([0] q + chain walk, [1] slots, [2] sums over the parts, [3] joints, [4] block stores, [5] step lengths + reduction,
+// (stamp builds, SecStamps: cycles per section of the part-wise sweep, summed over the calls of all wavefronts into g_sst
+//  -- [0] q + chain walk, [1] slots, [2] sums over the parts, [3] joints, [4] block stores, [5] step lengths + reduction,
 //  [6] reduction of the partials, [7] calls)
-#define AP_STAMP(i) do { const long long t_ = __builtin_amdgcn_s_memtime(); ap_acc[i] += t_ - ap_t0; ap_t0 = t_; } while (0)
-#else
-#define AP_STAMP(i)
-#endif
 // Element `slot` of an instance-block array for the lane's stage: the arrays of the fused layout are [slot][32 stages],
 // their bases are uniform (one instance per wavefront) -- 32-bit lane offsets on scalar bases, so that a request is
 // "scalar base + vector offset" instead of a 64-bit address computed per lane.
@@ -66,11 +61,7 @@ __device__ __forceinline__ double part_pick(const int p, const double v0, const 
 template <class C, int P, class RP, class SP, class V, int FIRSTC>
 __device__ __forceinline__ void sweep_part(const SweepK M, const V &v, const SweepIO<RP, SP> &io, const int k, const int p,
                                            const bool nostep, const double alpha, const double adual, const double mu,
-                                           Partials &out
-#ifdef RMPC_STAMPS
-                                           , long long (&ap_acc)[8], long long &ap_t0
-#endif
-                                           ) {
+                                           Partials &out, SecStamps &st) {
   static_assert(C::ROBOT == RMPC_ROBOT_CHAIN && C::NS == 0 && C::FKCURV, "part-wise sweep: the arms (holonomic chain, no slack)");
   constexpr int NQ = C::NQ, NX = C::NX, NQ2 = C::NQ2;
   constexpr int NJP = (NQ + P - 1) / P, NSP = (kMaxSlots + P - 1) / P;
@@ -214,7 +205,7 @@ __device__ __forceinline__ void sweep_part(const SweepK M, const V &v, const Swe
     }
   }
 
-  AP_STAMP(0);
+  st(0);
   // ---- this part's slots: GoalReaching (slot 0), distance rows, curvature blocks -----------------------------------
   double bq[NQ2], bc[NQ2], qgf[NQ], qq0[NQ], qq1[NQ], qrs[NQ];
 #pragma unroll
@@ -369,7 +360,7 @@ __device__ __forceinline__ void sweep_part(const SweepK M, const V &v, const Swe
       }
     }
   }
-  AP_STAMP(1);
+  st(1);
   // ---- row structure of a joint's variables (uniform: rmpc_create admits a model to this kernel only when every joint
   //      carries the same rows -- arm_rows_uniform -- so the descriptors of joint 0 tell which rows exist, whether their
   //      limit is a parameter and their sign, by scalar loads and scalar branches), then the per-lane descriptors of this
@@ -419,7 +410,7 @@ __device__ __forceinline__ void sweep_part(const SweepK M, const V &v, const Swe
       rec[C::R_C + e] = M.use_curv ? vc : 0.0;
     }
   }
-  AP_STAMP(2);
+  st(2);
   // ---- this part's joints: the variables q_a, v_a, u_a -------------------------------------------------------------
   double djq[NJP];   // what the single-variable rows of q_a add to the diagonal of the q block
 #pragma unroll
@@ -585,7 +576,7 @@ __device__ __forceinline__ void sweep_part(const SweepK M, const V &v, const Swe
       }
     }
   });
-  AP_STAMP(3);
+  st(3);
   // ---- the diagonal of the q block again, with the terms of the joints' own rows (every part stores the same values) ----
 #pragma unroll
   for (int a = 0; a < NQ; a++) {
@@ -597,7 +588,7 @@ __device__ __forceinline__ void sweep_part(const SweepK M, const V &v, const Swe
   bad |= (int)(!isfinite(f) | !isfinite(theta) | !isfinite(logsum));
   out.f = f; out.th = theta; out.logs = logsum; out.rstat = rstat; out.req = req; out.rineq = rineq;
   out.rcomp = rcomp; out.sumc = sumc; out.minc = minc; out.bad = (double)bad;
-  AP_STAMP(4);
+  st(4);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -777,9 +768,8 @@ __device__ __noinline__ void arm_sweep_call(__attribute__((address_space(3))) Ar
     Pw.pgf = (gdouble *)F.gfa + bu * F.nv * S;
     Pw.pwl = (gdouble *)F.wlam + bu * F.m * S; Pw.pwn = (gdouble *)F.wnu + bu * F.nx * S;
   }
-#ifdef RMPC_STAMPS
-  long long ap_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ap_t0 = __builtin_amdgcn_s_memtime();
-#endif
+  SecStamps st;
+  st.start();
   double ap = 1.0, ad = 1.0, gp = 0.0;
   if (fresh) {
     StepIO<ldouble> io;
@@ -800,7 +790,7 @@ __device__ __noinline__ void arm_sweep_call(__attribute__((address_space(3))) Ar
   const double gphi = fresh ? gp : gphi_in;
   const double alpha = nostep ? 0.0 : ldexp(amin_p, -ls), adual = nostep ? 0.0 : amin_d;
   Partials q = {0, 0, 0, 0, 0, 0, 0, 0, 1e300, 0};
-  AP_STAMP(5);
+  st(5);
   {
     SweepIO<gdouble, ldouble> io;
     io.zc = Pw.zc; io.tc = Pw.tc; io.lc = Pw.lc; io.nc = Pw.nc;
@@ -813,11 +803,7 @@ __device__ __noinline__ void arm_sweep_call(__attribute__((address_space(3))) Ar
     io.SSd = 1; io.loffd = (unsigned)(ks * SW); io.kstrided = live && k < N - 1 ? (unsigned)SW : 0u;
     io.wl = Pw.pwl; io.wn = Pw.pwn; io.warm = warm;
     const SweepK sk = {N, blk->M.dt, blk->M.use_curv};
-    sweep_part<C, P, gdouble, ldouble, GView, FIRSTC>(sk, v, io, k, p, nostep, alpha, adual, mu, q
-#ifdef RMPC_STAMPS
-                                                      , ap_acc, ap_t0
-#endif
-                                                      );
+    sweep_part<C, P, gdouble, ldouble, GView, FIRSTC>(sk, v, io, k, p, nostep, alpha, adual, mu, q, st);
   }
   {
     // (lanes without a stage contribute the neutral elements)
@@ -829,13 +815,8 @@ __device__ __noinline__ void arm_sweep_call(__attribute__((address_space(3))) Ar
     out->rstat = rm4[0]; out->req = rm4[1]; out->rineq = rm4[2]; out->rcomp = rm4[3]; out->minc = rn1[0];
     out->amin_p = amin_p; out->amin_d = amin_d; out->gphi = gphi;
   }
-#ifdef RMPC_STAMPS
-  AP_STAMP(6);
-  if (lane == 0) {
-    for (int i = 0; i < 7; i++) atomicAdd((unsigned long long *)&g_sst[i], (unsigned long long)ap_acc[i]);
-    atomicAdd((unsigned long long *)&g_sst[7], 1ull);
-  }
-#endif
+  st(6);
+  st.flush(lane == 0, 7);
 }
 
 template <class C>
@@ -901,10 +882,8 @@ void k_fused_arm(const DevModel M, const DevTables *__restrict__ Tp, const Fused
   int nextslot = blockIdx.x;
   int *const qhead = F.passes + 1;
   double gphi_sum = 0.0;
-#ifdef RMPC_STAMPS
-  long long st_sweep = 0, st_dec = 0, st_ric = 0, st_pro = 0, st_t0 = __builtin_amdgcn_s_memtime(), st_a = st_t0, st_b;
-  int st_pass = 0;
-#endif
+  PassStamps ps;
+  ps.start();
   for (;;) {
     // ---- a finished instance leaves, the next one of the queue comes in -----------------------------------------
     {
@@ -993,10 +972,8 @@ void k_fused_arm(const DevModel M, const DevTables *__restrict__ Tp, const Fused
     const bool act = valid && (s.status == ST_ACTIVE);
     if (!act) break;   // (uniform) the queue is empty
     ipass++;
-#ifdef RMPC_STAMPS
-    st_pass++;
-    STAMP_B(st_pro);
-#endif
+    ps.pass_begin(lane == 0, first);
+    ps(PH_STEP);   // (here: the hand-over and the top of the loop)
     // ---- step lengths of a fresh step, sweep at the trial point --------------------------------------------------------
     const bool nostep = first || (s.redo != 0);
     const bool fresh = !nostep && (s.newstep != 0);
@@ -1012,16 +989,12 @@ void k_fused_arm(const DevModel M, const DevTables *__restrict__ Tp, const Fused
     }
     r.gphi = first ? 0.0 : gphi_sum;
     GSYNC();   // trial point and records are complete before any lane reads another lane's part
-#ifdef RMPC_STAMPS
-    STAMP_B(st_sweep);
-#endif
+    ps(PH_SWEEP);
     // ---- decisions, then a new step when the trial was accepted ----------------------------------------------------------
     bool usec = false;
     const bool recurse = inst_decide<C>(M, s, r, first, usec);
     first = false;
-#ifdef RMPC_STAMPS
-    STAMP_B(st_dec);
-#endif
+    ps(PH_DEC);
     park();
     bool rec_ok = true;
     if (recurse)
@@ -1030,16 +1003,8 @@ void k_fused_arm(const DevModel M, const DevTables *__restrict__ Tp, const Fused
     unpark();
     if (recurse) inst_after_recursion(s, rec_ok, usec);
     GSYNC();   // dz, nu+
-#ifdef RMPC_STAMPS
-    STAMP_B(st_ric);
-#endif
+    ps(PH_RIC);
   }
-#ifdef RMPC_STAMPS
-  if (threadIdx.x == 0) {
-    long long *o = F.stamps + (size_t)blockIdx.x * 8;
-    o[0] = st_sweep; o[1] = st_dec; o[2] = st_ric; o[3] = st_pro; o[4] = __builtin_amdgcn_s_memtime() - st_t0; o[5] = st_pass;
-    o[6] = st_t0; o[7] = st_pass;
-  }
-#endif
+  ps.store(F.stamps, false);
 }
 

@@ -387,17 +387,17 @@ static int solve_device(rmpc_handle *h, int B, const double *d_xinit, const doub
 #if defined(RMPC_STAMPS) || defined(RMPC_RIC_STAMPS)
 // development aid: reads and clears the stamp counters of every variant unit (each code object holds its own copy;
 // the entries of one unit share its reader) and returns their sums
-static int sum_stamps(int (*VariantOps::*reader)(long long *), long long *out) {
-  std::vector<int (*)(long long *)> seen;
+static int sum_stamps(const int which, long long *out) {
+  std::vector<int (*)(int, long long *)> seen;
   for (int i = 0; i < 8; i++) out[i] = 0;
   for (const VariantOps &v : variant_table()) {
-    int (*const r)(long long *) = v.*reader;
+    int (*const r)(int, long long *) = v.read_stamps;
     bool dup = false;
     for (auto q : seen) dup = dup || q == r;
     if (dup) continue;
     seen.push_back(r);
     long long part[8];
-    if (r(part)) return 1;
+    if (r(which, part)) return 1;
     for (int i = 0; i < 8; i++) out[i] += part[i];
   }
   return 0;
@@ -807,10 +807,10 @@ int rmpc_last_passes(rmpc_handle *h) {
 
 /* development aid (builds with -DRMPC_STAMPS): per-block phase cycles of the last fused launch, 8 words per block */
 #ifdef RMPC_STAMPS
-int rmpc_debug_sweep_stamps(long long *out) { return sum_stamps(&VariantOps::sweep_stamps, out); }   // k_sweep's sections
+int rmpc_debug_sweep_stamps(long long *out) { return sum_stamps(STAMPS_SWEEP, out); }   // k_sweep's sections
 #endif
 #ifdef RMPC_RIC_STAMPS
-int rmpc_debug_ric_stamps(long long *out) { return sum_stamps(&VariantOps::ric_stamps, out); }   // the recursion's phases
+int rmpc_debug_ric_stamps(long long *out) { return sum_stamps(STAMPS_RIC, out); }   // the recursion's phases
 #endif
 int rmpc_debug_fused_stamps(rmpc_handle *h, long long *out, int nblocks) {
   if (!h || !h->fused) return fail("no fused workspace");

@@ -110,11 +110,9 @@ struct VariantOps {
   void (*advance)(rmpc_handle *h, int B, const double *d_z_prev, const int *ef, double *d_xinit, double *d_x0,
                   int previous_plan, hipStream_t st);
   void (*retarget)(rmpc_handle *h, int B, const RetargetDev &R, hipStream_t st);
-#ifdef RMPC_STAMPS
-  int (*sweep_stamps)(long long *out);   // reads and clears g_sst of the entry's unit
-#endif
-#ifdef RMPC_RIC_STAMPS
-  int (*ric_stamps)(long long *out);     // reads and clears g_rst of the entry's unit
+#if defined(RMPC_STAMPS) || defined(RMPC_RIC_STAMPS)
+  int (*read_stamps)(int which, long long *out);   // reads and clears g_sst / g_rst (STAMPS_*) of the entry's unit
 #endif
 };
+enum { STAMPS_SWEEP = 0, STAMPS_RIC = 1 };
 void add_variant_ops(const VariantOps &v);   // rmpc_host.hip

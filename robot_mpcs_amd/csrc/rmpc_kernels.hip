@@ -255,15 +255,133 @@ struct Partials {
   long long tk[6];   // development builds: cycles of the sections of the sweep ([4], [5]: step lengths and their reduction, fused_sweep_step_call)
 #endif
 };
+
+// Development aid (builds with -DRMPC_STAMPS): cycle stamps of the sweeps and of the fused kernels' pass loops.  Like
+// RicStamps (rmpc_riccati.hpp) the recorders have a body in those builds and none otherwise, so the places that
+// stamp carry no #ifdef and a production build is the code without them.
+enum StampPhase { PH_SWEEP = 0, PH_DEC = 1, PH_RIC = 2, PH_STEP = 3 };   // words 0 .. 3 of a wavefront's record
 #ifdef RMPC_STAMPS
-// development aid: cycles per section of k_sweep (pass kernels), summed over the wavefronts of all launches
+// cycles per section of k_sweep / of the arms' sweep call, summed over the wavefronts of all launches
 // (static: one copy per translation unit, read through the unit's entries of the variant table)
 static __device__ long long g_sst[8];
-#endif
-#ifdef RMPC_STAMPS
-#define SW_STAMP(i) do { long long t_ = __builtin_amdgcn_s_memtime(); out.tk[i] = t_ - sw_t0; sw_t0 = t_; } while (0)
+// Sections of a sweep: st(i) adds the cycles since the previous stamp to section i.
+struct SecStamps {
+  long long acc[8], t0;
+  __device__ __forceinline__ void start() {
+    for (int i = 0; i < 8; i++) acc[i] = 0;
+    t0 = __builtin_amdgcn_s_memtime();
+  }
+  __device__ __forceinline__ void operator()(const int i) {
+    const long long t = __builtin_amdgcn_s_memtime();
+    acc[i] += t - t0;
+    t0 = t;
+  }
+  // sections i0 .. i0 + n - 1 into / out of the tk words of a Partials or a SweepStepOut
+  template <class O>
+  __device__ __forceinline__ void put(O &o, const int i0, const int n) const {
+    for (int i = i0; i < i0 + n; i++) o.tk[i] = acc[i];
+  }
+  template <class O>
+  __device__ __forceinline__ void get(const O &o, const int i0, const int n) {
+    for (int i = i0; i < i0 + n; i++) acc[i] = o.tk[i];
+  }
+  // the first n sections and a call into g_sst (lane0: one lane of the wavefront)
+  __device__ __forceinline__ void flush(const bool lane0, const int n) {
+    if (lane0) {
+      for (int i = 0; i < n; i++) atomicAdd((unsigned long long *)&g_sst[i], (unsigned long long)acc[i]);
+      atomicAdd((unsigned long long *)&g_sst[7], 1ull);
+    }
+  }
+};
+// The pass loop of k_fused / k_fused_arm: cycles per phase, event counters and the wavefront's 8-word record in
+// FusedWs::stamps (read by scripts/fused_stamps.py and tests/tools/dev_arm_fused_stamps.py).
+struct PassStamps {
+  long long ph[4], sec[8], hand, t_start, t_a, t_top, t_sub;
+  int pass, ipass, nhand, both;
+  __device__ __forceinline__ void start() {
+    for (int i = 0; i < 4; i++) ph[i] = 0;
+    for (int i = 0; i < 8; i++) sec[i] = 0;
+    hand = 0;
+    pass = ipass = nhand = both = 0;
+    t_start = t_a = __builtin_amdgcn_s_memtime();
+  }
+  // hand-over: from the top of the pass loop to the test that ends it; events = epilogues + prologues (their lane 0)
+  __device__ __forceinline__ void hand_begin() { t_top = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void hand_events(const bool left, const bool took) {
+    nhand += __popcll(__ballot(left)) + __popcll(__ballot(took));
+  }
+  __device__ __forceinline__ void hand_end() { hand += __builtin_amdgcn_s_memtime() - t_top; }
+  // a pass of the wavefront.  inst: lane 0 of every instance that takes the pass; v1: the lane runs the first-pass copy
+  // of the sweep call (both copies run when the two halves of k_fused differ)
+  __device__ __forceinline__ void pass_begin(const bool inst, const bool v1) {
+    pass++;
+    ipass += __popcll(__ballot(inst));
+    both += (__ballot(v1) != 0ull && __ballot(!v1) != 0ull) ? 1 : 0;
+  }
+  __device__ __forceinline__ void mark() { t_a = __builtin_amdgcn_s_memtime(); }
+  // the cycles since the previous stamp (or mark) belong to phase p
+  __device__ __forceinline__ void operator()(const int p) {
+    const long long t = __builtin_amdgcn_s_memtime();
+    ph[p] += t - t_a;
+    t_a = t;
+  }
+  // k_fused, inside the sweep phase: the sections of the sweep call (lane 0's instance), then [6] unpark + reductions
+  // and [7] the ordering point's wait.  (By value: a reference to the caller's partials among the arguments, even of an
+  // empty function, changes how production code schedules their initialisation.)
+  template <class O>
+  __device__ __forceinline__ void sections(const O o) {
+    for (int i = 0; i < 6; i++) sec[i] += __builtin_amdgcn_readfirstlane((int)o.tk[i]);
+  }
+  __device__ __forceinline__ void sweep_returned() { t_sub = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void sweep_reduced() {
+    const long long t = __builtin_amdgcn_s_memtime();
+    sec[6] += t - t_sub;
+    t_sub = t;
+  }
+  __device__ __forceinline__ void sweep_end() {
+    (*this)(PH_SWEEP);
+    sec[7] += t_a - t_sub;
+  }
+  // Record of the wavefront: [0 .. 3] phases, [4] total, [5] passes | passes with both sweep copies << 32,
+  // [7] instance passes | hand-over events << 32.  k_fused (two = true): [6] hand-over cycles, and the sections as a
+  // second record at gridDim.x + blockIdx.x; k_fused_arm: [6] the start time.
+  __device__ __forceinline__ void store(long long *const stamps, const bool two) {
+    if (threadIdx.x == 0) {
+      long long *o = stamps + (size_t)blockIdx.x * 8;
+      if (two) {
+        long long *o2 = stamps + (size_t)(gridDim.x + blockIdx.x) * 8;
+        for (int i = 0; i < 8; i++) o2[i] = sec[i];
+      }
+      for (int i = 0; i < 4; i++) o[i] = ph[i];
+      o[4] = __builtin_amdgcn_s_memtime() - t_start;
+      o[5] = (long long)pass | ((long long)both << 32);
+      o[6] = two ? hand : t_start;
+      o[7] = (long long)ipass | ((long long)nhand << 32);
+    }
+  }
+};
 #else
-#define SW_STAMP(i)
+struct SecStamps {
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ void operator()(int) {}
+  template <class O> __device__ __forceinline__ void put(O &, int, int) const {}
+  template <class O> __device__ __forceinline__ void get(const O &, int, int) {}
+  __device__ __forceinline__ void flush(bool, int) {}
+};
+struct PassStamps {
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ void hand_begin() {}
+  __device__ __forceinline__ void hand_events(bool, bool) {}
+  __device__ __forceinline__ void hand_end() {}
+  __device__ __forceinline__ void pass_begin(bool, bool) {}
+  __device__ __forceinline__ void mark() {}
+  __device__ __forceinline__ void operator()(int) {}
+  template <class O> __device__ __forceinline__ void sections(O) {}
+  __device__ __forceinline__ void sweep_returned() {}
+  __device__ __forceinline__ void sweep_reduced() {}
+  __device__ __forceinline__ void sweep_end() {}
+  __device__ __forceinline__ void store(long long *, bool) {}
+};
 #endif
 
 // Order in which sweep_body takes the variables of a stage (positions 0 .. NV-1; the first NFIRST of them before
@@ -309,9 +427,8 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
   // kernel has no register to spare for them
   constexpr bool QLDS = C::FKCURV;
   auto qtri = [](int a, int c) __attribute__((always_inline)) { return a * C::NQ - a * (a - 1) / 2 + (c - a); };
-#ifdef RMPC_STAMPS
-  long long sw_t0 = __builtin_amdgcn_s_memtime();
-#endif
+  SecStamps st;
+  st.start();
   constexpr int NQ = C::NQ, NX = C::NX, NS = C::NS, NU = C::NU, NV = C::NV;
   const int N = M.N;
   const unsigned loff = io.loff;
@@ -515,7 +632,7 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
   double lprod = 1.0;
   int lexp = 0;
 
-  SW_STAMP(0);
+  st(0);
   // ---- control effort and slack penalty (ObjectiveManager.py:28-42) ----------
 #pragma unroll
   for (int j = 0; j < NU; j++) {
@@ -946,12 +1063,12 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
   do_slot(std::integral_constant<int, 2>{});
   do_slot(std::integral_constant<int, 3>{});
 
-  SW_STAMP(1);
+  st(1);
   // ---- the remaining single-variable rows -----------------------------------------------
   run_vars(std::integral_constant<int, Ord::NFIRST>{}, std::integral_constant<int, NV>{}, FalseT{},
            std::integral_constant<bool, PRE2>{});
 
-  SW_STAMP(2);
+  st(2);
   // ---- dynamics defect and stationarity -------------------------------------------
   double req = 0.0;
   if constexpr (CHAIN) {
@@ -1096,7 +1213,8 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
   rec[C::R_ZERO] = 0.0;
   const double logsum = log(lprod) + 0.6931471805599453094 * (double)lexp;
   bad |= (int)(!isfinite(f) | !isfinite(theta) | !isfinite(logsum));
-  SW_STAMP(3);
+  st(3);
+  st.put(out, 0, 4);
   out.f = f; out.th = theta; out.logs = logsum; out.rstat = rstat; out.req = req; out.rineq = rineq;
   out.rcomp = rcomp; out.sumc = sumc; out.minc = minc; out.bad = (double)bad;
 }
@@ -1104,9 +1222,8 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
 template <class C, class V>
 __global__ __launch_bounds__(kSweepBlock, C::SWEEP_WPE) void k_sweep(const DevModel M, const DevTables *__restrict__ Tp, const Ws W,
                                                const int B, const int first, const int warm) {
-#ifdef RMPC_STAMPS
-  const long long ks_t0 = __builtin_amdgcn_s_memtime();
-#endif
+  SecStamps st;   // [0 .. 3] the sections of sweep_body, [4] the whole kernel
+  st.start();
   const int gid = blockIdx.x * kSweepBlock + threadIdx.x;
   const int li = gid % W.Bp;   // position in the compacted list of iterating instances
   // (Bp % 64 == 0: the stage is the same for the 64 lanes of a wavefront; as a scalar, every test on it is a scalar
@@ -1160,13 +1277,9 @@ __global__ __launch_bounds__(kSweepBlock, C::SWEEP_WPE) void k_sweep(const DevMo
   W.part[IDXL(P_SUMC)] = pt.sumc;
   W.part[IDXL(P_MINC)] = pt.minc;
   W.part[IDXL(P_BAD)] = pt.bad;
-#ifdef RMPC_STAMPS
-  if ((threadIdx.x & 63) == 0) {
-    for (int i = 0; i < 4; i++) atomicAdd((unsigned long long *)&g_sst[i], (unsigned long long)pt.tk[i]);
-    atomicAdd((unsigned long long *)&g_sst[4], (unsigned long long)(__builtin_amdgcn_s_memtime() - ks_t0));
-    atomicAdd((unsigned long long *)&g_sst[7], 1ull);
-  }
-#endif
+  st(4);
+  st.get(pt, 0, 4);
+  st.flush((threadIdx.x & 63) == 0, 5);
 }
 
 // ===========================================================================
@@ -2264,10 +2377,8 @@ __device__ __noinline__ RMPC_ONE_WAVE void fused_sweep_step_call(__attribute__((
   SweepStepRes r;
   const Partials qn = {0, 0, 0, 0, 0, 0, 0, 0, 1e300, 0};
   r.q = qn;
-#ifdef RMPC_STAMPS
-  const long long ss_t0 = __builtin_amdgcn_s_memtime();
-  long long ss_t1 = ss_t0, ss_t2 = ss_t0;
-#endif
+  SecStamps st;   // [0 .. 3] the sections of sweep_body, [4] top loads + step lengths, [5] their reduction
+  st.start();
   if constexpr (FIRSTC != 0) {
     // the first pass of a solve takes no step: nothing to merge
     r.amin_p = amin_p_in; r.amin_d = amin_d_in; r.gphi = gphi_in;
@@ -2282,26 +2393,19 @@ __device__ __noinline__ RMPC_ONE_WAVE void fused_sweep_step_call(__attribute__((
     StepRow<C> sl;
     if (live) sweep_body<C, -1, ldouble, V, 0, 1>(sk, v, io, k, false, nostep, 0.0, 0.0, mu, r.q, nullptr, &top, &sl);
     double ap = (fresh && live) ? sl.ap : 1.0, ad = (fresh && live) ? sl.ad : 1.0, gp = (fresh && live) ? sl.gphi : 0.0;
-#ifdef RMPC_STAMPS
-    ss_t1 = __builtin_amdgcn_s_memtime();
-#endif
+    st(4);
     {
       double rs1[1] = {gp}, rm0[1] = {0.0}, rn2[2] = {ap, ad};
       wave_reduce_many<kFusedStages>(rs1, rm0, rn2);
       gp = rs1[0]; ap = rn2[0]; ad = rn2[1];
     }
-#ifdef RMPC_STAMPS
-    ss_t2 = __builtin_amdgcn_s_memtime();
-#endif
+    st(5);
     r.amin_p = fresh ? fmin(amin_p_in, ap) : amin_p_in;
     r.amin_d = fresh ? fmin(amin_d_in, ad) : amin_d_in;
     r.gphi = fresh ? gp : gphi_in;
     const double alpha = nostep ? 0.0 : ldexp(r.amin_p, -ls), adual = nostep ? 0.0 : r.amin_d;
     if (live) sweep_body<C, -1, ldouble, V, 0, 2>(sk, v, io, k, false, nostep, alpha, adual, mu, r.q, nullptr, &top);
   }
-#ifdef RMPC_STAMPS
-  r.q.tk[4] = ss_t1 - ss_t0; r.q.tk[5] = ss_t2 - ss_t1;
-#endif
   {
     // (idle lanes and idle halves contribute the neutral elements: their sums are discarded by the caller)
     const Partials &q = r.q;
@@ -2311,9 +2415,8 @@ __device__ __noinline__ RMPC_ONE_WAVE void fused_sweep_step_call(__attribute__((
     out->f = rs5[0]; out->th = rs5[1]; out->lgs = rs5[2]; out->sumc = rs5[3]; out->badf = rs5[4];
     out->rstat = rm4[0]; out->req = rm4[1]; out->rineq = rm4[2]; out->rcomp = rm4[3]; out->minc = rn1[0];
     out->amin_p = r.amin_p; out->amin_d = r.amin_d; out->gphi = r.gphi;
-#ifdef RMPC_STAMPS
-    if (k == 0) { for (int i = 0; i < 6; i++) out->tk[i] = q.tk[i]; }
-#endif
+    st.get(q, 0, 4);
+    if (k == 0) st.put(*out, 0, 6);
   }
 }
 
@@ -2403,25 +2506,11 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
     valid = hw.valid != 0; retired = hw.retired != 0; first = hw.first != 0;
   };
 
-#ifdef RMPC_STAMPS
-  long long st_sweep = 0, st_dec = 0, st_ric = 0, st_step = 0, st_t0 = __builtin_amdgcn_s_memtime(), st_a, st_b;
-  long long st_sw[6] = {0, 0, 0, 0, 0, 0}, st_sw2[2] = {0, 0};
-  long long st_hand = 0;   // cycles between the top of the pass loop and the test that ends it: epilogue, dequeue, prologue
-  int st_nhand = 0;        // hand-over events of this wavefront (epilogues + prologues, both halves)
-  int st_ipass = 0;   // instance passes of this wavefront (both halves)
-  int st_both = 0;    // wavefront passes in which both copies of the sweep call ran (the halves differed in `first`)
-#define STAMP_A() st_a = __builtin_amdgcn_s_memtime()
-#define STAMP_B(acc) do { st_b = __builtin_amdgcn_s_memtime(); acc += st_b - st_a; st_a = st_b; } while (0)
-#else
-#define STAMP_A()
-#define STAMP_B(acc)
-#endif
-  int pass = 0;   // passes of the wavefront
-  for (;; pass++) {
+  PassStamps ps;
+  ps.start();
+  for (;;) {
     // ---- finished instances leave, idle halves take the next instance of the queue -----------------------------------
-#ifdef RMPC_STAMPS
-    const long long st_top = __builtin_amdgcn_s_memtime();
-#endif
+    ps.hand_begin();
     {
       const bool over = valid && (s.status == ST_ACTIVE) && ipass >= max_passes;   // deadline (rmpc_set_pass_budget) or cap
       const bool done = valid && (s.status != ST_ACTIVE || over);
@@ -2573,34 +2662,20 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
           }
         }
         GSYNC();   // the new instance's block is complete before any lane reads another lane's part
-#ifdef RMPC_STAMPS
-        st_nhand += __popcll(__ballot(done && k == 0)) + __popcll(__ballot(took && k == 0));   // epilogues + prologues
-#else
-        (void)took;
-#endif
+        ps.hand_events(done && k == 0, took && k == 0);
       }
     }
     const bool act = valid && (s.status == ST_ACTIVE);
-#ifdef RMPC_STAMPS
-    st_hand += __builtin_amdgcn_s_memtime() - st_top;   // top of the pass loop .. here: the hand-over
-#endif
+    ps.hand_end();
     if (__ballot(act) == 0ull) break;   // both halves are idle and the queue is empty
     if (act) ipass++;
-#ifdef RMPC_STAMPS
-    st_ipass += __popcll(__ballot(act && k == 0));
-#endif
     // which copy of the sweep the lane runs this pass (first pass of its instance or not): the two halves of the
     // wavefront may differ (both copies then run, one after the other); an idle half follows its partner
     const bool v1 = act ? first : (__ballot(act && first) != 0ull);
-#ifdef RMPC_STAMPS
-    st_both += (__ballot(v1) != 0ull && __ballot(!v1) != 0ull) ? 1 : 0;
-#endif
-    STAMP_A();
+    ps.pass_begin(act && k == 0, v1);
+    ps.mark();
     // ---- sweep: trial point, model functions, condensing, stage partials -------------------------------
     Partials q = {0, 0, 0, 0, 0, 0, 0, 0, 1e300, 0};
-#ifdef RMPC_STAMPS
-    q.tk[0] = q.tk[1] = q.tk[2] = q.tk[3] = q.tk[4] = q.tk[5] = 0;
-#endif
     // Generated views with LDS records: the step lengths of a fresh step are formed inside the sweep call (MERGE2).
     // (The same reordering for the runtime tables, inline, is bit-identical too and no faster: boxer 0.48 vs 0.50 M.)
     constexpr bool MERGE2 = V::SPEC && REC_LDS;
@@ -2633,9 +2708,7 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
         else q = fused_sweep_call<C, VC, 0, REC_LDS>(Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, nostep, alpha, adual, s.mu, warm ? 1 : 0);
       }
     }
-#ifdef RMPC_STAMPS
-    const long long st_ret = __builtin_amdgcn_s_memtime();   // (the sweep call has returned)
-#endif
+    ps.sweep_returned();
     unpark();
     Reduced r;
     if constexpr (MERGE2) {
@@ -2644,32 +2717,25 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
       if (fresh) { s.amin_p = o.amin_p; s.amin_d = o.amin_d; gphi_sum = o.gphi; }
       r.f = o.f; r.th = o.th; r.lgs = o.lgs; r.sumc = o.sumc; r.badf = o.badf;
       r.rstat = o.rstat; r.req = o.req; r.rineq = o.rineq; r.rcomp = o.rcomp; r.minc = o.minc;
-#ifdef RMPC_STAMPS
-      for (int i = 0; i < 6; i++) q.tk[i] = o.tk[i];
-#endif
+      ps.sections(sres[half]);
     } else {
+      ps.sections(q);
       double rs5[5] = {q.f, q.th, q.logs, q.sumc, q.bad}, rm4[4] = {q.rstat, q.req, q.rineq, q.rcomp}, rn1[1] = {q.minc};
       wave_reduce_many<LPI>(rs5, rm4, rn1);
       r.f = rs5[0]; r.th = rs5[1]; r.lgs = rs5[2]; r.sumc = rs5[3]; r.badf = rs5[4];
       r.rstat = rm4[0]; r.req = rm4[1]; r.rineq = rm4[2]; r.rcomp = rm4[3]; r.minc = rn1[0];
     }
     r.gphi = first ? 0.0 : gphi_sum;
-#ifdef RMPC_STAMPS
-    const long long st_red = __builtin_amdgcn_s_memtime();
-#endif
+    ps.sweep_reduced();
     GSYNC();   // trial point and records are complete before any lane reads another lane's part
-    STAMP_B(st_sweep);
-#ifdef RMPC_STAMPS
-    for (int i = 0; i < 6; i++) st_sw[i] += __builtin_amdgcn_readfirstlane((int)q.tk[i]);
-    st_sw2[0] += st_red - st_ret; st_sw2[1] += st_b - st_red;   // unpark + reductions; the ordering point's wait
-#endif
+    ps.sweep_end();
     // ---- decisions, then a new step when the trial was accepted --------------------------------------
     bool usec = false;
     bool recurse = false;
     // (the tolerances and caps of the decision: scalar loads from the model's copy behind the row tables)
     if (act) recurse = inst_decide<C>(*(const DevModel *)&blk()->M, s, r, first, usec);
     if (act) first = false;
-    STAMP_B(st_dec);
+    ps(PH_DEC);
     park();
     const double mu_r = s.mu;
     const double cw_r = usec ? (C::CSCALE ? s.theta_c : 1.0) : 0.0;   // weight of the curvature terms in this recursion
@@ -2694,7 +2760,7 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
     unpark();
     if (recurse) inst_after_recursion(s, rec_ok, usec, C::BACKOFF, C::CSCALE);
     GSYNC();   // dz, nunew
-    STAMP_B(st_ric);
+    ps(PH_RIC);
     // ---- step lengths of the new step -----------------------------------------------------------------
     // (MERGE2: formed inside the next sweep call -- nothing to park, call or reduce here)
     if constexpr (!MERGE2) {
@@ -2718,23 +2784,9 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
         gphi_sum = gp;
       }
     }
-    STAMP_B(st_step);
+    ps(PH_STEP);
   }
-#ifdef RMPC_STAMPS
-  if (threadIdx.x == 0) {
-    long long *const stamps = blk()->F.stamps;
-    long long *o = stamps + (size_t)blockIdx.x * 8;
-    {
-      long long *o2 = stamps + (size_t)(gridDim.x + blockIdx.x) * 8;   // second half of the array: sweep sections
-      for (int i = 0; i < 6; i++) o2[i] = st_sw[i];
-      o2[6] = st_sw2[0]; o2[7] = st_sw2[1];
-    }
-    o[0] = st_sweep; o[1] = st_dec; o[2] = st_ric; o[3] = st_step; o[4] = __builtin_amdgcn_s_memtime() - st_t0;
-    o[5] = (long long)pass | ((long long)st_both << 32);   // (low word: passes of the wavefront; high word: those with both sweep copies)
-    o[6] = st_hand;   // hand-over: top of the pass loop to the test that ends it
-    o[7] = (long long)st_ipass | ((long long)st_nhand << 32);   // (low word: instance passes; high word: hand-over events)
-  }
-#endif
+  ps.store(((cArmBlock *)(Tp + 1))->F.stamps, true);
 }
 
 #include "rmpc_arm_fused.hpp"   // the arms in one launch (k_fused_arm: a wavefront per instance, a stage per P lanes)

@@ -165,18 +165,19 @@ bool spec_matches(const rmpc_desc &d, const DevModel &M, const DevTables &T) {
   return ok;
 }
 
+#if defined(RMPC_STAMPS) || defined(RMPC_RIC_STAMPS)
+// reads and clears a stamp array of this unit: STAMPS_SWEEP g_sst, STAMPS_RIC g_rst (1: failed, or the build has none)
+int read_stamps(const int which, long long *out) {
+  const void *sym = nullptr;
 #ifdef RMPC_STAMPS
-int sweep_stamps(long long *out) {
-  long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sst), sizeof(z)) != hipSuccess) return 1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_sst), z, sizeof(z)) != hipSuccess;
-}
+  if (which == STAMPS_SWEEP) sym = &g_sst;
 #endif
 #ifdef RMPC_RIC_STAMPS
-int ric_stamps(long long *out) {
-  long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rst), sizeof(z)) != hipSuccess) return 1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_rst), z, sizeof(z)) != hipSuccess;
+  if (which == STAMPS_RIC) sym = &g_rst;
+#endif
+  const long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (!sym || hipMemcpyFromSymbol(out, sym, sizeof(z)) != hipSuccess) return 1;
+  return hipMemcpyToSymbol(sym, z, sizeof(z)) != hipSuccess;
 }
 #endif
 
@@ -200,11 +201,8 @@ VariantOps ops(const char *spec, bool (*matches)(const rmpc_desc &, const DevMod
   }
   v.advance = launch_advance<C>;
   v.retarget = launch_retarget<C>;
-#ifdef RMPC_STAMPS
-  v.sweep_stamps = sweep_stamps;
-#endif
-#ifdef RMPC_RIC_STAMPS
-  v.ric_stamps = ric_stamps;
+#if defined(RMPC_STAMPS) || defined(RMPC_RIC_STAMPS)
+  v.read_stamps = read_stamps;
 #endif
   return v;
 }

@@ -1,5 +1,6 @@
-"""Instance hand-over of the fused kernel (k_fused): a half-wavefront that has finished an instance stores its plan
-(epilogue), takes the next position of the launch's queue and copies that instance's rows into its block (prologue).
+"""Instance hand-over of the fused kernels: a half-wavefront of k_fused (a wavefront of k_fused_arm, the cfg4 and chain5
+cases) that has finished an instance stores its plan (epilogue), takes the next position of the launch's queue and
+copies that instance's rows into its block (prologue).
 The arithmetic of an instance must depend neither on its position in the queue, nor on its partner half, nor on how
 many hand-overs its half-wavefront has behind it: a launch on a tiny grid (``RMPC_FUSED_GRID``, read at rmpc_create:
 every half-wavefront takes many instances, first and later sweeps mix inside a wavefront) returns bit for bit what the
@@ -72,6 +73,10 @@ CASES = [
     ("cfg2", 24, 14, {"time_horizon": 7}, 2),      # lanes >= N idle in the hand-over, odd b N + k
     ("chain2", 40, 15, {}, 2),                     # npar = 33 (odd), m = 23
     ("wc_boxer_slack", 24, 16, {}, 2),             # npar = 37 (odd), m = 37 (two sets of rows), slack variable
+    # k_fused_arm: a wavefront per instance, its own epilogue and prologue (copies by stage and half of the wavefront)
+    ("cfg4", 12, 17, {}, 2),                       # the panda, N = 20: three parts per stage
+    ("cfg4", 10, 19, {"time_horizon": 22}, 2),     # two parts per stage
+    ("chain5", 10, 20, {}, 2),                     # five joints
 ]
 
 
@@ -97,7 +102,7 @@ def test_halves_without_work(rt, B, monkeypatch):
     rt["check_plan"](one, cpu, sc.desc["nx"] + sc.desc["ns"])
 
 
-@pytest.mark.parametrize("name,B,seed", [("cfg2", 72, 31), ("cfg3", 40, 32)])
+@pytest.mark.parametrize("name,B,seed", [("cfg2", 72, 31), ("cfg3", 40, 32), ("cfg4", 12, 33)])
 def test_warm_path_through_the_epilogue(rt, name, B, seed, monkeypatch):
     """Warm-start mode: the epilogue leaves the multipliers, mu and the pass counts; the second solve starts from them,
     its queue ordered longest first."""
