@@ -53,7 +53,8 @@ extern "C" {
  *              rmpc_grid_cells_device, rmpc_follow_path_device; the lidar, rmpc_lidar, rmpc_lidar_scan_device,
  *              rmpc_plan_points_device (rmpc_free_space_device now runs on the device of d_points); fleet
  *              separation, rmpc_fleet_points_device, rmpc_fleet_planes_device; the test hook rmpc_debug_step_curv
- *              (rmpc_debug_step is that call at the weight 0 without out_C, results unchanged). */
+ *              (rmpc_debug_step is that call at the weight 0 without out_C, results unchanged); the map from the
+ *              scans, rmpc_grid_mark, rmpc_grid_mark_device, rmpc_grid_occupancy_device. */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -419,6 +420,57 @@ int rmpc_lidar_scan_device(int B, const rmpc_lidar *l, void *stream);
 int rmpc_plan_points_device(int B, int N, const double *d_z_prev, int nvar, const int32_t *d_exitflag,
                             const double *d_pose, int pose_stride, double offset_x, double offset_y, double height,
                             double *d_points, void *stream);
+
+/* The map from the fleet's scans: evidence in two int32 grids d_hits [H][W] and d_misses [H][W] in the
+ * plain frame of the global planner (cell (row, col) centred at (x0 + col cell, y0 + row cell)), and the occupancy
+ * grid classified from them.  Needs no handle; every pointer is a device pointer, each call runs on the device of its
+ * first pointer (origins, d_hits).  The counts are integers: the map does not depend on the order of the updates and is
+ * bitwise the same on every run.
+ * rmpc_grid_mark_device ADDS one scan of B robots to hits and misses.  origins [B][3]: the sensor origins, the output
+ * of rmpc_plan_points_device with N = 1 and d_z_prev = NULL; points [B][rays][3] and ranges [B][rays]: the outputs of
+ * rmpc_lidar_scan_device.  Ray (b, i) with o = origins [b][0 .. 1], e = points [b][i][0 .. 1], t = ranges [b][i], every
+ * floating-point operation in the order written:
+ *  1. the ray is skipped (and *skipped, when given, grows by 1) unless o, e and t are finite and 0 < t <= range;
+ *  2. hit = t < range; if hit: s = hit_depth / t, ex <- ex + s (ex - ox), ey likewise (the scan's end point lies on the
+ *     obstacle's face, in a world made by boxes_from_grid a cell edge: the end cell is taken hit_depth behind it);
+ *  3. ua = (ox - x0) / cell + 0.5, va = (oy - y0) / cell + 0.5, ub, vb likewise from e; c = floor(ua), r = floor(va),
+ *     c1 = floor(ub), r1 = floor(vb), n = |c1 - c| + |r1 - r|; the ray is skipped, counted as above, unless
+ *     n <= 2 ceil((range + hit_depth) / cell) + 4 (a garbage point cannot run an unbounded loop; a cell coordinate that
+ *     is not finite fails the test too);
+ *  4. du = ub - ua, dv = vb - va, sc = du > 0 ? 1 : -1, tx = du != 0 ? ((c + (du > 0 ? 1 : 0)) - ua) / du : +inf; sr and
+ *     ty likewise from dv, r, va;
+ *  5. n + 1 cells are visited from (r, c): a visited cell inside [0, H) x [0, W) gets misses += 1, but the last cell of
+ *     a ray with hit gets hits += 1; cells outside the map are passed over.  Between two visits the column steps
+ *     (c += sc, tx recomputed from the new c) when (tx <= ty and c != c1) or r == r1, otherwise the row does.
+ * This is the cell walk of Amanatides and Woo along o -> e; it ends on (r1, c1) and a ray visits a cell at most once.
+ * The cell of a point is floor((p - origin) / cell + 0.5) here, rint((p - origin) / cell) (half to even) in
+ * rmpc_grid_cells_device: the two differ only for a point exactly on a cell edge.
+ * The counters wrap unguarded: the calls between two resets times B rays must stay below 2^31 (rmpc_grid_occupancy_device
+ * with forget > 0 ages them).
+ * struct_size must equal sizeof(rmpc_grid_mark); refused (-1, rmpc_last_error): NULL pointers other than skipped, B < 1,
+ * rays < 1, H or W < 1, H W > RMPC_GRID_MAX_CELLS, a cell or range that is not positive and finite, a hit_depth that is
+ * negative or not finite, x0 or y0 not finite, B rays 3 beyond INT_MAX, and (range + hit_depth) / cell beyond 2^29. */
+typedef struct rmpc_grid_mark {
+  int32_t struct_size;                 /* sizeof(rmpc_grid_mark) */
+  int32_t rays;                        /* R >= 1 */
+  const double *origins;               /* [B][3] */
+  const double *points;                /* [B][R][3] */
+  const double *ranges;                /* [B][R] */
+  double range, hit_depth;             /* the scan's range (> 0); hit_depth >= 0 */
+  int32_t H, W;
+  double x0, y0, cell;
+  int32_t *hits, *misses;              /* [H][W] in/out */
+  int32_t *skipped;                    /* one counter in/out, may be NULL */
+} rmpc_grid_mark;
+int rmpc_grid_mark_device(int B, const rmpc_grid_mark *m, void *stream);
+/* d_grid [H][W] from the evidence, one cell each: unknown_value when hits + misses == 0, occ_value when
+ * (int64) hits w_hit > (int64) misses w_miss, free_value otherwise (equal weights of evidence: free).  Then, when
+ * forget > 0, both counters are shifted right by forget bits: ageing, which bounds the counters of a long loop and
+ * lets an obstacle that moved fade.  The three values are the caller's (68/256 free and 253/256 occupied are what
+ * rmpc_grid_inflate_device gets in the reference's PNG round trip).  Refused: NULL pointers, H or W < 1,
+ * H W > RMPC_GRID_MAX_CELLS, w_hit or w_miss < 1, forget outside [0, 31], a value that is not finite. */
+int rmpc_grid_occupancy_device(int H, int W, int32_t *d_hits, int32_t *d_misses, int w_hit, int w_miss, int forget,
+                               double free_value, double occ_value, double unknown_value, double *d_grid, void *stream);
 
 /* Fleet separation: a separating plane per neighbour pair and stage, in the style of buffered Voronoi
  * cells, written into the lin_constrs slots of an rmpc_scene: the LinearConstraints row |a.p + d| / |a| - r_body >= 0

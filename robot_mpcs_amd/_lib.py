@@ -96,6 +96,18 @@ class LidarArgs(C.Structure):
     ]
 
 
+class GridMarkArgs(C.Structure):
+    """Mirror of ``rmpc_grid_mark`` (include/rmpc.h): one scan of B robots added to the evidence grids, device pointers."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("rays", C.c_int32),
+        ("origins", C.c_void_p), ("points", C.c_void_p), ("ranges", C.c_void_p),
+        ("range", C.c_double), ("hit_depth", C.c_double),
+        ("H", C.c_int32), ("W", C.c_int32),
+        ("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double),
+        ("hits", C.c_void_p), ("misses", C.c_void_p), ("skipped", C.c_void_p),
+    ]
+
+
 # every symbol include/rmpc.h declares
 EXPORTED_SYMBOLS = [
     "rmpc_version", "rmpc_source_hash", "rmpc_last_error", "rmpc_desc_size", "rmpc_create", "rmpc_destroy", "rmpc_solve_batch",
@@ -104,7 +116,7 @@ EXPORTED_SYMBOLS = [
     "rmpc_debug_fused_stamps", "rmpc_pack_scene_device", "rmpc_solve_batch_scene_device", "rmpc_pack_scene_workspace", "rmpc_solve_batch_packed_device", "rmpc_advance_device", "rmpc_advance_device_flags", "rmpc_retarget_device", "rmpc_advance_obstacles_device", "rmpc_free_space_device",
     "rmpc_grid_inflate_device", "rmpc_grid_fields_device", "rmpc_grid_paths_device", "rmpc_grid_cells_device",
     "rmpc_follow_path_device", "rmpc_lidar_scan_device", "rmpc_plan_points_device", "rmpc_fleet_points_device",
-    "rmpc_fleet_planes_device",
+    "rmpc_fleet_planes_device", "rmpc_grid_mark_device", "rmpc_grid_occupancy_device",
 ]
 
 _lib = None
@@ -260,6 +272,10 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_fleet_points_device.argtypes = [i, i, vp, i, vp, vp, i, i, d, d, d, vp, vp]
     L.rmpc_fleet_planes_device.restype = C.c_int
     L.rmpc_fleet_planes_device.argtypes = [i, i, vp, vp, i, d, i, i, vp, vp]
+    L.rmpc_grid_mark_device.restype = C.c_int
+    L.rmpc_grid_mark_device.argtypes = [i, C.POINTER(GridMarkArgs), vp]
+    L.rmpc_grid_occupancy_device.restype = C.c_int
+    L.rmpc_grid_occupancy_device.argtypes = [i, i, vp, vp, i, i, i, d, d, d, vp, vp]
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
         raise RmpcError("rmpc_desc layout mismatch between _lib.py and librmpc_hip.so")
     want = _source_hash()
@@ -478,6 +494,41 @@ def fleet_planes_device(points, radius, planes, K: int, max_range: float = float
     B, N, nobst = int(points.shape[0]), int(points.shape[1]), int(planes.shape[2])
     _grid_call("rmpc_fleet_planes_device", B, N, _ptr(points), _ptr(radius), int(K), float(max_range), nobst, int(slot0),
                _ptr(planes), _stream_arg(stream))
+
+
+def grid_mark_args(origins, points, ranges, hits, misses, x0: float, y0: float, cell: float, max_range: float = 10.0,
+                   hit_depth: float = 1e-6, skipped=None) -> GridMarkArgs:
+    """The ``rmpc_grid_mark`` of one scan: origins (B, 1, 3) or (B, 3), points (B, R, 3), ranges (B, R) fp64; hits,
+    misses (H, W) int32; skipped a one-element int32 tensor or None -- contiguous device tensors."""
+    a = GridMarkArgs()
+    a.struct_size = C.sizeof(GridMarkArgs)
+    a.rays = int(points.shape[1])
+    a.origins, a.points, a.ranges = origins.data_ptr(), points.data_ptr(), ranges.data_ptr()
+    a.range, a.hit_depth = float(max_range), float(hit_depth)
+    a.H, a.W = int(hits.shape[0]), int(hits.shape[1])
+    a.x0, a.y0, a.cell = float(x0), float(y0), float(cell)
+    a.hits, a.misses = hits.data_ptr(), misses.data_ptr()
+    a.skipped = None if skipped is None else skipped.data_ptr()
+    return a
+
+
+def grid_mark_device(origins, points, ranges, hits, misses, x0: float, y0: float, cell: float, max_range: float = 10.0,
+                     hit_depth: float = 1e-6, skipped=None, stream=None):
+    """Adds one lidar scan of B robots to the evidence grids (``rmpc_grid_mark_device``): every ray origins [b] ->
+    points [b][i] is walked cell by cell, misses += 1 on the cells it crosses, hits += 1 on the cell ``hit_depth``
+    behind the end point of a ray that hit (ranges < max_range); skipped counts the rays left out."""
+    a = grid_mark_args(origins, points, ranges, hits, misses, x0, y0, cell, max_range, hit_depth, skipped)
+    _grid_call("rmpc_grid_mark_device", int(points.shape[0]), C.byref(a), _stream_arg(stream))
+
+
+def grid_occupancy_device(hits, misses, grid, free_value: float, occ_value: float, unknown_value: float, w_hit: int = 3,
+                          w_miss: int = 1, forget: int = 0, stream=None):
+    """hits, misses (H, W) int32, grid (H, W) fp64: the class of every cell (``rmpc_grid_occupancy_device``) --
+    unknown without evidence, occupied when hits w_hit > misses w_miss, free otherwise; forget > 0 then shifts both
+    counters right by that many bits."""
+    H, W = int(hits.shape[0]), int(hits.shape[1])
+    _grid_call("rmpc_grid_occupancy_device", H, W, _ptr(hits), _ptr(misses), int(w_hit), int(w_miss), int(forget),
+               float(free_value), float(occ_value), float(unknown_value), _ptr(grid), _stream_arg(stream))
 
 
 class Solver:

@@ -1,8 +1,8 @@
 // rmpc_world.hip -- the world around the solver, on the device: the moving obstacles between two control steps, the
 // free-space decomposition, the global planner (rmpc_grid.hpp), the lidar and the fleet's separating planes
-// (rmpc_sense.hpp), with their entries of the C ABI.  None of them takes a handle: each call runs on the device its
-// first pointer lives on, on the stream it is given.  A translation unit of its own, which needs rmpc.h, the HIP
-// runtime and the error channel only -- nothing of the solver.
+// (rmpc_sense.hpp), the map built from the scans (rmpc_map.hpp), with their entries of the C ABI.  None of them takes a
+// handle: each call runs on the device its first pointer lives on, on the stream it is given.  A translation unit of
+// its own, which needs rmpc.h, the HIP runtime and the error channel only -- nothing of the solver.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -88,6 +88,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 
 #include "rmpc_grid.hpp"
 #include "rmpc_sense.hpp"
+#include "rmpc_map.hpp"
 
 using namespace rmpc;
 
@@ -265,6 +266,46 @@ int rmpc_fleet_planes_device(int B, int N, const double *d_points, const double 
   const int nbt = (B + 255) / 256;
   hipLaunchKernelGGL(k_fleet_planes, dim3(nbt * N), dim3(256), 0, (hipStream_t)stream, d_points, d_radius, B, N, K,
                      range * range, nobst, slot0, d_planes);
+  return launch_status();
+}
+
+/* the map from the scans (rmpc_map.hpp): no handle; each call runs on the device its first pointer lives on */
+int rmpc_grid_mark_device(int B, const rmpc_grid_mark *m, void *stream) {
+  if (!m) return fail("null argument");
+  if (m->struct_size != (int)sizeof(rmpc_grid_mark)) return fail("rmpc_grid_mark.struct_size mismatch");
+  if (B < 1 || m->rays < 1) return fail("grid mark: need B >= 1 and rays >= 1");
+  if (!grid_fits(B, m->rays) || !grid_fits((long long)B * m->rays, 3)) return fail("grid mark: B*rays*3 must not exceed INT_MAX");
+  if (m->H < 1 || m->W < 1 || !grid_fits(m->H, m->W) || m->H * m->W > RMPC_GRID_MAX_CELLS)
+    return fail("grid mark: need H, W >= 1 and H*W <= RMPC_GRID_MAX_CELLS = " + std::to_string(RMPC_GRID_MAX_CELLS));
+  if (!(m->cell > 0.0) || std::isinf(m->cell) || !(m->range > 0.0) || std::isinf(m->range))
+    return fail("grid mark: cell and range must be positive and finite");
+  if (!(m->hit_depth >= 0.0) || std::isinf(m->hit_depth)) return fail("grid mark: hit_depth must be finite and >= 0");
+  if (!std::isfinite(m->x0) || !std::isfinite(m->y0)) return fail("grid mark: x0, y0 must be finite");
+  if (!m->origins || !m->points || !m->ranges || !m->hits || !m->misses) return fail("null argument");
+  const double reach = ceil((m->range + m->hit_depth) / m->cell);
+  if (!(2.0 * reach + 4.0 <= 1073741824.0)) return fail("grid mark: (range + hit_depth) / cell must not exceed 2^29 cells");
+  if (use_device_of(m->origins)) return -1;
+  MapGeom g;
+  g.H = m->H; g.W = m->W; g.x0 = m->x0; g.y0 = m->y0; g.cell = m->cell; g.range = m->range; g.hit_depth = m->hit_depth;
+  g.nmax = 2.0 * reach + 4.0;
+  const int R = m->rays;
+  hipLaunchKernelGGL(k_grid_mark, dim3((B * R + 255) / 256), dim3(256), 0, (hipStream_t)stream, m->origins, m->points,
+                     m->ranges, B, R, g, (int *)m->hits, (int *)m->misses, (int *)m->skipped);
+  return launch_status();
+}
+
+int rmpc_grid_occupancy_device(int H, int W, int32_t *d_hits, int32_t *d_misses, int w_hit, int w_miss, int forget,
+                               double free_value, double occ_value, double unknown_value, double *d_grid, void *stream) {
+  if (!d_hits || !d_misses || !d_grid) return fail("null argument");
+  if (H < 1 || W < 1 || !grid_fits(H, W) || H * W > RMPC_GRID_MAX_CELLS)
+    return fail("grid occupancy: need H, W >= 1 and H*W <= RMPC_GRID_MAX_CELLS = " + std::to_string(RMPC_GRID_MAX_CELLS));
+  if (w_hit < 1 || w_miss < 1) return fail("grid occupancy: need w_hit, w_miss >= 1");
+  if (forget < 0 || forget > 31) return fail("grid occupancy: forget must lie in [0, 31]");
+  if (!std::isfinite(free_value) || !std::isfinite(occ_value) || !std::isfinite(unknown_value))
+    return fail("grid occupancy: the three values must be finite");
+  if (use_device_of(d_hits)) return -1;
+  hipLaunchKernelGGL(k_grid_occupancy, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, H * W, (int *)d_hits,
+                     (int *)d_misses, w_hit, w_miss, forget, free_value, occ_value, unknown_value, d_grid);
   return launch_status();
 }
 

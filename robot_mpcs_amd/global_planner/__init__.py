@@ -2,14 +2,14 @@
 
 Mirrors ``robotmpcs.global_planner`` (``gridmap.OccupancyGridMap``, ``a_star.a_star``, ``globalPlanner.GlobalPlanner``:
 same module, class and method names, so that a port of ``examples/boxer_example_global.py`` changes only its imports)
-and adds the batched, device-resident fleet API (``plan_batch``, ``RouteFollower``, ``shelf_map``).  The work is done
+and adds the batched, device-resident fleet API (``plan_batch``, ``RouteFollower``, ``replan``, ``shelf_map``).  The work is done
 by the ``rmpc_grid_*_device`` / ``rmpc_follow_path_device`` kernels (include/rmpc.h); there is no CPU path.  Importing
 the package needs no GPU.
 """
 from .gridmap import OccupancyGridMap
 from .a_star import a_star
 from .globalPlanner import GlobalPlanner, png_values
-from .batch import RouteFollower, cell_xy, cells_from_positions, pick_routes, plan_batch, shelf_map, store_routes
+from .batch import RouteFollower, cell_xy, cells_from_positions, pick_routes, plan_batch, replan, shelf_map, store_routes
 
 __all__ = ["OccupancyGridMap", "a_star", "GlobalPlanner", "RouteFollower", "cell_xy", "cells_from_positions",
-           "pick_routes", "plan_batch", "png_values", "shelf_map", "store_routes"]
+           "pick_routes", "plan_batch", "png_values", "replan", "shelf_map", "store_routes"]

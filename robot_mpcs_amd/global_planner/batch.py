@@ -1,8 +1,9 @@
 """The fleet side of the global planner, in the plain frame (cell (row, col) centred at (x0 + col cell, y0 + row cell)):
 ``plan_batch`` computes one cost-to-go field per distinct goal and one path per query on the device, ``RouteFollower``
 keeps the routes on the device and hands every robot its next waypoint once per control step (``get_local_goal`` of
-the reference for B robots in one launch), ``shelf_map`` draws a seeded procedural store for tests, the examples and
-the benchmark, ``store_routes`` enlarges such a map and draws the fleet's (start, goal) cells on it (``pick_routes``)."""
+the reference for B robots in one launch) and takes new routes when the map changes (``RouteFollower.replace``,
+``replan``), ``shelf_map`` draws a seeded procedural store for tests, the examples and the benchmark, ``store_routes``
+enlarges such a map and draws the fleet's (start, goal) cells on it (``pick_routes``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -76,6 +77,18 @@ class RouteFollower:
                                 self.threshold,
                                 stream=stream if stream is not None else torch.cuda.current_stream(goal.device).cuda_stream)
 
+    def replace(self, paths, lens):
+        """New routes (paths (B, max_len) int32, lens (B,) int32, e.g. of ``plan_batch``): the robots with lens > 0 take
+        theirs and start at its first cell, the others keep the route and the waypoint they have.  Tensor operations
+        only, no host read."""
+        import torch
+        new = lens > 0
+        L = max(int(paths.shape[1]), int(self.paths.shape[1]))
+        pad = lambda p: p if p.shape[1] == L else torch.nn.functional.pad(p, (0, L - p.shape[1]))
+        self.paths = torch.where(new[:, None], pad(paths), pad(self.paths)).contiguous()
+        self.lens = torch.where(new, lens, self.lens)
+        self.idx = torch.where(new, torch.zeros_like(self.idx), self.idx)
+
     def final_goals(self):
         """(B, 2) world centres of the last cell of each route (NaN where a robot has none), on the device."""
         import torch
@@ -83,6 +96,18 @@ class RouteFollower:
         last = self.paths.gather(1, L[:, None])[:, 0].long()
         xy = torch.stack([self.x0 + (last % self.W).double() * self.cell, self.y0 + (last // self.W).double() * self.cell], 1)
         return torch.where((self.lens > 0)[:, None], xy, torch.full_like(xy, float("nan")))
+
+
+def replan(follower, grid, xinit, goal_cells, **plan_batch_kwargs):
+    """Re-routes a fleet on a new map: the robots' current cells (``cells_from_positions`` of xinit (B, stride >= 2)) ->
+    ``plan_batch`` on ``grid`` (H, W) to ``goal_cells`` (B,) -> ``follower.replace``.  A robot without a route on the
+    new map (its cell or its goal occupied, the goal unreachable, the robot outside the map) keeps the one it has.
+    Returns (paths, lens) of the new plan."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    cells = cells_from_positions(xinit, H, W, follower.x0, follower.y0, follower.cell, stream=plan_batch_kwargs.get("stream"))
+    paths, lens = plan_batch(grid, cells, goal_cells, **plan_batch_kwargs)
+    follower.replace(paths, lens)
+    return paths, lens
 
 
 def shelf_map(H=41, W=41, seed=0, aisle=4, shelf=2, gap=3, gaps_per_shelf=2):
