@@ -54,7 +54,9 @@ extern "C" {
  *              rmpc_plan_points_device (rmpc_free_space_device now runs on the device of d_points); fleet
  *              separation, rmpc_fleet_points_device, rmpc_fleet_planes_device; the test hook rmpc_debug_step_curv
  *              (rmpc_debug_step is that call at the weight 0 without out_C, results unchanged); the map from the
- *              scans, rmpc_grid_mark, rmpc_grid_mark_device, rmpc_grid_occupancy_device. */
+ *              scans, rmpc_grid_mark, rmpc_grid_mark_device, rmpc_grid_occupancy_device; exploration,
+ *              RMPC_GRID_BAD_SEED, rmpc_grid_frontier_device, rmpc_grid_fields_seeded_device,
+ *              rmpc_grid_descend_device. */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -349,6 +351,7 @@ int rmpc_free_space_device(int B, int N, int P, int K, double max_radius, const 
 #define RMPC_GRID_TOO_LONG (-4)         /* the path has more than max_len cells */
 #define RMPC_GRID_BAD_MAP (-5)          /* a free cell (data < occ_threshold) holds a negative value */
 #define RMPC_GRID_NO_FIXED_POINT (-6)   /* no fixed point after H W + 1 sweeps (not reached with prices >= 0) */
+#define RMPC_GRID_BAD_SEED (-7)         /* rmpc_grid_fields_seeded_device: a free cell holds a negative or NaN seed */
 
 /* get_enlarged_obstacles (globalPlanner.py:39-70): box mean over (2k+1)^2 cells, k = ceil(size_robot / cell), on the
  * cells at least k from the border (convolution_size_robot; the others keep their raw value), then 1 where the value is
@@ -371,6 +374,30 @@ int rmpc_grid_paths_device(int H, int W, const double *d_grid, int G, const doub
                            int B, const int32_t *d_start_cell, const int32_t *d_goal_index, int movement,
                            double occ_threshold, double cost_factor, int max_len, int32_t *d_path, int32_t *d_len,
                            void *stream);
+/* Fields to a set of cells: as rmpc_grid_fields_device, but field g takes its sources from
+ * d_seeds [g][H][W] instead of one goal cell: D(u) = min(seed(u), min_v (delta(u,v) + cost_factor data[v] + D(v))), +inf
+ * on occupied and unreachable cells -- the distance to the nearest source, the exact fixed point, bitwise the same on
+ * every run.  A seed is +inf (no source) or finite and >= 0: 0 an ordinary source, a positive one a start potential that
+ * prices the source; a neighbour may undercut it.  A seed on an occupied cell is ignored.  With seed 0 at one free cell
+ * and +inf elsewhere the field is that of rmpc_grid_fields_device for that goal, bit for bit.  d_status [G]:
+ * RMPC_GRID_OK (also for a field without a finite seed: all +inf), _BAD_MAP, _NO_FIXED_POINT, or RMPC_GRID_BAD_SEED when a
+ * free cell holds a negative or NaN seed (field all +inf, sweeps 0); the other fields of the launch are not affected.
+ * Arguments are refused as by rmpc_grid_fields_device. */
+int rmpc_grid_fields_seeded_device(int H, int W, const double *d_grid, int G, const double *d_seeds, int movement,
+                                   double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status,
+                                   int32_t *d_sweeps, void *stream);
+/* One path per query down a seeded field: from d_start_cell [b] down field d_field_index [b] of d_fields [G][H][W]
+ * (built from d_seeds [G][H][W] on d_grid) by the step rule of rmpc_grid_paths_device, until the first cell u with D(u)
+ * finite and D(u) == seed(u): a source that nothing undercuts.  A source whose seed a neighbour undercuts is passed
+ * through.  The start cell is exempt from the occupancy test (a robot stands where it stands): from a start with
+ * D = +inf the first step goes to the best free neighbour.  d_path [B][max_len] int32 cells with start and source;
+ * d_len [B] > 0 the path's cell count (1: the start is a source), 0 no neighbour of such a start has a finite D (or the
+ * start cannot reach a source), or RMPC_GRID_OUTSIDE (the start or the field index), RMPC_GRID_TOO_LONG.  Cells past
+ * d_len [b] are not written.  The loop is bounded by max_len.  Arguments are refused as by rmpc_grid_paths_device. */
+int rmpc_grid_descend_device(int H, int W, const double *d_grid, int G, const double *d_fields, const double *d_seeds,
+                             int B, const int32_t *d_start_cell, const int32_t *d_field_index, int movement,
+                             double occ_threshold, double cost_factor, int max_len, int32_t *d_path, int32_t *d_len,
+                             void *stream);
 /* World positions d_pos [b * stride + 0 .. 1] (e.g. xinit [B][nx], stride nx) to cells d_cells [B] of the plain frame,
  * rint((p - origin) / cell) (round half to even, gridmap.py:get_index_from_coordinates); -1 outside the map. */
 int rmpc_grid_cells_device(int B, const double *d_pos, int stride, int H, int W, double x0, double y0, double cell,
@@ -471,6 +498,20 @@ int rmpc_grid_mark_device(int B, const rmpc_grid_mark *m, void *stream);
  * H W > RMPC_GRID_MAX_CELLS, w_hit or w_miss < 1, forget outside [0, 31], a value that is not finite. */
 int rmpc_grid_occupancy_device(int H, int W, int32_t *d_hits, int32_t *d_misses, int w_hit, int w_miss, int forget,
                                double free_value, double occ_value, double unknown_value, double *d_grid, void *stream);
+/* The frontier of the map, one cell each, from the evidence d_hits, d_misses [H][W] and d_enlarged
+ * [H][W], the output of rmpc_grid_inflate_device on an occupancy grid whose unknown cells got the free value:
+ *   known(c)    = hits[c] + misses[c] != 0                       (the rule of rmpc_grid_occupancy_device)
+ *   d_plan[c]   = known(c) ? d_enlarged[c] : unknown_value       (the unknown region is not dilated; with
+ *                 unknown_value >= occ_threshold routes stay inside what has been seen)
+ *   frontier(c) = known(c) && d_enlarged[c] < occ_threshold && a neighbour of c inside the map is not known
+ *                 (nmoves 4 or 8: the first nmoves moves of the planner's order; the map's edge is not unknown)
+ *   d_seed[c]   = frontier(c) ? 0 : +inf                         (the d_seeds of rmpc_grid_fields_seeded_device)
+ * and *d_count grows by the number of frontier cells (int32 adds, independent of their order; the caller zeroes it).
+ * Runs on the device of d_hits.  Refused: NULL pointers, H or W < 1, H W > RMPC_GRID_MAX_CELLS, nmoves other than 4
+ * or 8, an occ_threshold or unknown_value that is not finite. */
+int rmpc_grid_frontier_device(int H, int W, const int32_t *d_hits, const int32_t *d_misses, const double *d_enlarged,
+                              double occ_threshold, int nmoves, double unknown_value, double *d_plan, double *d_seed,
+                              int32_t *d_count, void *stream);
 
 /* Fleet separation: a separating plane per neighbour pair and stage, in the style of buffered Voronoi
  * cells, written into the lin_constrs slots of an rmpc_scene: the LinearConstraints row |a.p + d| / |a| - r_body >= 0

@@ -117,6 +117,7 @@ EXPORTED_SYMBOLS = [
     "rmpc_grid_inflate_device", "rmpc_grid_fields_device", "rmpc_grid_paths_device", "rmpc_grid_cells_device",
     "rmpc_follow_path_device", "rmpc_lidar_scan_device", "rmpc_plan_points_device", "rmpc_fleet_points_device",
     "rmpc_fleet_planes_device", "rmpc_grid_mark_device", "rmpc_grid_occupancy_device",
+    "rmpc_grid_frontier_device", "rmpc_grid_fields_seeded_device", "rmpc_grid_descend_device",
 ]
 
 _lib = None
@@ -276,6 +277,12 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_grid_mark_device.argtypes = [i, C.POINTER(GridMarkArgs), vp]
     L.rmpc_grid_occupancy_device.restype = C.c_int
     L.rmpc_grid_occupancy_device.argtypes = [i, i, vp, vp, i, i, i, d, d, d, vp, vp]
+    L.rmpc_grid_frontier_device.restype = C.c_int
+    L.rmpc_grid_frontier_device.argtypes = [i, i, vp, vp, vp, d, i, d, vp, vp, vp, vp]
+    L.rmpc_grid_fields_seeded_device.restype = C.c_int
+    L.rmpc_grid_fields_seeded_device.argtypes = [i, i, vp, i, vp, i, d, d, vp, vp, vp, vp]
+    L.rmpc_grid_descend_device.restype = C.c_int
+    L.rmpc_grid_descend_device.argtypes = [i, i, vp, i, vp, vp, i, vp, vp, i, d, d, i, vp, vp, vp]
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
         raise RmpcError("rmpc_desc layout mismatch between _lib.py and librmpc_hip.so")
     want = _source_hash()
@@ -380,7 +387,7 @@ def free_space_decomposition_device(points, seeds, planes_out, max_radius: float
 # status codes of the global planner (include/rmpc.h)
 GRID_MAX_CELLS = 16384
 GRID_OK, GRID_START_OCCUPIED, GRID_GOAL_OCCUPIED, GRID_OUTSIDE, GRID_TOO_LONG = 0, -1, -2, -3, -4
-GRID_BAD_MAP, GRID_NO_FIXED_POINT = -5, -6
+GRID_BAD_MAP, GRID_NO_FIXED_POINT, GRID_BAD_SEED = -5, -6, -7
 
 
 def _grid_call(name, *args):
@@ -419,6 +426,27 @@ def grid_paths_device(grid, fields, goal_cells, start_cell, goal_index, path, le
     H, W = int(grid.shape[0]), int(grid.shape[1])
     _grid_call("rmpc_grid_paths_device", H, W, _ptr(grid), int(fields.shape[0]), _ptr(fields), _ptr(goal_cells),
                int(start_cell.shape[0]), _ptr(start_cell), _ptr(goal_index), int(movement), float(occ_threshold),
+               float(cost_factor), int(path.shape[1]), _ptr(path), _ptr(length), _stream_arg(stream))
+
+
+def grid_fields_seeded_device(grid, seeds, fields, status, movement: int = 8, occ_threshold: float = 0.8,
+                              cost_factor: float = 3.0, sweeps=None, stream=None):
+    """grid (H, W) fp64, seeds (G, H, W) fp64 (+inf no source, >= 0 a source's start potential), fields (G, H, W) fp64,
+    status (G,) int32, sweeps (G,) int32 or None: one field to the nearest source per seed grid
+    (``rmpc_grid_fields_seeded_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    _grid_call("rmpc_grid_fields_seeded_device", H, W, _ptr(grid), int(seeds.shape[0]), _ptr(seeds), int(movement),
+               float(occ_threshold), float(cost_factor), _ptr(fields), _ptr(status),
+               None if sweeps is None else _ptr(sweeps), _stream_arg(stream))
+
+
+def grid_descend_device(grid, fields, seeds, start_cell, field_index, path, length, movement: int = 8,
+                        occ_threshold: float = 0.8, cost_factor: float = 3.0, stream=None):
+    """start_cell, field_index (B,) int32, path (B, max_len) int32, length (B,) int32: descent of the seeded fields
+    (G, H, W) to a source nothing undercuts, from a start cell that may be occupied (``rmpc_grid_descend_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    _grid_call("rmpc_grid_descend_device", H, W, _ptr(grid), int(fields.shape[0]), _ptr(fields), _ptr(seeds),
+               int(start_cell.shape[0]), _ptr(start_cell), _ptr(field_index), int(movement), float(occ_threshold),
                float(cost_factor), int(path.shape[1]), _ptr(path), _ptr(length), _stream_arg(stream))
 
 
@@ -529,6 +557,17 @@ def grid_occupancy_device(hits, misses, grid, free_value: float, occ_value: floa
     H, W = int(hits.shape[0]), int(hits.shape[1])
     _grid_call("rmpc_grid_occupancy_device", H, W, _ptr(hits), _ptr(misses), int(w_hit), int(w_miss), int(forget),
                float(free_value), float(occ_value), float(unknown_value), _ptr(grid), _stream_arg(stream))
+
+
+def grid_frontier_device(hits, misses, enlarged, plan, seed, count, occ_threshold: float = 0.8, nmoves: int = 4,
+                         unknown_value: float = 1.0, stream=None):
+    """hits, misses (H, W) int32, enlarged (H, W) fp64 -> plan, seed (H, W) fp64 and count (1,) int32, which grows by
+    the number of frontier cells (``rmpc_grid_frontier_device``): plan is ``enlarged`` on the cells with evidence and
+    unknown_value elsewhere, seed 0 on the frontier (known, free on ``enlarged``, an unknown neighbour among the first
+    nmoves moves) and +inf elsewhere."""
+    H, W = int(hits.shape[0]), int(hits.shape[1])
+    _grid_call("rmpc_grid_frontier_device", H, W, _ptr(hits), _ptr(misses), _ptr(enlarged), float(occ_threshold),
+               int(nmoves), float(unknown_value), _ptr(plan), _ptr(seed), _ptr(count), _stream_arg(stream))
 
 
 class Solver:

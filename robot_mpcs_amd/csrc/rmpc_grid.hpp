@@ -8,6 +8,11 @@
 // reaches the same fixed point, the one a Dijkstra of this recursion computes ("Global planner").
 // Contraction is off in every function here: fields, paths and the follower are bitwise those of a plain double
 // restatement on the host.
+//
+// The seeded field (k_grid_fields_seeded) takes its sources from seeds [H][W] instead of one goal cell:
+// D(u) = min(seed(u), min_v (delta(u, v) + E(v))), a seed of +inf is no source, a finite one a start potential.  It is
+// the same recursion with a virtual source joined to every seeded cell by an edge of the seed's length, so the same
+// argument gives the same fixed point; k_grid_descend walks such a field down to a source.
 
 #include <climits>
 
@@ -45,20 +50,24 @@ __global__ __launch_bounds__(256) void k_grid_inflate(const double *__restrict__
 // an odd number, <= 17): their D and neighbour masks stay in registers, E of every cell lives in LDS.  Sweeps alternate their direction within a
 // thread's run and update in place; the loop ends after a sweep in which no thread lowered a value: all of E was
 // constant during that sweep, so every thread checked every edge against final values -- the fixed point.
-__global__ __launch_bounds__(kGridThreads) void k_grid_fields(const double *__restrict__ grid, int H, int W,
-                                                              const int *__restrict__ goal_cells, int nmoves,
-                                                              double occ_threshold, double cost_factor,
-                                                              double *__restrict__ fields, int *__restrict__ status,
-                                                              int *__restrict__ sweeps) {
+//
+// kSeeded: the sources are the cells with a finite seeds [g][c] (a start potential >= 0) instead of goal_cells [g].  Every
+// free cell takes part, a seeded one too: a neighbour may undercut its seed.  Only the set-up differs; the sweeps are
+// the same code, so the goal variant's fields are what they were.
+template <bool kSeeded>
+__device__ __forceinline__ void grid_fields(const double *__restrict__ grid, int H, int W, const int *__restrict__ goal_cells,
+                                            const double *__restrict__ seeds, int nmoves, double occ_threshold,
+                                            double cost_factor, double *__restrict__ fields, int *__restrict__ status,
+                                            int *__restrict__ sweeps) {
 #pragma clang fp contract(off)
   __shared__ double E[kGridMaxCells];
   const int HW = H * W, g = blockIdx.x, t = threadIdx.x;
   // runs of an odd length: the 32 lanes of one LDS access are `per` doubles = 2 per banks apart, which for odd per puts
   // every lane on its own bank pair (per = 16 would put them on 2 pairs: a 16-way conflict on every read)
   const int per = ((HW + kGridThreads - 1) / kGridThreads) | 1;
-  const int goal = goal_cells[g];
-  const bool goal_in = goal >= 0 && goal < HW;
-  const bool goal_ok = goal_in && grid[goal] < occ_threshold;
+  const int goal = kSeeded ? -1 : goal_cells[g];
+  const bool goal_in = kSeeded || (goal >= 0 && goal < HW);
+  const bool goal_ok = kSeeded || (goal_in && grid[goal] < occ_threshold);
   double *const F = fields + (size_t)g * HW;
   const double inf = __builtin_inf();
   if (!goal_ok) {
@@ -66,8 +75,10 @@ __global__ __launch_bounds__(kGridThreads) void k_grid_fields(const double *__re
     if (t == 0) { status[g] = goal_in ? RMPC_GRID_GOAL_OCCUPIED : RMPC_GRID_OUTSIDE; if (sweeps) sweeps[g] = 0; }
     return;
   }
+  const double *const S = kSeeded ? seeds + (size_t)g * HW : nullptr;
   double D[kGridPer];
   bool bad = false;           // a free cell with a negative value (a negative price would make the sweeps diverge)
+  bool bad_seed = false;      // a free cell with a negative or NaN seed
   // per cell 10 bits, three cells to a register: bit m = neighbour m inside the map, bit 8 = the cell takes part (owned,
   // free, not the goal)
   unsigned fw[(kGridPer + 2) / 3];
@@ -86,17 +97,33 @@ __global__ __launch_bounds__(kGridThreads) void k_grid_fields(const double *__re
         const int rr = r + grid_dr(m), cc = col + grid_dc(m);
         if (rr >= 0 && rr < H && cc >= 0 && cc < W) f |= 1u << m;
       }
-      if (c == goal) D[i] = 0.0;
-      else if (d < occ_threshold) f |= 256u;
+      if constexpr (kSeeded) {
+        const bool is_free = d < occ_threshold;
+        const double s = is_free ? S[c] : inf;        // a seed on an occupied cell is ignored
+        bad_seed = bad_seed || !(s >= 0.0);
+        D[i] = s;
+        if (is_free) f |= 256u;
+        E[c] = s < inf ? cost_factor * d + s : inf;
+      } else {
+        if (c == goal) D[i] = 0.0;
+        else if (d < occ_threshold) f |= 256u;
+        E[c] = c == goal ? cost_factor * d + 0.0 : inf;
+      }
       bad = bad || (d < occ_threshold && !(d >= 0.0));
       fw[i / 3] |= f << (10 * (i % 3));
-      E[c] = c == goal ? cost_factor * d + 0.0 : inf;
     }
   }
   if (__syncthreads_or(bad)) {
     for (int c = t; c < HW; c += kGridThreads) F[c] = inf;
     if (t == 0) { status[g] = RMPC_GRID_BAD_MAP; if (sweeps) sweeps[g] = 0; }
     return;
+  }
+  if constexpr (kSeeded) {
+    if (__syncthreads_or(bad_seed)) {
+      for (int c = t; c < HW; c += kGridThreads) F[c] = inf;
+      if (t == 0) { status[g] = RMPC_GRID_BAD_SEED; if (sweeps) sweeps[g] = 0; }
+      return;
+    }
   }
   // one cell of a sweep; the price f data[u] is read again only when D(u) drops (L1 / L2 hits), which keeps the
   // thread's D and flags in registers without scratch
@@ -147,6 +174,22 @@ __global__ __launch_bounds__(kGridThreads) void k_grid_fields(const double *__re
   }
 }
 
+__global__ __launch_bounds__(kGridThreads) void k_grid_fields(const double *__restrict__ grid, int H, int W,
+                                                              const int *__restrict__ goal_cells, int nmoves,
+                                                              double occ_threshold, double cost_factor,
+                                                              double *__restrict__ fields, int *__restrict__ status,
+                                                              int *__restrict__ sweeps) {
+  grid_fields<false>(grid, H, W, goal_cells, nullptr, nmoves, occ_threshold, cost_factor, fields, status, sweeps);
+}
+
+__global__ __launch_bounds__(kGridThreads) void k_grid_fields_seeded(const double *__restrict__ grid, int H, int W,
+                                                                     const double *__restrict__ seeds, int nmoves,
+                                                                     double occ_threshold, double cost_factor,
+                                                                     double *__restrict__ fields, int *__restrict__ status,
+                                                                     int *__restrict__ sweeps) {
+  grid_fields<true>(grid, H, W, nullptr, seeds, nmoves, occ_threshold, cost_factor, fields, status, sweeps);
+}
+
 // descent of field goal_index[b] from start_cell[b]: the neighbour with the least delta + f data[v] + D(v), the first in
 // move order on ties, until the goal
 __global__ __launch_bounds__(256) void k_grid_paths(const double *__restrict__ grid, int H, int W, const double *__restrict__ fields,
@@ -180,6 +223,48 @@ __global__ __launch_bounds__(256) void k_grid_paths(const double *__restrict__ g
       if (cand < best) { best = cand; next = v; }
     }
     if (next < 0) { len[b] = 0; return; }   // (not reached on a field of this grid: D(u) finite has a finite neighbour)
+    u = next;
+  }
+  len[b] = n;
+}
+
+// descent of the seeded field field_index[b] from start_cell[b] by the step rule of k_grid_paths, until the first cell u
+// with D(u) finite and D(u) == seed(u): a source that nothing undercuts (an undercut one is passed through).  The start
+// cell is not tested for occupancy -- a robot stands where it stands: from a start with D = +inf the first step goes to
+// the best neighbour, and the length is 0 when none is finite.  Every later cell has a finite D, which falls strictly
+// along the walk; max_len bounds the loop whatever the field holds.
+__global__ __launch_bounds__(256) void k_grid_descend(const double *__restrict__ grid, int H, int W, const double *__restrict__ fields,
+                                                      const double *__restrict__ seeds, int G, const int *__restrict__ start_cell,
+                                                      const int *__restrict__ field_index, int B, int nmoves, double occ_threshold,
+                                                      double cost_factor, int max_len, int *__restrict__ path, int *__restrict__ len) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const int HW = H * W, s = start_cell[b], fi = field_index[b];
+  int *const out = path + (size_t)b * max_len;
+  if (s < 0 || s >= HW || fi < 0 || fi >= G) { len[b] = RMPC_GRID_OUTSIDE; return; }
+  const double *const F = fields + (size_t)fi * HW, *const S = seeds + (size_t)fi * HW;
+  int u = s, n = 0;
+  for (;;) {
+    if (n >= max_len) { len[b] = RMPC_GRID_TOO_LONG; return; }
+    const double Du = F[u];
+    const bool source = Du < __builtin_inf() && Du == S[u];
+    int next = -1;
+    if (!source) {
+      const int r = u / W, col = u - r * W;
+      double best = __builtin_inf();
+      for (int m = 0; m < nmoves; m++) {
+        const int rr = r + grid_dr(m), cc = col + grid_dc(m);
+        if (rr < 0 || rr >= H || cc < 0 || cc >= W) continue;
+        const int v = rr * W + cc;
+        if (!(grid[v] < occ_threshold)) continue;
+        const double cand = grid_delta(m) + (cost_factor * grid[v] + F[v]);
+        if (cand < best) { best = cand; next = v; }
+      }
+      if (next < 0) { len[b] = 0; return; }   // only at the start: walled in, or no source reaches it
+    }
+    out[n++] = u;
+    if (source) break;
     u = next;
   }
   len[b] = n;

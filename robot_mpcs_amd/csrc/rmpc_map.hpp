@@ -114,4 +114,35 @@ __global__ __launch_bounds__(256) void k_grid_occupancy(int n, int *__restrict__
   }
 }
 
+// One lane per cell: the planning grid and the frontier of the map.  known(c) = hits + misses != 0, the
+// rule of k_grid_occupancy; plan = the enlarged grid on known cells and unknown_value elsewhere (the unknown region is
+// not dilated: that would block every frontier cell); a frontier cell is known, free on the enlarged grid and has a
+// neighbour inside the map without evidence; seed = 0 there, +inf elsewhere.  *count grows by the number of frontier
+// cells, one integer atomicAdd per workgroup that holds any: the sum does not depend on the order.
+__global__ __launch_bounds__(256) void k_grid_frontier(int H, int W, const int *__restrict__ hits, const int *__restrict__ misses,
+                                                       const double *__restrict__ enlarged, double occ_threshold, int nmoves,
+                                                       double unknown_value, double *__restrict__ plan,
+                                                       double *__restrict__ seed, int *__restrict__ count) {
+#pragma clang fp contract(off)
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  bool frontier = false;
+  if (c < H * W) {
+    const bool known = (long long)hits[c] + (long long)misses[c] != 0;
+    const double e = enlarged[c];
+    plan[c] = known ? e : unknown_value;
+    if (known && e < occ_threshold) {
+      const int r = c / W, col = c - r * W;
+      for (int m = 0; m < nmoves; m++) {
+        const int rr = r + grid_dr(m), cc = col + grid_dc(m);
+        if (rr < 0 || rr >= H || cc < 0 || cc >= W) continue;
+        const int v = rr * W + cc;
+        frontier = frontier || (long long)hits[v] + (long long)misses[v] == 0;
+      }
+    }
+    seed[c] = frontier ? 0.0 : __builtin_inf();
+  }
+  const int n = __syncthreads_count(frontier);
+  if (threadIdx.x == 0 && n > 0) atomicAdd(count, n);
+}
+
 }  // namespace rmpc

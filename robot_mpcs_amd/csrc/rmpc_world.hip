@@ -162,6 +162,22 @@ int rmpc_grid_fields_device(int H, int W, const double *d_grid, int G, const int
   return launch_status();
 }
 
+int rmpc_grid_fields_seeded_device(int H, int W, const double *d_grid, int G, const double *d_seeds, int movement,
+                                   double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status,
+                                   int32_t *d_sweeps, void *stream) {
+  if (!d_grid || !d_seeds || !d_fields || !d_status) return fail("null argument");
+  if (grid_check(H, W, movement)) return -1;
+  if (H * W > RMPC_GRID_MAX_CELLS)
+    return fail("grid fields: " + std::to_string(H) + "x" + std::to_string(W) + " map exceeds RMPC_GRID_MAX_CELLS = " +
+                std::to_string(RMPC_GRID_MAX_CELLS) + " cells (one field must fit in the LDS of a workgroup)");
+  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid fields: need 1 <= G and G*H*W <= INT_MAX");
+  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid fields: cost_factor must be finite and >= 0");
+  if (use_device_of(d_grid)) return -1;
+  hipLaunchKernelGGL(k_grid_fields_seeded, dim3(G), dim3(kGridThreads), 0, (hipStream_t)stream, d_grid, H, W, d_seeds,
+                     movement, occ_threshold, cost_factor, d_fields, (int *)d_status, (int *)d_sweeps);
+  return launch_status();
+}
+
 int rmpc_grid_paths_device(int H, int W, const double *d_grid, int G, const double *d_fields, const int32_t *d_goal_cells,
                            int B, const int32_t *d_start_cell, const int32_t *d_goal_index, int movement,
                            double occ_threshold, double cost_factor, int max_len, int32_t *d_path, int32_t *d_len,
@@ -175,6 +191,22 @@ int rmpc_grid_paths_device(int H, int W, const double *d_grid, int G, const doub
   hipLaunchKernelGGL(k_grid_paths, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, d_fields,
                      (const int *)d_goal_cells, G, (const int *)d_start_cell, (const int *)d_goal_index, B, movement,
                      occ_threshold, cost_factor, max_len, (int *)d_path, (int *)d_len);
+  return launch_status();
+}
+
+int rmpc_grid_descend_device(int H, int W, const double *d_grid, int G, const double *d_fields, const double *d_seeds,
+                             int B, const int32_t *d_start_cell, const int32_t *d_field_index, int movement,
+                             double occ_threshold, double cost_factor, int max_len, int32_t *d_path, int32_t *d_len,
+                             void *stream) {
+  if (!d_grid || !d_fields || !d_seeds || !d_start_cell || !d_field_index || !d_path || !d_len) return fail("null argument");
+  if (grid_check(H, W, movement)) return -1;
+  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid descend: need 1 <= G and G*H*W <= INT_MAX");
+  if (B < 1 || max_len < 1 || !grid_fits(B, max_len)) return fail("grid descend: need B, max_len >= 1 and B*max_len <= INT_MAX");
+  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid descend: cost_factor must be finite and >= 0");
+  if (use_device_of(d_grid)) return -1;
+  hipLaunchKernelGGL(k_grid_descend, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, d_fields,
+                     d_seeds, G, (const int *)d_start_cell, (const int *)d_field_index, B, movement, occ_threshold,
+                     cost_factor, max_len, (int *)d_path, (int *)d_len);
   return launch_status();
 }
 
@@ -306,6 +338,23 @@ int rmpc_grid_occupancy_device(int H, int W, int32_t *d_hits, int32_t *d_misses,
   if (use_device_of(d_hits)) return -1;
   hipLaunchKernelGGL(k_grid_occupancy, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, H * W, (int *)d_hits,
                      (int *)d_misses, w_hit, w_miss, forget, free_value, occ_value, unknown_value, d_grid);
+  return launch_status();
+}
+
+/* the frontier of the map (rmpc_map.hpp) */
+int rmpc_grid_frontier_device(int H, int W, const int32_t *d_hits, const int32_t *d_misses, const double *d_enlarged,
+                              double occ_threshold, int nmoves, double unknown_value, double *d_plan, double *d_seed,
+                              int32_t *d_count, void *stream) {
+  if (!d_hits || !d_misses || !d_enlarged || !d_plan || !d_seed || !d_count) return fail("null argument");
+  if (H < 1 || W < 1 || !grid_fits(H, W) || H * W > RMPC_GRID_MAX_CELLS)
+    return fail("grid frontier: need H, W >= 1 and H*W <= RMPC_GRID_MAX_CELLS = " + std::to_string(RMPC_GRID_MAX_CELLS));
+  if (nmoves != 4 && nmoves != 8) return fail("grid frontier: nmoves must be 4 or 8");
+  if (!std::isfinite(occ_threshold) || !std::isfinite(unknown_value))
+    return fail("grid frontier: occ_threshold and unknown_value must be finite");
+  if (use_device_of(d_hits)) return -1;
+  hipLaunchKernelGGL(k_grid_frontier, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, H, W,
+                     (const int *)d_hits, (const int *)d_misses, d_enlarged, occ_threshold, nmoves, unknown_value, d_plan,
+                     d_seed, (int *)d_count);
   return launch_status();
 }
 

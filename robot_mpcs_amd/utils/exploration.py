@@ -1,0 +1,101 @@
+"""Frontier exploration for a fleet that maps as it drives, on the device: ``FrontierGoals`` turns the
+evidence of a ``FleetMap`` into routes to the nearest frontier -- a known free cell next to unknown space -- for every
+robot, so that a fleet without a map and without goals explores until no frontier is left.  One re-plan is the chain
+
+    FleetMap.occupancy (unknown = free value) -> grid_inflate_device -> grid_frontier_device
+    -> grid_fields_seeded_device (G = 1) -> cells_from_positions -> grid_descend_device -> RouteFollower.replace
+
+on one stream without a host read.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .. import _lib
+
+FREE, OCC = 68.0 / 256.0, 253.0 / 256.0    # png_values: what grid_inflate_device gets in the reference
+
+
+def corner_starts(raw, B, clear=2):
+    """The B cells nearest the corner (row 0, col 0) of the map ``raw`` (H, W; > 0.5 occupied) that stay free when the
+    map is dilated by ``clear`` cells (Chebyshev): a fleet unloaded in one corner.  (B,) int32 cell indices row * W + col,
+    ordered by distance, then by index."""
+    H, W = raw.shape
+    occ = np.pad(raw > 0.5, clear, constant_values=True)
+    near = np.zeros((H, W), dtype=bool)
+    for dr in range(-clear, clear + 1):
+        for dc in range(-clear, clear + 1):
+            near |= occ[clear + dr:clear + dr + H, clear + dc:clear + dc + W]
+    cells = np.flatnonzero(~near.ravel())
+    if len(cells) < B:
+        raise ValueError(f"corner_starts: the map has {len(cells)} clear cells, {B} asked for")
+    d2 = (cells // W) ** 2 + (cells % W) ** 2
+    return cells[np.lexsort((cells, d2))][:B].astype(np.int32)
+
+
+class FrontierGoals:
+    """Routes to the nearest frontier of ``fmap`` (a ``FleetMap``) for its B robots.
+
+    Owns ``enlarged``, ``plan``, ``seed`` (H, W) fp64, ``count`` (1,) int32, one ``field`` (1, H, W) fp64 with its
+    ``status`` and ``sweeps`` (1,) int32, ``cells`` (B,) int32, ``paths`` (B, max_len) int32 and ``lens`` (B,) int32.
+    ``size_robot`` and ``threshold`` are those of ``grid_inflate_device`` on the classified map, whose unknown cells get
+    the free value; the planning grid ``plan`` then holds ``unknown_value`` (>= ``occ_threshold``: routes stay inside
+    what has been seen) on the cells without evidence, which are not dilated.  ``frontier_moves`` (4 or 8): which
+    neighbours count as next to unknown space.  The first ``replan`` must come after the first ``FleetMap.mark``: a map
+    without evidence has no frontier."""
+
+    def __init__(self, fmap, size_robot, threshold=0.29, free_value=FREE, occ_value=OCC, unknown_value=1.0,
+                 occ_threshold=0.8, cost_factor=3.0, movement=8, frontier_moves=4, max_len=None):
+        import torch
+        if not float(unknown_value) >= float(occ_threshold):
+            raise ValueError("FrontierGoals: unknown_value must be >= occ_threshold (unknown cells are not planned through)")
+        self.fmap = fmap
+        self.size_robot, self.threshold = float(size_robot), float(threshold)
+        self.free_value, self.occ_value, self.unknown_value = float(free_value), float(occ_value), float(unknown_value)
+        self.occ_threshold, self.cost_factor = float(occ_threshold), float(cost_factor)
+        self.movement, self.frontier_moves = int(movement), int(frontier_moves)
+        H, W, B, dev = fmap.H, fmap.W, fmap.B, fmap.device
+        self.max_len = int(max_len) if max_len is not None else min(H * W, 4 * (H + W))
+        f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+        self.enlarged = torch.zeros((H, W), **f64)
+        self.plan = torch.zeros((H, W), **f64)
+        self.seed = torch.full((H, W), float("inf"), **f64)
+        self.count = torch.zeros(1, **i32)
+        self.field = torch.full((1, H, W), float("inf"), **f64)
+        self.status = torch.zeros(1, **i32)
+        self.sweeps = torch.zeros(1, **i32)
+        self.cells = torch.zeros(B, **i32)
+        self.field_index = torch.zeros(B, **i32)
+        self.paths = torch.zeros((B, self.max_len), **i32)
+        self.lens = torch.zeros(B, **i32)
+        self._stream = None
+
+    def replan(self, follower, xinit, stream=None):
+        """xinit (B, stride >= 2) the robots' states; ``follower`` a ``RouteFollower``.  Enqueues the whole chain on
+        ``stream`` (a ``torch.cuda.Stream``; None = the current one) and never synchronises.  A robot with
+        ``lens`` <= 0 (no frontier reachable, outside the map, route too long) keeps the route it has; one that stands
+        on a frontier cell gets the route of that one cell.  Returns (paths, lens) of the new plan."""
+        import torch
+        fm = self.fmap
+        stream = stream if stream is not None else torch.cuda.current_stream(fm.device)
+        st = stream.cuda_stream
+        self._stream = stream
+        with torch.cuda.stream(stream):
+            grid = fm.occupancy(self.free_value, self.occ_value, self.free_value, stream=st)
+            _lib.grid_inflate_device(grid, self.enlarged, fm.cell, self.size_robot, self.threshold, stream=st)
+            self.count.zero_()
+            _lib.grid_frontier_device(fm.hits, fm.misses, self.enlarged, self.plan, self.seed, self.count,
+                                      self.occ_threshold, self.frontier_moves, self.unknown_value, stream=st)
+            _lib.grid_fields_seeded_device(self.plan, self.seed[None], self.field, self.status, self.movement,
+                                           self.occ_threshold, self.cost_factor, sweeps=self.sweeps, stream=st)
+            _lib.grid_cells_device(xinit, self.cells, fm.H, fm.W, fm.x0, fm.y0, fm.cell, stream=st)
+            _lib.grid_descend_device(self.plan, self.field, self.seed[None], self.cells, self.field_index, self.paths,
+                                     self.lens, self.movement, self.occ_threshold, self.cost_factor, stream=st)
+            follower.replace(self.paths, self.lens)
+        return self.paths, self.lens
+
+    def frontier_cells(self):
+        """The number of frontier cells the last ``replan`` found: the one host read (it waits for the device)."""
+        if self._stream is not None:
+            self._stream.synchronize()
+        return int(self.count.item())
