@@ -30,11 +30,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-# the store: 41 x 41 cells of 0.45 m centred on the origin (inside the point robot's +-10 m joint limits)
-H = W = 41
-CELL = 0.45
-X0 = Y0 = -9.0
-SIZE_ROBOT = 0.45     # k = 1: every cell that touches a shelf is blocked
+from robot_mpcs_amd.store import STORE  # noqa: E402
+
+# the store's frame (41 x 41 cells of 0.45 m centred on the origin: inside the point robot's +-10 m joint limits)
+H, W, CELL, X0, Y0 = STORE.H, STORE.W, STORE.cell, STORE.x0, STORE.y0
+SIZE_ROBOT = STORE.size_robot     # k = 1: every cell that touches a shelf is blocked
 
 
 def run(B=256, steps=1200, seed=0, dev="cuda:0", aisle=4, gap=3, size_robot=SIZE_ROBOT, threshold=1.3, shelf=2):

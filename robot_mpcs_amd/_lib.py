@@ -366,6 +366,13 @@ def _stream_arg(stream):
     return C.c_void_p(int(stream or 0))
 
 
+def stream_handle(stream, device):
+    """``stream`` (a raw handle), or when it is None that of the stream torch's ops run on on ``device`` -- the device of
+    the call's tensors, which need not be the current one (``_stream_arg(None)`` asks the current device)."""
+    import torch
+    return stream if stream is not None else torch.cuda.current_stream(device).cuda_stream
+
+
 def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 

@@ -106,6 +106,64 @@ static int launch_status() {
   return 0;
 }
 
+/* the global planner (rmpc_grid.hpp): no handle; each call runs on the device its first pointer lives on */
+static bool grid_fits(long long a, long long b) { return a >= 0 && b >= 0 && (b == 0 || a <= INT_MAX / b); }
+static int grid_check(int H, int W, int movement) {
+  if (H < 1 || W < 1 || !grid_fits(H, W)) return fail("grid: need H, W >= 1");
+  if (movement != 4 && movement != 8) return fail("grid: movement must be 4 or 8");
+  return 0;
+}
+// The checks several entries make, each under the entry's prefix `who`.  A map of more than RMPC_GRID_MAX_CELLS cells
+// (or of none) is refused in one of two wordings: `sized` names the map's size (the fields, behind grid_check).
+static int grid_cells_check(const std::string &who, int H, int W, bool sized) {
+  if (H >= 1 && W >= 1 && grid_fits(H, W) && H * W <= RMPC_GRID_MAX_CELLS) return 0;
+  const std::string max = "RMPC_GRID_MAX_CELLS = " + std::to_string(RMPC_GRID_MAX_CELLS);
+  if (!sized) return fail(who + ": need H, W >= 1 and H*W <= " + max);
+  return fail(who + ": " + std::to_string(H) + "x" + std::to_string(W) + " map exceeds " + max +
+              " cells (one field must fit in the LDS of a workgroup)");
+}
+static int grid_fields_check(const std::string &who, int G, int H, int W) {
+  return G < 1 || !grid_fits(G, (long long)H * W) ? fail(who + ": need 1 <= G and G*H*W <= INT_MAX") : 0;
+}
+static int grid_paths_check(const std::string &who, int B, int max_len) {
+  return B < 1 || max_len < 1 || !grid_fits(B, max_len) ? fail(who + ": need B, max_len >= 1 and B*max_len <= INT_MAX") : 0;
+}
+static int grid_cost_check(const std::string &who, double cost_factor) {
+  return !(cost_factor >= 0.0) || std::isinf(cost_factor) ? fail(who + ": cost_factor must be finite and >= 0") : 0;
+}
+
+// rmpc_grid_fields_device and rmpc_grid_fields_seeded_device (both speak as "grid fields"): `d_src` the goal cells or
+// the seed grids of `kernel`
+template <class Kernel, class T>
+static int grid_fields(Kernel kernel, int H, int W, const double *d_grid, int G, const T *d_src, int movement,
+                       double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status, int32_t *d_sweeps,
+                       void *stream) {
+  const char *who = "grid fields";
+  if (!d_grid || !d_src || !d_fields || !d_status) return fail("null argument");
+  if (grid_check(H, W, movement) || grid_cells_check(who, H, W, true) || grid_fields_check(who, G, H, W) ||
+      grid_cost_check(who, cost_factor) || use_device_of(d_grid))
+    return -1;
+  hipLaunchKernelGGL(kernel, dim3(G), dim3(kGridThreads), 0, (hipStream_t)stream, d_grid, H, W, d_src, movement,
+                     occ_threshold, cost_factor, d_fields, (int *)d_status, (int *)d_sweeps);
+  return launch_status();
+}
+
+// rmpc_grid_paths_device and rmpc_grid_descend_device: `d_ends` the goal cells or the seed grids of `kernel`
+template <class Kernel, class T>
+static int grid_descent(const char *who, Kernel kernel, int H, int W, const double *d_grid, int G, const double *d_fields,
+                        const T *d_ends, int B, const int32_t *d_start_cell, const int32_t *d_index, int movement,
+                        double occ_threshold, double cost_factor, int max_len, int32_t *d_path, int32_t *d_len,
+                        void *stream) {
+  if (!d_grid || !d_fields || !d_ends || !d_start_cell || !d_index || !d_path || !d_len) return fail("null argument");
+  if (grid_check(H, W, movement) || grid_fields_check(who, G, H, W) || grid_paths_check(who, B, max_len) ||
+      grid_cost_check(who, cost_factor) || use_device_of(d_grid))
+    return -1;
+  hipLaunchKernelGGL(kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, d_fields, d_ends, G,
+                     (const int *)d_start_cell, (const int *)d_index, B, movement, occ_threshold, cost_factor, max_len,
+                     (int *)d_path, (int *)d_len);
+  return launch_status();
+}
+
 extern "C" {
 
 int rmpc_advance_obstacles_device(int B, int nobst, double dt, double arena, double *d_obst_dyn, void *stream) {
@@ -125,14 +183,7 @@ int rmpc_free_space_device(int B, int N, int P, int K, double max_radius, const 
   return launch_status();
 }
 
-/* the global planner (rmpc_grid.hpp): no handle; each call runs on the device its first pointer lives on */
-static bool grid_fits(long long a, long long b) { return a >= 0 && b >= 0 && (b == 0 || a <= INT_MAX / b); }
-static int grid_check(int H, int W, int movement) {
-  if (H < 1 || W < 1 || !grid_fits(H, W)) return fail("grid: need H, W >= 1");
-  if (movement != 4 && movement != 8) return fail("grid: movement must be 4 or 8");
-  return 0;
-}
-
+/* the global planner's entries (rmpc_grid.hpp) */
 int rmpc_grid_inflate_device(int H, int W, double cell, double size_robot, double threshold, const double *d_grid,
                              double *d_out, void *stream) {
   if (!d_grid || !d_out) return fail("null argument");
@@ -148,66 +199,31 @@ int rmpc_grid_inflate_device(int H, int W, double cell, double size_robot, doubl
 int rmpc_grid_fields_device(int H, int W, const double *d_grid, int G, const int32_t *d_goal_cells, int movement,
                             double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status,
                             int32_t *d_sweeps, void *stream) {
-  if (!d_grid || !d_goal_cells || !d_fields || !d_status) return fail("null argument");
-  if (grid_check(H, W, movement)) return -1;
-  if (H * W > RMPC_GRID_MAX_CELLS)
-    return fail("grid fields: " + std::to_string(H) + "x" + std::to_string(W) + " map exceeds RMPC_GRID_MAX_CELLS = " +
-                std::to_string(RMPC_GRID_MAX_CELLS) + " cells (one field must fit in the LDS of a workgroup)");
-  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid fields: need 1 <= G and G*H*W <= INT_MAX");
-  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid fields: cost_factor must be finite and >= 0");
-  if (use_device_of(d_grid)) return -1;
-  hipLaunchKernelGGL(k_grid_fields, dim3(G), dim3(kGridThreads), 0, (hipStream_t)stream, d_grid, H, W,
-                     (const int *)d_goal_cells, movement, occ_threshold, cost_factor, d_fields, (int *)d_status,
-                     (int *)d_sweeps);
-  return launch_status();
+  return grid_fields(k_grid_fields, H, W, d_grid, G, (const int *)d_goal_cells, movement, occ_threshold, cost_factor,
+                     d_fields, d_status, d_sweeps, stream);
 }
 
 int rmpc_grid_fields_seeded_device(int H, int W, const double *d_grid, int G, const double *d_seeds, int movement,
                                    double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status,
                                    int32_t *d_sweeps, void *stream) {
-  if (!d_grid || !d_seeds || !d_fields || !d_status) return fail("null argument");
-  if (grid_check(H, W, movement)) return -1;
-  if (H * W > RMPC_GRID_MAX_CELLS)
-    return fail("grid fields: " + std::to_string(H) + "x" + std::to_string(W) + " map exceeds RMPC_GRID_MAX_CELLS = " +
-                std::to_string(RMPC_GRID_MAX_CELLS) + " cells (one field must fit in the LDS of a workgroup)");
-  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid fields: need 1 <= G and G*H*W <= INT_MAX");
-  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid fields: cost_factor must be finite and >= 0");
-  if (use_device_of(d_grid)) return -1;
-  hipLaunchKernelGGL(k_grid_fields_seeded, dim3(G), dim3(kGridThreads), 0, (hipStream_t)stream, d_grid, H, W, d_seeds,
-                     movement, occ_threshold, cost_factor, d_fields, (int *)d_status, (int *)d_sweeps);
-  return launch_status();
+  return grid_fields(k_grid_fields_seeded, H, W, d_grid, G, d_seeds, movement, occ_threshold, cost_factor, d_fields,
+                     d_status, d_sweeps, stream);
 }
 
 int rmpc_grid_paths_device(int H, int W, const double *d_grid, int G, const double *d_fields, const int32_t *d_goal_cells,
                            int B, const int32_t *d_start_cell, const int32_t *d_goal_index, int movement,
                            double occ_threshold, double cost_factor, int max_len, int32_t *d_path, int32_t *d_len,
                            void *stream) {
-  if (!d_grid || !d_fields || !d_goal_cells || !d_start_cell || !d_goal_index || !d_path || !d_len) return fail("null argument");
-  if (grid_check(H, W, movement)) return -1;
-  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid paths: need 1 <= G and G*H*W <= INT_MAX");
-  if (B < 1 || max_len < 1 || !grid_fits(B, max_len)) return fail("grid paths: need B, max_len >= 1 and B*max_len <= INT_MAX");
-  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid paths: cost_factor must be finite and >= 0");
-  if (use_device_of(d_grid)) return -1;
-  hipLaunchKernelGGL(k_grid_paths, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, d_fields,
-                     (const int *)d_goal_cells, G, (const int *)d_start_cell, (const int *)d_goal_index, B, movement,
-                     occ_threshold, cost_factor, max_len, (int *)d_path, (int *)d_len);
-  return launch_status();
+  return grid_descent("grid paths", k_grid_paths, H, W, d_grid, G, d_fields, (const int *)d_goal_cells, B, d_start_cell,
+                      d_goal_index, movement, occ_threshold, cost_factor, max_len, d_path, d_len, stream);
 }
 
 int rmpc_grid_descend_device(int H, int W, const double *d_grid, int G, const double *d_fields, const double *d_seeds,
                              int B, const int32_t *d_start_cell, const int32_t *d_field_index, int movement,
                              double occ_threshold, double cost_factor, int max_len, int32_t *d_path, int32_t *d_len,
                              void *stream) {
-  if (!d_grid || !d_fields || !d_seeds || !d_start_cell || !d_field_index || !d_path || !d_len) return fail("null argument");
-  if (grid_check(H, W, movement)) return -1;
-  if (G < 1 || !grid_fits(G, (long long)H * W)) return fail("grid descend: need 1 <= G and G*H*W <= INT_MAX");
-  if (B < 1 || max_len < 1 || !grid_fits(B, max_len)) return fail("grid descend: need B, max_len >= 1 and B*max_len <= INT_MAX");
-  if (!(cost_factor >= 0.0) || std::isinf(cost_factor)) return fail("grid descend: cost_factor must be finite and >= 0");
-  if (use_device_of(d_grid)) return -1;
-  hipLaunchKernelGGL(k_grid_descend, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, d_fields,
-                     d_seeds, G, (const int *)d_start_cell, (const int *)d_field_index, B, movement, occ_threshold,
-                     cost_factor, max_len, (int *)d_path, (int *)d_len);
-  return launch_status();
+  return grid_descent("grid descend", k_grid_descend, H, W, d_grid, G, d_fields, d_seeds, B, d_start_cell, d_field_index,
+                      movement, occ_threshold, cost_factor, max_len, d_path, d_len, stream);
 }
 
 int rmpc_grid_cells_device(int B, const double *d_pos, int stride, int H, int W, double x0, double y0, double cell,
@@ -225,7 +241,7 @@ int rmpc_follow_path_device(int B, const int32_t *d_path, const int32_t *d_len, 
                             const double *d_pos, int stride, int W, double x0, double y0, double cell, double threshold,
                             double *d_goal, void *stream) {
   if (!d_path || !d_len || !d_idx || !d_pos || !d_goal) return fail("null argument");
-  if (B < 1 || max_len < 1 || !grid_fits(B, max_len)) return fail("follow path: need B, max_len >= 1 and B*max_len <= INT_MAX");
+  if (grid_paths_check("follow path", B, max_len)) return -1;
   if (stride < 2 || !grid_fits(B, stride) || W < 1) return fail("follow path: need stride >= 2, W >= 1");
   if (use_device_of(d_path)) return -1;
   hipLaunchKernelGGL(k_follow_path, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int *)d_path,
@@ -307,8 +323,7 @@ int rmpc_grid_mark_device(int B, const rmpc_grid_mark *m, void *stream) {
   if (m->struct_size != (int)sizeof(rmpc_grid_mark)) return fail("rmpc_grid_mark.struct_size mismatch");
   if (B < 1 || m->rays < 1) return fail("grid mark: need B >= 1 and rays >= 1");
   if (!grid_fits(B, m->rays) || !grid_fits((long long)B * m->rays, 3)) return fail("grid mark: B*rays*3 must not exceed INT_MAX");
-  if (m->H < 1 || m->W < 1 || !grid_fits(m->H, m->W) || m->H * m->W > RMPC_GRID_MAX_CELLS)
-    return fail("grid mark: need H, W >= 1 and H*W <= RMPC_GRID_MAX_CELLS = " + std::to_string(RMPC_GRID_MAX_CELLS));
+  if (grid_cells_check("grid mark", m->H, m->W, false)) return -1;
   if (!(m->cell > 0.0) || std::isinf(m->cell) || !(m->range > 0.0) || std::isinf(m->range))
     return fail("grid mark: cell and range must be positive and finite");
   if (!(m->hit_depth >= 0.0) || std::isinf(m->hit_depth)) return fail("grid mark: hit_depth must be finite and >= 0");
@@ -329,8 +344,7 @@ int rmpc_grid_mark_device(int B, const rmpc_grid_mark *m, void *stream) {
 int rmpc_grid_occupancy_device(int H, int W, int32_t *d_hits, int32_t *d_misses, int w_hit, int w_miss, int forget,
                                double free_value, double occ_value, double unknown_value, double *d_grid, void *stream) {
   if (!d_hits || !d_misses || !d_grid) return fail("null argument");
-  if (H < 1 || W < 1 || !grid_fits(H, W) || H * W > RMPC_GRID_MAX_CELLS)
-    return fail("grid occupancy: need H, W >= 1 and H*W <= RMPC_GRID_MAX_CELLS = " + std::to_string(RMPC_GRID_MAX_CELLS));
+  if (grid_cells_check("grid occupancy", H, W, false)) return -1;
   if (w_hit < 1 || w_miss < 1) return fail("grid occupancy: need w_hit, w_miss >= 1");
   if (forget < 0 || forget > 31) return fail("grid occupancy: forget must lie in [0, 31]");
   if (!std::isfinite(free_value) || !std::isfinite(occ_value) || !std::isfinite(unknown_value))
@@ -346,8 +360,7 @@ int rmpc_grid_frontier_device(int H, int W, const int32_t *d_hits, const int32_t
                               double occ_threshold, int nmoves, double unknown_value, double *d_plan, double *d_seed,
                               int32_t *d_count, void *stream) {
   if (!d_hits || !d_misses || !d_enlarged || !d_plan || !d_seed || !d_count) return fail("null argument");
-  if (H < 1 || W < 1 || !grid_fits(H, W) || H * W > RMPC_GRID_MAX_CELLS)
-    return fail("grid frontier: need H, W >= 1 and H*W <= RMPC_GRID_MAX_CELLS = " + std::to_string(RMPC_GRID_MAX_CELLS));
+  if (grid_cells_check("grid frontier", H, W, false)) return -1;
   if (nmoves != 4 && nmoves != 8) return fail("grid frontier: nmoves must be 4 or 8");
   if (!std::isfinite(occ_threshold) || !std::isfinite(unknown_value))
     return fail("grid frontier: occ_threshold and unknown_value must be finite");

@@ -8,8 +8,8 @@ the package needs no GPU.
 """
 from .gridmap import OccupancyGridMap
 from .a_star import a_star
-from .globalPlanner import GlobalPlanner, png_values
+from .globalPlanner import FREE, OCC, GlobalPlanner, png_values
 from .batch import RouteFollower, cell_xy, cells_from_positions, pick_routes, plan_batch, replan, shelf_map, store_routes
 
-__all__ = ["OccupancyGridMap", "a_star", "GlobalPlanner", "RouteFollower", "cell_xy", "cells_from_positions",
+__all__ = ["FREE", "OCC", "OccupancyGridMap", "a_star", "GlobalPlanner", "RouteFollower", "cell_xy", "cells_from_positions",
            "pick_routes", "plan_batch", "png_values", "replan", "shelf_map", "store_routes"]

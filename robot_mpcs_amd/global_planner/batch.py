@@ -42,7 +42,7 @@ def plan_batch(grid, starts, goal_cells, movement="8N", occupancy_threshold=0.8,
     status = torch.empty(G, dtype=torch.int32, device=dev)
     paths = torch.empty((s.shape[0], max_len), dtype=torch.int32, device=dev)
     lens = torch.empty(s.shape[0], dtype=torch.int32, device=dev)
-    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    st = _lib.stream_handle(stream, dev)
     _lib.grid_fields_device(g, uniq, fields, status, MOVES[movement], occupancy_threshold, occupancy_cost_factor, stream=st)
     _lib.grid_paths_device(g, fields, uniq, s, inv, paths, lens, MOVES[movement], occupancy_threshold,
                            occupancy_cost_factor, stream=st)
@@ -55,8 +55,7 @@ def cells_from_positions(pos, H, W, x0, y0, cell, stream=None):
     """pos (B, stride >= 2) device tensor (e.g. xinit) -> cells (B,) int32 of the plain frame, -1 outside."""
     import torch
     cells = torch.empty(pos.shape[0], dtype=torch.int32, device=pos.device)
-    _lib.grid_cells_device(pos, cells, H, W, x0, y0, cell,
-                           stream=stream if stream is not None else torch.cuda.current_stream(pos.device).cuda_stream)
+    _lib.grid_cells_device(pos, cells, H, W, x0, y0, cell, stream=_lib.stream_handle(stream, pos.device))
     return cells
 
 
@@ -72,10 +71,8 @@ class RouteFollower:
         self.W, self.x0, self.y0, self.cell, self.threshold = int(W), float(x0), float(y0), float(cell), float(threshold)
 
     def step(self, xinit, goal, stream=None):
-        import torch
         _lib.follow_path_device(self.paths, self.lens, self.idx, xinit, goal, self.W, self.x0, self.y0, self.cell,
-                                self.threshold,
-                                stream=stream if stream is not None else torch.cuda.current_stream(goal.device).cuda_stream)
+                                self.threshold, stream=_lib.stream_handle(stream, goal.device))
 
     def replace(self, paths, lens):
         """New routes (paths (B, max_len) int32, lens (B,) int32, e.g. of ``plan_batch``): the robots with lens > 0 take

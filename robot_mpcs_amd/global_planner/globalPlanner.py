@@ -30,6 +30,9 @@ def png_values(map2d):
     return colormaps["viridis"](scaled, bytes=True)[..., 0].astype(np.float64) / 256.0
 
 
+FREE, OCC = 68.0 / 256.0, 253.0 / 256.0    # png_values of a map of two values: what grid_inflate_device gets in the reference
+
+
 class GlobalPlanner(object):
     def __init__(self, dim_pixels, limits_low, limits_high, BOOL_PLOTTING=True, threshold=0.29,
                  convolution_blur=(5, 5), enlarge_obstacles=True, threshold_local_goal=1.3):

@@ -12,21 +12,16 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib
-
-FREE, OCC = 68.0 / 256.0, 253.0 / 256.0    # png_values: what grid_inflate_device gets in the reference
+from ..global_planner import FREE, OCC
+from ..store import clear_cells
 
 
 def corner_starts(raw, B, clear=2):
     """The B cells nearest the corner (row 0, col 0) of the map ``raw`` (H, W; > 0.5 occupied) that stay free when the
     map is dilated by ``clear`` cells (Chebyshev): a fleet unloaded in one corner.  (B,) int32 cell indices row * W + col,
     ordered by distance, then by index."""
-    H, W = raw.shape
-    occ = np.pad(raw > 0.5, clear, constant_values=True)
-    near = np.zeros((H, W), dtype=bool)
-    for dr in range(-clear, clear + 1):
-        for dc in range(-clear, clear + 1):
-            near |= occ[clear + dr:clear + dr + H, clear + dc:clear + dc + W]
-    cells = np.flatnonzero(~near.ravel())
+    W = raw.shape[1]
+    cells = np.flatnonzero(clear_cells(raw, clear).ravel())
     if len(cells) < B:
         raise ValueError(f"corner_starts: the map has {len(cells)} clear cells, {B} asked for")
     d2 = (cells // W) ** 2 + (cells % W) ** 2
@@ -77,10 +72,9 @@ class FrontierGoals:
         on a frontier cell gets the route of that one cell.  Returns (paths, lens) of the new plan."""
         import torch
         fm = self.fmap
-        stream = stream if stream is not None else torch.cuda.current_stream(fm.device)
-        st = stream.cuda_stream
-        self._stream = stream
-        with torch.cuda.stream(stream):
+        with torch.cuda.stream(stream):     # (None: the current one stays)
+            self._stream = torch.cuda.current_stream(fm.device)
+            st = self._stream.cuda_stream
             grid = fm.occupancy(self.free_value, self.occ_value, self.free_value, stream=st)
             _lib.grid_inflate_device(grid, self.enlarged, fm.cell, self.size_robot, self.threshold, stream=st)
             self.count.zero_()

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .._lib import free_space_decomposition_device
+from .._lib import free_space_decomposition_device, stream_handle
 
 
 class FreeSpaceDecomposition:
@@ -36,8 +36,7 @@ class FreeSpaceDecomposition:
         if pts.dim() != 3 or sds.dim() != 3 or pts.shape[0] != sds.shape[0] or pts.shape[2] != 3 or sds.shape[2] != 3:
             raise ValueError("points must be (B, P, 3) and seeds (B, N, 3)")
         out = torch.empty((pts.shape[0], sds.shape[1], self._number_constraints, 4), dtype=torch.float64, device=dev)
-        free_space_decomposition_device(pts, sds, out, self._max_radius,
-                                        stream=torch.cuda.current_stream(dev).cuda_stream)
+        free_space_decomposition_device(pts, sds, out, self._max_radius, stream=stream_handle(None, dev))
         return out
 
     def compute_constraints(self, points):

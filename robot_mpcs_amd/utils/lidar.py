@@ -77,8 +77,7 @@ class LidarPlanes:
     def step(self, xinit, z_prev=None, exitflag=None, stream=None):
         """xinit (B, stride >= 3) poses; z_prev (B, N, nvar) the previous plan or None (first step); exitflag (B,) int32
         or None.  Returns ``planes``."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+        st = _lib.stream_handle(stream, self.device)
         _lib.lidar_scan_device(xinit, self.points, self.boxes, self.circles, self.angle_min, self.angle_max,
                                self.max_range, self.offset, self.height, ranges=self.ranges, stream=st)
         _lib.plan_points_device(xinit, self.seeds, z_prev, exitflag, self.offset, self.height, stream=st)

@@ -38,15 +38,11 @@ class FleetMap:
         self.origins = torch.zeros((self.B, 1, 3), dtype=torch.float64, device=dev)
         self.grid = torch.zeros((self.H, self.W), dtype=torch.float64, device=dev)
 
-    def _stream(self, stream):
-        import torch
-        return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
-
     def mark(self, xinit, points, ranges, stream=None):
         """xinit (B, stride >= 3) the poses the scan was taken from, points (B, rays, 3) and ranges (B, rays) the scan
         (``LidarPlanes.points``, ``LidarPlanes.ranges``): two launches on the current (or the given) stream, the sensor
         origins and the marks; never synchronises."""
-        st = self._stream(stream)
+        st = _lib.stream_handle(stream, self.device)
         _lib.plan_points_device(xinit, self.origins, None, None, self.offset, self.height, stream=st)
         _lib.grid_mark_device(self.origins, points, ranges, self.hits, self.misses, self.x0, self.y0, self.cell,
                               self.max_range, self.hit_depth, skipped=self.skipped, stream=st)
@@ -54,7 +50,7 @@ class FleetMap:
     def occupancy(self, free_value, occ_value, unknown_value, forget=0, stream=None):
         """Classifies the evidence into ``grid`` (returned) and, with forget > 0, ages the counters."""
         _lib.grid_occupancy_device(self.hits, self.misses, self.grid, free_value, occ_value, unknown_value, self.w_hit,
-                                   self.w_miss, forget, stream=self._stream(stream))
+                                   self.w_miss, forget, stream=_lib.stream_handle(stream, self.device))
         return self.grid
 
     def reset(self):

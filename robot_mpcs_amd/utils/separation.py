@@ -55,8 +55,7 @@ class NeighbourPlanes:
     def step(self, xinit, r_body, z_prev=None, exitflag=None, stream=None):
         """xinit (B, stride >= 3) poses; r_body (B,) fp64; z_prev (B, N, nvar) the previous plan or None (first step);
         exitflag (B,) int32 or None.  Returns ``planes``."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+        st = _lib.stream_handle(stream, self.device)
         _lib.fleet_points_device(xinit, self.points, z_prev, exitflag, self.heading, self.offset, self.height, stream=st)
         _lib.fleet_planes_device(self.points, r_body, self.planes, self.K, self.range, self.slot0, stream=st)
         return self.planes

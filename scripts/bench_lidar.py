@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Throughput of the lidar chain on one GPU: the scan (rmpc_lidar_scan_device), the per-stage seeds
 (rmpc_plan_points_device) and the free-space decomposition (rmpc_free_space_device), R = 64 rays, N = 10 stages,
-B = 256 and 4096 robots, K = 1 and 4 planes, in two worlds: the store of examples/fleet_store_lidar.py (41 x 41 cells of
-0.45 m) and a 128 x 128 store (0.15 m cells), both merged into boxes by boxes_from_grid.
+B = 256 and 4096 robots, K = 1 and 4 planes, in two worlds: the examples' store (robot_mpcs_amd/store.py: 41 x 41
+cells of 0.45 m) and a 128 x 128 store (0.15 m cells), both merged into boxes by boxes_from_grid.
 
   - times are medians of --reps event-timed launches (each synchronised), after one warm-up launch;
   - rays/s and box tests/s of the scan (B R and B R nbox over its time);
@@ -53,13 +53,15 @@ def main():
     from robot_mpcs_amd import _lib
     from robot_mpcs_amd.fleet import event_ms
     from robot_mpcs_amd.global_planner import shelf_map
+    from robot_mpcs_amd.store import STORE
     from robot_mpcs_amd.utils.lidar import boxes_from_grid
 
     dev = "cuda:0"
     rng = np.random.default_rng(0)
     R, N = 64, 10
     res = {}
-    for H, cell, kw in ((41, 0.45, dict(aisle=6, shelf=2, gap=5)), (128, 0.15, dict(aisle=9, shelf=4, gap=6))):
+    for H, cell, kw in ((STORE.H, STORE.cell, dict(aisle=STORE.aisle, shelf=STORE.shelf, gap=STORE.gap)),
+                        (128, 0.15, dict(aisle=9, shelf=4, gap=6))):
         raw = shelf_map(H, H, seed=0, **kw)
         x0 = -0.5 * (H - 1) * cell
         boxes_np = boxes_from_grid(raw, x0, x0, cell)

@@ -2,7 +2,7 @@
 """Time of the mapping kernels on one GPU beside the lidar chain that feeds them: ``FleetMap.mark`` (the origins
 launch and k_grid_mark: one lane per ray, global atomics) and k_grid_occupancy, against ``LidarPlanes.step`` (scan,
 seeds, free-space decomposition; N = 10, K = 4) at the same B.  The worlds and sizes of scripts/bench_lidar.py: the
-store of examples/fleet_store_lidar.py (41 x 41 cells of 0.45 m) and a 128 x 128 store (0.15 m cells), R = 64 rays of
+examples' store (robot_mpcs_amd/store.py: 41 x 41 cells of 0.45 m) and a 128 x 128 store (0.15 m cells), R = 64 rays of
 range 10, B = 256 and 4096 robots on free cells.
 
   - times are medians of --reps event-timed launches (each synchronised), after one warm-up launch;
@@ -33,7 +33,8 @@ def main():
     g.build()
     import torch
     from robot_mpcs_amd.fleet import event_ms
-    from robot_mpcs_amd.global_planner import shelf_map
+    from robot_mpcs_amd.global_planner import FREE, OCC, shelf_map
+    from robot_mpcs_amd.store import STORE
     from robot_mpcs_amd.utils.lidar import LidarPlanes, boxes_from_grid
     from robot_mpcs_amd.utils.mapping import FleetMap
 
@@ -41,7 +42,7 @@ def main():
     rng = np.random.default_rng(0)
     R, N, K = 64, 10, 4
     res = {}
-    for H, cell, max_range, kw in ((41, 0.45, 10.0, dict(aisle=6, shelf=2, gap=5)),
+    for H, cell, max_range, kw in ((STORE.H, STORE.cell, 10.0, dict(aisle=STORE.aisle, shelf=STORE.shelf, gap=STORE.gap)),
                                    (128, 0.15, 10.0, dict(aisle=9, shelf=4, gap=6))):
         raw = shelf_map(H, H, seed=0, **kw)
         x0 = -0.5 * (H - 1) * cell
@@ -65,7 +66,7 @@ def main():
             r[f"B{B}_mark_ms"] = round(event_ms(lambda: fmap.mark(pose, lp.points, lp.ranges), a.reps), 4)
             r[f"B{B}_visits"] = int(h.sum().item() + m.sum().item())
             r[f"B{B}_unique_cells"] = int(((h + m) > 0).sum().item())
-            r[f"B{B}_occupancy_ms"] = round(event_ms(lambda: fmap.occupancy(68 / 256, 253 / 256, 68 / 256), a.reps), 4)
+            r[f"B{B}_occupancy_ms"] = round(event_ms(lambda: fmap.occupancy(FREE, OCC, FREE), a.reps), 4)
         res[f"{H}x{H}"] = r
     print(json.dumps(dict(bench="mapping", device=torch.cuda.get_device_name(0), rays=R, N=N, K=K, results=res)))
 

@@ -2,13 +2,14 @@
 rmpc_grid_descend_device, FrontierGoals) against the numpy restatements of tests/test_exploration_cpu.py; the seeded
 field against rmpc_grid_fields_device, bit for bit; stream ordering; the closed loop of
 examples/fleet_store_frontier.py."""
-import importlib.util
 import math
 import os
 import sys
 
 import numpy as np
 import pytest
+
+from example_loader import load_example
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -334,13 +335,6 @@ def test_frontier_goals_chain_and_stream_ordering(rt):
 
 
 # ---- the closed loop ---------------------------------------------------------------------------------------------------
-def _example():
-    spec = importlib.util.spec_from_file_location("fleet_store_frontier", os.path.join(ROOT, "examples", "fleet_store_frontier.py"))
-    ex = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ex)
-    return ex
-
-
 MEASURED_END_STEP = 80   # MI355X, seed 0, B = 64: the first re-plan without a frontier
 
 
@@ -353,7 +347,7 @@ def test_closed_loop_fleet_explores_the_store(rt):
     MI355X, the margin the other loops use for run-to-run changes of the solver's constants.  Measured there: the run
     ends at step 80 (the ninth re-plan) with 1371 of 1371 free cells seen, none of the 1677 seen cells classified
     against the truth, no failed solve, the end link 0.590 m and the base 0.203 m from the nearest shelf."""
-    ex = _example()
+    ex = load_example("fleet_store_frontier")
     r = ex.run(B=64, seed=0, steps=3000)
     print(r)
     assert r["fused"]

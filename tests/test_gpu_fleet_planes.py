@@ -1,18 +1,16 @@
 """Fleet separation on the device (rmpc_fleet_points_device, rmpc_fleet_planes_device, NeighbourPlanes) against the
 numpy restatement of tests/test_fleet_planes_cpu.py; stream ordering; solves with mid-loop planes against the CPU
 oracle; the closed loops of examples/fleet_crossing.py with and without the neighbours."""
-import importlib.util
 import math
-import os
 
 import numpy as np
 import pytest
 
+from example_loader import load_example
 from test_fleet_planes_cpu import fleet_planes_ref, fleet_points_ref, neighbours_ref
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 
 
@@ -173,13 +171,6 @@ def test_neighbour_planes_on_a_side_stream(rt):
     assert np.array_equal(npl.planes.cpu().numpy(), ref)
 
 
-def _example():
-    spec = importlib.util.spec_from_file_location("fleet_crossing", os.path.join(ROOT, "examples", "fleet_crossing.py"))
-    ex = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ex)
-    return ex
-
-
 @pytest.mark.parametrize("robot", ["boxer", "pointRobot"])
 def test_mid_loop_planes_hip_vs_oracle(rt, robot):
     """Run the crossing loop 40 control steps, then solve the last state with its planes on the device and in the CPU
@@ -188,7 +179,7 @@ def test_mid_loop_planes_hip_vs_oracle(rt, robot):
     from robot_mpcs_amd.fleet import flags_consistent, limit_tensors, make_block, step_block
     from robot_mpcs_amd.utils.separation import NeighbourPlanes
     torch = rt["torch"]
-    ex = _example()
+    ex = load_example("fleet_crossing")
     cfg = ex.ROBOTS[robot]
     B, K = 48, 4
     rng = np.random.default_rng(1)
@@ -264,7 +255,7 @@ def test_closed_loop_crossing(rt, robot):
     1 % failed robot-steps, SHARE of the robots arrived within STEPS; the same seed with --no-neighbours brings some
     pair below 0.5 (r_i + r_j)."""
     g = LOOPS[robot]
-    ex = _example()
+    ex = load_example("fleet_crossing")
     r = ex.run(robot, B=g["B"], steps=g["STEPS"], seed=0)
     print(r)
     assert r["below_ok_mutual"] == 0, r

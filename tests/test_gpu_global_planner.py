@@ -1,18 +1,16 @@
 """The global planner on the device (rmpc_grid_*_device, rmpc_follow_path_device) against the CPU restatement of the
 reference's rules in tests/test_global_planner_cpu.py: enlarged obstacles, cost-to-go fields (bitwise on binary maps),
 paths, the batched planner, the mirror of the reference's API, the waypoint follower and a closed loop."""
-import importlib.util
 import math
-import os
 
 import numpy as np
 import pytest
 
+from example_loader import load_example
 from test_global_planner_cpu import LocalGoalRef, astar_ref, descend_ref, field_ref, inflate_ref, path_cost
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 
 
@@ -309,9 +307,7 @@ def test_closed_loop_reaches_final_goals_across_shelves(rt):
     Gate: no failed solve, clearance > 0 throughout, SHARE = 0.9 of the robots arrived by STEPS = 420 (35 % more
     steps than the last arrival)."""
     SHARE, STEPS = 0.9, 420
-    spec = importlib.util.spec_from_file_location("fleet_global_route", os.path.join(ROOT, "examples", "fleet_global_route.py"))
-    ex = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ex)
+    ex = load_example("fleet_global_route")
     r = ex.run(B=256, steps=STEPS, seed=0)
     assert r["routes"] == 256
     assert r["failed_solves"] == 0

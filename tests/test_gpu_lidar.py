@@ -2,18 +2,16 @@
 against the numpy restatement of tests/test_lidar_cpu.py and oracle/fsd_numpy.py; the refusals of the C ABI; stream
 and device selection; the closed loop of examples/fleet_store_lidar.py with and without the lidar."""
 import ctypes as C
-import importlib.util
 import math
-import os
 
 import numpy as np
 import pytest
 
+from example_loader import load_example
 from test_lidar_cpu import plan_points_ref, scan_ref
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 SWEEPS = {"full": (-math.pi, math.pi), "sector": (-math.pi + math.pi / 8, -math.pi / 8)}
 # a last-bit difference of d (the device's and numpy's sin / cos) moves the circle hit t = -b - sqrt(b^2 - c) by about
@@ -287,13 +285,6 @@ def test_device_selection_on_a_second_gpu(rt):
     assert all(np.array_equal(a, b) for a, b in zip(ref, got))
 
 
-def _example():
-    spec = importlib.util.spec_from_file_location("fleet_store_lidar", os.path.join(ROOT, "examples", "fleet_store_lidar.py"))
-    ex = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ex)
-    return ex
-
-
 def test_closed_loop_planes_keep_boxers_off_the_shelves(rt):
     """256 boxers (boxerMpc.yaml, K = 4 planes per stage, r_body = 0.6) cross a 41 x 41 store of 0.45 m cells on routes
     from the map enlarged by one cell, with the lidar planes as hard constraints of the end link
@@ -307,7 +298,7 @@ def test_closed_loop_planes_keep_boxers_off_the_shelves(rt):
     same seed without the lidar brings some end link within 0.5 r_body of a shelf (the planes, not the route, keep the
     robots off)."""
     SHARE, STEPS = 0.9, 137
-    ex = _example()
+    ex = load_example("fleet_store_lidar")
     r = ex.run(B=256, steps=STEPS, seed=0)
     print(r)
     assert r["fused"]

@@ -3,13 +3,14 @@ the numpy restatement of tests/test_mapping_cpu.py, integer for integer; contain
 of the C ABI; stream and device selection; RouteFollower.replace and replan; the closed loop of
 examples/fleet_store_explore.py."""
 import ctypes as C
-import importlib.util
 import math
 import os
 import sys
 
 import numpy as np
 import pytest
+
+from example_loader import load_example
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -387,13 +388,6 @@ def test_replan_routes_around_a_new_wall(rt):
         assert max(step) <= 1
 
 
-def _example():
-    spec = importlib.util.spec_from_file_location("fleet_store_explore", os.path.join(ROOT, "examples", "fleet_store_explore.py"))
-    ex = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ex)
-    return ex
-
-
 MEASURED_LAST_ARRIVAL = 131   # MI355X, seed 0 (the known-map loop of the same seed: 101)
 
 
@@ -406,7 +400,7 @@ def test_closed_loop_fleet_maps_the_store_and_arrives(rt):
     90 % of the robots arrive, and the last arrival by LAST = 1.35 x the measured one (the margin of the lidar test,
     for run-to-run differences in which robots meet).  MI355X measurements: DESIGN.md 14."""
     LAST = MEASURED_LAST_ARRIVAL * 1.35
-    ex = _example()
+    ex = load_example("fleet_store_explore")
     r = ex.run(B=256, steps=1200, seed=0)
     print(r)
     assert r["fused"]
