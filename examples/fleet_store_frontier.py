@@ -13,14 +13,16 @@ and at step 0 and every ``--replan-every`` steps, after the mark:
 ``FrontierGoals.replan`` (robot_mpcs_amd/utils/exploration.py) classifies the evidence, enlarges the map, finds the
 frontier -- the known free cells next to unknown space --, builds one cost-to-go field to the nearest frontier cell
 and gives every robot the route down that field.  ``frontier_cells()`` is the loop's one host read: the run ends at the
-first re-plan that finds no frontier, or after ``--steps`` control steps.
+first re-plan that finds no frontier, or after ``--steps`` control steps.  With ``--tile`` > 0 the robots are
+coordinated instead: one target per tile of that many cells, a field per target, and a greedy assignment
+of robots to targets by route cost, so that the fleet spreads over the frontier.
 
-    python examples/fleet_store_frontier.py [--robots 64] [--steps 3000] [--seed 0] [--replan-every 10]
+    python examples/fleet_store_frontier.py [--robots 64] [--steps 3000] [--seed 0] [--replan-every 10] [--tile 0]
 
 Prints one JSON line: the step at which exploration ended (null if it did not), the store's free cells and those seen,
 the seen cells and those among them classified against the true map, failed robot-steps, the least distance from the
-end link and from the base centre to any shelf box, ms per control step and ms of ``FrontierGoals.replan`` (median of
-20 event-timed calls).
+end link and from the base centre to any shelf box, ms per control step, ms of ``FrontierGoals.replan`` (median of
+20 event-timed calls) and ``tile`` (``run`` returns the same record without ``tile``).
 """
 import argparse
 import json
@@ -35,7 +37,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def run(B=64, steps=3000, seed=0, dev="cuda:0", K=4, rays=64, threshold=1.3, replan_every=10):
+def run(B=64, steps=3000, seed=0, dev="cuda:0", K=4, rays=64, threshold=1.3, replan_every=10, tile=0):
     import torch
     from robot_mpcs_amd.fleet import event_ms
     from robot_mpcs_amd.store import STORE, BoxerStore, map_errors, store_map
@@ -45,7 +47,7 @@ def run(B=64, steps=3000, seed=0, dev="cuda:0", K=4, rays=64, threshold=1.3, rep
     fleet = BoxerStore(B, seed, dev, K, rays, corner_starts(store_map(seed), B, STORE.clear_cells), rng)
     lp, tx = fleet.lp, fleet.x
     fmap = fleet.fleet_map()
-    fg = FrontierGoals(fmap, STORE.size_robot, 0.29)
+    fg = FrontierGoals(fmap, STORE.size_robot, 0.29, tile=tile)
     follower = fleet.follower(threshold, max_len=fg.max_len)
     ended, replans, frontier = None, 0, None
 
@@ -91,11 +93,12 @@ def main():
     ap.add_argument("--rays", type=int, default=64)
     ap.add_argument("--threshold", type=float, default=1.3)
     ap.add_argument("--replan-every", type=int, default=10)
+    ap.add_argument("--tile", type=int, default=0)
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build()
-    print(json.dumps(run(a.robots, a.steps, a.seed, K=a.K, rays=a.rays, threshold=a.threshold,
-                         replan_every=a.replan_every)))
+    print(json.dumps(dict(run(a.robots, a.steps, a.seed, K=a.K, rays=a.rays, threshold=a.threshold,
+                              replan_every=a.replan_every, tile=a.tile), tile=a.tile)))
 
 
 if __name__ == "__main__":

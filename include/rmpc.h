@@ -56,7 +56,8 @@ extern "C" {
  *              (rmpc_debug_step is that call at the weight 0 without out_C, results unchanged); the map from the
  *              scans, rmpc_grid_mark, rmpc_grid_mark_device, rmpc_grid_occupancy_device; exploration,
  *              RMPC_GRID_BAD_SEED, rmpc_grid_frontier_device, rmpc_grid_fields_seeded_device,
- *              rmpc_grid_descend_device. */
+ *              rmpc_grid_descend_device; coordinated exploration, RMPC_ASSIGN_MAX_ROBOTS, RMPC_ASSIGN_MAX_TARGETS,
+ *              rmpc_grid_targets_device, rmpc_grid_route_costs_device, rmpc_assign_greedy_device. */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -512,6 +513,55 @@ int rmpc_grid_occupancy_device(int H, int W, int32_t *d_hits, int32_t *d_misses,
 int rmpc_grid_frontier_device(int H, int W, const int32_t *d_hits, const int32_t *d_misses, const double *d_enlarged,
                               double occ_threshold, int nmoves, double unknown_value, double *d_plan, double *d_seed,
                               int32_t *d_count, void *stream);
+
+/* Coordinated exploration: distinct frontier targets for the robots of a fleet.  Needs no handle; every
+ * pointer is a device pointer, each call runs on the device of its first pointer and never synchronises.  The chain is
+ *   rmpc_grid_frontier_device -> rmpc_grid_targets_device -> rmpc_grid_fields_seeded_device (G = T, d_seeds = d_tseeds)
+ *   -> rmpc_grid_route_costs_device -> rmpc_assign_greedy_device -> rmpc_grid_descend_device (d_field_index = d_assign,
+ *   d_seeds = d_tseeds),
+ * and a robot left with d_assign = -1 gets RMPC_GRID_OUTSIDE from the descent.  Every result is a minimum under a strict
+ * total order, so none depends on the order in which the device's lanes meet.
+ *
+ * rmpc_grid_targets_device: one target per tile of the frontier.  The map is cut into tiles of tile x tile cells, edge
+ * tiles smaller: T = ceil(H / tile) ceil(W / tile), cell (r, c) lies in tile (r / tile) ceil(W / tile) + c / tile.  A
+ * source is a cell with d_seed [c] < +inf (d_seed [H][W]: the seed output of rmpc_grid_frontier_device).  For a tile
+ * with n sources whose rows sum to Sr and columns to Sc, the target is the source that minimises
+ * (n r - Sr)^2 + (n c - Sc)^2 in int64, the lower cell index on ties: the source nearest the centroid of the tile's
+ * sources, in exact integer arithmetic.  d_target_cells [T] int32: that cell, -1 for a tile without a source.
+ * d_tseeds [T][H][W] (may be NULL) is written completely: 0 at tile t's target, +inf on every other cell.  Refused:
+ * NULL d_seed or d_target_cells, H or W < 1, H W > RMPC_GRID_MAX_CELLS, tile < 1, T > RMPC_ASSIGN_MAX_TARGETS.
+ *
+ * rmpc_grid_route_costs_device: d_cost [B][T] fp64, the cost of robot b's route to target t, from the seeded fields
+ * d_fields [T][H][W] of d_grid [H][W].  With u = d_start_cell [b] and D = d_fields [t]: +inf when u lies outside
+ * [0, H W); D(u) when that is finite; otherwise -- the robot stands on a cell the planning grid calls occupied, the
+ * start rule of rmpc_grid_descend_device -- the least delta_m + (cost_factor d_grid [v] + D(v)), each operation
+ * rounded as written, over the moves m (the first `movement`, 4 or 8) whose v = u + m lies inside the map with
+ * d_grid [v] < occ_threshold, +inf when there is none.  Refused: NULL pointers, H or W < 1, a movement other than 4 or
+ * 8, B outside [1, RMPC_ASSIGN_MAX_ROBOTS], T outside [1, RMPC_ASSIGN_MAX_TARGETS], T H W beyond INT_MAX, a cost_factor
+ * that is negative or not finite.
+ *
+ * rmpc_assign_greedy_device: d_assign [B] int32, the target of every robot or -1, from any cost matrix d_cost [B][T]
+ * (it knows nothing of grids); d_pass [B] int32 (may be NULL): the pass, counted from 0, in which the robot was taken,
+ * or -1.  An entry is takeable when it is >= 0 and < +inf: NaN, negative and +inf entries are never taken.  The rule:
+ *  1. all robots are free;
+ *  2. a pass starts with every target available;
+ *  3. within a pass, repeatedly: among free robots x available targets the takeable pair that is least by
+ *     (cost, b, t), lexicographically, is assigned; its robot is no longer free, its target no longer available;
+ *  4. the pass ends when no target is available or no takeable pair remains;
+ *  5. if the pass assigned at least one robot and free robots remain, another pass starts;
+ *  6. otherwise the rule stops; the robots still free get -1.
+ * With B > T the targets are shared out round by round, with B <= T this is plain greedy matching.  The device takes
+ * all pairs that are the least of their row and of their column at once, which gives this rule's result bit for bit
+ * (DESIGN.md 16).  Refused: NULL d_cost or d_assign, B outside [1, RMPC_ASSIGN_MAX_ROBOTS], T outside
+ * [1, RMPC_ASSIGN_MAX_TARGETS]. */
+#define RMPC_ASSIGN_MAX_ROBOTS 4096
+#define RMPC_ASSIGN_MAX_TARGETS 1024
+int rmpc_grid_targets_device(int H, int W, const double *d_seed, int tile, int32_t *d_target_cells, double *d_tseeds,
+                             void *stream);
+int rmpc_grid_route_costs_device(int H, int W, const double *d_grid, int T, const double *d_fields, int B,
+                                 const int32_t *d_start_cell, int movement, double occ_threshold, double cost_factor,
+                                 double *d_cost, void *stream);
+int rmpc_assign_greedy_device(int B, int T, const double *d_cost, int32_t *d_assign, int32_t *d_pass, void *stream);
 
 /* Fleet separation: a separating plane per neighbour pair and stage, in the style of buffered Voronoi
  * cells, written into the lin_constrs slots of an rmpc_scene: the LinearConstraints row |a.p + d| / |a| - r_body >= 0

@@ -118,6 +118,7 @@ EXPORTED_SYMBOLS = [
     "rmpc_follow_path_device", "rmpc_lidar_scan_device", "rmpc_plan_points_device", "rmpc_fleet_points_device",
     "rmpc_fleet_planes_device", "rmpc_grid_mark_device", "rmpc_grid_occupancy_device",
     "rmpc_grid_frontier_device", "rmpc_grid_fields_seeded_device", "rmpc_grid_descend_device",
+    "rmpc_grid_targets_device", "rmpc_grid_route_costs_device", "rmpc_assign_greedy_device",
 ]
 
 _lib = None
@@ -283,6 +284,12 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_grid_fields_seeded_device.argtypes = [i, i, vp, i, vp, i, d, d, vp, vp, vp, vp]
     L.rmpc_grid_descend_device.restype = C.c_int
     L.rmpc_grid_descend_device.argtypes = [i, i, vp, i, vp, vp, i, vp, vp, i, d, d, i, vp, vp, vp]
+    L.rmpc_grid_targets_device.restype = C.c_int
+    L.rmpc_grid_targets_device.argtypes = [i, i, vp, i, vp, vp, vp]
+    L.rmpc_grid_route_costs_device.restype = C.c_int
+    L.rmpc_grid_route_costs_device.argtypes = [i, i, vp, i, vp, i, vp, i, d, d, vp, vp]
+    L.rmpc_assign_greedy_device.restype = C.c_int
+    L.rmpc_assign_greedy_device.argtypes = [i, i, vp, vp, vp, vp]
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
         raise RmpcError("rmpc_desc layout mismatch between _lib.py and librmpc_hip.so")
     want = _source_hash()
@@ -395,6 +402,8 @@ def free_space_decomposition_device(points, seeds, planes_out, max_radius: float
 GRID_MAX_CELLS = 16384
 GRID_OK, GRID_START_OCCUPIED, GRID_GOAL_OCCUPIED, GRID_OUTSIDE, GRID_TOO_LONG = 0, -1, -2, -3, -4
 GRID_BAD_MAP, GRID_NO_FIXED_POINT, GRID_BAD_SEED = -5, -6, -7
+# limits of the assignment (include/rmpc.h)
+ASSIGN_MAX_ROBOTS, ASSIGN_MAX_TARGETS = 4096, 1024
 
 
 def _grid_call(name, *args):
@@ -575,6 +584,49 @@ def grid_frontier_device(hits, misses, enlarged, plan, seed, count, occ_threshol
     H, W = int(hits.shape[0]), int(hits.shape[1])
     _grid_call("rmpc_grid_frontier_device", H, W, _ptr(hits), _ptr(misses), _ptr(enlarged), float(occ_threshold),
                int(nmoves), float(unknown_value), _ptr(plan), _ptr(seed), _ptr(count), _stream_arg(stream))
+
+
+def grid_tiles(H: int, W: int, tile: int) -> int:
+    """T = ceil(H / tile) ceil(W / tile), the tiles (and targets) of ``rmpc_grid_targets_device``."""
+    if int(tile) < 1:
+        raise ValueError("grid_tiles: need tile >= 1")
+    return -(-int(H) // int(tile)) * -(-int(W) // int(tile))
+
+
+def grid_targets_device(seed, tile: int, target_cells, tseeds=None, stream=None):
+    """seed (H, W) fp64 (the seed of ``grid_frontier_device``) -> target_cells (T,) int32 and, when given, tseeds
+    (T, H, W) fp64 with T = ``grid_tiles(H, W, tile)``: per tile of tile x tile cells the source nearest the centroid of
+    the tile's sources, -1 without one; tseeds[t] is 0 at that cell and +inf elsewhere (``rmpc_grid_targets_device``)."""
+    H, W = int(seed.shape[0]), int(seed.shape[1])
+    T = grid_tiles(H, W, tile)
+    if int(target_cells.shape[0]) != T or (tseeds is not None and tuple(tseeds.shape) != (T, H, W)):
+        raise ValueError(f"grid_targets_device: {H}x{W} cells in tiles of {int(tile)} need target_cells ({T},) and "
+                         f"tseeds ({T}, {H}, {W})")
+    _grid_call("rmpc_grid_targets_device", H, W, _ptr(seed), int(tile), _ptr(target_cells),
+               None if tseeds is None else _ptr(tseeds), _stream_arg(stream))
+
+
+def grid_route_costs_device(grid, fields, start_cell, cost, movement: int = 8, occ_threshold: float = 0.8,
+                            cost_factor: float = 3.0, stream=None):
+    """grid (H, W) fp64, fields (T, H, W) fp64, start_cell (B,) int32 -> cost (B, T) fp64: the field's value at the
+    robot's cell, from an occupied cell the best step out of it, +inf outside the map
+    (``rmpc_grid_route_costs_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    B, T = int(start_cell.shape[0]), int(fields.shape[0])
+    if tuple(fields.shape) != (T, H, W) or tuple(cost.shape) != (B, T):
+        raise ValueError(f"grid_route_costs_device: need fields ({T}, {H}, {W}) and cost ({B}, {T})")
+    _grid_call("rmpc_grid_route_costs_device", H, W, _ptr(grid), T, _ptr(fields), B, _ptr(start_cell), int(movement),
+               float(occ_threshold), float(cost_factor), _ptr(cost), _stream_arg(stream))
+
+
+def assign_greedy_device(cost, assign, passes=None, stream=None):
+    """cost (B, T) fp64 -> assign (B,) int32, the target of every robot or -1, and passes (B,) int32 or None, the pass
+    (from 0) in which it was taken or -1: greedy assignment by (cost, b, t) in passes (``rmpc_assign_greedy_device``)."""
+    B, T = int(cost.shape[0]), int(cost.shape[1])
+    if int(assign.shape[0]) != B or (passes is not None and int(passes.shape[0]) != B):
+        raise ValueError(f"assign_greedy_device: need assign and passes ({B},)")
+    _grid_call("rmpc_assign_greedy_device", B, T, _ptr(cost), _ptr(assign), None if passes is None else _ptr(passes),
+               _stream_arg(stream))
 
 
 class Solver:

@@ -1,6 +1,7 @@
 // rmpc_world.hip -- the world around the solver, on the device: the moving obstacles between two control steps, the
 // free-space decomposition, the global planner (rmpc_grid.hpp), the lidar and the fleet's separating planes
-// (rmpc_sense.hpp), the map built from the scans (rmpc_map.hpp), with their entries of the C ABI.  None of them takes a
+// (rmpc_sense.hpp), the map built from the scans (rmpc_map.hpp), the assignment of robots to frontier targets
+// (rmpc_assign.hpp), with their entries of the C ABI.  None of them takes a
 // handle: each call runs on the device its first pointer lives on, on the stream it is given.  A translation unit of
 // its own, which needs rmpc.h, the HIP runtime and the error channel only -- nothing of the solver.
 #include <hip/hip_runtime.h>
@@ -89,6 +90,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_grid.hpp"
 #include "rmpc_sense.hpp"
 #include "rmpc_map.hpp"
+#include "rmpc_assign.hpp"
 
 using namespace rmpc;
 
@@ -368,6 +370,49 @@ int rmpc_grid_frontier_device(int H, int W, const int32_t *d_hits, const int32_t
   hipLaunchKernelGGL(k_grid_frontier, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, H, W,
                      (const int *)d_hits, (const int *)d_misses, d_enlarged, occ_threshold, nmoves, unknown_value, d_plan,
                      d_seed, (int *)d_count);
+  return launch_status();
+}
+
+/* coordinated exploration (rmpc_assign.hpp) */
+int rmpc_grid_targets_device(int H, int W, const double *d_seed, int tile, int32_t *d_target_cells, double *d_tseeds,
+                             void *stream) {
+  if (!d_seed || !d_target_cells) return fail("null argument");
+  if (grid_cells_check("grid targets", H, W, false)) return -1;
+  if (tile < 1) return fail("grid targets: need tile >= 1");
+  const long long ntr = ((long long)H + tile - 1) / tile, ntc = ((long long)W + tile - 1) / tile;
+  if (ntr * ntc > RMPC_ASSIGN_MAX_TARGETS)
+    return fail("grid targets: " + std::to_string(ntr * ntc) + " tiles exceed RMPC_ASSIGN_MAX_TARGETS = " +
+                std::to_string(RMPC_ASSIGN_MAX_TARGETS));
+  if (use_device_of(d_seed)) return -1;
+  hipLaunchKernelGGL(k_grid_targets, dim3((int)(ntr * ntc)), dim3(256), 0, (hipStream_t)stream, H, W, d_seed, tile,
+                     (int)ntc, (int *)d_target_cells, d_tseeds);
+  return launch_status();
+}
+
+static int assign_sizes_check(const std::string &who, int B, int T) {
+  if (B >= 1 && B <= RMPC_ASSIGN_MAX_ROBOTS && T >= 1 && T <= RMPC_ASSIGN_MAX_TARGETS) return 0;
+  return fail(who + ": need 1 <= B <= RMPC_ASSIGN_MAX_ROBOTS = " + std::to_string(RMPC_ASSIGN_MAX_ROBOTS) +
+              " and 1 <= T <= RMPC_ASSIGN_MAX_TARGETS = " + std::to_string(RMPC_ASSIGN_MAX_TARGETS));
+}
+
+int rmpc_grid_route_costs_device(int H, int W, const double *d_grid, int T, const double *d_fields, int B,
+                                 const int32_t *d_start_cell, int movement, double occ_threshold, double cost_factor,
+                                 double *d_cost, void *stream) {
+  const char *who = "grid route costs";
+  if (!d_grid || !d_fields || !d_start_cell || !d_cost) return fail("null argument");
+  if (grid_check(H, W, movement) || assign_sizes_check(who, B, T) || grid_fields_check(who, T, H, W) ||
+      grid_cost_check(who, cost_factor) || use_device_of(d_grid))
+    return -1;
+  hipLaunchKernelGGL(k_grid_route_costs, dim3((B * T + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, T,
+                     d_fields, B, (const int *)d_start_cell, movement, occ_threshold, cost_factor, d_cost);
+  return launch_status();
+}
+
+int rmpc_assign_greedy_device(int B, int T, const double *d_cost, int32_t *d_assign, int32_t *d_pass, void *stream) {
+  if (!d_cost || !d_assign) return fail("null argument");
+  if (assign_sizes_check("assign greedy", B, T) || use_device_of(d_cost)) return -1;
+  hipLaunchKernelGGL(k_assign_greedy, dim3(1), dim3(kAssignThreads), 0, (hipStream_t)stream, B, T, d_cost,
+                     (int *)d_assign, (int *)d_pass);
   return launch_status();
 }
 
