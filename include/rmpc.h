@@ -57,7 +57,9 @@ extern "C" {
  *              scans, rmpc_grid_mark, rmpc_grid_mark_device, rmpc_grid_occupancy_device; exploration,
  *              RMPC_GRID_BAD_SEED, rmpc_grid_frontier_device, rmpc_grid_fields_seeded_device,
  *              rmpc_grid_descend_device; coordinated exploration, RMPC_ASSIGN_MAX_ROBOTS, RMPC_ASSIGN_MAX_TARGETS,
- *              rmpc_grid_targets_device, rmpc_grid_route_costs_device, rmpc_assign_greedy_device. */
+ *              rmpc_grid_targets_device, rmpc_grid_route_costs_device, rmpc_assign_greedy_device; localisation,
+ *              RMPC_MATCH_MAX_RAYS, rmpc_scan_match, rmpc_grid_edge_distance_device, rmpc_lidar_project_device,
+ *              rmpc_scan_match_device. */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -562,6 +564,76 @@ int rmpc_grid_route_costs_device(int H, int W, const double *d_grid, int T, cons
                                  const int32_t *d_start_cell, int movement, double occ_threshold, double cost_factor,
                                  double *d_cost, void *stream);
 int rmpc_assign_greedy_device(int B, int T, const double *d_cost, int32_t *d_assign, int32_t *d_pass, void *stream);
+
+/* Localisation: a pose estimate from a lidar scan and a map, by correlative scan matching (Olson 2009).
+ * Needs no handle; every pointer is a device pointer, each call runs on the device of its first pointer (d_grid,
+ * l->pose, m->pose), takes a stream and never synchronises.  The chain per control step is
+ *   rmpc_lidar_project_device (the measured ranges at the believed pose) -> rmpc_scan_match_device,
+ * against a table that rmpc_grid_edge_distance_device makes once per map.  Scores are int32 sums of table entries and
+ * the choice is a minimum under a strict total order of integers: every result is bitwise the same on every run.
+ *
+ * rmpc_grid_edge_distance_device: the likelihood field as exact integers.  Every cell of d_grid [H][W] is cut into
+ * sub x sub fine cells; fine cell (R, C) has the class d_grid [R / sub][C / sub] >= occ_threshold (a NaN is not
+ * occupied).  d_d2 [H sub][W sub] int32 = min(cap, the least (R - R')^2 + (C - C')^2 over the fine cells (R', C') of the
+ * other class inside the map), cap when there is none: the squared distance, in fine cells, to the nearest obstacle
+ * face from either side (an end point inside a shelf is penalised like one short of it).  The map's edge is not a
+ * face.  Refused: NULL pointers, H or W < 1, H W > RMPC_GRID_MAX_CELLS, sub outside [1, 8], cap outside [1, 65535], an
+ * occ_threshold that is not finite.
+ *
+ * rmpc_lidar_project_device: the rmpc_lidar of a scan with ranges as an INPUT (must not be NULL); boxes and circles are
+ * ignored.  points [b][i] = (o + t d, height) with t = ranges [b][i] and o, d formed from pose [b] exactly as
+ * rmpc_lidar_scan_device forms them: with the scan's pose and the scan's ranges these are the scan's points bit for
+ * bit, with a believed pose the scan as that pose would place it.  Refused as by rmpc_lidar_scan_device, except that
+ * boxes and circles may be NULL whatever their counts, and a NULL ranges.
+ *
+ * rmpc_scan_match_device: per robot b with the prior (x, y, th) = pose [b * pose_stride + 0 .. 2], the points
+ * [b][i][0 .. 1] = (px, py) projected at that prior and t = ranges [b][i]; every floating-point operation in the order
+ * written:
+ *  1. ray i is used iff t, px and py are finite and 0 < t < range (a hit); n = the number of used rays.  If
+ *     n < min_hits: pose_out [b] = (x, y, th), best [b] = -1, score [b] = score0 [b] = 0, used [b] = n, and the robot is
+ *     done (so is a robot with a NaN pose: its points are not finite);
+ *  2. ux = px - x, uy = py - y;
+ *  3. candidate (jth, jy, jx), 0 <= jth <= 2 nth, 0 <= jy, jx <= 2 nxy, with ith = jth - nth, iy = jy - nxy,
+ *     ix = jx - nxy, has the index k = (jth (2 nxy + 1) + jy) (2 nxy + 1) + jx; with (c, s) = rot [jth] it places the
+ *     ray's end at qx = (c ux - s uy) + (x + ix step_xy), qy = (s ux + c uy) + (y + iy step_xy): the scan turned about
+ *     the robot's own position and shifted;
+ *  4. C = floor(((qx - x0) / cell + 0.5) sub), R = floor(((qy - y0) / cell + 0.5) sub), compared as doubles: the ray
+ *     costs d2 [R][C] when 0 <= R < H sub and 0 <= C < W sub, otherwise cap (a NaN fails the test); score(k) = the int32
+ *     sum over the used rays;
+ *  5. best [b] = the candidate that is least by (score, m, k), m = ix^2 + iy^2 + ith^2: ties go to the candidate
+ *     nearest the prior, so a scan that tells nothing keeps the prior; score [b] = its score, score0 [b] the score of
+ *     the centre candidate ix = iy = ith = 0; pose_out [b] = (x + ix step_xy, y + iy step_xy, th + ith step_th).
+ * rot [2 nth + 1][2] = (cos, sin) of (j - nth) step_th comes from the caller, so that the device does only
+ * * + - / floor and a host restatement that shares the table agrees bit for bit.  d2 [H sub][W sub] is the table of
+ * rmpc_grid_edge_distance_device for the same cap (entries in [0, cap]), x0, y0, cell the map's plain frame.
+ * struct_size must equal sizeof(rmpc_scan_match); refused (-1, rmpc_last_error): NULL pointers other than score0 and
+ * used, B < 1, rays outside [1, RMPC_MATCH_MAX_RAYS], pose_stride < 3, min_hits < 1, a range that is not positive and
+ * finite, H or W < 1, H W > RMPC_GRID_MAX_CELLS, sub outside [1, 8], cap outside [1, 65535], rays cap beyond INT_MAX, a
+ * cell that is not positive and finite, x0 or y0 not finite, nxy or nth outside [0, 15], a step that is negative or
+ * not finite, or 0 while its n is positive, and B rays 3 or B pose_stride beyond INT_MAX. */
+#define RMPC_MATCH_MAX_RAYS 2048
+typedef struct rmpc_scan_match {
+  int32_t struct_size;                 /* sizeof(rmpc_scan_match) */
+  int32_t rays;                        /* R in [1, RMPC_MATCH_MAX_RAYS] */
+  const double *pose;                  /* [B][pose_stride]: the priors, x, y, heading at 0, 1, 2 */
+  const double *points;                /* [B][R][3]: the scan projected at the priors */
+  const double *ranges;                /* [B][R] */
+  double range;                        /* the scan's range (> 0): t < range is a hit */
+  int32_t pose_stride, min_hits;       /* >= 3; >= 1 */
+  const int32_t *d2;                   /* [H sub][W sub] */
+  int32_t H, W, sub, cap;
+  double x0, y0, cell;
+  int32_t nxy, nth;                    /* the lattice: (2 nxy + 1)^2 (2 nth + 1) candidates */
+  double step_xy, step_th;
+  const double *rot;                   /* [2 nth + 1][2] */
+  double *pose_out;                    /* [B][3] out */
+  int32_t *best, *score;               /* [B] out */
+  int32_t *score0, *used;              /* [B] out, may be NULL */
+} rmpc_scan_match;
+int rmpc_grid_edge_distance_device(int H, int W, const double *d_grid, double occ_threshold, int sub, int cap,
+                                   int32_t *d_d2, void *stream);
+int rmpc_lidar_project_device(int B, const rmpc_lidar *l, void *stream);
+int rmpc_scan_match_device(int B, const rmpc_scan_match *m, void *stream);
 
 /* Fleet separation: a separating plane per neighbour pair and stage, in the style of buffered Voronoi
  * cells, written into the lin_constrs slots of an rmpc_scene: the LinearConstraints row |a.p + d| / |a| - r_body >= 0

@@ -108,6 +108,25 @@ class GridMarkArgs(C.Structure):
     ]
 
 
+class ScanMatchArgs(C.Structure):
+    """Mirror of ``rmpc_scan_match`` (include/rmpc.h): one scan of B robots matched against the edge-distance table,
+    device pointers."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("rays", C.c_int32),
+        ("pose", C.c_void_p), ("points", C.c_void_p), ("ranges", C.c_void_p),
+        ("range", C.c_double),
+        ("pose_stride", C.c_int32), ("min_hits", C.c_int32),
+        ("d2", C.c_void_p),
+        ("H", C.c_int32), ("W", C.c_int32), ("sub", C.c_int32), ("cap", C.c_int32),
+        ("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double),
+        ("nxy", C.c_int32), ("nth", C.c_int32),
+        ("step_xy", C.c_double), ("step_th", C.c_double),
+        ("rot", C.c_void_p),
+        ("pose_out", C.c_void_p), ("best", C.c_void_p), ("score", C.c_void_p),
+        ("score0", C.c_void_p), ("used", C.c_void_p),
+    ]
+
+
 # every symbol include/rmpc.h declares
 EXPORTED_SYMBOLS = [
     "rmpc_version", "rmpc_source_hash", "rmpc_last_error", "rmpc_desc_size", "rmpc_create", "rmpc_destroy", "rmpc_solve_batch",
@@ -119,6 +138,7 @@ EXPORTED_SYMBOLS = [
     "rmpc_fleet_planes_device", "rmpc_grid_mark_device", "rmpc_grid_occupancy_device",
     "rmpc_grid_frontier_device", "rmpc_grid_fields_seeded_device", "rmpc_grid_descend_device",
     "rmpc_grid_targets_device", "rmpc_grid_route_costs_device", "rmpc_assign_greedy_device",
+    "rmpc_grid_edge_distance_device", "rmpc_lidar_project_device", "rmpc_scan_match_device",
 ]
 
 _lib = None
@@ -290,6 +310,12 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_grid_route_costs_device.argtypes = [i, i, vp, i, vp, i, vp, i, d, d, vp, vp]
     L.rmpc_assign_greedy_device.restype = C.c_int
     L.rmpc_assign_greedy_device.argtypes = [i, i, vp, vp, vp, vp]
+    L.rmpc_grid_edge_distance_device.restype = C.c_int
+    L.rmpc_grid_edge_distance_device.argtypes = [i, i, vp, d, i, i, vp, vp]
+    L.rmpc_lidar_project_device.restype = C.c_int
+    L.rmpc_lidar_project_device.argtypes = [i, C.POINTER(LidarArgs), vp]
+    L.rmpc_scan_match_device.restype = C.c_int
+    L.rmpc_scan_match_device.argtypes = [i, C.POINTER(ScanMatchArgs), vp]
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
         raise RmpcError("rmpc_desc layout mismatch between _lib.py and librmpc_hip.so")
     want = _source_hash()
@@ -404,6 +430,8 @@ GRID_OK, GRID_START_OCCUPIED, GRID_GOAL_OCCUPIED, GRID_OUTSIDE, GRID_TOO_LONG = 
 GRID_BAD_MAP, GRID_NO_FIXED_POINT, GRID_BAD_SEED = -5, -6, -7
 # limits of the assignment (include/rmpc.h)
 ASSIGN_MAX_ROBOTS, ASSIGN_MAX_TARGETS = 4096, 1024
+# limits of the scan match (include/rmpc.h)
+MATCH_MAX_RAYS, MATCH_MAX_N = 2048, 15
 
 
 def _grid_call(name, *args):
@@ -627,6 +655,50 @@ def assign_greedy_device(cost, assign, passes=None, stream=None):
         raise ValueError(f"assign_greedy_device: need assign and passes ({B},)")
     _grid_call("rmpc_assign_greedy_device", B, T, _ptr(cost), _ptr(assign), None if passes is None else _ptr(passes),
                _stream_arg(stream))
+
+
+def grid_edge_distance_device(grid, d2, occ_threshold: float, sub: int, cap: int, stream=None):
+    """grid (H, W) fp64 -> d2 (H sub, W sub) int32: per fine cell the squared distance, in fine cells and capped at
+    ``cap``, to the nearest fine cell of the other class (``rmpc_grid_edge_distance_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    if tuple(d2.shape) != (H * int(sub), W * int(sub)):
+        raise ValueError(f"grid_edge_distance_device: need d2 ({H * int(sub)}, {W * int(sub)})")
+    _grid_call("rmpc_grid_edge_distance_device", H, W, _ptr(grid), float(occ_threshold), int(sub), int(cap), _ptr(d2),
+               _stream_arg(stream))
+
+
+def lidar_project_device(pose, ranges, points, angle_min: float = -np.pi, angle_max: float = np.pi,
+                         max_range: float = 10.0, offset=(0.4, 0.0), height: float = 0.02, stream=None):
+    """The ranges (B, R) of a scan as points (B, R, 3) at the believed pose (B, stride >= 3), formed as the scan forms
+    them (``rmpc_lidar_project_device``)."""
+    a = lidar_args(pose, points, None, None, angle_min, angle_max, max_range, offset, height, ranges)
+    _grid_call("rmpc_lidar_project_device", int(points.shape[0]), C.byref(a), _stream_arg(stream))
+
+
+def scan_match_args(pose, points, ranges, d2, rot, pose_out, best, score, H: int, W: int, sub: int, cap: int, x0: float,
+                    y0: float, cell: float, nxy: int, step_xy: float, nth: int, step_th: float, max_range: float = 10.0,
+                    min_hits: int = 8, score0=None, used=None) -> ScanMatchArgs:
+    """The ``rmpc_scan_match`` of one scan: pose (B, stride >= 3), points (B, R, 3), ranges (B, R) fp64; d2
+    (H sub, W sub) int32; rot (2 nth + 1, 2) fp64; pose_out (B, 3) fp64; best, score and, when given, score0, used (B,)
+    int32 -- contiguous device tensors."""
+    a = ScanMatchArgs()
+    a.struct_size = C.sizeof(ScanMatchArgs)
+    a.rays = int(points.shape[1])
+    a.pose, a.points, a.ranges = pose.data_ptr(), points.data_ptr(), ranges.data_ptr()
+    a.range, a.pose_stride, a.min_hits = float(max_range), int(pose.stride(0)), int(min_hits)
+    a.d2, a.H, a.W, a.sub, a.cap = d2.data_ptr(), int(H), int(W), int(sub), int(cap)
+    a.x0, a.y0, a.cell = float(x0), float(y0), float(cell)
+    a.nxy, a.nth, a.step_xy, a.step_th = int(nxy), int(nth), float(step_xy), float(step_th)
+    a.rot = rot.data_ptr()
+    a.pose_out, a.best, a.score = pose_out.data_ptr(), best.data_ptr(), score.data_ptr()
+    a.score0 = None if score0 is None else score0.data_ptr()
+    a.used = None if used is None else used.data_ptr()
+    return a
+
+
+def scan_match_device(args: ScanMatchArgs, B: int, stream=None):
+    """Correlative scan matching of B robots (``rmpc_scan_match_device``) with the ``scan_match_args`` of the call."""
+    _grid_call("rmpc_scan_match_device", int(B), C.byref(args), _stream_arg(stream))
 
 
 class Solver:

@@ -1,9 +1,9 @@
 // rmpc_world.hip -- the world around the solver, on the device: the moving obstacles between two control steps, the
 // free-space decomposition, the global planner (rmpc_grid.hpp), the lidar and the fleet's separating planes
 // (rmpc_sense.hpp), the map built from the scans (rmpc_map.hpp), the assignment of robots to frontier targets
-// (rmpc_assign.hpp), with their entries of the C ABI.  None of them takes a
-// handle: each call runs on the device its first pointer lives on, on the stream it is given.  A translation unit of
-// its own, which needs rmpc.h, the HIP runtime and the error channel only -- nothing of the solver.
+// (rmpc_assign.hpp), localisation by scan matching (rmpc_locate.hpp), with their entries of the C ABI.  None of them
+// takes a handle: each call runs on the device its first pointer lives on, on the stream it is given.  A translation
+// unit of its own, which needs rmpc.h, the HIP runtime and the error channel only -- nothing of the solver.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -91,6 +91,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_sense.hpp"
 #include "rmpc_map.hpp"
 #include "rmpc_assign.hpp"
+#include "rmpc_locate.hpp"
 
 using namespace rmpc;
 
@@ -413,6 +414,74 @@ int rmpc_assign_greedy_device(int B, int T, const double *d_cost, int32_t *d_ass
   if (assign_sizes_check("assign greedy", B, T) || use_device_of(d_cost)) return -1;
   hipLaunchKernelGGL(k_assign_greedy, dim3(1), dim3(kAssignThreads), 0, (hipStream_t)stream, B, T, d_cost,
                      (int *)d_assign, (int *)d_pass);
+  return launch_status();
+}
+
+/* localisation (rmpc_locate.hpp) */
+static int edge_table_check(const std::string &who, int H, int W, int sub, int cap) {
+  if (grid_cells_check(who, H, W, false)) return -1;
+  if (sub < 1 || sub > 8) return fail(who + ": sub must lie in [1, 8]");
+  if (cap < 1 || cap > 65535) return fail(who + ": cap must lie in [1, 65535]");
+  return 0;
+}
+
+int rmpc_grid_edge_distance_device(int H, int W, const double *d_grid, double occ_threshold, int sub, int cap,
+                                   int32_t *d_d2, void *stream) {
+  if (!d_grid || !d_d2) return fail("null argument");
+  if (edge_table_check("grid edge distance", H, W, sub, cap)) return -1;
+  if (!std::isfinite(occ_threshold)) return fail("grid edge distance: occ_threshold must be finite");
+  if (use_device_of(d_grid)) return -1;
+  const int win = (int)ceil(sqrt((double)cap));                       // <= kEdgeMaxWin at cap <= 65535
+  const int ntile = (W * sub + kEdgeTile - 1) / kEdgeTile;
+  hipLaunchKernelGGL(k_edge_distance, dim3(H * sub * ntile), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, occ_threshold,
+                     sub, cap, win, ntile, (int *)d_d2);
+  return launch_status();
+}
+
+int rmpc_lidar_project_device(int B, const rmpc_lidar *l, void *stream) {
+  if (!l) return fail("null argument");
+  if (l->struct_size != (int)sizeof(rmpc_lidar)) return fail("rmpc_lidar.struct_size mismatch");
+  if (B < 1 || l->rays < 1) return fail("lidar project: need B >= 1 and rays >= 1");
+  if (l->pose_stride < 3) return fail("lidar project: pose_stride must be >= 3 (x, y, heading)");
+  if (l->nbox < 0 || l->ncircle < 0) return fail("lidar project: negative shape count");
+  if (!grid_fits(B, l->rays) || !grid_fits(B, l->pose_stride) || !grid_fits(l->nbox, 4) || !grid_fits(l->ncircle, 3))
+    return fail("lidar project: B*rays, B*pose_stride, nbox*4 and ncircle*3 must not exceed INT_MAX");
+  if (!(l->range > 0.0) || std::isinf(l->range)) return fail("lidar project: range must be positive and finite");
+  if (!l->pose || !l->points || !l->ranges) return fail("null argument");
+  if (use_device_of(l->pose)) return -1;
+  const int n = B * l->rays;
+  const double step = (l->angle_max - l->angle_min) / (double)l->rays;
+  hipLaunchKernelGGL(k_lidar_project, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, l->pose, l->pose_stride, B,
+                     l->rays, l->angle_min, step, l->offset_x, l->offset_y, l->height, l->ranges, l->points);
+  return launch_status();
+}
+
+int rmpc_scan_match_device(int B, const rmpc_scan_match *m, void *stream) {
+  const char *who = "scan match";
+  if (!m) return fail("null argument");
+  if (m->struct_size != (int)sizeof(rmpc_scan_match)) return fail("rmpc_scan_match.struct_size mismatch");
+  if (B < 1) return fail("scan match: need B >= 1");
+  if (m->rays < 1 || m->rays > RMPC_MATCH_MAX_RAYS)
+    return fail("scan match: need 1 <= rays <= RMPC_MATCH_MAX_RAYS = " + std::to_string(RMPC_MATCH_MAX_RAYS));
+  if (m->pose_stride < 3) return fail("scan match: pose_stride must be >= 3 (x, y, heading)");
+  if (m->min_hits < 1) return fail("scan match: need min_hits >= 1");
+  if (!grid_fits((long long)B * m->rays, 3) || !grid_fits(B, m->pose_stride))
+    return fail("scan match: B*rays*3 and B*pose_stride must not exceed INT_MAX");
+  if (!(m->range > 0.0) || std::isinf(m->range)) return fail("scan match: range must be positive and finite");
+  if (edge_table_check(who, m->H, m->W, m->sub, m->cap)) return -1;
+  if (!grid_fits(m->rays, m->cap)) return fail("scan match: rays*cap must not exceed INT_MAX");
+  if (!(m->cell > 0.0) || std::isinf(m->cell) || !std::isfinite(m->x0) || !std::isfinite(m->y0))
+    return fail("scan match: cell must be positive and finite, x0 and y0 finite");
+  if (m->nxy < 0 || m->nxy > kMatchMaxN || m->nth < 0 || m->nth > kMatchMaxN)
+    return fail("scan match: nxy and nth must lie in [0, 15]");
+  if (!(m->step_xy >= 0.0) || std::isinf(m->step_xy) || !(m->step_th >= 0.0) || std::isinf(m->step_th))
+    return fail("scan match: step_xy and step_th must be finite and >= 0");
+  if ((m->nxy > 0 && m->step_xy == 0.0) || (m->nth > 0 && m->step_th == 0.0))
+    return fail("scan match: a step of 0 needs nxy or nth of 0");
+  if (!m->pose || !m->points || !m->ranges || !m->d2 || !m->rot || !m->pose_out || !m->best || !m->score)
+    return fail("null argument");
+  if (use_device_of(m->pose)) return -1;
+  hipLaunchKernelGGL(k_scan_match, dim3(B), dim3(kMatchThreads), 0, (hipStream_t)stream, *m);
   return launch_status();
 }
 
