@@ -1615,12 +1615,21 @@ struct StepOut {
 };
 
 // v moved between lanes by a DPP control word (quad permutations, row mirrors): full-rate vector moves, no LDS
-// crossbar round trip.  All lanes of the wavefront must be active.
+// crossbar round trip.  Every lane of the 8 aligned lanes a reader belongs to must be active: the control words in use
+// (quad permutations, row_half_mirror) read only those, so the `old` operand of the move is never taken -- it is left
+// undefined, with bound_ctrl, and no instruction is spent on setting it (a zero cost two v_mov_b32 per move).
 template <int CTRL>
 __device__ __forceinline__ double dpp_move(const double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
   return __hiloint2double(hi, lo);
+}
+
+// Address of a per-lane LDS access that moves with the stage: base + k * strb bytes (k uniform, below 2^24).  A lane
+// without that access has stride 0 and a word of its own as base: one v_mad_u32_u24, no select.
+typedef __attribute__((address_space(3))) char lbyte;
+__device__ __forceinline__ ldouble *stage_ptr(ldouble *const base, const unsigned strb, const int k) {
+  return (ldouble *)((lbyte *)base + __umul24((unsigned)k, strb));
 }
 
 #include "rmpc_riccati.hpp"   // the Riccati recursion (riccati_recursion: one function per path)

@@ -207,17 +207,20 @@ struct RicCtx {
 template <class C, int LPI>
 __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldouble *const slots, const StepOut<ldouble> so) {
   constexpr int NQ = C::NQ, NX = C::NX, NW = C::NW, NP2 = RicCtx<C, LPI>::NP2, GS = FusedSlots<C>::GS;
-  const int N = ctx.N, lane = ctx.lane;
+  // (the horizon is the same in every lane: as a scalar, the stage loops count and branch in scalar registers)
+  const int N = __builtin_amdgcn_readfirstlane(ctx.N), lane = ctx.lane;
   const double h = ctx.h, h2 = ctx.h2, mu = ctx.mu, cwt = ctx.cwt;
   ldouble *const img = ctx.img;
   bool chol_ok = true;
   constexpr int n = NQ;
   constexpr int OFF_KFF = NW * NX, OFF_PT = OFF_KFF + NW, OFF_P = OFF_PT + NP2, OFF_RC = OFF_P + NX;
+  constexpr unsigned SB = GS * 8;   // bytes from a slot to the next
   static_assert(LPI == 32 && NW == n && NX == 2 * n && NX + 1 <= 8, "point-robot path: holonomic chain without slack, n <= 3");
-  static_assert(20 * NW + 48 <= RicLds<C, LPI>::LDSW, "point-robot path: work area");
-  // work area: [Qux | qu] (NW rows of 8) | Quu (NW rows of 4) | Y (NW rows of 8) | dx (2 x 8) | a word per idle lane
+  static_assert(20 * NW + 16 + 4 + 32 + NX <= RicLds<C, LPI>::LDSW, "point-robot path: work area");
+  // work area: [Qux | qu] (NW rows of 8) | Quu (NW rows of 4) | Y (NW rows of 8) | dx (2 x 8) | four zeros | a word per
+  // idle lane (and NX behind them: an idle lane's stores go to its word plus the offset the busy lanes use)
   ldouble *const aQux = img, *const aQuu = aQux + 8 * NW, *const aY = aQuu + 4 * NW, *const adx = aY + 8 * NW,
-               *const adum = adx + 16;
+               *const azero = adx + 16, *const adum = azero + 4;
   ldouble *const dummy = adum + lane;
   // -- lane (gi, gj), block position (ii, jj): the lane keeps its entries S, T, T', V of the cost-to-go (and p_i in
   //    lanes gj = 0, p_{n+i} in lanes gj = 1) in registers from stage to stage -----------------------------------------
@@ -229,54 +232,70 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
   const int tq = qlo * n - qlo * (qlo - 1) / 2 + (qhi - qlo);
   const int jme = gj == 0 ? ii : (gj == 1 ? n + ii : (gj == 2 ? 2 * n + ii : 0));   // gradient entry of lanes gj <= 2
   const double gc1 = gj == 0 ? 1.0 : (gj == 1 ? h : h2), gc2 = gj == 0 ? 0.0 : (gj == 1 ? 1.0 : h);
-  int ro[8];   // record entries of this lane
-  ro[0] = C::R_Q + tq; ro[1] = C::R_C + tq; ro[2] = C::R_DG + ii; ro[3] = C::R_DG + n + ii;
-  ro[4] = C::R_RC + jj; ro[5] = C::R_RC + n + jj; ro[6] = C::R_Q0 + jme; ro[7] = C::R_Q1 + jme;
+  // Record entries of this lane, as four pairs at a fixed distance: (Q, C) at tq, the diagonal entries (DG_i, DG_{n+i}),
+  // the defect (rc_j, rc_{n+j}), (q0, q1) at jme.  Every access of the stage loops is base + k * stride with a per-lane
+  // base and stride set here, once: a lane whose block position takes no diagonal entry, or no defect entry, reads the
+  // zeros of the work area with stride 0 -- the same 0.0 into the same operation as a select would give, without the
+  // select -- and a lane without a store writes to its dummy word with stride 0.
+  static_assert(n + 1 <= 4, "point-robot path: zeros of the work area");
+  constexpr int DQC = C::R_C - C::R_Q, DQ01 = C::R_Q1 - C::R_Q0;
+  ldouble *const rQ = slots + C::R_Q + tq, *const rG = slots + C::R_Q0 + jme;
+  ldouble *const rD = gdiag ? slots + C::R_DG + ii : azero, *const rR = gj < n ? slots + C::R_RC + jj : azero;
+  const unsigned strD = gdiag ? SB : 0u, strR = gj < n ? SB : 0u;
+  unsigned strU = SB;   // (every lane: kept in a vector register like the others, so that these addresses are one multiply-add too)
+  asm volatile("" : "+v"(strU));
   ldouble *const dUq = gon ? aQux + ii * 8 + jj : dummy, *const dUv = gon ? aQux + ii * 8 + n + jj : dummy,
                *const dUu = gon ? aQuu + ii * 4 + jj : dummy;
   ldouble *const dqu = (gval && gj == 2) ? aQux + ii * 8 + NX : dummy;   // gradient of u_i (q_i, v_i stay in registers)
   const bool rcw = lane < n;   // lanes (0, jj) put the defect of the stage into the image
+  ldouble *const wRC = rcw ? slots + OFF_RC + lane : dummy;
+  const unsigned strRC = rcw ? SB : 0u;
   const int myrow = gj == 1 ? n + ii : ii;   // row of [P | p] whose p entry this lane forms (lanes gj = 0, 1)
   // where the lane's entries of the new cost-to-go go in the image of the stage (packed upper triangle; p)
-  const int sS = (gon && ii <= jj) ? OFF_PT + ric_tri<NX>(ii, jj) : -1, sT = gon ? OFF_PT + ric_tri<NX>(ii, n + jj) : -1,
-            sV = (gon && ii <= jj) ? OFF_PT + ric_tri<NX>(n + ii, n + jj) : -1, sp_ = (gval && gj <= 1) ? OFF_P + myrow : -1;
+  const bool wST = gon && ii <= jj, wp = gval && gj <= 1;
+  ldouble *const wS = wST ? slots + OFF_PT + ric_tri<NX>(ii, jj) : dummy, *const wT = gon ? slots + OFF_PT + ric_tri<NX>(ii, n + jj) : dummy,
+               *const wV = wST ? slots + OFF_PT + ric_tri<NX>(n + ii, n + jj) : dummy, *const wP = wp ? slots + OFF_P + myrow : dummy;
+  const unsigned strST = wST ? SB : 0u, strT = gon ? SB : 0u, strP = wp ? SB : 0u;
   // -- phase B: gain column of this lane (NX: the gradient column) ---------------------------------------------------
   const int bc = lane <= NX ? lane : 0;
   ldouble *const dY = lane <= NX ? aY + bc : dummy;
   const int ystr = lane <= NX ? 8 : 0;
-  const int koff = lane < NX ? lane : (lane == NX ? OFF_KFF : -1), kstr = lane < NX ? NX : (lane == NX ? 1 : 0);
-  double rn[8];
+  const int koff = lane < NX ? lane : OFF_KFF, kstr = lane < NX ? NX : (lane == NX ? 1 : 0);
+  ldouble *wK[NW];   // the lane's column of K (lanes < NX: entries NX apart), kff (lane NX: consecutive)
 #pragma unroll
-  for (int u = 0; u < 8; u++) rn[u] = slots[(size_t)(N - 1) * GS + ro[u]];
+  for (int i = 0; i < NW; i++) wK[i] = lane <= NX ? slots + koff + i * kstr : dummy;
+  const unsigned strK = lane <= NX ? SB : 0u;
+  if (lane < 4) azero[lane] = 0.0;
+  WSYNC();
+  double rn[8];   // record of the stage at hand; the next stage's is requested into it once phase A has used it
+  rn[0] = stage_ptr(rQ, strU, (N - 1))[0]; rn[1] = stage_ptr(rQ, strU, (N - 1))[DQC];
+  rn[2] = stage_ptr(rD, strD, N - 1)[0]; rn[3] = stage_ptr(rD, strD, N - 1)[n];
+  rn[4] = stage_ptr(rR, strR, N - 1)[0]; rn[5] = stage_ptr(rR, strR, N - 1)[n];
+  rn[6] = stage_ptr(rG, strU, (N - 1))[0]; rn[7] = stage_ptr(rG, strU, (N - 1))[DQ01];
   double S = 0.0, T = 0.0, U = 0.0, V = 0.0, p1 = 0.0, p2 = 0.0;   // P = 0, p = 0 behind the last stage
   WSYNC();
   RicStamps rst;
   rst.start();
   for (int k = N - 1; k >= 0; k--) {
-    ldouble *const slot = slots + (size_t)k * GS;   // record of stage k (in registers by now); becomes its image
-    double rc_[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) rc_[u] = rn[u];
-    {
-      const int kn = k > 0 ? k - 1 : 0;
-#pragma unroll
-      for (int u = 0; u < 8; u++) rn[u] = slots[(size_t)kn * GS + ro[u]];   // arrives while this stage is computed
-    }
+    // (slot k: the record of stage k, in registers by now; becomes its image)
     // ---- phase A: the blocks of [A|B]^T P [A|B] at (ii, jj); Qxx stays in registers --------------------------------
-    const double rcj = gj < n ? rc_[4] : 0.0, rcnj = gj < n ? rc_[5] : 0.0;
+    const double rcj = rn[4], rcnj = rn[5];   // (0.0 in the lanes gj >= n)
     const double tv = h * S + T, tu = h2 * S + h * T, bv = h * U + V, bu = h2 * U + h * V;
-    const double qq = S + (rc_[0] - cwt * rc_[1]);
+    const double qq = S + (rn[0] - cwt * rn[1]);
     const double vq = h * S + U;
-    const double vv = (h * (h * S + (T + U)) + V) + (gdiag ? rc_[2] : 0.0);
+    double vv = (h * (h * S + (T + U)) + V) + rn[2];   // (the diagonal entries: 0.0 off the diagonal)
+    asm volatile("" : "+v"(vv));   // formed here, not where phase C takes it: the record's registers are free for the next stage's
     const double uq = h2 * S + h * U, uv = h2 * tv + h * bv;
-    const double uu = (h2 * tu + h * bu) + (gdiag ? rc_[3] : 0.0);
+    const double uu = (h2 * tu + h * bu) + rn[3];
     *dUq = uq; *dUv = uv; *dUu = uu;
     // g = P rc + p: the group's partial products, summed over its lanes (gj < n <= 3: one quad)
     const double g1 = p1 + dpp_sum4(S * rcj + T * rcnj), g2 = p2 + dpp_sum4(U * rcj + V * rcnj);
-    const double gme = (rc_[6] - mu * rc_[7]) + (gc1 * g1 + gc2 * g2);   // gradient entry q_i / v_i / u_i (gj = 0, 1, 2)
+    const double gme = (rn[6] - mu * rn[7]) + (gc1 * g1 + gc2 * g2);   // gradient entry q_i / v_i / u_i (gj = 0, 1, 2)
     *dqu = gme;
-    *(rcw ? slot + OFF_RC + lane : dummy) = rc_[4];
-    *(rcw ? slot + OFF_RC + n + lane : dummy) = rc_[5];
+    {
+      ldouble *const w = stage_ptr(wRC, strRC, k);
+      w[0] = rn[4]; w[n] = rn[5];
+    }
     WSYNC();
     rst(1);
     // ---- phase B: Cholesky of Quu (every lane), Y = L^-1 [Qux | qu] (one column per lane) ------------------------------
@@ -289,6 +308,17 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
 #pragma unroll
       for (int i = 0; i < NW; i++) colv[i] = aQux[i * 8 + bc];
       __builtin_amdgcn_sched_barrier(0);
+      // The record of the next stage (stage k - 1) is requested here: phase A, above the scheduling barrier, has taken
+      // every entry of this stage's, so it arrives in the same registers -- no copy from a prefetch buffer -- behind the
+      // operands of the factorisation and long before the next phase A.  (Stage 0 requests its own slot again and
+      // nobody takes the answer.)
+      {
+        const int kn = k > 0 ? k - 1 : 0;
+        rn[0] = stage_ptr(rQ, strU, kn)[0]; rn[1] = stage_ptr(rQ, strU, kn)[DQC];
+        rn[2] = stage_ptr(rD, strD, kn)[0]; rn[3] = stage_ptr(rD, strD, kn)[n];
+        rn[4] = stage_ptr(rR, strR, kn)[0]; rn[5] = stage_ptr(rR, strR, kn)[n];
+        rn[6] = stage_ptr(rG, strU, kn)[0]; rn[7] = stage_ptr(rG, strU, kn)[DQ01];
+      }
       double L[NW][NW], invd[NW];
 #pragma unroll
       for (int j = 0; j < NW; j++) {
@@ -338,9 +368,8 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
         for (int l = i + 1; l < NW; l++) sacc -= L[l][i] * x[l];
         x[i] = sacc * invd[i];
       }
-      ldouble *const kd = koff >= 0 ? slot + koff : dummy;
 #pragma unroll
-      for (int i = 0; i < NW; i++) kd[i * kstr] = -x[i];
+      for (int i = 0; i < NW; i++) *stage_ptr(wK[i], strK, k) = -x[i];
       double sn = qq, tn_ = tv, un = vq, vn = vv, pn = gme;
 #pragma unroll
       for (int l = 0; l < NW; l++) {
@@ -350,10 +379,10 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
       S = sn; T = tn_; U = un; V = vn;
       p1 = dpp_move<0x00>(pn);   // quad_perm [0, 0, 0, 0]: p_i from lane gj = 0 of the quad
       p2 = dpp_move<0x55>(pn);   // quad_perm [1, 1, 1, 1]: p_{n+i} from lane gj = 1
-      *(sS >= 0 ? slot + sS : dummy) = sn;
-      *(sT >= 0 ? slot + sT : dummy) = tn_;
-      *(sV >= 0 ? slot + sV : dummy) = vn;
-      *(sp_ >= 0 ? slot + sp_ : dummy) = pn;
+      *stage_ptr(wS, strST, k) = sn;
+      *stage_ptr(wT, strT, k) = tn_;
+      *stage_ptr(wV, strST, k) = vn;
+      *stage_ptr(wP, strP, k) = pn;
     }
     rst(4);
   }
@@ -363,27 +392,32 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
   const bool fA = lane < NW, fB = lane >= NW && lane < NW + NX, fC = lane >= NW + NX && lane < NW + 2 * NX;
   const int fi = fA ? lane : (fB ? lane - NW : (fC ? lane - NW - NX : 0));   // entry of dw / nu+ / dx+
   const int fw = fC ? (fi < n ? fi : fi - n) : fi;                             // the entry of dw a dx+ lane needs
-  const int foff = fB ? OFF_P + fi : OFF_KFF + fw;
-  int frow[NX];
+  // (every lane reads a row of the image, idle lanes that of lane 0: the image addresses are slot + a per-lane constant)
+  const ldouble *const imoff = slots + (fB ? OFF_P + fi : OFF_KFF + fw), *const imrc = slots + OFF_RC + fi;
+  const ldouble *imrow[NX];
 #pragma unroll
-  for (int j = 0; j < NX; j++) frow[j] = fB ? OFF_PT + ric_tri<NX>(fi, j) : fw * NX + j;
+  for (int j = 0; j < NX; j++) imrow[j] = slots + (fB ? OFF_PT + ric_tri<NX>(fi, j) : fw * NX + j);
   const int fx1 = fi < n ? n + fi : fi;
   const double fca = fi < n ? h : 0.0, fcb = fi < n ? h2 : h;
-  const int dzslot = fA ? NX + lane : fi;
+  // the lane's stores: dz (dw of lanes fA, dx of lanes fC), nu+ (lanes fB), dx+ (lanes fC, into the other half of adx)
+  ldouble *const wdz = (fA || fC) ? so.dz + (fA ? NX + lane : fi) : dummy, *const wnu = fB ? so.nunew + fi : dummy;
+  const unsigned strdz = (fA || fC) ? SB : 0u, strnu = fB ? SB : 0u;
+  ldouble *const wdx[2] = {fC ? adx + 8 + fi : dummy, fC ? adx + fi : dummy};   // by the parity of the stage
   // (dx through the crossbar -- ds_bpermute, no store / ordering point / read-back, the image rows requested a stage
   //  ahead -- was measured slower: 16 crossbar instructions per stage cost more LDS issue than the exchange saves,
   //  2.85 -> 2.75 M solves/s on cfg2 with four batches in flight)
   if (lane < 16) adx[lane] = 0.0;
-  for (int k = 0; k < N; k++) {
-    const ldouble *const im = slots + (size_t)k * GS;
-    const ldouble *const dxc = adx + 8 * (k & 1);
-    ldouble *const dxn = adx + 8 * ((k & 1) ^ 1);
+  // One stage; par = k & 1 picks the half of adx that holds dx (the other half takes dx+).  The stage loop runs two stages
+  // per turn, so that par is a constant of each copy, the second copy's image addresses are the first's plus a constant,
+  // and nothing is selected or rebuilt per stage.  The last stage's dx+ goes to adx like every other (nobody reads it).
+  auto fwd = [&](const int k, const int par, const bool first) __attribute__((always_inline)) {
+    const ldouble *const dxc = adx + 8 * par;
     // (the lane's row of the image does not depend on dx: requested before the ordering point, it arrives with it)
     double rowv[NX];
 #pragma unroll
-    for (int j = 0; j < NX; j++) rowv[j] = im[frow[j]];
-    double sacc = im[foff];
-    const double rcv = im[OFF_RC + fi];
+    for (int j = 0; j < NX; j++) rowv[j] = imrow[j][k * GS];
+    double sacc = imoff[k * GS];
+    const double rcv = imrc[k * GS];
     WSYNC();
     double dxv[NX];
 #pragma unroll
@@ -392,15 +426,22 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
     __builtin_amdgcn_sched_barrier(0);   // (the image of the stage is read before its step is stored over it)
 #pragma unroll
     for (int j = 0; j < NX; j++) sacc += rowv[j] * dxv[j];
-    *((fA || fC) ? so.dz + dzslot + (size_t)k * GS : dummy) = fA ? sacc : d0;
-    *((fB && k >= 1) ? so.nunew + fi + (size_t)k * GS : dummy) = sacc;
+    *stage_ptr(wdz, strdz, k) = fA ? sacc : d0;
+    if (!first) *stage_ptr(wnu, strnu, k) = sacc;   // (no nu+ of stage 0: x_0 is given)
     double sx = rcv;
     sx += d0;
     sx += fca * d1;
     sx += fcb * sacc;
-    *((fC && k < N - 1) ? dxn + fi : dummy) = sx;
+    *wdx[par] = sx;
     rst(6);
+  };
+  fwd(0, 0, true);
+  int k = 1;
+  for (; k + 1 < N; k += 2) {
+    fwd(k, 1, false);
+    fwd(k + 1, 0, false);
   }
+  if (k < N) fwd(k, 1, false);
   rst.flush(lane);
   return true;
 }
