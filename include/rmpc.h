@@ -151,8 +151,8 @@ typedef struct rmpc_desc {
 typedef struct rmpc_handle rmpc_handle;
 
 int rmpc_version(void);
-/* sha256 (first 16 hex digits) of the sources this binary was built from (csrc/rmpc_kernels.hip,
- * csrc/rmpc_model.hpp, csrc/rmpc_spec_gen.hpp, include/rmpc.h), embedded by __graft_entry__.build(); the Python binding
+/* sha256 (first 16 hex digits) of the sources this binary was built from (the files listed in
+ * csrc/sources.txt, this header among them), embedded by __graft_entry__.build(); the Python binding
  * refuses a library whose hash differs from the sources next to it. */
 const char *rmpc_source_hash(void);
 const char *rmpc_last_error(void);

@@ -1,5 +1,5 @@
 // rmpc_arm_fused.hpp -- the arms in ONE launch: a wavefront owns an instance from the first sweep to the plan.
-// Included by rmpc_kernels.hip (behind k_fused: it uses that kernel's workspace, queue and decision logic).
+// Included by rmpc_kernels.hip behind rmpc_fused.hpp (k_fused: it uses that kernel's workspace, queue and decision logic).
 //
 // Round 4.  The pass kernels of the arm (k_sweep, k_riccati, k_compact, k_step: four launches per pass) spend, per
 // instance and pass, ~70 k SIMD cycles in a sweep of 28 k instructions per lane with 420 B of scratch, 94 k in the

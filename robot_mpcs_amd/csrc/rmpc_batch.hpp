@@ -1,7 +1,7 @@
 // rmpc_batch.hpp -- the solver kernels that do not depend on a kernel variant: they work on the batch workspace (Ws)
 // whatever the robot -- pack / unpack between the ABI layout and the workspace, k_init, the warm-start copy, the list
 // of iterating instances, the migration to the compact workspace, the launch order of a fused launch and the scene
-// packer.  Included by rmpc_host.hip only, behind rmpc_kernels.hip (Ws, IDX, ST_ACTIVE, warm_mu, ...).
+// packer.  Included by rmpc_host.hip only, behind rmpc_kernels.hip (rmpc_solver.hpp: Ws, IDX, ST_ACTIVE, warm_mu, ...).
 #pragma once
 
 namespace rmpc {

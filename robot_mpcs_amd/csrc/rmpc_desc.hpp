@@ -15,7 +15,7 @@
 
 namespace rmpc {
 
-// rmpc_desc.ls_max <= 0 means this many step halvings.  It is the solver's kLsMax (rmpc_kernels.hip), which this
+// rmpc_desc.ls_max <= 0 means this many step halvings.  It is the solver's kLsMax (rmpc_solver.hpp), which this
 // header does not see; rmpc_host.hip sees both and asserts that they agree.
 constexpr int kDescLsMax = 25;
 

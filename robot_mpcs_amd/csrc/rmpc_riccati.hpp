@@ -1,5 +1,7 @@
 // rmpc_riccati.hpp -- block-tridiagonal Riccati recursion of one instance, the Riccati step of every kernel family
-// (k_riccati, k_fused, k_fused_arm).  Part of rmpc_kernels.hip (included there, inside namespace rmpc).
+// (k_riccati, k_fused, k_fused_arm).  Part of rmpc_kernels.hip (included there, inside namespace rmpc, ahead of the
+// kernels); needs rmpc_solver.hpp.  Opens with what only the recursion and its callers use (chol_solve, WSYNC, StepOut,
+// dpp_move, stage_ptr).
 //
 // riccati_recursion picks one path per model and kernel at compile time; each path is a function of its own:
 //   ric_point_robot           fused kernel, chains without slack (n <= 3): Schur form on the LDS slots, with its rollout
@@ -8,6 +10,60 @@
 //   ric_arm_block             pass and fused arm kernels, n = 5 .. 7 without slack: Schur form + MFMA, with its rollout
 //   ric_backward              pass kernels, every other model (generic dense form)               -> ric_rollout
 // They share the layout of the instance's LDS row (RicLds) and the per-lane constants of RicCtx.
+
+template <int NW>
+__device__ __forceinline__ void chol_solve(const double (&L)[NW][NW], const double (&invd)[NW], double (&v)[NW]) {
+  // L L^T x = v with the reciprocals of the diagonal supplied (no divisions on the chain)
+#pragma unroll
+  for (int i = 0; i < NW; i++) {
+    double s = v[i];
+#pragma unroll
+    for (int l = 0; l < i; l++) s -= L[i][l] * v[l];
+    v[i] = s * invd[i];
+  }
+#pragma unroll
+  for (int i = NW - 1; i >= 0; i--) {
+    double s = v[i];
+#pragma unroll
+    for (int l = i + 1; l < NW; l++) s -= L[l][i] * v[l];
+    v[i] = s * invd[i];
+  }
+}
+
+// LDS hand-off inside ONE wavefront: DS instructions of a wave execute in issue order, so a
+// compiler-level ordering point is all that is needed (a __syncthreads() would also drain the
+// global loads that are deliberately left in flight as the next stage's prefetch).
+#define WSYNC()                                              \
+  do {                                                       \
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   \
+    __builtin_amdgcn_wave_barrier();                         \
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
+  } while (0)
+
+// where the recursion leaves the step: dz[slot * SS + k * KS], nunew likewise (pointers advanced to the instance)
+template <class RP = gdouble>
+struct StepOut {
+  RP *dz, *nunew;
+  size_t SS, KS;
+};
+
+// v moved between lanes by a DPP control word (quad permutations, row mirrors): full-rate vector moves, no LDS
+// crossbar round trip.  Every lane of the 8 aligned lanes a reader belongs to must be active: the control words in use
+// (quad permutations, row_half_mirror) read only those, so the `old` operand of the move is never taken -- it is left
+// undefined, with bound_ctrl, and no instruction is spent on setting it (a zero cost two v_mov_b32 per move).
+template <int CTRL>
+__device__ __forceinline__ double dpp_move(const double v) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+
+// Address of a per-lane LDS access that moves with the stage: base + k * strb bytes (k uniform, below 2^24).  A lane
+// without that access has stride 0 and a word of its own as base: one v_mad_u32_u24, no select.
+typedef __attribute__((address_space(3))) char lbyte;
+__device__ __forceinline__ ldouble *stage_ptr(ldouble *const base, const unsigned strb, const int k) {
+  return (ldouble *)((lbyte *)base + __umul24((unsigned)k, strb));
+}
 
 #ifdef RMPC_RIC_STAMPS
 // development aid: cycles per phase of the recursion, summed over the wavefronts of all launches

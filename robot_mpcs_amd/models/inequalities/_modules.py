@@ -4,7 +4,7 @@ The reference resolves the YAML ``constraints`` list to classes by name
 (``getattr(robotmpcs.models.inequalities, name)``, ``InequalityManager.py:17-21``)
 and asks each for its row count and its ``paramMap`` entries.  Here every plug-in
 is ONE row of ``SPECS``: the HIP kernel kind (``rmpc.h`` ``RMPC_MOD_*``; the
-arithmetic lives in ``csrc/rmpc_kernels.hip``), the number of rows and the
+arithmetic lives in ``csrc/rmpc_sweep.hpp``), the number of rows and the
 parameter entries in registration order.  A class per YAML name is generated from
 the table so that the lookup by name -- and its ``AttributeError`` for unknown
 names -- stays what users of the reference expect.

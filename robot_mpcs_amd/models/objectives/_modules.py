@@ -5,7 +5,7 @@
                        module; the redundant ``for j in range(N)`` of the reference multiplies the term
                        by N -- kept                                                    constraint_avoidance.py:22-31
 
-Each plug-in only contributes parameter entries here; the arithmetic is in csrc/rmpc_kernels.hip.
+Each plug-in only contributes parameter entries here; the arithmetic is in csrc/rmpc_sweep.hpp.
 """
 from robot_mpcs_amd.models.mpcBase import ModelContext, ParamLayout
 

@@ -1,7 +1,7 @@
 // Host build of the device functions for the sanitizers (tests/host/README in DESIGN.md 6): every __device__ function
-// of csrc/rmpc_kernels.hip becomes __host__ __device__ and the gfx950 builtins get scalar stand-ins, so that the
-// single-lane functions (sweep_body, step_body: one lane = one stage) can be called from a host harness under
-// AddressSanitizer / UBSan.  Compiled with --cuda-host-only: no device pass sees these macros.
+// of csrc/rmpc_kernels.hip and the headers it includes becomes __host__ __device__ and the gfx950 builtins get scalar
+// stand-ins, so that the single-lane functions (sweep_body, step_body: one lane = one stage) can be called from a host
+// harness under AddressSanitizer / UBSan.  Compiled with --cuda-host-only: no device pass sees these macros.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>

@@ -1,8 +1,9 @@
-// Host harness for the sanitizers: the single-lane device functions of csrc/rmpc_kernels.hip -- sweep_body and
-// step_body, one call per (instance, stage) -- compiled for x86 (tests/host/host_prelude.h) and run over the pass kernels'
-// workspace layout with every array allocated on its own, so that AddressSanitizer sees an access behind any of them and
-// UBSan any undefined operation in the row, kinematics and dynamics code.  Test infrastructure only: nothing in the
-// product includes or links this file.  Build and run: tests/host/run_asan.sh.
+// Host harness for the sanitizers: the single-lane device functions behind csrc/rmpc_kernels.hip -- sweep_body
+// (rmpc_sweep.hpp) and step_body (rmpc_step.hpp), one call per (instance, stage) -- compiled for x86
+// (tests/host/host_prelude.h) and run over the pass kernels' workspace layout with every array allocated on its own, so
+// that AddressSanitizer sees an access behind any of them and UBSan any undefined operation in the row, kinematics and
+// dynamics code.  Test infrastructure only: nothing in the product includes or links this file.  Build and run:
+// tests/host/run_asan.sh.
 #include "host_prelude.h"
 #include "../../robot_mpcs_amd/csrc/rmpc_kernels.hip"   // (the device code)
 #include "../../robot_mpcs_amd/csrc/rmpc_desc.hpp"      // (build_model / build_tables)
