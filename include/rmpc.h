@@ -303,11 +303,31 @@ int rmpc_advance_device_flags(rmpc_handle *h, int B, const double *d_z_prev, con
  *  - mu_regoal > 0 (with rmpc_set_warm_start(1)): the next solve of an instance that has just taken a new goal keeps its
  *    multipliers but restarts its barrier parameter from mu_regoal; 0: plain warm start.
  *  - goal [B][3] is the array the scene (rmpc_scene.goal) points at.
- *  - counts (may be NULL): twelve int64 counters, incremented: [0] arrivals, [1] settled, [2] time-outs, [3] resets,
+ *  - counts (may be NULL): sixteen int64 counters, incremented: [0] arrivals, [1] settled, [2] time-outs, [3] resets,
  *    [4..7] the control step's exit flags (1, 2, 0, < 0), [8] sum of iters (may be NULL), [9] sum of the distance to the
  *    goal at the hand-overs in micrometres, [10] hand-overs counted in [9], [11] instances inside a run of failed
- *    solves this step, [12] resets because the robot had left its workspace, [13..15] reserved -- loop statistics
- *    without a host read per control step (64-bit: a loop may run for days). */
+ *    solves this step, [12] resets because the robot had left its workspace, [13..15] reserved (never written) -- loop
+ *    statistics without a host read per control step (64-bit: a loop may run for days).
+ *  The order of one call, per instance (tests/steady_loop_reference.py restates it in numpy):
+ *   1. the fail run: failrun + 1 when exitflag < 0, else 0 (exitflag NULL: nothing has failed; failrun NULL: the run
+ *      before this step counts as 0, so only fail_reset_after = 1 can fire).
+ *   2. RESET when a joint q_j < lo_j - 0.05 (hi_j - lo_j) or q_j > hi_j + 0.05 (hi_j - lo_j) (strict; counts[12]), or
+ *      when the solve failed and the fail run has reached fail_reset_after (>=).  A reset writes x_start to xinit and
+ *      to the state part of every stage of x0, zeroes the slack and control part of x0, and ends the fail run (0).
+ *      counts[11] counts the instances whose fail run is > 0 AFTER this, so an instance that is reset is not in it.
+ *   3. distance (end frame of the descriptor at q = x[0..n) to goal) and speed (chain: max |x[n + j]|, j < n;
+ *      diff-drive base: max(|x[6]|, |x[7]|)) are taken from the state after step 2 (x_start for a reset instance), the
+ *      goal is the one before the hand-over.  dwell + 1 is the
+ *      number of control steps on this goal.  ARRIVED: distance < tol (strict).  SETTLED: not arrived, settle_vel > 0,
+ *      dwell + 1 >= settle_min_dwell and speed < settle_vel (strict).  TIMED OUT: max_dwell > 0 and dwell + 1 >=
+ *      max_dwell.
+ *   4. any of the four hands over: cursor + 1, goal = goal_pool[b][cursor mod pool_len] (cursor itself is not
+ *      wrapped), dwell = 0; otherwise dwell + 1 is stored and xinit, x0 and goal are not written.  A hand-over is
+ *      counted ONCE, for the first that holds of: reset [3], arrived [0], settled [1], timed out [2].  counts[9] and
+ *      [10] take the hand-overs that are not resets (the distance truncated to whole micrometres).
+ *   5. mu_regoal applies to every hand-over, a reset included, unless exitflag < 0 this step (the next solve of a
+ *      failed instance keeps the barrier parameter the failed solve left for it).
+ *  [4..8] are counted only when both counts and exitflag are given; flags other than 1, 2, 0 and < 0 are in no class. */
 typedef struct rmpc_retarget {
   int32_t struct_size;            /* sizeof(rmpc_retarget) */
   int32_t pool_len;
