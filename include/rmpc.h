@@ -655,6 +655,94 @@ int rmpc_grid_edge_distance_device(int H, int W, const double *d_grid, double oc
 int rmpc_lidar_project_device(int B, const rmpc_lidar *l, void *stream);
 int rmpc_scan_match_device(int B, const rmpc_scan_match *m, void *stream);
 
+/* Timed routes: conflict-free space-time routes for a fleet, decided before anyone moves, and the
+ * follower that keeps their order.  Needs no handle; every pointer is a device pointer, each call runs on the device of
+ * its first pointer (grid, d_paths), takes a stream and never synchronises.  Everything is integer work on cells except
+ * the ranking of end cells, which compares the doubles of a field as written: every result is bitwise the same on every
+ * run.  Cell c = row * W + col; d2(c, c') = (r - r')^2 + (col - col')^2; two cells CONFLICT when d2 < sep2.
+ *
+ * rmpc_timed_plan_device: prioritised planning (cooperative A*, Silver 2005) of B robots over the window t = 0 .. T, for
+ * G priority orders at once.  grid [H][W] with the class data >= occ_threshold occupied (a NaN is free); movement 4 or
+ * 8: the planner's first `movement` moves m = (dcol, drow) in its own order; start_cell [B]; goal_index [B] into
+ * fields [Gf][H][W], the output of rmpc_grid_fields_device for goal_cells [Gf] on this grid (read only to rank end
+ * cells and to tell arrival; they must hold no NaN); orders [G][B] int32, each row a permutation of 0 .. B - 1, rank 0
+ * planned first.  Order g takes its robots in rank order; res[t] (t = 0 .. T) starts empty:
+ *  1. robot b is SKIPPED when start_cell [b] lies outside [0, H W) or goal_index [b] outside [0, Gf): status
+ *     RMPC_GRID_OUTSIDE, path all -1, arrive T + 1; it stamps nothing and blocks nobody;
+ *  2. reach[0] = {start}: the start is exempt from every test (a robot stands where it stands, as in
+ *     rmpc_grid_descend_device);
+ *  3. for t = 1 .. T, reach[t] holds c when c is free on the grid, res[t] does not hold c, for t <= lag c does not
+ *     conflict with the start of a later-ranked robot that is not skipped, and reach[t - 1] holds c (a wait) or c - m
+ *     for a move m with c - m inside the map (a diagonal move needs only its end cell free, as in the reference's A*);
+ *  4. if reach[f] is empty for a least f >= 1 the robot FAILS: status = f, te = f - 1; otherwise status = 0, te = T;
+ *  5. the end cell is the c of reach[te] that is least by (D(c), c), D = fields [goal_index [b]]; a D that is not below
+ *     +inf ranks as +inf, ties go to the lower cell;
+ *  6. p[te .. T] = the end cell; backwards from te, the predecessor of (t, c) is c itself when reach[t - 1] holds c (wait
+ *     first), otherwise c - m for the first move m in move order with c - m inside the map and in reach[t - 1].  Waiting
+ *     first at the end cell makes the arrival the earliest that can be held until T;
+ *  7. arrive [b] = the least a with p[a .. T] all equal to goal_cells [goal_index [b]], T + 1 when there is none;
+ *  8. for every t, the cells that conflict with p[t] are set in res[s] for every s in [0, T] with |s - t| <= lag.  A
+ *     failed robot stamps too, so that later ranks avoid it.
+ * Outputs: paths [G][B][T + 1], status [G][B], arrive [G][B] int32; key [G] int64 = (fails << 44) | (late << 32) |
+ * sum_arrive with fails the robots of status > 0, late those with arrive > T (skipped ones too), sum_arrive the sum of
+ * arrive (a late robot adds T + 1): the limits below keep every part inside its bits; best: one int32, the g with the
+ * least (key, g) among the rows that are permutations.  A row that is not a permutation gets RMPC_TIMED_BAD_ORDER in
+ * every status, -1 in every path cell, arrive T + 1 and the key INT64_MAX; best = -1 when no row is valid.
+ * GUARANTEE: between two robots i, j of one order that both have status 0, d2(p_i[t], p_j[s]) >= sep2 whenever
+ * |s - t| <= lag, by construction: the later-ranked of the two reached every p[t], t >= 1, through res[t], which holds
+ * the earlier one's stamps of all s within lag of t; at t = 0 it stands on its start, which the earlier one avoided
+ * during its first `lag` layers and which differs from the earlier one's start by the caller's choice (starts closer
+ * than sep2 are planned all the same: the exemption).  Vertex, swap and following conflicts are instances of it.
+ * work: a workspace of rmpc_timed_plan_work_bytes(H, W, T, G) bytes (work_bytes: its size), contents irrelevant.
+ * struct_size must equal sizeof(rmpc_timed_plan); refused (-1, rmpc_last_error): NULL pointers, H or W < 1,
+ * H W > RMPC_GRID_MAX_CELLS, a movement other than 4 or 8, B outside [1, RMPC_TIMED_MAX_ROBOTS], T outside
+ * [1, RMPC_TIMED_MAX_T], G outside [1, RMPC_TIMED_MAX_ORDERS], sep2 outside [1, RMPC_TIMED_MAX_SEP2], lag outside
+ * [1, RMPC_TIMED_MAX_LAG], Gf < 1, Gf H W or G B (T + 1) beyond INT_MAX, a workspace that is too small.
+ * rmpc_timed_plan_work_bytes returns -1 for sizes the plan refuses.
+ *
+ * rmpc_timed_follow_device: rmpc_follow_path_device for one order's d_paths [B][T + 1], one simultaneous step of all
+ * robots: d_idx_out [B] is a different buffer from d_idx_in [B] (refused otherwise), so the result does not depend on
+ * the order in which the device's lanes meet.  With i = d_idx_in [b] clamped to [0, T], robot b advances to i + 1 when
+ *  - i < T and the distance from d_pos [b * stride + 0 .. 1] to the centre of p_b[i] is <= threshold, and
+ *  - for every j != b whose path is valid and every s <= i - lag with d2(p_j[s], p_b[i + 1]) < sep2:
+ *    d_idx_in [j] >= s + lag (j has left the layers whose stamps b's next cell was planned around).
+ * d_blocked [b] (may be NULL) = the lowest j that fails the second test, -1 when none does or the first test fails.
+ * Then d_goal [b] = (centre of p_b[d_idx_out [b]], 0).  A robot whose path starts with -1 keeps its goal and its index
+ * (d_idx_out [b] = d_idx_in [b], d_blocked [b] = -1) and blocks nobody.
+ * LIVENESS: among robots that are all at their waypoints and not all at T, take one whose pending layer t = idx + 1 is
+ * least: every idx_j >= t - 1, and every blocking s has s + lag <= idx = t - 1 <= idx_j, so it is not blocked.  The
+ * plan's order is kept and cannot deadlock: a robot that runs late delays the others and does not meet them.
+ * Refused: NULL pointers other than d_blocked, d_idx_out == d_idx_in, B, T, sep2 or lag outside the plan's limits,
+ * stride < 2, W < 1, B stride beyond INT_MAX. */
+#define RMPC_TIMED_MAX_ROBOTS 1024
+#define RMPC_TIMED_MAX_T 1023
+#define RMPC_TIMED_MAX_ORDERS 1024
+#define RMPC_TIMED_MAX_SEP2 4096
+#define RMPC_TIMED_MAX_LAG 4
+#define RMPC_TIMED_BAD_ORDER (-8)       /* the row of orders is not a permutation of 0 .. B - 1 */
+typedef struct rmpc_timed_plan {
+  int32_t struct_size;                 /* sizeof(rmpc_timed_plan) */
+  int32_t H, W, movement;
+  const double *grid;                  /* [H][W] */
+  double occ_threshold;
+  int32_t B, Gf;
+  const int32_t *start_cell;           /* [B] */
+  const int32_t *goal_index;           /* [B] into fields / goal_cells */
+  const double *fields;                /* [Gf][H][W] */
+  const int32_t *goal_cells;           /* [Gf] */
+  int32_t T, sep2, lag, G;
+  const int32_t *orders;               /* [G][B] */
+  void *work; int64_t work_bytes;
+  int32_t *paths, *status, *arrive;    /* [G][B][T + 1], [G][B], [G][B] out */
+  int64_t *key;                        /* [G] out */
+  int32_t *best;                       /* one int32 out */
+} rmpc_timed_plan;
+int64_t rmpc_timed_plan_work_bytes(int H, int W, int T, int G);
+int rmpc_timed_plan_device(const rmpc_timed_plan *p, void *stream);
+int rmpc_timed_follow_device(int B, int T, const int32_t *d_paths, const int32_t *d_idx_in, int32_t *d_idx_out,
+                             const double *d_pos, int stride, int W, double x0, double y0, double cell, double threshold,
+                             int sep2, int lag, double *d_goal, int32_t *d_blocked, void *stream);
+
 /* Fleet separation: a separating plane per neighbour pair and stage, in the style of buffered Voronoi
  * cells, written into the lin_constrs slots of an rmpc_scene: the LinearConstraints row |a.p + d| / |a| - r_body >= 0
  * keeps the collision link clear of each.

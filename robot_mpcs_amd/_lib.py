@@ -127,6 +127,22 @@ class ScanMatchArgs(C.Structure):
     ]
 
 
+class TimedPlanArgs(C.Structure):
+    """Mirror of ``rmpc_timed_plan`` (include/rmpc.h): one prioritised space-time plan of B robots for G orders, device
+    pointers."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("movement", C.c_int32),
+        ("grid", C.c_void_p), ("occ_threshold", C.c_double),
+        ("B", C.c_int32), ("Gf", C.c_int32),
+        ("start_cell", C.c_void_p), ("goal_index", C.c_void_p), ("fields", C.c_void_p), ("goal_cells", C.c_void_p),
+        ("T", C.c_int32), ("sep2", C.c_int32), ("lag", C.c_int32), ("G", C.c_int32),
+        ("orders", C.c_void_p),
+        ("work", C.c_void_p), ("work_bytes", C.c_int64),
+        ("paths", C.c_void_p), ("status", C.c_void_p), ("arrive", C.c_void_p),
+        ("key", C.c_void_p), ("best", C.c_void_p),
+    ]
+
+
 # every symbol include/rmpc.h declares
 EXPORTED_SYMBOLS = [
     "rmpc_version", "rmpc_source_hash", "rmpc_last_error", "rmpc_desc_size", "rmpc_create", "rmpc_destroy", "rmpc_solve_batch",
@@ -139,6 +155,7 @@ EXPORTED_SYMBOLS = [
     "rmpc_grid_frontier_device", "rmpc_grid_fields_seeded_device", "rmpc_grid_descend_device",
     "rmpc_grid_targets_device", "rmpc_grid_route_costs_device", "rmpc_assign_greedy_device",
     "rmpc_grid_edge_distance_device", "rmpc_lidar_project_device", "rmpc_scan_match_device",
+    "rmpc_timed_plan_work_bytes", "rmpc_timed_plan_device", "rmpc_timed_follow_device",
 ]
 
 _lib = None
@@ -316,6 +333,12 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_lidar_project_device.argtypes = [i, C.POINTER(LidarArgs), vp]
     L.rmpc_scan_match_device.restype = C.c_int
     L.rmpc_scan_match_device.argtypes = [i, C.POINTER(ScanMatchArgs), vp]
+    L.rmpc_timed_plan_work_bytes.restype = C.c_int64
+    L.rmpc_timed_plan_work_bytes.argtypes = [i, i, i, i]
+    L.rmpc_timed_plan_device.restype = C.c_int
+    L.rmpc_timed_plan_device.argtypes = [C.POINTER(TimedPlanArgs), vp]
+    L.rmpc_timed_follow_device.restype = C.c_int
+    L.rmpc_timed_follow_device.argtypes = [i, i, vp, vp, vp, vp, i, i, d, d, d, d, i, i, vp, vp, vp]
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
         raise RmpcError("rmpc_desc layout mismatch between _lib.py and librmpc_hip.so")
     want = _source_hash()
@@ -699,6 +722,55 @@ def scan_match_args(pose, points, ranges, d2, rot, pose_out, best, score, H: int
 def scan_match_device(args: ScanMatchArgs, B: int, stream=None):
     """Correlative scan matching of B robots (``rmpc_scan_match_device``) with the ``scan_match_args`` of the call."""
     _grid_call("rmpc_scan_match_device", int(B), C.byref(args), _stream_arg(stream))
+
+
+# limits and the status of the timed routes (include/rmpc.h)
+TIMED_MAX_ROBOTS, TIMED_MAX_T, TIMED_MAX_ORDERS, TIMED_MAX_SEP2, TIMED_MAX_LAG = 1024, 1023, 1024, 4096, 4
+TIMED_BAD_ORDER = -8
+
+
+def timed_plan_work_bytes(H: int, W: int, T: int, G: int) -> int:
+    """bytes of workspace of ``timed_plan_device`` (``rmpc_timed_plan_work_bytes``)"""
+    L = load_library()
+    n = L.rmpc_timed_plan_work_bytes(int(H), int(W), int(T), int(G))
+    if n < 0:
+        raise RmpcError("rmpc_timed_plan_work_bytes failed: " + L.rmpc_last_error().decode())
+    return int(n)
+
+
+def timed_plan_args(grid, start_cell, goal_index, fields, goal_cells, orders, work, paths, status, arrive, key, best,
+                    movement: int = 4, occ_threshold: float = 0.8, sep2: int = 9, lag: int = 1) -> TimedPlanArgs:
+    """The ``rmpc_timed_plan`` of one plan: grid (H, W) fp64, start_cell, goal_index (B,) int32, fields (Gf, H, W) fp64,
+    goal_cells (Gf,) int32, orders (G, B) int32, work a uint8 tensor of ``timed_plan_work_bytes``, paths (G, B, T + 1),
+    status, arrive (G, B) int32, key (G,) int64, best (1,) int32 -- contiguous device tensors."""
+    a = TimedPlanArgs()
+    a.struct_size = C.sizeof(TimedPlanArgs)
+    a.H, a.W, a.movement = int(grid.shape[0]), int(grid.shape[1]), int(movement)
+    a.grid, a.occ_threshold = grid.data_ptr(), float(occ_threshold)
+    a.B, a.Gf = int(start_cell.shape[0]), int(fields.shape[0])
+    a.start_cell, a.goal_index, a.fields, a.goal_cells = (start_cell.data_ptr(), goal_index.data_ptr(), fields.data_ptr(),
+                                                          goal_cells.data_ptr())
+    a.T, a.sep2, a.lag, a.G = int(paths.shape[2]) - 1, int(sep2), int(lag), int(orders.shape[0])
+    a.orders = orders.data_ptr()
+    a.work, a.work_bytes = work.data_ptr(), int(work.numel() * work.element_size())
+    a.paths, a.status, a.arrive, a.key, a.best = (paths.data_ptr(), status.data_ptr(), arrive.data_ptr(), key.data_ptr(),
+                                                  best.data_ptr())
+    a._keep = (grid, start_cell, goal_index, fields, goal_cells, orders, work, paths, status, arrive, key, best)
+    return a
+
+
+def timed_plan_device(args: TimedPlanArgs, stream=None):
+    """One prioritised space-time plan per order (``rmpc_timed_plan_device``)."""
+    _grid_call("rmpc_timed_plan_device", C.byref(args), _stream_arg(stream))
+
+
+def timed_follow_device(paths, idx_in, idx_out, pos, goal, W: int, x0: float, y0: float, cell: float, threshold: float,
+                        sep2: int, lag: int = 1, blocked=None, stream=None):
+    """paths (B, T + 1), idx_in, idx_out (B,) int32 (two buffers); pos (B, stride >= 2) fp64; goal (B, 3) fp64; blocked
+    (B,) int32 or None: one simultaneous step of the order-preserving follower (``rmpc_timed_follow_device``)."""
+    _grid_call("rmpc_timed_follow_device", int(paths.shape[0]), int(paths.shape[1]) - 1, _ptr(paths), _ptr(idx_in),
+               _ptr(idx_out), _ptr(pos), int(pos.stride(0)), int(W), float(x0), float(y0), float(cell), float(threshold),
+               int(sep2), int(lag), _ptr(goal), None if blocked is None else _ptr(blocked), _stream_arg(stream))
 
 
 class Solver:

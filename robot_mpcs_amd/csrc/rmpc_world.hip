@@ -1,7 +1,8 @@
 // rmpc_world.hip -- the world around the solver, on the device: the moving obstacles between two control steps, the
 // free-space decomposition, the global planner (rmpc_grid.hpp), the lidar and the fleet's separating planes
 // (rmpc_sense.hpp), the map built from the scans (rmpc_map.hpp), the assignment of robots to frontier targets
-// (rmpc_assign.hpp), localisation by scan matching (rmpc_locate.hpp), with their entries of the C ABI.  None of them
+// (rmpc_assign.hpp), localisation by scan matching (rmpc_locate.hpp), the fleet's timed routes (rmpc_timed.hpp), with
+// their entries of the C ABI.  None of them
 // takes a handle: each call runs on the device its first pointer lives on, on the stream it is given.  A translation
 // unit of its own, which needs rmpc.h, the HIP runtime and the error channel only -- nothing of the solver.
 #include <hip/hip_runtime.h>
@@ -92,6 +93,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_map.hpp"
 #include "rmpc_assign.hpp"
 #include "rmpc_locate.hpp"
+#include "rmpc_timed.hpp"
 
 using namespace rmpc;
 
@@ -482,6 +484,74 @@ int rmpc_scan_match_device(int B, const rmpc_scan_match *m, void *stream) {
     return fail("null argument");
   if (use_device_of(m->pose)) return -1;
   hipLaunchKernelGGL(k_scan_match, dim3(B), dim3(kMatchThreads), 0, (hipStream_t)stream, *m);
+  return launch_status();
+}
+
+/* timed routes (rmpc_timed.hpp) */
+static int timed_common_check(const std::string &who, int B, int T, int sep2, int lag) {
+  if (B < 1 || B > RMPC_TIMED_MAX_ROBOTS)
+    return fail(who + ": need 1 <= B <= RMPC_TIMED_MAX_ROBOTS = " + std::to_string(RMPC_TIMED_MAX_ROBOTS));
+  if (T < 1 || T > RMPC_TIMED_MAX_T) return fail(who + ": need 1 <= T <= RMPC_TIMED_MAX_T = " + std::to_string(RMPC_TIMED_MAX_T));
+  if (sep2 < 1 || sep2 > RMPC_TIMED_MAX_SEP2)
+    return fail(who + ": need 1 <= sep2 <= RMPC_TIMED_MAX_SEP2 = " + std::to_string(RMPC_TIMED_MAX_SEP2));
+  if (lag < 1 || lag > RMPC_TIMED_MAX_LAG) return fail(who + ": lag must lie in [1, " + std::to_string(RMPC_TIMED_MAX_LAG) + "]");
+  return 0;
+}
+
+int64_t rmpc_timed_plan_work_bytes(int H, int W, int T, int G) {
+  if (grid_cells_check("timed plan", H, W, false)) return -1;
+  if (T < 1 || T > RMPC_TIMED_MAX_T || G < 1 || G > RMPC_TIMED_MAX_ORDERS)
+    return fail("timed plan: need 1 <= T <= RMPC_TIMED_MAX_T and 1 <= G <= RMPC_TIMED_MAX_ORDERS");
+  return (int64_t)G * timed_order_words(H, W, T) * (int64_t)sizeof(timed_word);
+}
+
+int rmpc_timed_plan_device(const rmpc_timed_plan *p, void *stream) {
+  const char *who = "timed plan";
+  if (!p) return fail("null argument");
+  if (p->struct_size != (int)sizeof(rmpc_timed_plan)) return fail("rmpc_timed_plan.struct_size mismatch");
+  if (!p->grid || !p->start_cell || !p->goal_index || !p->fields || !p->goal_cells || !p->orders || !p->work || !p->paths ||
+      !p->status || !p->arrive || !p->key || !p->best)
+    return fail("null argument");
+  if (grid_check(p->H, p->W, p->movement) || grid_cells_check(who, p->H, p->W, false) ||
+      timed_common_check(who, p->B, p->T, p->sep2, p->lag) || grid_fields_check(who, p->Gf, p->H, p->W))
+    return -1;
+  if (p->G < 1 || p->G > RMPC_TIMED_MAX_ORDERS)
+    return fail("timed plan: need 1 <= G <= RMPC_TIMED_MAX_ORDERS = " + std::to_string(RMPC_TIMED_MAX_ORDERS));
+  if (!grid_fits((long long)p->G * p->B, p->T + 1)) return fail("timed plan: G*B*(T+1) must not exceed INT_MAX");
+  const int64_t need = rmpc_timed_plan_work_bytes(p->H, p->W, p->T, p->G);
+  if (need < 0) return -1;
+  if (p->work_bytes < need)
+    return fail("timed plan: the workspace holds " + std::to_string(p->work_bytes) + " bytes, " + std::to_string(need) +
+                " are needed (rmpc_timed_plan_work_bytes)");
+  if (use_device_of(p->grid)) return -1;
+  TimedGeom q;
+  q.Wd = (p->W + 63) / 64;
+  q.L = p->H * q.Wd;
+  q.rad = 0;
+  while ((q.rad + 1) * (q.rad + 1) < p->sep2) q.rad++;
+  q.per_order = timed_order_words(p->H, p->W, p->T);
+  const size_t hist = (size_t)(p->T + 1) * q.L * sizeof(timed_word);
+  const int nt = q.L <= 64 ? 64 : (q.L <= 128 ? 128 : kTimedThreads);      // a power of two: the end cell's reduction
+  if (hist <= (size_t)kTimedHistLds)
+    hipLaunchKernelGGL(k_timed_plan<true>, dim3(p->G), dim3(nt), hist, (hipStream_t)stream, *p, q, (timed_word *)p->work);
+  else
+    hipLaunchKernelGGL(k_timed_plan<false>, dim3(p->G), dim3(nt), 0, (hipStream_t)stream, *p, q, (timed_word *)p->work);
+  hipLaunchKernelGGL(k_timed_best, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int64_t *)p->key, p->G, (int *)p->best);
+  return launch_status();
+}
+
+int rmpc_timed_follow_device(int B, int T, const int32_t *d_paths, const int32_t *d_idx_in, int32_t *d_idx_out,
+                             const double *d_pos, int stride, int W, double x0, double y0, double cell, double threshold,
+                             int sep2, int lag, double *d_goal, int32_t *d_blocked, void *stream) {
+  const char *who = "timed follow";
+  if (!d_paths || !d_idx_in || !d_idx_out || !d_pos || !d_goal) return fail("null argument");
+  if (d_idx_in == d_idx_out) return fail("timed follow: d_idx_out must not be d_idx_in");
+  if (timed_common_check(who, B, T, sep2, lag)) return -1;
+  if (stride < 2 || !grid_fits(B, stride) || W < 1) return fail("timed follow: need stride >= 2, W >= 1");
+  if (use_device_of(d_paths)) return -1;
+  hipLaunchKernelGGL(k_timed_follow, dim3(B), dim3(256), 0, (hipStream_t)stream, (const int *)d_paths, B, T,
+                     (const int *)d_idx_in, (int *)d_idx_out, d_pos, stride, W, x0, y0, cell, threshold, sep2, lag, d_goal,
+                     (int *)d_blocked);
   return launch_status();
 }
 

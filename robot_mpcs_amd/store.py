@@ -73,24 +73,34 @@ class BoxerStore:
     ``rays`` rays at its end link whose planes are the scene's ``lin_constrs`` (``lidar=False``: in an empty world) and
     its own position as its first goal.  Owns ``raw``, ``boxes`` (nbox, 4), the scenario ``sc``, ``lp``
     (``LidarPlanes``), ``goal`` (B, 3), the block ``f`` with its ``x, z, ef``, and on the device the statistics
-    ``fails``, ``ee_clear``, ``base_clear`` (B,) of the ``steps`` control steps driven so far."""
+    ``fails``, ``ee_clear``, ``base_clear`` (B,) of the ``steps`` control steps driven so far.  With ``neighbours`` > 0
+    the model has K + neighbours linear constraints: ``planes`` (B, N, K + neighbours, 4) holds the lidar's planes in
+    its first K slots (copied by ``scan``) and the fleet's separating planes (``npl``: ``NeighbourPlanes`` within
+    ``neighbour_range`` m) in the others."""
 
-    def __init__(self, B, seed, device, K, rays, start_cells, rng, lidar=True):
+    def __init__(self, B, seed, device, K, rays, start_cells, rng, lidar=True, neighbours=0, neighbour_range=3.0):
         import torch
         S = STORE
         self.B, self.K, self.rays, self.device = B, K, rays, device
         self.raw = store_map(seed)
         boxes = boxes_from_grid(self.raw, S.x0, S.y0, S.cell)
         self.boxes = dev_f64(boxes, device)
-        self.sc = sc = make_scenario("boxer", B=B, seed=seed, number_obstacles=K)
+        self.sc = sc = make_scenario("boxer", B=B, seed=seed, number_obstacles=K + neighbours)
         xinit = np.zeros((B, sc.desc["nx"]))
         xinit[:, :2] = cell_xy(start_cells, S.W, S.x0, S.y0, S.cell)
         xinit[:, 2] = rng.uniform(-math.pi, math.pi, B)
         self.lp = LidarPlanes(B, sc.desc["N"], K, boxes=boxes if lidar else None, rays=rays, offset=(S.ee_offset, 0.0),
                               device=device)
         self.goal = dev_f64(np.concatenate([xinit[:, :2], np.zeros((B, 1))], 1), device)
+        self.rad = dev_f64(np.full(B, S.r_body), device)
+        self.planes, self.npl = self.lp.planes, None
+        if neighbours > 0:
+            from .utils.separation import NeighbourPlanes
+            self.planes = torch.zeros((B, sc.desc["N"], K + neighbours, 4), dtype=torch.float64, device=device)
+            self.npl = NeighbourPlanes(B, sc.desc["N"], neighbours, range=neighbour_range, heading=1,
+                                       offset=(S.ee_offset, 0.0), slot0=K, planes=self.planes)
         self.f = f = make_block(sc.desc, sc.setup["mpc"]["weights"], B, xinit, device, goal=self.goal,
-                                r_body=dev_f64(np.full(B, S.r_body), device), lin_constrs=self.lp.planes,
+                                r_body=self.rad, lin_constrs=self.planes,
                                 **limit_tensors(*LIMITS["boxer"], B, device))
         self.x, self.z, self.ef = f["x"], f["z"], f["ef"]
         self.fails = torch.zeros((), dtype=torch.int64, device=device)
@@ -116,9 +126,15 @@ class BoxerStore:
                         device=self.device)
 
     def scan(self):
-        """``LidarPlanes.step`` at the current poses, seeded by the previous plan (before the first ``drive``: by none)"""
+        """``LidarPlanes.step`` at the current poses, seeded by the previous plan (before the first ``drive``: by none);
+        with neighbours, ``NeighbourPlanes.step`` beside it.  Returns the scene's planes."""
         first = self.steps == 0
-        return self.lp.step(self.x, None if first else self.z, None if first else self.ef)
+        z, ef = (None, None) if first else (self.z, self.ef)
+        planes = self.lp.step(self.x, z, ef)
+        if self.npl is None:
+            return planes
+        self.planes[:, :, :self.K].copy_(planes)
+        return self.npl.step(self.x, self.rad, z, ef)
 
     def drive(self):
         """One control step (``step_block``), then the statistics of the new poses.  Returns the end links' positions
