@@ -47,15 +47,34 @@ struct StepOut {
   size_t SS, KS;
 };
 
-// v moved between lanes by a DPP control word (quad permutations, row mirrors): full-rate vector moves, no LDS
-// crossbar round trip.  Every lane of the 8 aligned lanes a reader belongs to must be active: the control words in use
-// (quad permutations, row_half_mirror) read only those, so the `old` operand of the move is never taken -- it is left
-// undefined, with bound_ctrl, and no instruction is spent on setting it (a zero cost two v_mov_b32 per move).
+// v moved between lanes by a DPP control word (quad permutations, row mirrors; the row broadcast of dpp_row_bcast below):
+// full-rate vector moves, no LDS crossbar round trip.  Every lane a reader takes its value from must be active.  The quad
+// permutations and row_half_mirror read only the 8 aligned lanes the reader belongs to, the row controls (row_newbcast)
+// only the reader's 16-lane row, and the callers keep those busy together: the paths that use them run with whole
+// wavefronts or whole halves (a half that sits a call out leaves no hole in the other half's two rows).  So the `old`
+// operand of the move is never taken -- it is left undefined, with bound_ctrl, and no instruction is spent on setting it
+// (a zero cost two v_mov_b32 per move).
 template <int CTRL>
 __device__ __forceinline__ double dpp_move(const double v) {
   const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
   const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
   return __hiloint2double(hi, lo);
+}
+// v of lane L of the reader's 16-lane row, in every lane of that row (row_newbcast:L, the one control that exists as a
+// 64-bit move: one v_mov_b64_dpp).  With bound_ctrl and all rows and banks enabled `old` is never taken.
+template <int L>
+__device__ __forceinline__ double dpp_row_bcast(const double v) {
+  static_assert(L >= 0 && L < 16, "dpp_row_bcast: lane of a 16-lane row");
+  return __builtin_amdgcn_update_dpp(v, v, 0x150 + L, 0xF, 0xF, true);
+}
+// q[i][j] = v of lane 4 i + j of the reader's row, over the lower triangle from (I, J) on, row by row
+template <int I, int J, int NW>
+__device__ __forceinline__ void dpp_tri_gather(const double v, double (&q)[NW][NW]) {
+  if constexpr (I < NW) {
+    q[I][J] = dpp_row_bcast<4 * I + J>(v);
+    if constexpr (J < I) dpp_tri_gather<I, J + 1>(v, q);
+    else dpp_tri_gather<I + 1, 0>(v, q);
+  }
 }
 
 // Address of a per-lane LDS access that moves with the stage: base + k * strb bytes (k uniform, below 2^24).  A lane
@@ -253,10 +272,13 @@ struct RicCtx {
 // (ric_chain_slack_backward, kept for the chains with the slack variable) reads 78 doubles per lane and backward stage
 // and 24 per forward stage; this one reads 37 and 17 -- the block form of the arms' path (ric_arm_block) at
 // half-wavefront width:
-//   A  lane (i, j) of an n x n grid (8-lane groups) reads S, T, T', V of the cost-to-go once and forms the seven
-//      block entries of [A|B]^T P [A|B]; its eight record entries come from the stage's slot one stage ahead;
-//      g = P rc + p by DPP sums over the group, lanes j = 0, 1, 2 finish the gradient entries q_i, v_i, u_i;
-//   B  Cholesky of Quu in every lane, Y = L^-1 [Qux | qu] (a column per lane), the gains K = -L^-T Y behind it;
+//   A  lane (i, j) of an n x n grid (lane 4 i + j: a quad per row of the grid, all of it in the first 16-lane row of the
+//      instance) reads S, T, T', V of the cost-to-go once and forms the seven block entries of [A|B]^T P [A|B]; its eight
+//      record entries come from the stage's slot one stage ahead; g = P rc + p by DPP sums over the quad, lanes
+//      j = 0, 1, 2 finish the gradient entries q_i, v_i, u_i;
+//   B  Cholesky of Quu in every lane of the first row -- its entries come straight from phase A's registers by DPP row
+//      broadcast, so the factorisation runs while [Qux | qu] goes through LDS --, Y = L^-1 [Qux | qu] (a column per
+//      lane), the gains K = -L^-T Y behind it;
 //   C  [P | p] = [Qxx | qx] - Y^T [Y | y]: an entry per lane and turn, (i, j) and (j, i) the same products in the
 //      same order (Qxx is formed symmetrically): symmetric without the 0.5 (a + a^T) of the gain form.
 // The rollout forms dw, nu+ and dx+ from dx alone with one role per lane (one row of the image per lane).
@@ -273,14 +295,16 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
   constexpr unsigned SB = GS * 8;   // bytes from a slot to the next
   static_assert(LPI == 32 && NW == n && NX == 2 * n && NX + 1 <= 8, "point-robot path: holonomic chain without slack, n <= 3");
   static_assert(20 * NW + 16 + 4 + 32 + NX <= RicLds<C, LPI>::LDSW, "point-robot path: work area");
-  // work area: [Qux | qu] (NW rows of 8) | Quu (NW rows of 4) | Y (NW rows of 8) | dx (2 x 8) | four zeros | a word per
-  // idle lane (and NX behind them: an idle lane's stores go to its word plus the offset the busy lanes use)
+  // work area: [Qux | qu] (NW rows of 8) | 4 NW words, the first of them the factorisation's flag | Y (NW rows of 8) |
+  // dx (2 x 8) | four zeros | a word per idle lane (and NX behind them: an idle lane's stores go to its word plus the
+  // offset the busy lanes use)
   ldouble *const aQux = img, *const aQuu = aQux + 8 * NW, *const aY = aQuu + 4 * NW, *const adx = aY + 8 * NW,
                *const azero = adx + 16, *const adum = azero + 4;
   ldouble *const dummy = adum + lane;
   // -- lane (gi, gj), block position (ii, jj): the lane keeps its entries S, T, T', V of the cost-to-go (and p_i in
   //    lanes gj = 0, p_{n+i} in lanes gj = 1) in registers from stage to stage -----------------------------------------
-  const int gi = lane >> 3, gj = lane & 7;
+  static_assert(4 * NW <= 16 && NX + 1 <= 16, "point-robot path: block grid and gain columns in one 16-lane row");
+  const int gi = lane >> 2, gj = lane & 3;
   const bool gval = gi < n, gon = gval && gj < n;
   const int ii = gval ? gi : 0, jj = gj < n ? gj : 0;
   const bool gdiag = gon && ii == jj;
@@ -300,8 +324,7 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
   const unsigned strD = gdiag ? SB : 0u, strR = gj < n ? SB : 0u;
   unsigned strU = SB;   // (every lane: kept in a vector register like the others, so that these addresses are one multiply-add too)
   asm volatile("" : "+v"(strU));
-  ldouble *const dUq = gon ? aQux + ii * 8 + jj : dummy, *const dUv = gon ? aQux + ii * 8 + n + jj : dummy,
-               *const dUu = gon ? aQuu + ii * 4 + jj : dummy;
+  ldouble *const dUq = gon ? aQux + ii * 8 + jj : dummy, *const dUv = gon ? aQux + ii * 8 + n + jj : dummy;
   ldouble *const dqu = (gval && gj == 2) ? aQux + ii * 8 + NX : dummy;   // gradient of u_i (q_i, v_i stay in registers)
   const bool rcw = lane < n;   // lanes (0, jj) put the defect of the stage into the image
   ldouble *const wRC = rcw ? slots + OFF_RC + lane : dummy;
@@ -343,7 +366,7 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
     asm volatile("" : "+v"(vv));   // formed here, not where phase C takes it: the record's registers are free for the next stage's
     const double uq = h2 * S + h * U, uv = h2 * tv + h * bv;
     const double uu = (h2 * tu + h * bu) + rn[3];
-    *dUq = uq; *dUv = uv; *dUu = uu;
+    *dUq = uq; *dUv = uv;   // (Quu stays in registers: phase B takes it by row broadcast)
     // g = P rc + p: the group's partial products, summed over its lanes (gj < n <= 3: one quad)
     const double g1 = p1 + dpp_sum4(S * rcj + T * rcnj), g2 = p2 + dpp_sum4(U * rcj + V * rcnj);
     const double gme = (rn[6] - mu * rn[7]) + (gc1 * g1 + gc2 * g2);   // gradient entry q_i / v_i / u_i (gj = 0, 1, 2)
@@ -358,10 +381,6 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
     {
       double qw[NW][NW], colv[NW];
 #pragma unroll
-      for (int j = 0; j < NW; j++)
-#pragma unroll
-        for (int i = j; i < NW; i++) qw[i][j] = aQuu[i * 4 + j];
-#pragma unroll
       for (int i = 0; i < NW; i++) colv[i] = aQux[i * 8 + bc];
       __builtin_amdgcn_sched_barrier(0);
       // The record of the next stage (stage k - 1) is requested here: phase A, above the scheduling barrier, has taken
@@ -375,6 +394,11 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
         rn[4] = stage_ptr(rR, strR, kn)[0]; rn[5] = stage_ptr(rR, strR, kn)[n];
         rn[6] = stage_ptr(rG, strU, kn)[0]; rn[7] = stage_ptr(rG, strU, kn)[DQ01];
       }
+      __builtin_amdgcn_sched_barrier(0);   // (every read of the phase is out before the chain of the factorisation begins)
+      // Quu (lower triangle) from the lanes 4 i + j that formed it in phase A: vector moves, no LDS, so the factorisation
+      // starts here and the wait for [Qux | qu] stands behind it, before the forward substitution.  Only the first row of
+      // the instance holds Quu: the other lanes factor what their own row hands them, into their dummy words.
+      dpp_tri_gather<0, 0>(uu, qw);
       double L[NW][NW], invd[NW];
 #pragma unroll
       for (int j = 0; j < NW; j++) {
@@ -442,7 +466,11 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
     }
     rst(4);
   }
+  // the flag of the first row (its lanes agree: the same Quu) for all lanes of the instance, once, through a word of the
+  // work area and the ordering point that ends the loop anyway
+  *(lane == 0 ? aQuu : dummy) = chol_ok ? 1.0 : 0.0;
   WSYNC();
+  chol_ok = aQuu[0] != 0.0;
   if (!chol_ok) return false;
   // ---- rollout: dw = kff + K dx, nu+ = p + P dx, dx+ = rc + [A|B][dx; dw], one ordering point per stage ---------------
   const bool fA = lane < NW, fB = lane >= NW && lane < NW + NX, fC = lane >= NW + NX && lane < NW + 2 * NX;
@@ -461,7 +489,9 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
   ldouble *const wdx[2] = {fC ? adx + 8 + fi : dummy, fC ? adx + fi : dummy};   // by the parity of the stage
   // (dx through the crossbar -- ds_bpermute, no store / ordering point / read-back, the image rows requested a stage
   //  ahead -- was measured slower: 16 crossbar instructions per stage cost more LDS issue than the exchange saves,
-  //  2.85 -> 2.75 M solves/s on cfg2 with four batches in flight)
+  //  2.85 -> 2.75 M solves/s on cfg2 with four batches in flight; dx kept in the registers of its lanes and handed round
+  //  by DPP row moves -- row_newbcast, row_shl:n, no LDS at all -- took 1.7 k cycles off the call, but its gain on the
+  //  headline stayed inside the spread of the runs: DESIGN.md 5.1)
   if (lane < 16) adx[lane] = 0.0;
   // One stage; par = k & 1 picks the half of adx that holds dx (the other half takes dx+).  The stage loop runs two stages
   // per turn, so that par is a constant of each copy, the second copy's image addresses are the first's plus a constant,
