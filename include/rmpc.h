@@ -59,7 +59,8 @@ extern "C" {
  *              rmpc_grid_descend_device; coordinated exploration, RMPC_ASSIGN_MAX_ROBOTS, RMPC_ASSIGN_MAX_TARGETS,
  *              rmpc_grid_targets_device, rmpc_grid_route_costs_device, rmpc_assign_greedy_device; localisation,
  *              RMPC_MATCH_MAX_RAYS, rmpc_scan_match, rmpc_grid_edge_distance_device, rmpc_lidar_project_device,
- *              rmpc_scan_match_device. */
+ *              rmpc_scan_match_device; moving obstacles, RMPC_TRACK_MAX_RAYS, RMPC_TRACK_MAX_TRACKS,
+ *              RMPC_TRACK_MAX_DET, rmpc_tracks, rmpc_lidar_tracks_device. */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -654,6 +655,75 @@ int rmpc_grid_edge_distance_device(int H, int W, const double *d_grid, double oc
                                    int32_t *d_d2, void *stream);
 int rmpc_lidar_project_device(int B, const rmpc_lidar *l, void *stream);
 int rmpc_scan_match_device(int B, const rmpc_scan_match *m, void *stream);
+
+/* Moving obstacles: a multi-target tracker per robot, from one lidar scan to the obst_dyn array a scene
+ * points at (rmpc_scene.obst_dyn, predicted by the solver per stage at dt k).  Needs no handle; every pointer is a
+ * device pointer, the call runs on the device of its first pointer (points), takes a stream and never synchronises.  The
+ * chain per control step is
+ *   rmpc_lidar_scan_device (or rmpc_lidar_project_device) -> [rmpc_lidar_scan_device of the static world alone]
+ *   -> rmpc_plan_points_device (d_z_prev = NULL, N = 1: the sensor origins) -> rmpc_lidar_tracks_device.
+ * The kernel evaluates + - * / sqrt on doubles in the order written (no sin / cos, no contraction) and every choice is
+ * a minimum under a strict total order: every result is bitwise the same on every run and equals the numpy restatement
+ * (tests/tracking_reference.py).  The rules are the project's own.  Per robot b with p_i = points [b][i][0 .. 1],
+ * t_i = ranges [b][i], o = origin [b][0 .. 1], R = rays, T = n_tracks:
+ *  1. ray i is MOVING iff t_i < static_ranges [b][i] - margin, or, when static_ranges is NULL, iff t_i < range (a NaN
+ *     compares false);
+ *  2. the predecessor of ray i is i - 1, of ray 0 it is R - 1 when closed != 0 (a full sweep) and none otherwise; it
+ *     LINKS when it is moving and (dx dx + dy dy) <= gap gap, d = p_i - p_pred.  Ray i STARTS a segment iff it is moving
+ *     and its predecessor does not link; a closed sweep whose rays are all moving and none of which starts takes ray 0
+ *     as its start.  A segment runs from its start to the ray before the next start or the next ray that is not
+ *     moving, around the seam when closed.  Segments are ordered by start ray; counts [b][0] = their number.  A segment
+ *     is dropped when it has fewer than min_rays rays, or when max_extent > 0 and the squared distance from its first
+ *     to its last point exceeds max_extent max_extent; the first RMPC_TRACK_MAX_DET that remain are the detections,
+ *     counts [b][1] = their number;
+ *  3. a detection's centre, the circle of the known radius through its n points: m = (the sum of the points in segment
+ *     order) / n; w = m - o, c = m + radius (w / sqrt(wx wx + wy wy)); then four times: per point q = p_i - c,
+ *     r = sqrt(qx qx + qy qy), u = q / r, e = r - radius, the sums a11 += ux ux, a12 += ux uy, a22 += uy uy, gx += ux e,
+ *     gy += uy e in segment order from 0; a11 += 1e-3, a22 += 1e-3, D = a11 a22 - a12 a12,
+ *     cx += (a22 gx - a12 gy) / D, cy += (a11 gy - a12 gx) / D.  No case split for n = 1 or 2.  det [b][k] = the centre
+ *     z_k of detection k, (0, 0) in the unused rows;
+ *  4. slot j is LIVE iff age [b][j] > 0.  Predict: pred_j = p_j + v_j dt.  Associate: the pairs (live j, k) with
+ *     s = (dx dx + dy dy) <= gate gate, d = pred_j - z_k, are visited in ascending (s, j, k) and a pair is taken when
+ *     neither side has been.  A matched track: res = z - pred, p = pred + alpha res, v = v + (beta res) / dt, each
+ *     component of v then limited to [-v_max, v_max] when v_max > 0; age + 1 (held at INT32_MAX), miss = 0.  An
+ *     unmatched live track coasts: p = pred, miss + 1 (held at INT32_MAX), and age = 0 (the slot is free, its other
+ *     words stay) when miss > max_miss.  Births: the unmatched detections in their order take the lowest free slots,
+ *     those freed in this call included, with p = z, v = 0, age = 1, miss = 0; detections that find none are lost;
+ *  5. the CONFIRMED tracks (age >= confirm) ordered by ((dx dx + dy dy), j), d = p_j - o (a NaN distance counts as
+ *     +inf): the first n_out become obst_dyn [b][row] = (px, py, 0, vx, vy, 0, 0, 0, 0), every further row is
+ *     (park_x, park_y, 0, 0, 0, 0, 0, 0, 0).  counts [b][2] = the live tracks, counts [b][3] = the confirmed ones, both
+ *     after the call.
+ * track, age and miss are the filter's state, zero-filled by the caller before the first call and carried between
+ * calls.  A robot's rows are written by its own workgroup alone; there are no atomics on memory.
+ * struct_size must equal sizeof(rmpc_tracks); refused (-1, rmpc_last_error) before any device call: NULL pointers other
+ * than static_ranges, det and counts, B < 1, rays outside [1, RMPC_TRACK_MAX_RAYS], n_tracks outside
+ * [1, RMPC_TRACK_MAX_TRACKS], n_out < 1, min_rays < 1, confirm < 1, max_miss < 0, a range, gap, radius, gate or dt that
+ * is not positive and finite, alpha outside (0, 1], beta outside [0, 2], a margin, max_extent or v_max that is negative
+ * (or NaN), park_x or park_y not finite, obst_dyn overlapping track, and B rays 3, B n_tracks 4 or B n_out 9 beyond
+ * INT_MAX. */
+#define RMPC_TRACK_MAX_RAYS 2048
+#define RMPC_TRACK_MAX_TRACKS 16
+#define RMPC_TRACK_MAX_DET 16
+typedef struct rmpc_tracks {
+  int32_t struct_size;                 /* sizeof(rmpc_tracks) */
+  int32_t rays;                        /* R in [1, RMPC_TRACK_MAX_RAYS] */
+  int32_t closed, min_rays;            /* != 0: rays R - 1 and 0 are neighbours; >= 1 */
+  const double *points;                /* [B][R][3]: the scan */
+  const double *ranges;                /* [B][R] */
+  const double *static_ranges;         /* [B][R]: the scan of the known static world at the same pose, may be NULL */
+  const double *origin;                /* [B][3]: the sensor origins */
+  double range, margin, gap, radius, max_extent;
+  double gate, dt, alpha, beta, v_max;
+  double park_x, park_y;
+  int32_t confirm, max_miss;           /* >= 1; >= 0 */
+  int32_t n_tracks, n_out;             /* T in [1, RMPC_TRACK_MAX_TRACKS]; >= 1 */
+  double *track;                       /* [B][T][4] in/out: px, py, vx, vy */
+  int32_t *age, *miss;                 /* [B][T] in/out; age 0 = a free slot */
+  double *obst_dyn;                    /* [B][n_out][9] out */
+  double *det;                         /* [B][RMPC_TRACK_MAX_DET][2] out, may be NULL */
+  int32_t *counts;                     /* [B][4] out, may be NULL: segments, detections, live, confirmed */
+} rmpc_tracks;
+int rmpc_lidar_tracks_device(int B, const rmpc_tracks *t, void *stream);
 
 /* Timed routes: conflict-free space-time routes for a fleet, decided before anyone moves, and the
  * follower that keeps their order.  Needs no handle; every pointer is a device pointer, each call runs on the device of

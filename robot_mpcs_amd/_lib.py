@@ -127,6 +127,22 @@ class ScanMatchArgs(C.Structure):
     ]
 
 
+class TracksArgs(C.Structure):
+    """Mirror of ``rmpc_tracks`` (include/rmpc.h): one scan of B robots through the moving-obstacle tracker, device
+    pointers."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("rays", C.c_int32), ("closed", C.c_int32), ("min_rays", C.c_int32),
+        ("points", C.c_void_p), ("ranges", C.c_void_p), ("static_ranges", C.c_void_p), ("origin", C.c_void_p),
+        ("range", C.c_double), ("margin", C.c_double), ("gap", C.c_double), ("radius", C.c_double),
+        ("max_extent", C.c_double),
+        ("gate", C.c_double), ("dt", C.c_double), ("alpha", C.c_double), ("beta", C.c_double), ("v_max", C.c_double),
+        ("park_x", C.c_double), ("park_y", C.c_double),
+        ("confirm", C.c_int32), ("max_miss", C.c_int32), ("n_tracks", C.c_int32), ("n_out", C.c_int32),
+        ("track", C.c_void_p), ("age", C.c_void_p), ("miss", C.c_void_p),
+        ("obst_dyn", C.c_void_p), ("det", C.c_void_p), ("counts", C.c_void_p),
+    ]
+
+
 class TimedPlanArgs(C.Structure):
     """Mirror of ``rmpc_timed_plan`` (include/rmpc.h): one prioritised space-time plan of B robots for G orders, device
     pointers."""
@@ -155,7 +171,7 @@ EXPORTED_SYMBOLS = [
     "rmpc_grid_frontier_device", "rmpc_grid_fields_seeded_device", "rmpc_grid_descend_device",
     "rmpc_grid_targets_device", "rmpc_grid_route_costs_device", "rmpc_assign_greedy_device",
     "rmpc_grid_edge_distance_device", "rmpc_lidar_project_device", "rmpc_scan_match_device",
-    "rmpc_timed_plan_work_bytes", "rmpc_timed_plan_device", "rmpc_timed_follow_device",
+    "rmpc_lidar_tracks_device", "rmpc_timed_plan_work_bytes", "rmpc_timed_plan_device", "rmpc_timed_follow_device",
 ]
 
 _lib = None
@@ -333,6 +349,8 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_lidar_project_device.argtypes = [i, C.POINTER(LidarArgs), vp]
     L.rmpc_scan_match_device.restype = C.c_int
     L.rmpc_scan_match_device.argtypes = [i, C.POINTER(ScanMatchArgs), vp]
+    L.rmpc_lidar_tracks_device.restype = C.c_int
+    L.rmpc_lidar_tracks_device.argtypes = [i, C.POINTER(TracksArgs), vp]
     L.rmpc_timed_plan_work_bytes.restype = C.c_int64
     L.rmpc_timed_plan_work_bytes.argtypes = [i, i, i, i]
     L.rmpc_timed_plan_device.restype = C.c_int
@@ -722,6 +740,39 @@ def scan_match_args(pose, points, ranges, d2, rot, pose_out, best, score, H: int
 def scan_match_device(args: ScanMatchArgs, B: int, stream=None):
     """Correlative scan matching of B robots (``rmpc_scan_match_device``) with the ``scan_match_args`` of the call."""
     _grid_call("rmpc_scan_match_device", int(B), C.byref(args), _stream_arg(stream))
+
+
+# limits of the moving-obstacle tracker (include/rmpc.h)
+TRACK_MAX_RAYS, TRACK_MAX_TRACKS, TRACK_MAX_DET = 2048, 16, 16
+
+
+def tracks_args(points, ranges, origin, track, age, miss, obst_dyn, radius: float, dt: float, static_ranges=None,
+                closed: bool = True, max_range: float = 10.0, margin: float = 0.05, gap: float = 0.3, min_rays: int = 2,
+                max_extent: float = 0.0, gate: float = 1.0, alpha: float = 0.4, beta: float = 0.1, v_max: float = 0.0,
+                confirm: int = 3, max_miss: int = 5, park=(100.0, 100.0), det=None, counts=None) -> TracksArgs:
+    """The ``rmpc_tracks`` of one call: points (B, R, 3), ranges (B, R), origin (B, 3), track (B, T, 4), obst_dyn
+    (B, n_out, 9) fp64; age, miss (B, T) int32; static_ranges (B, R) fp64, det (B, 16, 2) fp64 and counts (B, 4) int32 or
+    None -- contiguous device tensors."""
+    a = TracksArgs()
+    a.struct_size = C.sizeof(TracksArgs)
+    a.rays, a.closed, a.min_rays = int(points.shape[1]), int(bool(closed)), int(min_rays)
+    a.points, a.ranges, a.origin = points.data_ptr(), ranges.data_ptr(), origin.data_ptr()
+    a.static_ranges = None if static_ranges is None else static_ranges.data_ptr()
+    a.range, a.margin, a.gap, a.radius, a.max_extent = float(max_range), float(margin), float(gap), float(radius), float(max_extent)
+    a.gate, a.dt, a.alpha, a.beta, a.v_max = float(gate), float(dt), float(alpha), float(beta), float(v_max)
+    a.park_x, a.park_y = float(park[0]), float(park[1])
+    a.confirm, a.max_miss, a.n_tracks, a.n_out = int(confirm), int(max_miss), int(track.shape[1]), int(obst_dyn.shape[1])
+    a.track, a.age, a.miss, a.obst_dyn = track.data_ptr(), age.data_ptr(), miss.data_ptr(), obst_dyn.data_ptr()
+    a.det = None if det is None else det.data_ptr()
+    a.counts = None if counts is None else counts.data_ptr()
+    a._keep = (points, ranges, origin, static_ranges, track, age, miss, obst_dyn, det, counts)
+    return a
+
+
+def lidar_tracks_device(args: TracksArgs, B: int, stream=None):
+    """One step of the moving-obstacle tracker of B robots (``rmpc_lidar_tracks_device``) with the ``tracks_args`` of
+    the call: the filter's state (track, age, miss) is updated in place and obst_dyn written."""
+    _grid_call("rmpc_lidar_tracks_device", int(B), C.byref(args), _stream_arg(stream))
 
 
 # limits and the status of the timed routes (include/rmpc.h)

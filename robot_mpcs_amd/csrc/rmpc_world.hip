@@ -94,6 +94,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_assign.hpp"
 #include "rmpc_locate.hpp"
 #include "rmpc_timed.hpp"
+#include "rmpc_track.hpp"
 
 using namespace rmpc;
 
@@ -484,6 +485,42 @@ int rmpc_scan_match_device(int B, const rmpc_scan_match *m, void *stream) {
     return fail("null argument");
   if (use_device_of(m->pose)) return -1;
   hipLaunchKernelGGL(k_scan_match, dim3(B), dim3(kMatchThreads), 0, (hipStream_t)stream, *m);
+  return launch_status();
+}
+
+/* moving obstacles (rmpc_track.hpp) */
+int rmpc_lidar_tracks_device(int B, const rmpc_tracks *t, void *stream) {
+  const char *who = "lidar tracks";
+  const auto pos = [](double v) { return v > 0.0 && !std::isinf(v); };          // positive and finite
+  if (!t) return fail("null argument");
+  if (t->struct_size != (int)sizeof(rmpc_tracks)) return fail("rmpc_tracks.struct_size mismatch");
+  if (!t->points || !t->ranges || !t->origin || !t->track || !t->age || !t->miss || !t->obst_dyn) return fail("null argument");
+  if (B < 1) return fail(std::string(who) + ": need B >= 1");
+  if (t->rays < 1 || t->rays > RMPC_TRACK_MAX_RAYS)
+    return fail(std::string(who) + ": need 1 <= rays <= RMPC_TRACK_MAX_RAYS = " + std::to_string(RMPC_TRACK_MAX_RAYS));
+  if (t->n_tracks < 1 || t->n_tracks > RMPC_TRACK_MAX_TRACKS)
+    return fail(std::string(who) + ": need 1 <= n_tracks <= RMPC_TRACK_MAX_TRACKS = " + std::to_string(RMPC_TRACK_MAX_TRACKS));
+  if (t->n_out < 1) return fail(std::string(who) + ": need n_out >= 1");
+  if (t->min_rays < 1 || t->confirm < 1 || t->max_miss < 0)
+    return fail(std::string(who) + ": need min_rays >= 1, confirm >= 1 and max_miss >= 0");
+  if (!pos(t->range) || !pos(t->gap) || !pos(t->radius) || !pos(t->gate) || !pos(t->dt))
+    return fail(std::string(who) + ": range, gap, radius, gate and dt must be positive and finite");
+  if (!(t->alpha > 0.0 && t->alpha <= 1.0)) return fail(std::string(who) + ": alpha must lie in (0, 1]");
+  if (!(t->beta >= 0.0 && t->beta <= 2.0)) return fail(std::string(who) + ": beta must lie in [0, 2]");
+  if (!(t->margin >= 0.0) || !(t->max_extent >= 0.0) || !(t->v_max >= 0.0))
+    return fail(std::string(who) + ": margin, max_extent and v_max must be >= 0");
+  if (!std::isfinite(t->park_x) || !std::isfinite(t->park_y)) return fail(std::string(who) + ": park_x, park_y must be finite");
+  if (!grid_fits((long long)B * t->rays, 3) || !grid_fits((long long)B * t->n_tracks, 4) || !grid_fits(B, t->n_out) ||
+      !grid_fits((long long)B * t->n_out, 9))
+    return fail(std::string(who) + ": B*rays*3, B*n_tracks*4 and B*n_out*9 must not exceed INT_MAX");
+  {
+    const char *const t0 = (const char *)t->track, *const o0 = (const char *)t->obst_dyn;
+    const char *const t1 = t0 + (size_t)B * t->n_tracks * 4 * sizeof(double);
+    const char *const o1 = o0 + (size_t)B * t->n_out * 9 * sizeof(double);
+    if (o0 < t1 && t0 < o1) return fail(std::string(who) + ": obst_dyn must not overlap track");
+  }
+  if (use_device_of(t->points)) return -1;
+  hipLaunchKernelGGL(k_lidar_tracks, dim3(B), dim3(kTrackThreads), 0, (hipStream_t)stream, *t);
   return launch_status();
 }
 
