@@ -903,6 +903,15 @@ const char *rmpc_spec_for(const rmpc_desc *desc);   /* the view rmpc_create woul
  * a solve must not depend on what a previous kernel left in LDS). */
 int rmpc_debug_poison_lds(rmpc_handle *h);
 
+/* Test aid: the whole-horizon reductions of the kernels (sums, maxima, minima over the lpi = 32 or 64 consecutive lanes of
+ * an instance) run by one wavefront on device `device` over caller-supplied lane values, once with the shuffle exchanges
+ * (the reference form) and once with the vector-move exchanges the kernels use.  in, out_shfl, out_dpp: [10][64] doubles,
+ * word w of lane l at [w][l].  op 0 / 1 / 2: sum / maximum / minimum of word 0; op 3: the sweep's partials together, sums
+ * of words 0 .. 4, maxima of 5 .. 8, minimum of 9; op 4: the step lengths together, the sum of word 0 and the minima of
+ * words 1 and 2 (word 3 of the outputs: the maximum of the constant zero the kernels pass along).  Every lane's result
+ * is returned; words an op does not use come back as zeros. */
+int rmpc_debug_wave_reduce(int device, int lpi, int op, const double *in, double *out_shfl, double *out_dpp);
+
 /* Development aid: per-block phase cycle counts of the last fused launch (8 words per block: sweep, decisions,
  * recursion, step, total, passes, start, -); all zero unless the library was built with -DRMPC_STAMPS. */
 int rmpc_debug_fused_stamps(rmpc_handle *h, long long *out, int nblocks);

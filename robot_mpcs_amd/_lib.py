@@ -164,7 +164,7 @@ EXPORTED_SYMBOLS = [
     "rmpc_version", "rmpc_source_hash", "rmpc_last_error", "rmpc_desc_size", "rmpc_create", "rmpc_destroy", "rmpc_solve_batch",
     "rmpc_solve_batch_device", "rmpc_workspace_bytes", "rmpc_set_warm_start", "rmpc_set_pass_budget", "rmpc_is_fused", "rmpc_fused_kernel_name", "rmpc_is_async", "rmpc_set_profiling", "rmpc_get_profile",
     "rmpc_kernel_name", "rmpc_last_passes", "rmpc_debug_sweep", "rmpc_debug_step", "rmpc_debug_step_curv", "rmpc_spec_source", "rmpc_spec_name", "rmpc_spec_for", "rmpc_debug_poison_lds",
-    "rmpc_debug_fused_stamps", "rmpc_pack_scene_device", "rmpc_solve_batch_scene_device", "rmpc_pack_scene_workspace", "rmpc_solve_batch_packed_device", "rmpc_advance_device", "rmpc_advance_device_flags", "rmpc_retarget_device", "rmpc_advance_obstacles_device", "rmpc_free_space_device",
+    "rmpc_debug_fused_stamps", "rmpc_debug_wave_reduce", "rmpc_pack_scene_device", "rmpc_solve_batch_scene_device", "rmpc_pack_scene_workspace", "rmpc_solve_batch_packed_device", "rmpc_advance_device", "rmpc_advance_device_flags", "rmpc_retarget_device", "rmpc_advance_obstacles_device", "rmpc_free_space_device",
     "rmpc_grid_inflate_device", "rmpc_grid_fields_device", "rmpc_grid_paths_device", "rmpc_grid_cells_device",
     "rmpc_follow_path_device", "rmpc_lidar_scan_device", "rmpc_plan_points_device", "rmpc_fleet_points_device",
     "rmpc_fleet_planes_device", "rmpc_grid_mark_device", "rmpc_grid_occupancy_device",
@@ -288,6 +288,8 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_debug_poison_lds.argtypes = [C.c_void_p]
     L.rmpc_spec_for.restype = C.c_char_p
     L.rmpc_spec_for.argtypes = [C.POINTER(RmpcDesc)]
+    L.rmpc_debug_wave_reduce.restype = C.c_int
+    L.rmpc_debug_wave_reduce.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp]
     L.rmpc_debug_fused_stamps.restype = C.c_int
     L.rmpc_debug_fused_stamps.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.c_int]
     L.rmpc_pack_scene_device.restype = C.c_int
@@ -449,6 +451,25 @@ def stream_handle(stream, device):
 
 def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+WAVE_REDUCE_OPS = {"sum": 0, "max": 1, "min": 2, "many541": 3, "many102": 4}
+
+
+def debug_wave_reduce(values, op: str, lpi: int, device: int = 0):
+    """Test aid (``rmpc_debug_wave_reduce``): the kernels' whole-horizon reductions over ``lpi`` (32 or 64) consecutive
+    lanes of one wavefront.  ``values`` [words][64] float64, at most 10 words per lane (``op``: "sum" / "max" / "min"
+    reduce word 0; "many541" sums words 0 .. 4, takes the maxima of 5 .. 8 and the minimum of 9; "many102" sums word 0
+    and takes the minima of words 1, 2, word 3 of the result being the maximum of the kernels' constant zero).  Returns
+    (shuffle form, vector-move form), each [10][64]: every lane's result."""
+    v = np.zeros((10, 64), dtype=np.float64)
+    a = np.asarray(values, dtype=np.float64).reshape(-1, 64)
+    v[:a.shape[0]] = a
+    ref, new = np.empty_like(v), np.empty_like(v)
+    L = load_library()
+    if L.rmpc_debug_wave_reduce(int(device), int(lpi), WAVE_REDUCE_OPS[op], _dp(v), _dp(ref), _dp(new)) != 0:
+        raise RmpcError("rmpc_debug_wave_reduce: " + L.rmpc_last_error().decode())
+    return ref, new
 
 
 def free_space_decomposition_device(points, seeds, planes_out, max_radius: float, stream=None):

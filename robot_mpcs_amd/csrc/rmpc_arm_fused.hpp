@@ -781,8 +781,14 @@ __device__ __noinline__ void arm_sweep_call(__attribute__((address_space(3))) Ar
     ap = live ? ap : 1.0; ad = live ? ad : 1.0; gp = live ? gp : 0.0;
   }
   {
+    // (the whole wavefront makes the call, and `fresh` is the same in all its lanes: all 64 lanes are here.  The shuffle
+    //  form is kept in this call, here and at its end, although no lane is missing: with the vector-move exchanges at
+    //  both places k_fused_arm<Cfg<CHAIN, 6, 0>, 2> left two of the 48 instances of
+    //  test_fused_arm_two_parts_per_stage_match_oracle[chain6-48-77] at the iteration cap, while either place alone, and
+    //  both with only level 32 through the shuffle, gave the parent's results, as did every other size and dealing.  The
+    //  listing shows the exchanges as written and the wait states the moves need; the cause was not found: DESIGN.md 5.1)
     double rs1[1] = {gp}, rm0[1] = {0.0}, rn2[2] = {ap, ad};
-    wave_reduce_many<64>(rs1, rm0, rn2);
+    wave_reduce_many<64, XCHG_SHFL>(rs1, rm0, rn2);
     gp = rs1[0]; ap = rn2[0]; ad = rn2[1];
   }
   const double amin_p = fresh ? fmin(amin_p_in, ap) : amin_p_in;
@@ -806,11 +812,11 @@ __device__ __noinline__ void arm_sweep_call(__attribute__((address_space(3))) Ar
     sweep_part<C, P, gdouble, ldouble, GView, FIRSTC>(sk, v, io, k, p, nostep, alpha, adual, mu, q, st);
   }
   {
-    // (lanes without a stage contribute the neutral elements)
+    // (lanes without a stage contribute the neutral elements: all 64 lanes reduce; the shuffle form: see above)
     double rs5[5] = {live ? q.f : 0.0, live ? q.th : 0.0, live ? q.logs : 0.0, live ? q.sumc : 0.0, live ? q.bad : 0.0};
     double rm4[4] = {live ? q.rstat : 0.0, live ? q.req : 0.0, live ? q.rineq : 0.0, live ? q.rcomp : 0.0};
     double rn1[1] = {live ? q.minc : 1e300};
-    wave_reduce_many<64>(rs5, rm4, rn1);
+    wave_reduce_many<64, XCHG_SHFL>(rs5, rm4, rn1);
     out->f = rs5[0]; out->th = rs5[1]; out->lgs = rs5[2]; out->sumc = rs5[3]; out->badf = rs5[4];
     out->rstat = rm4[0]; out->req = rm4[1]; out->rineq = rm4[2]; out->rcomp = rm4[3]; out->minc = rn1[0];
     out->amin_p = amin_p; out->amin_d = amin_d; out->gphi = gphi;

@@ -272,6 +272,8 @@ __device__ __noinline__ RMPC_ONE_WAVE void fused_sweep_step_call(__attribute__((
     double ap = (fresh && live) ? sl.ap : 1.0, ad = (fresh && live) ? sl.ad : 1.0, gp = (fresh && live) ? sl.gphi : 0.0;
     st(4);
     {
+      // (vector-move exchanges: the caller sends whole halves -- both, or on a pass whose halves differ in the copy they
+      //  run the one half of this copy --, and only the bodies above and below are under `live`)
       double rs1[1] = {gp}, rm0[1] = {0.0}, rn2[2] = {ap, ad};
       wave_reduce_many<kFusedStages>(rs1, rm0, rn2);
       gp = rs1[0]; ap = rn2[0]; ad = rn2[1];
@@ -284,7 +286,8 @@ __device__ __noinline__ RMPC_ONE_WAVE void fused_sweep_step_call(__attribute__((
     if (live) sweep_body<C, -1, ldouble, V, 0, 2>(sk, v, io, k, false, nostep, alpha, adual, mu, r.q, nullptr, &top);
   }
   {
-    // (idle lanes and idle halves contribute the neutral elements: their sums are discarded by the caller)
+    // (idle lanes and idle halves contribute the neutral elements: their sums are discarded by the caller; all 32 lanes
+    //  of a half are here, as the vector-move exchanges need)
     const Partials &q = r.q;
     double rs5[5] = {q.f, q.th, q.logs, q.sumc, q.bad}, rm4[4] = {q.rstat, q.req, q.rineq, q.rcomp}, rn1[1] = {q.minc};
     wave_reduce_many<kFusedStages>(rs5, rm4, rn1);
@@ -597,6 +600,7 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
       ps.sections(sres[half]);
     } else {
       ps.sections(q);
+      // (outside `act && stage`: the whole wavefront reduces, idle lanes with the neutral elements)
       double rs5[5] = {q.f, q.th, q.logs, q.sumc, q.bad}, rm4[4] = {q.rstat, q.req, q.rineq, q.rcomp}, rn1[1] = {q.minc};
       wave_reduce_many<LPI>(rs5, rm4, rn1);
       r.f = rs5[0]; r.th = rs5[1]; r.lgs = rs5[2]; r.sumc = rs5[3]; r.badf = rs5[4];
@@ -651,6 +655,7 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
       }
       unpark();
       {
+        // (the whole wavefront: lanes that are not stepping bring the neutral elements)
         double rs1[1] = {gp}, rm0[1] = {0.0}, rn2[2] = {ap, ad};
         wave_reduce_many<LPI>(rs1, rm0, rn2);
         gp = rs1[0]; ap = rn2[0]; ad = rn2[1];

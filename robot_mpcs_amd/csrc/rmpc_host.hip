@@ -452,6 +452,45 @@ static void unpack_records(const DevModel &M, int B, RecFn rec, double *out_Q, d
     }
 }
 
+// rmpc_debug_wave_reduce (test aid): one wavefront runs the whole-horizon reductions of rmpc_inst.hpp over the caller's
+// lane values, once with the shuffle exchanges and once with the vector-move exchanges the kernels use
+// (tests/test_gpu_wave_reduce.py)
+constexpr int kWaveReduceWords = 10;   // words per lane: the most a call of the kernels reduces together
+template <int LPI, bool DPP>
+__device__ void wave_reduce_debug(const int op, const double (&v)[kWaveReduceWords], double *out) {
+  const int lane = threadIdx.x;
+  double r[kWaveReduceWords];
+  for (int w = 0; w < kWaveReduceWords; w++) r[w] = 0.0;
+  if (op == 0) r[0] = wave_sum<LPI, DPP>(v[0]);
+  else if (op == 1) r[0] = wave_max<LPI, DPP>(v[0]);
+  else if (op == 2) r[0] = wave_min<LPI, DPP>(v[0]);
+  else if (op == 3) {
+    // the partials of a sweep: five sums, four maxima, one minimum
+    double rs5[5] = {v[0], v[1], v[2], v[3], v[4]}, rm4[4] = {v[5], v[6], v[7], v[8]}, rn1[1] = {v[9]};
+    wave_reduce_many<LPI, DPP>(rs5, rm4, rn1);
+    for (int i = 0; i < 5; i++) r[i] = rs5[i];
+    for (int i = 0; i < 4; i++) r[5 + i] = rm4[i];
+    r[9] = rn1[0];
+  } else {
+    // the step lengths: one sum, no maximum (the kernels pass a constant zero in its place), two minima
+    double rs1[1] = {v[0]}, rm0[1] = {0.0}, rn2[2] = {v[1], v[2]};
+    wave_reduce_many<LPI, DPP>(rs1, rm0, rn2);
+    r[0] = rs1[0]; r[1] = rn2[0]; r[2] = rn2[1]; r[3] = rm0[0];
+  }
+  for (int w = 0; w < kWaveReduceWords; w++) out[w * 64 + lane] = r[w];
+}
+__global__ __launch_bounds__(64) void k_wave_reduce_debug(const int lpi, const int op, const double *in, double *out_shfl, double *out_dpp) {
+  // (lpi and op are uniform: every branch is taken by the whole wavefront)
+  double v[kWaveReduceWords];
+  for (int w = 0; w < kWaveReduceWords; w++) v[w] = in[w * 64 + threadIdx.x];
+  if (lpi == 32) {
+    wave_reduce_debug<32, XCHG_SHFL>(op, v, out_shfl);
+    wave_reduce_debug<32, XCHG_DPP>(op, v, out_dpp);
+  } else {
+    wave_reduce_debug<64, XCHG_SHFL>(op, v, out_shfl);
+    wave_reduce_debug<64, XCHG_DPP>(op, v, out_dpp);
+  }
+}
 extern "C" {
 
 int rmpc_version(void) { return RMPC_VERSION; }
@@ -857,6 +896,29 @@ int rmpc_debug_poison_lds(rmpc_handle *h) {
   HIPCHK(hipStreamSynchronize(h->stream));
   h->have_duals = false;
   h->packed_B = 0;
+  return 0;
+}
+
+/* test aid: see k_wave_reduce_debug */
+int rmpc_debug_wave_reduce(int device, int lpi, int op, const double *in, double *out_shfl, double *out_dpp) {
+  if (lpi != 32 && lpi != 64) return fail("rmpc_debug_wave_reduce: 32 or 64 lanes per instance");
+  if (op < 0 || op > 4) return fail("rmpc_debug_wave_reduce: op 0 sum, 1 max, 2 min, 3 many (5, 4, 1), 4 many (1, 0, 2)");
+  if (!in || !out_shfl || !out_dpp) return fail("rmpc_debug_wave_reduce: null array");
+  HIPCHK(hipSetDevice(device));
+  const size_t bytes = sizeof(double) * kWaveReduceWords * 64;
+  double *d = nullptr;
+  HIPCHK(hipMalloc(&d, 3 * bytes));
+  hipError_t e = hipMemcpy(d, in, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d + kWaveReduceWords * 64, 0, 2 * bytes);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_wave_reduce_debug, dim3(1), dim3(64), 0, 0, lpi, op, d, d + kWaveReduceWords * 64, d + 2 * kWaveReduceWords * 64);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out_shfl, d + kWaveReduceWords * 64, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out_dpp, d + 2 * kWaveReduceWords * 64, bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(std::string("rmpc_debug_wave_reduce: ") + hipGetErrorString(e));
   return 0;
 }
 

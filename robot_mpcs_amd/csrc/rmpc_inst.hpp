@@ -3,39 +3,96 @@
 // namespace rmpc); the pass kernels and both fused kernels run this one copy.  Needs rmpc_solver.hpp.
 
 // reductions over the LPI consecutive lanes that work on one instance (a whole wavefront or half of one)
-template <int LPI>
+//
+// The value of the partner lane of a butterfly level OFF.  XCHG_SHFL: __shfl_xor, lane ^ OFF through the LDS crossbar
+// (ds_bpermute_b32 per word and a wait for its answer: a dependent LDS round trip per level, on the CU's LDS queue behind
+// the other wavefronts).  XCHG_DPP: vector moves inside the SIMD, no LDS instruction and no counter to wait for --
+//   32, 16  v_permlane32_swap_b32 / v_permlane16_swap_b32 (gfx950) of the word with a copy of itself: the instruction swaps
+//           the odd halves / odd 16-lane rows of its first operand with the even ones of its second, so the partner's
+//           word is in the first operand for a lane of an odd half / row and in the second for the others (one select
+//           per word): exactly lane ^ 32 / lane ^ 16;
+//   8       row_ror:8, exactly lane ^ 8 (a rotation by half a row);
+//   4       row_ror:4, the lane four places round its row: lane ^ 4 or (lane ^ 4) ^ 8;
+//   2, 1    quad_perm [2, 3, 0, 1] / [1, 0, 3, 2], exactly lane ^ 2 / lane ^ 1.
+// Same results as the shuffle tree bit for bit, level by level in the same order (LPI / 2 .. 1) with the lane's own
+// value as the first operand: every level but 4 reads lane ^ OFF itself; at level 4 the lane read is either lane ^ 4 or
+// its level-8 partner, and after the level-8 step a lane and its level-8 partner hold the same word -- a + b and b + a,
+// or max / min of the same pair, and the hardware's add, max and min are commutative down to the bits: the sum of +0
+// and -0 is +0 either way, v_max_f64 / v_min_f64 order -0 below +0 whichever operand holds it, and return the other
+// operand when one is a NaN.  NaNs are the one exception: with two NaNs the payload returned may depend on the operand
+// order, so a result that is NaN is NaN in the same lanes as with the shuffle tree, with a payload that is not pinned
+// (nothing reads payloads; the kernel's max operands are absolute values and products of positive numbers).
+// tests/test_gpu_wave_reduce.py compares the two forms lane by lane (rmpc_debug_wave_reduce).
+//
+// A DPP or permlane move reads a register of another lane, and that lane must be active: XCHG_DPP needs all LPI lanes of
+// the instance in the call (level 16 pairs the two rows of a half, level 32 the two halves; the other levels stay inside
+// a 16-lane row).  Every call site has them -- whole wavefronts, or whole halves where LPI = 32 and a half can sit the
+// call out (noted at each) --; one that could be entered by a part of an instance's lanes has to ask for XCHG_SHFL.
+// (arm_sweep_call asks for it for another reason, given there.)
+constexpr bool XCHG_DPP = true, XCHG_SHFL = false;
+template <int OFF, bool DPP>
+__device__ __forceinline__ double lane_xchg(const double v) {
+  static_assert(OFF == 32 || OFF == 16 || OFF == 8 || OFF == 4 || OFF == 2 || OFF == 1, "lane_xchg: a butterfly level of a wavefront");
+  if constexpr (!DPP) return __shfl_xor(v, OFF, 64);
+  else if constexpr (OFF >= 16) {
+    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+    const bool odd = (threadIdx.x & OFF) != 0;   // (blocks are whole wavefronts: bit OFF of the lane index)
+    if constexpr (OFF == 32) {
+      const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+      return __hiloint2double((int)(odd ? b[0] : b[1]), (int)(odd ? a[0] : a[1]));
+    } else {
+      const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+      return __hiloint2double((int)(odd ? b[0] : b[1]), (int)(odd ? a[0] : a[1]));
+    }
+  }
+  else if constexpr (OFF == 8) return dpp_move<0x128>(v);   // row_ror:8
+  else if constexpr (OFF == 4) return dpp_move<0x124>(v);   // row_ror:4
+  else if constexpr (OFF == 2) return dpp_move<0x4E>(v);    // quad_perm [2, 3, 0, 1]
+  else return dpp_move<0xB1>(v);                            // quad_perm [1, 0, 3, 2]
+}
+// fn(integral_constant<int, OFF>) for the levels OFF = LPI / 2 .. 1 of the butterfly, in that order
+template <int LPI, class F>
+__device__ __forceinline__ void wave_levels(F &&fn) {
+  static_assert(LPI == 32 || LPI == 64, "wave_levels: a whole wavefront or half of one");
+  if constexpr (LPI == 64) fn(std::integral_constant<int, 32>{});
+  fn(std::integral_constant<int, 16>{});
+  fn(std::integral_constant<int, 8>{});
+  fn(std::integral_constant<int, 4>{});
+  fn(std::integral_constant<int, 2>{});
+  fn(std::integral_constant<int, 1>{});
+}
+template <int LPI, bool DPP = XCHG_DPP>
 __device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = LPI / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  wave_levels<LPI>([&](auto off) __attribute__((always_inline)) { v += lane_xchg<decltype(off)::value, DPP>(v); });
   return v;
 }
-template <int LPI>
+template <int LPI, bool DPP = XCHG_DPP>
 __device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = LPI / 2; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  wave_levels<LPI>([&](auto off) __attribute__((always_inline)) { v = fmax(v, lane_xchg<decltype(off)::value, DPP>(v)); });
   return v;
 }
-template <int LPI>
+template <int LPI, bool DPP = XCHG_DPP>
 __device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int off = LPI / 2; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
+  wave_levels<LPI>([&](auto off) __attribute__((always_inline)) { v = fmin(v, lane_xchg<decltype(off)::value, DPP>(v)); });
   return v;
 }
 
-// Several reductions at once, step by step: the exchanges of one step of all of them are issued together (a single
-// reduction is a chain of dependent LDS-crossbar round trips; done one after the other, eleven of them cost eleven
-// chains).  Same partner pattern, hence the same rounding, as wave_sum / wave_max / wave_min.
-template <int LPI, int NS_, int NM_, int NN_>
+// Several reductions at once, step by step: the exchanges of one step of all of them are issued together (with the
+// shuffle form a single reduction is a chain of dependent LDS-crossbar round trips; done one after the other, eleven of
+// them cost eleven chains; with the vector moves a step pays the wait states between an operand's last write and the
+// move that reads it once, not once per value).  Same partner pattern, hence the same rounding, as wave_sum / wave_max /
+// wave_min.
+template <int LPI, bool DPP = XCHG_DPP, int NS_, int NM_, int NN_>
 __device__ __forceinline__ void wave_reduce_many(double (&sums)[NS_], double (&maxs)[NM_], double (&mins)[NN_]) {
-#pragma unroll
-  for (int off = LPI / 2; off >= 1; off >>= 1) {
+  wave_levels<LPI>([&](auto off) __attribute__((always_inline)) {
+    constexpr int OFF = decltype(off)::value;
     double ts[NS_], tm[NM_], tn[NN_];
 #pragma unroll
-    for (int i = 0; i < NS_; i++) ts[i] = __shfl_xor(sums[i], off, 64);
+    for (int i = 0; i < NS_; i++) ts[i] = lane_xchg<OFF, DPP>(sums[i]);
 #pragma unroll
-    for (int i = 0; i < NM_; i++) tm[i] = __shfl_xor(maxs[i], off, 64);
+    for (int i = 0; i < NM_; i++) tm[i] = lane_xchg<OFF, DPP>(maxs[i]);
 #pragma unroll
-    for (int i = 0; i < NN_; i++) tn[i] = __shfl_xor(mins[i], off, 64);
+    for (int i = 0; i < NN_; i++) tn[i] = lane_xchg<OFF, DPP>(mins[i]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < NS_; i++) sums[i] += ts[i];
@@ -43,7 +100,7 @@ __device__ __forceinline__ void wave_reduce_many(double (&sums)[NS_], double (&m
     for (int i = 0; i < NM_; i++) maxs[i] = fmax(maxs[i], tm[i]);
 #pragma unroll
     for (int i = 0; i < NN_; i++) mins[i] = fmin(mins[i], tn[i]);
-  }
+  });
 }
 
 // ---- per-instance solver state ------------------------------------------------------------------------

@@ -46,7 +46,9 @@ __global__ __launch_bounds__(64 * IPB, C::RIC_WPE) void k_riccati(const DevModel
   for (int k = lane; k < N; k += LPI) reduced_add(r, W, k, b, first != 0);
   {
     // (all quantities through the xor tree together, step by step: 6 exchange rounds instead of 11 x 6 dependent ones;
-    //  the same trees as wave_sum / wave_max / wave_min)
+    //  the same trees as wave_sum / wave_max / wave_min.  The early returns above are uniform over the LPI lanes of an
+    //  instance, so whole instances arrive here: the wavefront, or in the grouped regime one or both of its halves --
+    //  what the vector-move exchanges need)
     double rs6[6] = {r.f, r.th, r.lgs, r.sumc, r.badf, r.gphi}, rm4[4] = {r.rstat, r.req, r.rineq, r.rcomp}, rn1[1] = {r.minc};
     wave_reduce_many<LPI>(rs6, rm4, rn1);
     r.f = rs6[0]; r.th = rs6[1]; r.lgs = rs6[2]; r.sumc = rs6[3]; r.badf = rs6[4]; r.gphi = rs6[5];

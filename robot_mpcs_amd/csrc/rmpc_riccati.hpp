@@ -1,7 +1,7 @@
 // rmpc_riccati.hpp -- block-tridiagonal Riccati recursion of one instance, the Riccati step of every kernel family
 // (k_riccati, k_fused, k_fused_arm).  Part of rmpc_kernels.hip (included there, inside namespace rmpc, ahead of the
 // kernels); needs rmpc_solver.hpp.  Opens with what only the recursion and its callers use (chol_solve, WSYNC, StepOut,
-// dpp_move, stage_ptr).
+// stage_ptr; the DPP moves dpp_move / dpp_row_bcast are in rmpc_solver.hpp, beside the reductions' exchanges).
 //
 // riccati_recursion picks one path per model and kernel at compile time; each path is a function of its own:
 //   ric_point_robot           fused kernel, chains without slack (n <= 3): Schur form on the LDS slots, with its rollout
@@ -47,26 +47,6 @@ struct StepOut {
   size_t SS, KS;
 };
 
-// v moved between lanes by a DPP control word (quad permutations, row mirrors; the row broadcast of dpp_row_bcast below):
-// full-rate vector moves, no LDS crossbar round trip.  Every lane a reader takes its value from must be active.  The quad
-// permutations and row_half_mirror read only the 8 aligned lanes the reader belongs to, the row controls (row_newbcast)
-// only the reader's 16-lane row, and the callers keep those busy together: the paths that use them run with whole
-// wavefronts or whole halves (a half that sits a call out leaves no hole in the other half's two rows).  So the `old`
-// operand of the move is never taken -- it is left undefined, with bound_ctrl, and no instruction is spent on setting it
-// (a zero cost two v_mov_b32 per move).
-template <int CTRL>
-__device__ __forceinline__ double dpp_move(const double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-// v of lane L of the reader's 16-lane row, in every lane of that row (row_newbcast:L, the one control that exists as a
-// 64-bit move: one v_mov_b64_dpp).  With bound_ctrl and all rows and banks enabled `old` is never taken.
-template <int L>
-__device__ __forceinline__ double dpp_row_bcast(const double v) {
-  static_assert(L >= 0 && L < 16, "dpp_row_bcast: lane of a 16-lane row");
-  return __builtin_amdgcn_update_dpp(v, v, 0x150 + L, 0xF, 0xF, true);
-}
 // q[i][j] = v of lane 4 i + j of the reader's row, over the lower triangle from (I, J) on, row by row
 template <int I, int J, int NW>
 __device__ __forceinline__ void dpp_tri_gather(const double v, double (&q)[NW][NW]) {
@@ -74,6 +54,15 @@ __device__ __forceinline__ void dpp_tri_gather(const double v, double (&q)[NW][N
     q[I][J] = dpp_row_bcast<4 * I + J>(v);
     if constexpr (J < I) dpp_tri_gather<I, J + 1>(v, q);
     else dpp_tri_gather<I + 1, 0>(v, q);
+  }
+}
+
+// q[j] = v of lane L0 + j of the reader's row, j = J .. NQ - 1
+template <int J, int L0, int NQ>
+__device__ __forceinline__ void dpp_row_gather(const double v, double (&q)[NQ]) {
+  if constexpr (J < NQ) {
+    q[J] = dpp_row_bcast<L0 + J>(v);
+    dpp_row_gather<J + 1, L0>(v, q);
   }
 }
 
@@ -281,7 +270,8 @@ struct RicCtx {
 //      lane), the gains K = -L^-T Y behind it;
 //   C  [P | p] = [Qxx | qx] - Y^T [Y | y]: an entry per lane and turn, (i, j) and (j, i) the same products in the
 //      same order (Qxx is formed symmetrically): symmetric without the 0.5 (a + a^T) of the gain form.
-// The rollout forms dw, nu+ and dx+ from dx alone with one role per lane (one row of the image per lane).
+// The rollout forms dw, nu+ and dx+ from dx alone with one role per lane (one row of the image per lane); dx goes from
+// lane to lane by DPP row moves, not through LDS.
 template <class C, int LPI>
 __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldouble *const slots, const StepOut<ldouble> so) {
   constexpr int NQ = C::NQ, NX = C::NX, NW = C::NW, NP2 = RicCtx<C, LPI>::NP2, GS = FusedSlots<C>::GS;
@@ -296,8 +286,8 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
   static_assert(LPI == 32 && NW == n && NX == 2 * n && NX + 1 <= 8, "point-robot path: holonomic chain without slack, n <= 3");
   static_assert(20 * NW + 16 + 4 + 32 + NX <= RicLds<C, LPI>::LDSW, "point-robot path: work area");
   // work area: [Qux | qu] (NW rows of 8) | 4 NW words, the first of them the factorisation's flag | Y (NW rows of 8) |
-  // dx (2 x 8) | four zeros | a word per idle lane (and NX behind them: an idle lane's stores go to its word plus the
-  // offset the busy lanes use)
+  // 16 words without a use (dx of the rollout, before it stayed in registers: the layout is kept) | four zeros | a word
+  // per idle lane (and NX behind them: an idle lane's stores go to its word plus the offset the busy lanes use)
   ldouble *const aQux = img, *const aQuu = aQux + 8 * NW, *const aY = aQuu + 4 * NW, *const adx = aY + 8 * NW,
                *const azero = adx + 16, *const adum = azero + 4;
   ldouble *const dummy = adum + lane;
@@ -472,7 +462,7 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
   WSYNC();
   chol_ok = aQuu[0] != 0.0;
   if (!chol_ok) return false;
-  // ---- rollout: dw = kff + K dx, nu+ = p + P dx, dx+ = rc + [A|B][dx; dw], one ordering point per stage ---------------
+  // ---- rollout: dw = kff + K dx, nu+ = p + P dx, dx+ = rc + [A|B][dx; dw]: dx stays in registers, no ordering point -------
   const bool fA = lane < NW, fB = lane >= NW && lane < NW + NX, fC = lane >= NW + NX && lane < NW + 2 * NX;
   const int fi = fA ? lane : (fB ? lane - NW : (fC ? lane - NW - NX : 0));   // entry of dw / nu+ / dx+
   const int fw = fC ? (fi < n ? fi : fi - n) : fi;                             // the entry of dw a dx+ lane needs
@@ -481,53 +471,69 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
   const ldouble *imrow[NX];
 #pragma unroll
   for (int j = 0; j < NX; j++) imrow[j] = slots + (fB ? OFF_PT + ric_tri<NX>(fi, j) : fw * NX + j);
-  const int fx1 = fi < n ? n + fi : fi;
+  const bool fpos = fC && fi < n;   // a position lane of dx+: it takes the velocity entry n lanes up
   const double fca = fi < n ? h : 0.0, fcb = fi < n ? h2 : h;
-  // the lane's stores: dz (dw of lanes fA, dx of lanes fC), nu+ (lanes fB), dx+ (lanes fC, into the other half of adx)
-  ldouble *const wdz = (fA || fC) ? so.dz + (fA ? NX + lane : fi) : dummy, *const wnu = fB ? so.nunew + fi : dummy;
-  const unsigned strdz = (fA || fC) ? SB : 0u, strnu = fB ? SB : 0u;
-  ldouble *const wdx[2] = {fC ? adx + 8 + fi : dummy, fC ? adx + fi : dummy};   // by the parity of the stage
-  // (dx through the crossbar -- ds_bpermute, no store / ordering point / read-back, the image rows requested a stage
-  //  ahead -- was measured slower: 16 crossbar instructions per stage cost more LDS issue than the exchange saves,
-  //  2.85 -> 2.75 M solves/s on cfg2 with four batches in flight; dx kept in the registers of its lanes and handed round
-  //  by DPP row moves -- row_newbcast, row_shl:n, no LDS at all -- took 1.7 k cycles off the call, but its gain on the
-  //  headline stayed inside the spread of the runs: DESIGN.md 5.1)
-  if (lane < 16) adx[lane] = 0.0;
-  // One stage; par = k & 1 picks the half of adx that holds dx (the other half takes dx+).  The stage loop runs two stages
-  // per turn, so that par is a constant of each copy, the second copy's image addresses are the first's plus a constant,
-  // and nothing is selected or rebuilt per stage.  The last stage's dx+ goes to adx like every other (nobody reads it).
-  auto fwd = [&](const int k, const int par, const bool first) __attribute__((always_inline)) {
-    const ldouble *const dxc = adx + 8 * par;
-    // (the lane's row of the image does not depend on dx: requested before the ordering point, it arrives with it)
-    double rowv[NX];
+  // the lane's store, one per stage: dz (dw of lanes fA, dx of lanes fC) or nu+ (lanes fB; none at stage 0: x_0 is given)
+  ldouble *const wst0 = (fA || fC) ? so.dz + (fA ? NX + lane : fi) : dummy, *const wst = fB ? so.nunew + fi : wst0;
+  const unsigned strst0 = (fA || fC) ? SB : 0u, strst = fB ? SB : strst0;
+  // dx lives in the registers of the lanes that form it: lane NW + NX + j holds entry j (`dxme`; the other lanes carry a
+  // finite word nobody takes).  A stage hands it round by DPP row moves -- every lane takes the NX entries by
+  // row_newbcast (dpp_row_bcast: one v_mov_b64_dpp each), a position lane its velocity by row_shl:n, made in every lane
+  // and selected afterwards (inside a branch the source lanes would sit the move out) -- where it used to be stored to
+  // the work area, ordered and read back: no store of dx, no ordering point in the stage, no LDS read that waits on
+  // the previous stage.  All of it is in the first 16-lane row of the instance, and whole halves are here (the flag
+  // above is the instance's).  The lane's row of the image does not depend on dx: it is requested a stage ahead into
+  // the other of two register sets (`ra` / `rb`: NX entries of the row, the offset kff / p, the defect), so a stage
+  // waits for no LDS answer it has just asked for.  The image of a stage is read a stage before its step is stored over
+  // it (same wavefront: DS instructions execute in issue order).  Same operations on the same values in the same order
+  // as the exchange through LDS; the first dx is zero.
+  // (dx through the crossbar -- ds_bpermute, 16 crossbar instructions per stage -- was measured slower than the store and
+  //  read-back: 2.85 -> 2.75 M solves/s on cfg2 with four batches in flight; the row moves are vector moves: DESIGN.md 5.1)
+  static_assert(NW + 2 * NX <= 16, "point-robot path: the rollout's lanes in one 16-lane row");
+  constexpr int FC0 = NW + NX;   // lane of dx_0
+  auto request = [&](double (&r)[NX + 2], const int k) __attribute__((always_inline)) {
 #pragma unroll
-    for (int j = 0; j < NX; j++) rowv[j] = imrow[j][k * GS];
-    double sacc = imoff[k * GS];
-    const double rcv = imrc[k * GS];
-    WSYNC();
+    for (int j = 0; j < NX; j++) r[j] = imrow[j][k * GS];
+    r[NX] = imoff[k * GS];
+    r[NX + 1] = imrc[k * GS];
+  };
+  double dxme = 0.0;
+  // One stage on the image in `cur`; the image of stage kn is requested into `nxt` first (`pf`; the last stage asks for
+  // nothing).  The stage loop runs two stages per turn, so that the two register sets change roles without a copy and
+  // the requests of a turn are one set of addresses plus constants.
+  auto fwd = [&](const int k, const double (&cur)[NX + 2], double (&nxt)[NX + 2], const int kn, const bool pf,
+                 const bool first) __attribute__((always_inline)) {
+    if (pf) request(nxt, kn);
+    __builtin_amdgcn_sched_barrier(0);   // (the requests leave before the chain of the stage begins)
     double dxv[NX];
+    dpp_row_gather<0, FC0>(dxme, dxv);
+    const double dsh = dpp_move<0x100 + n>(dxme);   // row_shl:n
+    const double d0 = dxme, d1 = fpos ? dsh : dxme;
+    double sacc = cur[NX];
 #pragma unroll
-    for (int j = 0; j < NX; j++) dxv[j] = dxc[j];
-    const double d0 = dxc[fi], d1 = dxc[fx1];
-    __builtin_amdgcn_sched_barrier(0);   // (the image of the stage is read before its step is stored over it)
-#pragma unroll
-    for (int j = 0; j < NX; j++) sacc += rowv[j] * dxv[j];
-    *stage_ptr(wdz, strdz, k) = fA ? sacc : d0;
-    if (!first) *stage_ptr(wnu, strnu, k) = sacc;   // (no nu+ of stage 0: x_0 is given)
-    double sx = rcv;
+    for (int j = 0; j < NX; j++) sacc += cur[j] * dxv[j];
+    *stage_ptr(first ? wst0 : wst, first ? strst0 : strst, k) = fC ? d0 : sacc;
+    double sx = cur[NX + 1];
     sx += d0;
     sx += fca * d1;
     sx += fcb * sacc;
-    *wdx[par] = sx;
+    dxme = sx;   // (the last stage's dx+ is formed like every other: nobody takes it)
     rst(6);
   };
-  fwd(0, 0, true);
+  double ra[NX + 2], rb[NX + 2];
+  request(ra, 0);
+  fwd(0, ra, rb, N > 1 ? 1 : 0, true, true);
   int k = 1;
-  for (; k + 1 < N; k += 2) {
-    fwd(k, 1, false);
-    fwd(k + 1, 0, false);
+  for (; k + 2 < N; k += 2) {
+    fwd(k, rb, ra, k + 1, true, false);
+    fwd(k + 1, ra, rb, k + 2, true, false);
   }
-  if (k < N) fwd(k, 1, false);
+  // (behind the pairs: one stage or two, the last one without a request)
+  if (k < N) {
+    const bool two = k + 1 < N;
+    fwd(k, rb, ra, two ? k + 1 : k, true, false);
+    if (two) fwd(k + 1, ra, rb, 0, false, false);
+  }
   rst.flush(lane);
   return true;
 }

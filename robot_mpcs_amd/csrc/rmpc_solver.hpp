@@ -109,3 +109,24 @@ template <int L, int H, class F>
 __device__ __forceinline__ void for_range(F &&fn) {
   for_range_impl<L>(fn, std::make_integer_sequence<int, (H > L ? H - L : 0)>{});
 }
+
+// v moved between lanes by a DPP control word (quad permutations, row mirrors and rotations; the row broadcast of dpp_row_bcast below):
+// full-rate vector moves, no LDS crossbar round trip.  Every lane a reader takes its value from must be active.  The quad
+// permutations and row_half_mirror read only the 8 aligned lanes the reader belongs to, the row controls (row_newbcast)
+// only the reader's 16-lane row, and the callers keep those busy together: the paths that use them run with whole
+// wavefronts or whole halves (a half that sits a call out leaves no hole in the other half's two rows).  So the `old`
+// operand of the move is never taken -- it is left undefined, with bound_ctrl, and no instruction is spent on setting it
+// (a zero cost two v_mov_b32 per move).
+template <int CTRL>
+__device__ __forceinline__ double dpp_move(const double v) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+// v of lane L of the reader's 16-lane row, in every lane of that row (row_newbcast:L, the one control that exists as a
+// 64-bit move: one v_mov_b64_dpp).  With bound_ctrl and all rows and banks enabled `old` is never taken.
+template <int L>
+__device__ __forceinline__ double dpp_row_bcast(const double v) {
+  static_assert(L >= 0 && L < 16, "dpp_row_bcast: lane of a 16-lane row");
+  return __builtin_amdgcn_update_dpp(v, v, 0x150 + L, 0xF, 0xF, true);
+}
