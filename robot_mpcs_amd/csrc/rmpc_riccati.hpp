@@ -40,6 +40,16 @@ __device__ __forceinline__ void chol_solve(const double (&L)[NW][NW], const doub
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
   } while (0)
 
+// Completes the LDS requests of the wavefront that are out (s_waitcnt lgkmcnt(0); vmcnt and expcnt stay open: global
+// loads in flight are not drained).  For the preheader of a stage loop that takes its first record from requests made
+// in front of the loop and every later one from requests made inside it: WSYNC() is a compiler fence and emits no
+// instruction, so the requests are still pending at the loop header, and the wait the compiler must then put at the top
+// of the stage -- counted for the way in -- on the back edge counts the previous stage's stores instead: LDS operations
+// complete in issue order, so every stage waits for stores nobody reads.  With the requests complete before the loop
+// is entered the header carries no pending read and the stage's first wait is the one for its own requests.  (The
+// builtin, not an asm statement: the compiler's wait insertion sees it and drops the waits it covers.)
+__device__ __forceinline__ void lds_requests_done() { __builtin_amdgcn_s_waitcnt(0xC07F); }
+
 // where the recursion leaves the step: dz[slot * SS + k * KS], nunew likewise (pointers advanced to the instance)
 template <class RP = gdouble>
 struct StepOut {
@@ -343,6 +353,7 @@ __device__ __forceinline__ bool ric_point_robot(const RicCtx<C, LPI> &ctx, ldoub
   rn[6] = stage_ptr(rG, strU, (N - 1))[0]; rn[7] = stage_ptr(rG, strU, (N - 1))[DQ01];
   double S = 0.0, T = 0.0, U = 0.0, V = 0.0, p1 = 0.0, p2 = 0.0;   // P = 0, p = 0 behind the last stage
   WSYNC();
+  lds_requests_done();   // (the record of stage N - 1 is in: no stage waits at its top)
   RicStamps rst;
   rst.start();
   for (int k = N - 1; k >= 0; k--) {

@@ -10,6 +10,11 @@ enum StampPhase { PH_SWEEP = 0, PH_DEC = 1, PH_RIC = 2, PH_STEP = 3 };   // word
 // cycles per section of k_sweep / of the arms' sweep call, summed over the wavefronts of all launches
 // (static: one copy per translation unit, read through the unit's entries of the variant table)
 static __device__ long long g_sst[8];
+#endif
+// (-DRMPC_STAMPS_CALLS_ONLY beside -DRMPC_STAMPS: the pass loop's stamps alone.  The section stamps stand inside the sweep
+//  call and every one of them is a scalar-memory read with its wait: they move what the call's stamp is taken to measure,
+//  DESIGN.md 5.1.  The section lines of scripts/fused_stamps.py are empty then.)
+#if defined(RMPC_STAMPS) && !defined(RMPC_STAMPS_CALLS_ONLY)
 // Sections of a sweep: st(i) adds the cycles since the previous stamp to section i.
 struct SecStamps {
   long long acc[8], t0;
@@ -39,6 +44,16 @@ struct SecStamps {
     }
   }
 };
+#else
+struct SecStamps {
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ void operator()(int) {}
+  template <class O> __device__ __forceinline__ void put(O &, int, int) const {}
+  template <class O> __device__ __forceinline__ void get(const O &, int, int) {}
+  __device__ __forceinline__ void flush(bool, int) {}
+};
+#endif
+#ifdef RMPC_STAMPS
 // The pass loop of k_fused / k_fused_arm: cycles per phase, event counters and the wavefront's 8-word record in
 // FusedWs::stamps (read by scripts/fused_stamps.py and tests/tools/dev_arm_fused_stamps.py).
 struct PassStamps {
@@ -76,7 +91,9 @@ struct PassStamps {
   // empty function, changes how production code schedules their initialisation.)
   template <class O>
   __device__ __forceinline__ void sections(const O o) {
+#ifndef RMPC_STAMPS_CALLS_ONLY
     for (int i = 0; i < 6; i++) sec[i] += __builtin_amdgcn_readfirstlane((int)o.tk[i]);
+#endif
   }
   __device__ __forceinline__ void sweep_returned() { t_sub = __builtin_amdgcn_s_memtime(); }
   __device__ __forceinline__ void sweep_reduced() {
@@ -107,13 +124,6 @@ struct PassStamps {
   }
 };
 #else
-struct SecStamps {
-  __device__ __forceinline__ void start() {}
-  __device__ __forceinline__ void operator()(int) {}
-  template <class O> __device__ __forceinline__ void put(O &, int, int) const {}
-  template <class O> __device__ __forceinline__ void get(const O &, int, int) {}
-  __device__ __forceinline__ void flush(bool, int) {}
-};
 struct PassStamps {
   __device__ __forceinline__ void start() {}
   __device__ __forceinline__ void hand_begin() {}

@@ -529,7 +529,7 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
           var_load(std::integral_constant<int, j>{}, vring[0]);
           var_compute(std::integral_constant<int, j>{}, vring[0]);
         }
-        if constexpr (FIN) finalize_var(std::integral_constant<int, j>{});
+        if constexpr (FIN && j >= NQ) finalize_var(std::integral_constant<int, j>{});   // (the first range holds no j < NQ)
       });
     }
   };
@@ -785,7 +785,13 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
 
   st(1);
   // ---- the remaining single-variable rows -----------------------------------------------
-  run_vars(std::integral_constant<int, Ord::NFIRST>{}, std::integral_constant<int, NV>{}, FalseT{},
+  // (FINROWS, the chain without slack in its own order under a generated view: a variable j >= NQ is finalised right
+  //  behind its rows and the q variables behind the defect as before, where all at the end kept every accumulator alive to
+  //  the end of the stage and the merged form paid for that in register copies.  Nothing a variable j >= NQ contributes
+  //  to is formed after its rows, and rstat is a maximum: the same values.  Finalising the q variables right behind the
+  //  range as well costs the later-pass call 8 accumulation registers more than it had: DESIGN.md 5.1)
+  constexpr bool FINROWS = CHAIN && !EARLY && NS == 0 && V::SPEC;
+  run_vars(std::integral_constant<int, Ord::NFIRST>{}, std::integral_constant<int, NV>{}, std::integral_constant<bool, FINROWS>{},
            std::integral_constant<bool, PRE2>{});
 
   st(2);
@@ -811,6 +817,8 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
     if constexpr (EARLY) {
       for_range<0, NQ>(finalize_var);
       if constexpr (NS > 0) finalize_var(std::integral_constant<int, NX>{});
+    } else if constexpr (FINROWS) {
+      for_range<0, NQ>(finalize_var);
     } else {
       for_range<0, NV>(finalize_var);
     }

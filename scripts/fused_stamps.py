@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Development aid: phase breakdown of the fused kernel (library built with -DRMPC_STAMPS, RMPC_LIB_PATH set)."""
+"""Development aid: phase breakdown of the fused kernel (library built with -DRMPC_STAMPS, RMPC_LIB_PATH set).
+With -DRMPC_STAMPS_CALLS_ONLY beside it the sweep call carries no section stamps and the section lines are left out:
+the phase figures are then those of the calls as a production build runs them (rmpc_stamps.hpp)."""
 import os
 import sys
 
