@@ -1,6 +1,7 @@
 // rmpc_fused.hpp -- k_fused: whole interior-point iterations of an instance inside one wavefront, with its workspace
 // (FusedWs), its phase functions and the sweep / step calls.  Part of rmpc_kernels.hip (included there, inside namespace
-// rmpc); needs rmpc_sweep.hpp, rmpc_inst.hpp, rmpc_riccati.hpp and rmpc_step.hpp.  rmpc_arm_fused.hpp follows it.
+// rmpc); needs rmpc_sweep.hpp, rmpc_inst.hpp, rmpc_riccati.hpp (riccati_recursion, and from rmpc_ric_common.hpp the slots'
+// layout FusedSlots, RicLds, StepOut and WSYNC) and rmpc_step.hpp.  rmpc_arm_fused.hpp follows it.
 
 // ===========================================================================
 // k_fused: whole interior-point iterations of an instance inside ONE wavefront

@@ -52,7 +52,8 @@ namespace rmpc {
 #include "rmpc_solver.hpp"         // constants, the workspace Ws, IDX, small helpers
 #include "rmpc_sweep.hpp"          // sweep_body, k_sweep (+ rmpc_stamps.hpp: the stamp recorders)
 #include "rmpc_inst.hpp"           // per-instance state and decisions (inst_decide, inst_after_recursion)
-#include "rmpc_riccati.hpp"        // the Riccati recursion (riccati_recursion: one function per path)
+#include "rmpc_riccati.hpp"        // the Riccati recursion (riccati_recursion; + rmpc_ric_common.hpp: what the paths share,
+                                   //  and one header per path: rmpc_ric_point / _slack / _dd / _arm / _dense.hpp)
 #include "rmpc_pass_riccati.hpp"   // k_riccati, k_riccati_lane
 #include "rmpc_step.hpp"           // step_body, k_step
 #include "rmpc_fused.hpp"          // k_fused

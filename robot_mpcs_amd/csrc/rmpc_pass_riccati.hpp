@@ -1,6 +1,7 @@
 // rmpc_pass_riccati.hpp -- the pass kernels around the recursion: k_riccati (a wavefront, or half of one, per instance)
 // and k_riccati_lane (a lane per instance).  Part of rmpc_kernels.hip (included there, inside namespace rmpc); needs
-// rmpc_inst.hpp and rmpc_riccati.hpp.
+// rmpc_inst.hpp and rmpc_riccati.hpp (riccati_recursion; the lane kernel takes the small linear algebra, ric_tri and the
+// chain's [A|B] from rmpc_ric_common.hpp).
 
 // ===========================================================================
 // k_riccati: per-instance decisions + block-tridiagonal Riccati recursion
@@ -116,14 +117,6 @@ __global__ __launch_bounds__(64) void k_riccati_lane(const DevModel M, const Ws 
   const double h = M.dt, h2 = 0.5 * M.dt * M.dt;
   constexpr int NP2 = NX * (NX + 1) / 2;
   constexpr int OFF_KFF = NW * NX, OFF_PT = NW * NX + NW, OFF_P = OFF_PT + NP2, OFF_RC = OFF_P + NX;
-  auto tri = [](int i, int j) __attribute__((always_inline)) {
-    const int lo = i < j ? i : j, hi = i < j ? j : i;
-    return lo * NX - lo * (lo - 1) / 2 + (hi - lo);
-  };
-  // kind of a variable (0 q, 1 v, 2 u, 3 slack) and its joint: rows of [A | B]^T are (1, 0), (h, 1), (h2, h) on the
-  // (q+, v+) block rows
-  auto kind = [](int i) __attribute__((always_inline)) { return i < NQ ? 0 : (i < NX ? 1 : (i >= NX + NS ? 2 : 3)); };
-  auto joint = [](int i) __attribute__((always_inline)) { return i < NQ ? i : (i < NX ? i - NQ : (i >= NX + NS ? i - NX - NS : 0)); };
   double P[NX][NX], pv[NX];
 #pragma unroll
   for (int i = 0; i < NX; i++) {
@@ -150,7 +143,7 @@ __global__ __launch_bounds__(64) void k_riccati_lane(const DevModel M, const Ws 
         const int lo = i < j ? i : j, hi = i < j ? j : i;
         double v = 0.0;
         if (hi < NQ) {
-          const int t = lo * NQ - lo * (lo - 1) / 2 + (hi - lo);
+          const int t = ric_tri<NQ>(i, j);
           v = rec[C::R_Q + t] - cwt * (C::CURV ? (double)rec[C::R_C + t] : 0.0);
         } else if (lo == hi) {
           v = rec[C::R_DG + (lo - NQ)];
@@ -159,12 +152,11 @@ __global__ __launch_bounds__(64) void k_riccati_lane(const DevModel M, const Ws 
         } else if (NS > 0 && hi == NX) {
           v = rec[C::R_CS + lo];
         }
-        const int ki = kind(i), kj = kind(j);
-        if (ki != 3 && kj != 3) {
-          const int ii = joint(i), jj = joint(j);
-          const double l1 = ki == 0 ? 1.0 : (ki == 1 ? h : h2), l2 = ki == 0 ? 0.0 : (ki == 1 ? 1.0 : h);
-          const double c1 = kj == 0 ? 1.0 : (kj == 1 ? h : h2), c2 = kj == 0 ? 0.0 : (kj == 1 ? 1.0 : h);
-          const double add = l1 * (c1 * P[ii][jj] + c2 * P[ii][NQ + jj]) + l2 * (c1 * P[NQ + ii][jj] + c2 * P[NQ + ii][NQ + jj]);
+        const ChainVar<C> vi(i), vj(j);
+        if (vi.kind != 3 && vj.kind != 3) {
+          const int ii = vi.joint(), jj = vj.joint();
+          const ChainRow l = vi.row(h, h2), c = vj.row(h, h2);
+          const double add = l.f1 * (c.f1 * P[ii][jj] + c.f2 * P[ii][NQ + jj]) + l.f2 * (c.f1 * P[NQ + ii][jj] + c.f2 * P[NQ + ii][NQ + jj]);
           v += rec_cost ? add : 0.0;
         }
         Q[i][j] = v;
@@ -180,36 +172,18 @@ __global__ __launch_bounds__(64) void k_riccati_lane(const DevModel M, const Ws 
 #pragma unroll
     for (int i = 0; i < NV; i++) {
       double v = rec[C::R_Q0 + i] - mu * rec[C::R_Q1 + i];
-      const int ki = kind(i);
-      if (ki != 3) {
-        const int ii = joint(i);
-        const double l1 = ki == 0 ? 1.0 : (ki == 1 ? h : h2), l2 = ki == 0 ? 0.0 : (ki == 1 ? 1.0 : h);
-        const double add = l1 * Pc[ii] + l2 * Pc[NQ + ii];
+      const ChainVar<C> vi(i);
+      if (vi.kind != 3) {
+        const int ii = vi.joint();
+        const ChainRow l = vi.row(h, h2);
+        const double add = l.f1 * Pc[ii] + l.f2 * Pc[NQ + ii];
         v += rec_cost ? add : 0.0;
       }
       q[i] = v;
     }
     // ---- Cholesky of Qww, gains ----------------------------------------------------------------------------------
     double L[NW][NW], invd[NW];
-#pragma unroll
-    for (int j = 0; j < NW; j++) {
-      double dg = Q[NX + j][NX + j];
-#pragma unroll
-      for (int l = 0; l < j; l++) dg -= L[j][l] * L[j][l];
-      if (!(dg > 0.0)) chol_ok = false;
-      double inv = __builtin_amdgcn_rsq(dg);
-      inv = inv * (1.5 - 0.5 * dg * inv * inv);
-      inv = inv * (1.5 - 0.5 * dg * inv * inv);
-      L[j][j] = dg * inv;
-      invd[j] = inv;
-#pragma unroll
-      for (int i = j + 1; i < NW; i++) {
-        double sacc = Q[NX + i][NX + j];
-#pragma unroll
-        for (int l = 0; l < j; l++) sacc -= L[i][l] * L[j][l];
-        L[i][j] = sacc * inv;
-      }
-    }
+    chol_factor<NW, NX>(Q, L, invd, chol_ok);
     double K[NW][NX], kff[NW];
 #pragma unroll
     for (int c = 0; c < NX; c++) {
@@ -258,7 +232,7 @@ __global__ __launch_bounds__(64) void k_riccati_lane(const DevModel M, const Ws 
 #pragma unroll
     for (int i = 0; i < NX; i++) {
 #pragma unroll
-      for (int j = i; j < NX; j++) kpk[OFF_PT + tri(i, j)] = P[i][j];
+      for (int j = i; j < NX; j++) kpk[OFF_PT + ric_tri<NX>(i, j)] = P[i][j];
       kpk[OFF_P + i] = pv[i];
       kpk[OFF_RC + i] = rcv[i];
     }
@@ -289,7 +263,7 @@ __global__ __launch_bounds__(64) void k_riccati_lane(const DevModel M, const Ws 
         for (int i = 0; i < NX; i++) {
           double sacc = im[OFF_P + i];
 #pragma unroll
-          for (int j = 0; j < NX; j++) sacc += im[OFF_PT + tri(i, j)] * dx[j];
+          for (int j = 0; j < NX; j++) sacc += im[OFF_PT + ric_tri<NX>(i, j)] * dx[j];
           W.nunew[(size_t)i * SS + o] = sacc;
         }
       }

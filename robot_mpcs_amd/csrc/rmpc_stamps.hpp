@@ -3,7 +3,7 @@
 // Partials, whose tk words they fill; needs nothing else.
 
 // Development aid (builds with -DRMPC_STAMPS): cycle stamps of the sweeps and of the fused kernels' pass loops.  Like
-// RicStamps (rmpc_riccati.hpp) the recorders have a body in those builds and none otherwise, so the places that
+// RicStamps (rmpc_ric_common.hpp) the recorders have a body in those builds and none otherwise, so the places that
 // stamp carry no #ifdef and a production build is the code without them.
 enum StampPhase { PH_SWEEP = 0, PH_DEC = 1, PH_RIC = 2, PH_STEP = 3 };   // words 0 .. 3 of a wavefront's record
 #ifdef RMPC_STAMPS

@@ -10,15 +10,16 @@ In the same test the returned blocks are checked against the numpy formula of te
 with the returned t, lam and mu, at that test's tolerances, and t / lam against the cold and the warm start rule: the
 warm first pass at block level.
 
-Paths (rmpc_riccati.hpp) and how a handle reaches them:
-  ric_point_robot           fused, chains n <= 3 without slack        cfg2, chain2; N = 1, 2, 5, 31, 32
-  ric_chain_slack_backward  fused, point robot with the slack        cfg2 slack; the same horizons
-  ric_dd_backward           fused, diff-drive                         cfg3, boxer, wc_boxer_slack
-  ric_arm_block             k_fused_arm, three parts (3 N <= 64)     cfg4, chain5, chain6; N = 12, 17, 21
+Paths (riccati_recursion in rmpc_riccati.hpp picks one; each is in the header named in brackets) and how a handle
+reaches them:
+  ric_point_robot           fused, chains n <= 3 without slack        cfg2, chain2; N = 1, 2, 5, 31, 32      [rmpc_ric_point.hpp]
+  ric_chain_slack_backward  fused, point robot with the slack        cfg2 slack; the same horizons           [rmpc_ric_slack.hpp]
+  ric_dd_backward           fused, diff-drive                         cfg3, boxer, wc_boxer_slack             [rmpc_ric_dd.hpp]
+  ric_arm_block             k_fused_arm, three parts (3 N <= 64)     cfg4, chain5, chain6; N = 12, 17, 21    [rmpc_ric_arm.hpp]
   ric_arm_block             k_fused_arm, two parts                   the same, RMPC_ARM_TWO_PARTS=1; N = 22, 30 (no room for three)
   ric_arm_block             k_riccati (RMPC_NO_FUSED=1)               the same arms; N = 40 without the switch
-  ric_backward              pass kernels                              chain4, chain8, wc_panda, boxer, cfg2 N = 40
-  k_riccati_lane            RMPC_NO_FUSED=1 RMPC_RIC_LANE=2           cfg2, chain2
+  ric_backward              pass kernels                              chain4, chain8, wc_panda, boxer, cfg2 N = 40 [rmpc_ric_dense.hpp]
+  k_riccati_lane            RMPC_NO_FUSED=1 RMPC_RIC_LANE=2           cfg2, chain2                            [rmpc_pass_riccati.hpp]
   runtime tables            RMPC_NO_SPEC=1                            cfg2
 and one case per pass-kernel family at B = 520 >= kGroupedMin (eight instances tiled 65 times, not a multiple of 64):
 copies equal bit for bit, each compared with its reference.
