@@ -3,7 +3,7 @@
 // pose (k_lidar_project, the expressions of k_lidar) and correlative scan matching over a lattice of poses around that
 // pose (k_scan_match; Olson 2009, the brute-force half).  A score is an int32 sum of table entries and the choice a
 // minimum of one 64-bit key, so no result depends on the order in which lanes meet.  Contraction is off in every
-// function here: the kernels evaluate the restatement's expressions (tests/test_localization_cpu.py).
+// function here: the kernels evaluate the restatement's expressions (tests/localization_reference.py).
 
 namespace rmpc {
 

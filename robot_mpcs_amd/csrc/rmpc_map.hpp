@@ -11,7 +11,7 @@
 //   5. n + 1 cells from (r, c): misses += 1 on a cell inside the map, hits += 1 instead on the last cell of a hit;
 //      between two visits the column steps (c += sc, tx from the new c) when (tx <= ty and c != c1) or r == r1, else
 //      the row.  The walk (Amanatides & Woo) moves towards (r1, c1) in both coordinates and ends there.
-// Contraction is off: the kernels evaluate the restatement's expressions (tests/test_mapping_cpu.py), and the counts
+// Contraction is off: the kernels evaluate the restatement's expressions (tests/mapping_reference.py), and the counts
 // are integers, so a map is bitwise the same whatever the order of the adds.
 
 namespace rmpc {

@@ -11,7 +11,7 @@
 //   a shape that contains the origin is ignored by that ray (t_enter <= 0, c <= 0): FSD would otherwise get a point
 //   at its own seed, a plane with normal 0;
 //   t              the least hit distance, range when nothing is hit within range.
-// Contraction is off: the kernels evaluate the restatement's expressions (tests/test_lidar_cpu.py).
+// Contraction is off: the kernels evaluate the restatement's expressions (tests/lidar_reference.py).
 // The fleet's separating planes (k_fleet_planes, below) live here too: their points come from k_plan_points.
 
 namespace rmpc {

@@ -6,7 +6,7 @@ cells of 0.45 m) and a 128 x 128 store (0.15 m cells), both merged into boxes by
 
   - times are medians of --reps event-timed launches (each synchronised), after one warm-up launch;
   - rays/s and box tests/s of the scan (B R and B R nbox over its time);
-  - the per-robot numpy restatement of tests/test_lidar_cpu.py (scan_ref, plan_points_ref, oracle/fsd_numpy.py) on the
+  - the per-robot numpy restatement of tests/lidar_reference.py (scan_ref, plan_points_ref, oracle/fsd_numpy.py) on the
     host CPU of the same box, one robot at a time: a yardstick of the scale, not a tuned CPU baseline.
 
     timeout -k 10 300 python scripts/bench_lidar.py [--reps 20]
@@ -31,7 +31,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 def cpu_ms_per_robot(pose, boxes, N, K, robots=8):
     """Median ms of the numpy restatement for one robot: scan, seeds, N decompositions."""
     from oracle.fsd_numpy import free_space_decomposition
-    from test_lidar_cpu import plan_points_ref, scan_ref
+    from lidar_reference import plan_points_ref, scan_ref
     times = []
     for b in range(robots):
         t0 = time.perf_counter()

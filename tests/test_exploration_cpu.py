@@ -1,102 +1,19 @@
 """The rules of frontier exploration (include/rmpc.h: rmpc_grid_frontier_device, rmpc_grid_fields_seeded_device,
-rmpc_grid_descend_device) restated in numpy, checked on hand-computed cases and in a kinematic
-exploration of seeded stores; tests/test_gpu_exploration.py holds the device against the restatements."""
+rmpc_grid_descend_device) as restated in tests/exploration_reference.py, checked on hand-computed cases
+and in the kinematic exploration of seeded stores of tests/exploration_cases.py; tests/test_gpu_exploration.py holds the
+device against the restatements."""
 import ctypes as C
-import functools
-import heapq
 import math
 
 import numpy as np
 import pytest
 
-from robot_mpcs_amd.global_planner import FREE, OCC
-from test_global_planner_cpu import MOVES, MOVES8, S2, descend_ref, field_ref, inflate_ref
-from test_lidar_cpu import scan_ref
-from test_mapping_cpu import mark_ref, occupancy_ref
+from exploration_cases import KINEMATIC, kinematic, one_seed
+from exploration_reference import (BAD_MAP, BAD_SEED, OK, OUTSIDE, TOO_LONG, descend_seeded_ref, field_seeded_ref,
+                                   frontier_ref)
+from global_planner_reference import S2, descend_ref, field_ref
 
 INF = math.inf
-OK, OUTSIDE, TOO_LONG, BAD_MAP, BAD_SEED = 0, -3, -4, -5, -7
-
-
-def frontier_ref(hits, misses, enlarged, occ=0.8, nmoves=4, unknown_value=1.0):
-    """rmpc_grid_frontier_device: (plan (H, W), seed (H, W), count)"""
-    known = (np.asarray(hits).astype(np.int64) + np.asarray(misses).astype(np.int64)) != 0
-    H, W = known.shape
-    plan = np.where(known, enlarged, unknown_value)
-    unknown = np.pad(~known, 1, constant_values=False)          # the map's edge is not unknown
-    beside = np.zeros((H, W), dtype=bool)
-    for dx, dy, _ in MOVES8[:nmoves]:
-        beside |= unknown[1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
-    frontier = known & (np.asarray(enlarged) < occ) & beside
-    return plan, np.where(frontier, 0.0, INF), int(frontier.sum())
-
-
-def field_seeded_ref(data, seeds, movement=8, f=3.0, occ=0.8):
-    """rmpc_grid_fields_seeded_device for one field, a heap Dijkstra from every finite seed on a free cell:
-    D(u) = min(seed(u), min_v (delta + (f data[v] + D(v)))), +inf on occupied cells.  Returns (D (H, W), status)."""
-    H, W = data.shape
-    free = data < occ
-    if (free & ~(data >= 0.0)).any():
-        return np.full((H, W), INF), BAD_MAP
-    s = np.where(free, seeds, INF)
-    if (~(s >= 0.0)).any():
-        return np.full((H, W), INF), BAD_SEED
-    D = s.astype(float).ravel().copy()
-    heap = [(D[c], int(c)) for c in np.flatnonzero(np.isfinite(D))]
-    heapq.heapify(heap)
-    done = np.zeros(H * W, bool)
-    while heap:
-        d, v = heapq.heappop(heap)
-        if done[v]:
-            continue
-        done[v] = True
-        vr, vc = divmod(v, W)
-        ev = f * data[vr, vc] + D[v]
-        for dx, dy, dc in MOVES[movement]:
-            ur, uc = vr - dy, vc - dx           # u + move = v
-            if 0 <= ur < H and 0 <= uc < W and free[ur, uc]:
-                u = ur * W + uc
-                cand = dc + ev
-                if cand < D[u]:
-                    D[u] = cand
-                    heapq.heappush(heap, (cand, u))
-    return D.reshape(H, W), OK
-
-
-def descend_seeded_ref(data, D, seeds, start_cell, movement=8, f=3.0, occ=0.8, max_len=None):
-    """rmpc_grid_descend_device for one robot: (cells written, len)"""
-    H, W = data.shape
-    max_len = H * W if max_len is None else max_len
-    if not 0 <= start_cell < H * W:
-        return [], OUTSIDE
-    Df, Sf = D.ravel(), np.asarray(seeds).ravel()
-    u, path = int(start_cell), []
-    while True:
-        if len(path) >= max_len:
-            return path, TOO_LONG
-        source = Df[u] < INF and Df[u] == Sf[u]
-        nxt = -1
-        if not source:
-            r, c = divmod(u, W)
-            best = INF
-            for dx, dy, dc in MOVES[movement]:
-                rr, cc = r + dy, c + dx
-                if 0 <= rr < H and 0 <= cc < W and data[rr, cc] < occ:
-                    cand = dc + (f * data[rr, cc] + D[rr, cc])
-                    if cand < best:
-                        best, nxt = cand, rr * W + cc
-            if nxt < 0:
-                return [], 0
-        path.append(u)
-        if source:
-            return path, len(path)
-        u = nxt
-
-
-def one_seed(shape, cells, values=None):
-    s = np.full(shape, INF)
-    s.ravel()[list(cells)] = 0.0 if values is None else values
-    return s
 
 
 # ---- hand cases on a 4 x 6 map ---------------------------------------------------------------------------------------
@@ -232,67 +149,6 @@ def test_descent_starts_and_ends():
 
 
 # ---- kinematic exploration: robots that move one cell per step along the descent ---------------------------------------
-def explore_kinematic(seed, B, max_steps=1500, replan_every=5, rays=64, max_range=10.0):
-    """Robots without a map or goals in the examples' store (robot_mpcs_amd/store.py), packed into one corner, in the order of
-    that example's control step (follower -> scan -> mark -> re-plan -> move): the follower moves on by one waypoint;
-    the robot scans from its cell's centre and the scan is marked; every replan_every steps the evidence is classified
-    with unknown = free, enlarged, the frontier found, the seeded field built and one descent per robot made, which
-    restarts the route at the robot's own cell (RouteFollower.replace); then the robot stands on its waypoint.  So a
-    re-plan step moves nobody, and a route is followed for replan_every - 1 cells before the next one.  Returns the step
-    of the first re-plan without a frontier (None if there was none), the free cells and those among them never seen,
-    and the number of robot-steps spent on a cell of the truly enlarged map."""
-    from robot_mpcs_amd.global_planner import png_values
-    from robot_mpcs_amd.store import STORE, store_map
-    from robot_mpcs_amd.utils.exploration import corner_starts
-    from robot_mpcs_amd.utils.lidar import boxes_from_grid
-    H, W, cell, x0 = STORE.H, STORE.W, STORE.cell, STORE.x0
-    raw = store_map(seed)
-    boxes = boxes_from_grid(raw, x0, x0, cell)
-    truly_enlarged = inflate_ref(png_values(raw), cell, STORE.size_robot, 0.29)[0] > 0.5
-    cells = corner_starts(raw, B).astype(np.int64)
-    hits, misses = np.zeros((H, W), dtype=np.int64), np.zeros((H, W), dtype=np.int64)
-    routes, idx = [[int(c)] for c in cells], [0] * B
-    ended, on_enlarged = None, 0
-    for step in range(max_steps):
-        for b in range(B):
-            if idx[b] < len(routes[b]) - 1:
-                idx[b] += 1
-        pose = np.stack([x0 + (cells % W) * cell, x0 + (cells // W) * cell, np.zeros(B)], 1)
-        pts, t, _ = scan_ref(pose, rays, -math.pi, math.pi, max_range, (0.0, 0.0), 0.02, boxes)
-        org = np.concatenate([pose[:, :2], np.full((B, 1), 0.02)], 1)
-        _, _, skipped = mark_ref(org, pts, t, H, W, x0, x0, cell, max_range, 1e-6, hits, misses)
-        assert skipped == 0
-        if step % replan_every == 0:
-            grid, _, _ = occupancy_ref(hits, misses, 3, 1, 0, FREE, OCC, FREE)
-            enlarged, _ = inflate_ref(grid, cell, STORE.size_robot, 0.29)
-            plan, seeds, count = frontier_ref(hits, misses, enlarged)
-            if count == 0:
-                ended = step
-                break
-            D, status = field_seeded_ref(plan, seeds)
-            assert status == OK
-            for b in range(B):
-                path, n = descend_seeded_ref(plan, D, seeds, int(cells[b]), max_len=4 * (H + W))
-                if n > 0:
-                    routes[b], idx[b] = path, 0
-        for b in range(B):
-            cells[b] = routes[b][idx[b]]
-        on_enlarged += int(truly_enlarged.ravel()[cells].sum())
-    free = raw < 0.5
-    unseen = free & (hits + misses == 0)
-    return dict(ended=ended, free=int(free.sum()), unseen=int(unseen.sum()), on_enlarged=on_enlarged)
-
-
-KINEMATIC = [(0, 1, 1371), (0, 8, 1371), (0, 32, 1371), (3, 8, 1365)]     # (store seed, robots, free cells of the store)
-
-
-@functools.lru_cache(maxsize=None)
-def kinematic(seed, B):
-    r = explore_kinematic(seed, B)
-    print(dict(seed=seed, B=B, **r))
-    return r
-
-
 @pytest.mark.parametrize("seed,B,free", KINEMATIC)
 def test_kinematic_exploration_ends_sees_every_free_cell_and_stays_clear(seed, B, free):
     """The rules end on their own: no frontier is left within 1500 steps (the first re-plan without one came at step

@@ -1,30 +1,23 @@
 """Coordinated exploration on the device (rmpc_grid_targets_device, rmpc_grid_route_costs_device,
-rmpc_assign_greedy_device, FrontierGoals(tile=...)) against the numpy restatements of tests/test_assignment_cpu.py, bit
+rmpc_assign_greedy_device, FrontierGoals(tile=...)) against the numpy restatements of tests/assignment_reference.py, bit
 for bit; stream ordering; the closed loop of examples/fleet_store_frontier.py with and without coordination."""
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
+from assignment_cases import random_costs
+from assignment_reference import greedy_ref, greedy_sorted_ref, route_costs_ref, targets_ref, tiles_of
 from example_loader import load_example
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from test_assignment_cpu import (greedy_ref, greedy_sorted_ref, random_costs, route_costs_ref, targets_ref,  # noqa: E402
-                                 tiles_of)
-from test_exploration_cpu import (FREE, OCC, OK, OUTSIDE, descend_seeded_ref, field_seeded_ref,  # noqa: E402
-                                  frontier_ref)
-from test_global_planner_cpu import inflate_ref  # noqa: E402
-from test_gpu_exploration import evidence, grid_of  # noqa: E402
-from test_mapping_cpu import occupancy_ref  # noqa: E402
+from exploration_cases import evidence, grid_of
+from exploration_reference import OK, OUTSIDE, descend_seeded_ref, field_seeded_ref, frontier_ref
+from global_planner_reference import inflate_ref
+from gpu_support import DEV, _t
+from mapping_reference import occupancy_ref
+from robot_mpcs_amd.global_planner import FREE, OCC
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 INF = math.inf
 
 
@@ -37,14 +30,10 @@ def rt():
     return dict(torch=torch, lib=_lib)
 
 
-def _t(torch, a, dtype=None):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype if dtype is not None else torch.float64).to(DEV)
-
-
 # ---- targets ---------------------------------------------------------------------------------------------------------
 def seed_grid(H, W, kind, rng):
     """"binary": a fifth of the cells are sources, some with a start potential; "frontier": the frontier of sparse random
-    evidence (tests/test_gpu_exploration.py); "none": no source"""
+    evidence (tests/exploration_cases.py); "none": no source"""
     if kind == "none":
         return np.full((H, W), INF)
     if kind == "frontier":

@@ -1,28 +1,23 @@
 """Frontier exploration on the device (rmpc_grid_frontier_device, rmpc_grid_fields_seeded_device,
-rmpc_grid_descend_device, FrontierGoals) against the numpy restatements of tests/test_exploration_cpu.py; the seeded
+rmpc_grid_descend_device, FrontierGoals) against the numpy restatements of tests/exploration_reference.py; the seeded
 field against rmpc_grid_fields_device, bit for bit; stream ordering; the closed loop of
 examples/fleet_store_frontier.py."""
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
 from example_loader import load_example
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from test_exploration_cpu import (BAD_MAP, BAD_SEED, FREE, OCC, OK, OUTSIDE, TOO_LONG, descend_seeded_ref,  # noqa: E402
-                                  field_seeded_ref, frontier_ref, one_seed)
-from test_global_planner_cpu import inflate_ref  # noqa: E402
-from test_mapping_cpu import occupancy_ref  # noqa: E402
+from exploration_cases import evidence, grid_of, one_seed
+from exploration_reference import (BAD_MAP, BAD_SEED, OK, OUTSIDE, TOO_LONG, descend_seeded_ref, field_seeded_ref,
+                                   frontier_ref)
+from global_planner_reference import inflate_ref
+from gpu_support import DEV, _t
+from mapping_reference import occupancy_ref
+from robot_mpcs_amd.global_planner import FREE, OCC
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 INF = math.inf
 
 
@@ -35,29 +30,7 @@ def rt():
     return dict(torch=torch, lib=_lib)
 
 
-def _t(torch, a, dtype=None):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype if dtype is not None else torch.float64).to(DEV)
-
-
 # ---- the frontier ----------------------------------------------------------------------------------------------------
-def evidence(H, W, kind, rng):
-    """(hits, misses, enlarged): "sparse" random evidence on about 40 % of the cells in blobs and single cells"""
-    if kind == "unknown":
-        hits = misses = np.zeros((H, W), dtype=np.int32)
-    elif kind == "known":
-        hits, misses = rng.integers(0, 3, (H, W)).astype(np.int32), rng.integers(1, 9, (H, W)).astype(np.int32)
-    else:
-        known = rng.uniform(size=(H, W)) < 0.15
-        for _ in range(max(1, H * W // 200)):
-            r, c, h, w = rng.integers(0, H), rng.integers(0, W), rng.integers(1, 12), rng.integers(1, 12)
-            known[r:r + h, c:c + w] = True
-        hits = np.where(known & (rng.uniform(size=(H, W)) < 0.3), rng.integers(1, 5, (H, W)), 0).astype(np.int32)
-        misses = np.where(known & (hits == 0), rng.integers(1, 50, (H, W)), 0).astype(np.int32)
-        hits[0, 0], misses[0, 0] = -(1 << 31), -(1 << 31)     # wrapped counters: known in 64 bits, 0 in 32
-    enlarged = (rng.uniform(size=(H, W)) < 0.3).astype(np.float64)
-    return hits, misses, enlarged
-
-
 @pytest.mark.parametrize("H,W", [(1, 1), (1, 7), (3, 3), (37, 53), (41, 41), (128, 128)])
 @pytest.mark.parametrize("kind", ["sparse", "unknown", "known"])
 def test_frontier_matches_restatement(rt, H, W, kind):
@@ -83,18 +56,6 @@ def test_frontier_matches_restatement(rt, H, W, kind):
 
 
 # ---- the seeded field --------------------------------------------------------------------------------------------------
-def grid_of(H, W, kind, seed):
-    rng = np.random.default_rng(seed)
-    if kind == "store":
-        from robot_mpcs_amd.global_planner import shelf_map
-        big = H >= 100
-        return shelf_map(H, W, seed=3, aisle=9 if big else 6, shelf=4 if big else 2, gap=6 if big else 5)
-    occ = rng.uniform(size=(H, W)) < 0.25
-    if kind == "binary":
-        return occ.astype(np.float64)
-    return np.where(occ, 1.0, rng.uniform(0.0, 0.7, (H, W)))
-
-
 def seeds_of(data, G, seed):
     """G seed grids: 1 .. 12 sources each on free cells, a third of them with a start potential in [0, 6), two seeds on
     occupied cells"""

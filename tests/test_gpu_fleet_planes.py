@@ -1,5 +1,5 @@
 """Fleet separation on the device (rmpc_fleet_points_device, rmpc_fleet_planes_device, NeighbourPlanes) against the
-numpy restatement of tests/test_fleet_planes_cpu.py; stream ordering; solves with mid-loop planes against the CPU
+numpy restatement of tests/fleet_planes_reference.py; stream ordering; solves with mid-loop planes against the CPU
 oracle; the closed loops of examples/fleet_crossing.py with and without the neighbours."""
 import math
 
@@ -7,11 +7,11 @@ import numpy as np
 import pytest
 
 from example_loader import load_example
-from test_fleet_planes_cpu import fleet_planes_ref, fleet_points_ref, neighbours_ref
+from fleet_planes_reference import fleet_planes_ref, fleet_points_ref, neighbours_ref
+from gpu_support import DEV, _t
+from lidar_reference import plan_points_ref
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module")
@@ -21,10 +21,6 @@ def rt():
     g.build()
     from robot_mpcs_amd import _lib
     return dict(torch=torch, lib=_lib)
-
-
-def _t(torch, a, dtype=None):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype if dtype is not None else torch.float64).to(DEV)
 
 
 def _planes(rt, pts, radius, K, max_range, nobst=None, slot0=0, init=None, stream=None):
@@ -71,7 +67,6 @@ def test_points_match_restatement(rt, heading):
 
 def test_plan_points_entry_is_unchanged(rt):
     """rmpc_plan_points_device reads stage k (no shift) with the sensor offset: the lidar's seeds"""
-    from test_lidar_cpu import plan_points_ref
     torch = rt["torch"]
     rng = np.random.default_rng(3)
     B, N = 300, 10

@@ -2,7 +2,7 @@
 call (wave_reduce_many: permlane swaps and DPP row moves instead of the LDS crossbar) and the rollout of the point
 robot's recursion (ric_point_robot: dx handed round in registers by DPP row moves instead of a store, an ordering point
 and a read-back per stage).  Both are arithmetic-neutral, so the bar is the one of tests/test_gpu_parity.py -- flags,
-iteration counts and plans against the CPU oracle (_check_plan), the objective to 1e-9, every oracle flag 1 or 2 -- at
+iteration counts and plans against the CPU oracle (check_plan), the objective to 1e-9, every oracle flag 1 or 2 -- at
 the smallest shapes that take each path: the rollout's first stage alone (N = 2), an odd stage behind the pairs of its
 loop (N = 3, 29, 31) and none (N = 4, 30, 32), both ends of the 32 slots, an idle half (odd B; B = 1), the gantry's lanes
 (chain2), the reductions in the body of k_fused (cfg3), the 64-lane tree (the pass kernels of chain4; cfg4's k_fused_arm,
@@ -19,7 +19,7 @@ import sys
 import numpy as np
 import pytest
 
-from test_gpu_parity import _check_plan
+from gpu_support import check_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -39,7 +39,7 @@ def rt():
 def _against_oracle(rt, sc, gpu):
     cpu = rt["Oracle"](sc.desc).solve_batch(sc.xinit, sc.x0, sc.params)
     assert np.all(np.isin(cpu["exitflag"], (1, 2))), cpu["exitflag"]
-    _check_plan(gpu, cpu, sc.desc["nx"] + sc.desc["ns"])
+    check_plan(gpu, cpu, sc.desc["nx"] + sc.desc["ns"])
     np.testing.assert_allclose(gpu["obj"], cpu["obj"], rtol=1e-9, atol=1e-9)
 
 

@@ -18,9 +18,11 @@ chain2 and wc_boxer_slack have an odd npar: every other stage row of the caller'
 16-byte boundaries and takes the path with a single word in front.  Both are cases below, and cfg2 with an odd horizon
 (time_horizon = 7) has odd b N + k at even npar.
 
-The comparisons with the oracle use the bars of tests/test_gpu_parity.py::_check_plan."""
+The comparisons with the oracle use the bars of tests/test_gpu_parity.py (check_plan of tests/gpu_support.py)."""
 import numpy as np
 import pytest
+
+from gpu_support import check_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -34,8 +36,7 @@ def rt():
     from oracle.oracle import Oracle
     from robot_mpcs_amd._lib import Solver
     from robot_mpcs_amd.scenarios import make_scenario
-    from test_gpu_parity import _check_plan
-    return dict(Oracle=Oracle, Solver=Solver, make_scenario=make_scenario, check_plan=_check_plan)
+    return dict(Oracle=Oracle, Solver=Solver, make_scenario=make_scenario, check_plan=check_plan)
 
 
 def _on_grid(rt, sc, B, grid, monkeypatch, run):

@@ -27,7 +27,7 @@ import tempfile
 import numpy as np
 import pytest
 
-from test_gpu_parity import _check_plan
+from gpu_support import check_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +48,7 @@ def _compare(name, kw, B, gpu, cpu, nxs):
     print("%s %s B=%d: flags %s, iterations gpu %s oracle %s, max plan error %.3e, max objective error %.3e" % (
         name, kw, B, gpu["exitflag"].tolist(), gpu["iters"].tolist(), cpu["iters"].tolist(),
         np.abs(gpu["z"] - cpu["z"]).max(), np.abs(gpu["obj"] - cpu["obj"]).max()))
-    _check_plan(gpu, cpu, nxs)
+    check_plan(gpu, cpu, nxs)
     np.testing.assert_allclose(gpu["obj"], cpu["obj"], rtol=1e-9, atol=1e-9)
     assert np.isin(cpu["exitflag"], (1, 2)).all()   # (every plan was compared)
 

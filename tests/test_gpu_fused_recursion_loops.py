@@ -22,7 +22,7 @@ import sys
 import numpy as np
 import pytest
 
-from test_gpu_parity import _check_plan
+from gpu_support import check_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +48,7 @@ def _against_oracle(rt, name, B, seed, **kw):
     s.close()
     print("%s %s B=%d: flags %s, iterations gpu %s oracle %s, max plan error %.3e" % (
         name, kw, B, gpu["exitflag"].tolist(), gpu["iters"].tolist(), cpu["iters"].tolist(), np.abs(gpu["z"] - cpu["z"]).max()))
-    _check_plan(gpu, cpu, sc.desc["nx"] + sc.desc["ns"])
+    check_plan(gpu, cpu, sc.desc["nx"] + sc.desc["ns"])
     np.testing.assert_allclose(gpu["obj"], cpu["obj"], rtol=1e-9, atol=1e-9)
     assert np.isin(cpu["exitflag"], (1, 2)).all()   # (every plan was compared)
     return fused
@@ -90,7 +90,7 @@ def test_runtime_tables_in_a_fresh_process(rt, tmp_path):
     gpu = dict(np.load(out))
     print("runtime tables: flags %s, iterations gpu %s oracle %s, max plan error %.3e" % (
         gpu["exitflag"].tolist(), gpu["iters"].tolist(), cpu["iters"].tolist(), np.abs(gpu["z"] - cpu["z"]).max()))
-    _check_plan(gpu, cpu, sc.desc["nx"] + sc.desc["ns"])
+    check_plan(gpu, cpu, sc.desc["nx"] + sc.desc["ns"])
     np.testing.assert_allclose(gpu["obj"], cpu["obj"], rtol=1e-9, atol=1e-9)
 
 
@@ -112,7 +112,7 @@ def test_zeros_and_dummy_words_are_the_calls_own(rt):
     s.close()
     assert np.array_equal(clean["exitflag"], dirty["exitflag"]) and np.array_equal(clean["iters"], dirty["iters"])
     assert np.array_equal(clean["z"], dirty["z"])
-    _check_plan(dirty, cpu, sc.desc["nx"] + sc.desc["ns"])
+    check_plan(dirty, cpu, sc.desc["nx"] + sc.desc["ns"])
 
 
 def test_arm_sums_over_eight_lanes_unchanged(rt):

@@ -3,7 +3,7 @@ loop of the point robot's recursion (ric_point_robot) takes the record of its fi
 the loop, and an explicit wait (lds_requests_done) completes them there, so that no stage waits at its top for the image
 stores of the stage before it.  The sweep of the chain without slack finalises a variable right behind its rows under a
 generated view.  No floating-point operation changes, so every case is held to the oracle at the bars of
-tests/test_gpu_parity.py (_check_plan: equal flags, iteration counts, plans to 1e-6 relative), and the oracle ends every
+tests/test_gpu_parity.py (check_plan: equal flags, iteration counts, plans to 1e-6 relative), and the oracle ends every
 instance of every case with flag 1 or 2, so every plan is compared.  The wait stands where the loop's first stage takes
 its record: the cases are the shapes that enter and leave the loops differently.
 
@@ -27,7 +27,7 @@ import sys
 import numpy as np
 import pytest
 
-from test_gpu_parity import _check_plan
+from gpu_support import check_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -57,7 +57,7 @@ def _oracle(rt, sc):
 def _compare(what, gpu, cpu, sc):
     print("%s: flags %s, iterations gpu %s oracle %s, max plan error %.3e" % (
         what, gpu["exitflag"].tolist(), gpu["iters"].tolist(), cpu["iters"].tolist(), np.abs(gpu["z"] - cpu["z"]).max()))
-    _check_plan(gpu, cpu, sc.desc["nx"] + sc.desc["ns"])
+    check_plan(gpu, cpu, sc.desc["nx"] + sc.desc["ns"])
     np.testing.assert_allclose(gpu["obj"], cpu["obj"], rtol=1e-9, atol=1e-9)
 
 

@@ -1,5 +1,5 @@
 """The global planner on the device (rmpc_grid_*_device, rmpc_follow_path_device) against the CPU restatement of the
-reference's rules in tests/test_global_planner_cpu.py: enlarged obstacles, cost-to-go fields (bitwise on binary maps),
+reference's rules in tests/global_planner_reference.py: enlarged obstacles, cost-to-go fields (bitwise on binary maps),
 paths, the batched planner, the mirror of the reference's API, the waypoint follower and a closed loop."""
 import math
 
@@ -7,11 +7,10 @@ import numpy as np
 import pytest
 
 from example_loader import load_example
-from test_global_planner_cpu import LocalGoalRef, astar_ref, descend_ref, field_ref, inflate_ref, path_cost
+from global_planner_reference import LocalGoalRef, astar_ref, descend_ref, field_ref, inflate_ref, path_cost
+from gpu_support import DEV, _t
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module")
@@ -21,10 +20,6 @@ def rt():
     g.build()
     from robot_mpcs_amd import _lib
     return dict(torch=torch, lib=_lib)
-
-
-def _t(torch, a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV) if dtype is None else torch.as_tensor(np.asarray(a), dtype=dtype).to(DEV)
 
 
 def _inflated_shelves(rt, H, W, seed, cell=0.45):

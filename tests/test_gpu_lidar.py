@@ -1,5 +1,5 @@
 """The lidar on the device (rmpc_lidar_scan_device, rmpc_plan_points_device) and LidarPlanes (scan -> seeds -> FSD)
-against the numpy restatement of tests/test_lidar_cpu.py and oracle/fsd_numpy.py; the refusals of the C ABI; stream
+against the numpy restatement of tests/lidar_reference.py and oracle/fsd_numpy.py; the refusals of the C ABI; stream
 and device selection; the closed loop of examples/fleet_store_lidar.py with and without the lidar."""
 import ctypes as C
 import math
@@ -8,11 +8,11 @@ import numpy as np
 import pytest
 
 from example_loader import load_example
-from test_lidar_cpu import plan_points_ref, scan_ref
+from gpu_support import DEV, _t
+from lidar_reference import plan_points_ref, scan_ref
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 SWEEPS = {"full": (-math.pi, math.pi), "sector": (-math.pi + math.pi / 8, -math.pi / 8)}
 # a last-bit difference of d (the device's and numpy's sin / cos) moves the circle hit t = -b - sqrt(b^2 - c) by about
 # |b| eps / sqrt(b^2 - c): unbounded at tangency.  Rays on which that exceeds 1e-13 m are excluded as well as the rays
@@ -27,10 +27,6 @@ def rt():
     g.build()
     from robot_mpcs_amd import _lib
     return dict(torch=torch, lib=_lib)
-
-
-def _t(torch, a, dtype=None, dev=DEV):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype if dtype is not None else torch.float64).to(dev)
 
 
 def _world(rng, nbox, ncircle):

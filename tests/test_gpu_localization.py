@@ -1,5 +1,5 @@
 """Localisation on the device (rmpc_grid_edge_distance_device, rmpc_lidar_project_device, rmpc_scan_match_device,
-ScanMatcher) against the numpy restatements of tests/test_localization_cpu.py, bit for bit, each launch into poisoned
+ScanMatcher) against the numpy restatements of tests/localization_reference.py, bit for bit, each launch into poisoned
 output buffers; and the closed loop of examples/fleet_store_localize.py with the matcher, with dead reckoning and
 with the true pose."""
 import math
@@ -8,15 +8,16 @@ import numpy as np
 import pytest
 
 from example_loader import load_example
+from gpu_support import DEV, _t
+from lidar_reference import scan_ref
+from localization_cases import LIDAR, clear_poses, store_world
+from localization_reference import edge_distance_ref, match_ref, project_ref
 from robot_mpcs_amd.global_planner import shelf_map
 from robot_mpcs_amd.store import STORE, store_map
 from robot_mpcs_amd.utils.localization import rotation_table
-from test_lidar_cpu import scan_ref
-from test_localization_cpu import LIDAR, clear_poses, edge_distance_ref, match_ref, project_ref, store_world
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 POISON = -559038737          # 0xDEADBEEF as an int32
 
 
@@ -27,10 +28,6 @@ def rt():
     g.build()
     from robot_mpcs_amd import _lib
     return dict(torch=torch, lib=_lib)
-
-
-def _t(torch, a, dtype=None):
-    return torch.tensor(np.asarray(a), dtype=dtype if dtype is not None else torch.float64).to(DEV)    # (a copy)
 
 
 # ---- edge distance -----------------------------------------------------------------------------------------------------

@@ -1,26 +1,19 @@
 """The map from the fleet's scans on the device (rmpc_grid_mark_device, rmpc_grid_occupancy_device, FleetMap) against
-the numpy restatement of tests/test_mapping_cpu.py, integer for integer; containment of non-finite robots; the refusals
+the numpy restatement of tests/mapping_reference.py, integer for integer; containment of non-finite robots; the refusals
 of the C ABI; stream and device selection; RouteFollower.replace and replan; the closed loop of
 examples/fleet_store_explore.py."""
 import ctypes as C
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
 from example_loader import load_example
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from test_mapping_cpu import mark_ref, occupancy_ref  # noqa: E402
+from gpu_support import DEV, _t
+from mapping_reference import mark_ref, occupancy_ref
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 OFFSET, HEIGHT, HIT_DEPTH = (0.4, 0.0), 0.02, 1e-6
 # the maps, centred on the origin: (H, W, cell)
 MAPS = {"5x7": (5, 7, 0.45), "41": (41, 41, 0.45), "128": (128, 128, 0.15)}
@@ -39,10 +32,6 @@ CASES = {
     "b37_r64_128_store_cap": (37, 64, "128", "store", 10.0, None),
     "b37_r64_41_outside": (37, 64, "41", "random", 9.0, 16.0),     # origins up to 7 m outside the map
 }
-
-
-def _t(torch, a, dtype=None, dev=DEV):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype if dtype is not None else torch.float64).to(dev)
 
 
 def _geom(mp):

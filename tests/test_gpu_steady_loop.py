@@ -11,11 +11,11 @@ import numpy as np
 import pytest
 
 import steady_loop_cases as cases
+from gpu_support import DEV
 from steady_loop_reference import advance_step, obstacles_step, retarget_step
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 MAX_B = 300
 STATE_KEYS = ("xinit", "x0", "goal", "cursor", "dwell", "failrun")
 

@@ -7,11 +7,11 @@ import numpy as np
 import pytest
 
 from example_loader import load_example
+from gpu_support import DEV, _t
 from timed_reference import BAD_ORDER, OUTSIDE, conflicts, fields_for, follow_ref, plan_ref, store_case
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 POISON = -559038737          # 0xDEADBEEF as an int32
 KEYS = ("paths", "status", "arrive", "key", "best")
 
@@ -23,10 +23,6 @@ def rt():
     g.build()
     from robot_mpcs_amd import _lib
     return dict(torch=torch, lib=_lib)
-
-
-def _t(torch, a, dtype=None):
-    return torch.tensor(np.asarray(a), dtype=dtype if dtype is not None else torch.float64).to(DEV)    # (a copy)
 
 
 def _device_plan(rt, grid, starts, goals, orders, T, sep2, lag=1, movement=4, occ=0.8, stream=None):

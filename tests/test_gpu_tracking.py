@@ -10,12 +10,12 @@ import numpy as np
 import pytest
 
 from example_loader import load_example
+from gpu_support import DEV
 from tracking_cases import CASES
 from tracking_reference import MAX_DET, params, tracks_ref
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 POISON = -559038737          # 0xDEADBEEF as an int32
 GUARD = 32                   # poisoned words behind every output
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "moving_loops.json")

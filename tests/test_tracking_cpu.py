@@ -8,7 +8,7 @@ import math
 import numpy as np
 import pytest
 
-from test_lidar_cpu import scan_ref
+from lidar_reference import scan_ref
 from tracking_cases import CASES, dets_of
 from tracking_reference import MAX_DET, associate, detect, fit_circle, moving_rays, params, segments, tracks_ref
 

@@ -6,7 +6,7 @@ each other and against hand-worked cases, tests/test_gpu_timed.py holds the devi
 planner's order."""
 import numpy as np
 
-from test_global_planner_cpu import MOVES, field_ref, inflate_ref
+from global_planner_reference import MOVES, field_ref, inflate_ref
 
 OUTSIDE, BAD_ORDER = -3, -8
 INT64_MAX = (1 << 63) - 1
