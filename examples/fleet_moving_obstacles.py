@@ -12,7 +12,8 @@ What the solver is told about the walkers is the mode:
 
 Every control step, on one stream:  [tracker | nearest five]  ->  solve_scene_device  ->  advance_device  ->
 rmpc_advance_obstacles_device.  Nothing crosses PCIe between control steps; the statistics stay on the device.  The
-robots do not see each other (the lidar world holds the walkers only).
+robots do not see each other here (the lidar world holds the walkers only); ``ObstacleTracker.step(..., bodies=...)``
+puts the fleet into the scan, as examples/fleet_crossing_lidar.py --mode tracked does.
 
     python examples/fleet_moving_obstacles.py [--robots 64] [--walkers 24] [--steps 300] [--seed 0]
                                               [--obstacles truth|tracked|blind]

@@ -60,7 +60,8 @@ extern "C" {
  *              rmpc_grid_targets_device, rmpc_grid_route_costs_device, rmpc_assign_greedy_device; localisation,
  *              RMPC_MATCH_MAX_RAYS, rmpc_scan_match, rmpc_grid_edge_distance_device, rmpc_lidar_project_device,
  *              rmpc_scan_match_device; moving obstacles, RMPC_TRACK_MAX_RAYS, RMPC_TRACK_MAX_TRACKS,
- *              RMPC_TRACK_MAX_DET, rmpc_tracks, rmpc_lidar_tracks_device. */
+ *              RMPC_TRACK_MAX_DET, rmpc_tracks, rmpc_lidar_tracks_device; the fleet in the scan, rmpc_lidar_bodies,
+ *              rmpc_lidar_scan_fleet_device. */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -461,6 +462,29 @@ typedef struct rmpc_lidar {
   double *ranges;                              /* [B][R] out, may be NULL */
 } rmpc_lidar;
 int rmpc_lidar_scan_device(int B, const rmpc_lidar *l, void *stream);
+/* The fleet in the scan: the scan of l plus P round bodies, one per robot of the fleet, so that the
+ * robots see each other.  Ray (b, i): origin o, direction d and the static hit distance ts are exactly those of
+ * rmpc_lidar_scan_device on l (the same expressions in the same order).  Body j = (centres [j * centre_stride + 0 .. 1],
+ * radius [j]) is a candidate when j != self0 + b (the scanning robot's own body) and radius [j] > 0; a candidate is
+ * tested by the circle rule above: u = o - c_j, bb = d.u, cc = |u|^2 - r^2, disc = bb^2 - cc, a hit iff cc > 0,
+ * disc >= 0 and tc = -bb - sqrt(disc) > 0.  A body that contains the origin is ignored, as any shape is; a NaN centre
+ * or radius never hits.  t is the least of ts and all tc; a body replaces the static world only when tc < ts strictly,
+ * and among bodies the least (tc, j) wins: nothing depends on the order in which the bodies are met.
+ * points and ranges of l are as in the plain scan, with this t; static_ranges = ts; owner = j when a body gave t, -2 when
+ * a box or a circle of l did, -1 when t == range.  P == 0 gives the plain scan's result.
+ * Runs on the device of l->pose, on the given stream, and never synchronises.  struct_size must equal
+ * sizeof(rmpc_lidar_bodies); refused (-1, rmpc_last_error): everything rmpc_lidar_scan_device refuses, P < 0, NULL
+ * centres or radius with P > 0, centre_stride < 2, and P*centre_stride beyond INT_MAX. */
+typedef struct rmpc_lidar_bodies {
+  int32_t struct_size;                 /* sizeof(rmpc_lidar_bodies) */
+  int32_t P;                           /* bodies, >= 0 */
+  const double *centres; int32_t centre_stride;  /* [P][stride >= 2]: cx, cy at 0, 1 (rmpc_fleet_points_device, N = 1: stride 3) */
+  const double *radius;                /* [P] */
+  int32_t self0;                       /* scanning robot b is body self0 + b (outside [0, P): it has none) */
+  int32_t *owner;                      /* [B][R] out, may be NULL */
+  double *static_ranges;               /* [B][R] out, may be NULL */
+} rmpc_lidar_bodies;
+int rmpc_lidar_scan_fleet_device(int B, const rmpc_lidar *l, const rmpc_lidar_bodies *f, void *stream);
 /* The seeds of the free-space decomposition (examples/boxer_example_supermarket.py, "Preprocessing for planner"):
  * d_points [B][N][3] = (sensor origin of q, height) with q = d_z_prev [b][k][0 .. 2] (stage k of the previous plan,
  * [B][N][nvar] with z_k = [x_k; s_k; u_k]), or q = the current pose d_pose [b * pose_stride + 0 .. 2] when d_z_prev is

@@ -96,6 +96,18 @@ class LidarArgs(C.Structure):
     ]
 
 
+class LidarBodiesArgs(C.Structure):
+    """Mirror of ``rmpc_lidar_bodies`` (include/rmpc.h): the fleet's bodies a scan sees besides its world, device
+    pointers."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("P", C.c_int32),
+        ("centres", C.c_void_p), ("centre_stride", C.c_int32),
+        ("radius", C.c_void_p),
+        ("self0", C.c_int32),
+        ("owner", C.c_void_p), ("static_ranges", C.c_void_p),
+    ]
+
+
 class GridMarkArgs(C.Structure):
     """Mirror of ``rmpc_grid_mark`` (include/rmpc.h): one scan of B robots added to the evidence grids, device pointers."""
     _fields_ = [
@@ -172,6 +184,7 @@ EXPORTED_SYMBOLS = [
     "rmpc_grid_targets_device", "rmpc_grid_route_costs_device", "rmpc_assign_greedy_device",
     "rmpc_grid_edge_distance_device", "rmpc_lidar_project_device", "rmpc_scan_match_device",
     "rmpc_lidar_tracks_device", "rmpc_timed_plan_work_bytes", "rmpc_timed_plan_device", "rmpc_timed_follow_device",
+    "rmpc_lidar_scan_fleet_device",
 ]
 
 _lib = None
@@ -323,6 +336,8 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_follow_path_device.argtypes = [i, vp, vp, i, vp, vp, i, i, d, d, d, d, vp, vp]
     L.rmpc_lidar_scan_device.restype = C.c_int
     L.rmpc_lidar_scan_device.argtypes = [i, C.POINTER(LidarArgs), vp]
+    L.rmpc_lidar_scan_fleet_device.restype = C.c_int
+    L.rmpc_lidar_scan_fleet_device.argtypes = [i, C.POINTER(LidarArgs), C.POINTER(LidarBodiesArgs), vp]
     L.rmpc_plan_points_device.restype = C.c_int
     L.rmpc_plan_points_device.argtypes = [i, i, vp, i, vp, vp, i, d, d, d, vp, vp]
     L.rmpc_fleet_points_device.restype = C.c_int
@@ -597,6 +612,38 @@ def lidar_scan_device(pose, points, boxes=None, circles=None, angle_min: float =
     ``compute_point_cloud``, ranges (B, R) the hit distances (max_range on a miss)."""
     a = lidar_args(pose, points, boxes, circles, angle_min, angle_max, max_range, offset, height, ranges)
     _grid_call("rmpc_lidar_scan_device", int(points.shape[0]), C.byref(a), _stream_arg(stream))
+
+
+# entries of k_lidar_fleet's LDS list (kFleetListMax, csrc/rmpc_sense.hpp): with more bodies in range it drains and refills
+LIDAR_FLEET_LIST = 512
+
+
+def lidar_bodies_args(centres, radius, self0: int = 0, owner=None, static_ranges=None) -> LidarBodiesArgs:
+    """The ``rmpc_lidar_bodies`` of one fleet scan: centres (P, stride >= 2) or (P, 1, 3) fp64 (the output of
+    ``fleet_points_device`` with N = 1), radius (P,) fp64; owner (B, R) int32 and static_ranges (B, R) fp64 or None --
+    contiguous device tensors.  Scanning robot b is body self0 + b."""
+    a = LidarBodiesArgs()
+    a.struct_size = C.sizeof(LidarBodiesArgs)
+    a.P = int(centres.shape[0])
+    a.centres = centres.data_ptr() if a.P else None
+    a.centre_stride = int(centres.stride(0)) if a.P else max(2, int(centres.shape[-1]))
+    a.radius = radius.data_ptr() if a.P else None
+    a.self0 = int(self0)
+    a.owner = None if owner is None else owner.data_ptr()
+    a.static_ranges = None if static_ranges is None else static_ranges.data_ptr()
+    return a
+
+
+def lidar_scan_fleet_device(pose, points, centres, radius, boxes=None, circles=None, angle_min: float = -np.pi,
+                            angle_max: float = np.pi, max_range: float = 10.0, offset=(0.4, 0.0), height: float = 0.02,
+                            self0: int = 0, owner=None, static_ranges=None, ranges=None, stream=None):
+    """One lidar scan of B robots that also sees the fleet (``rmpc_lidar_scan_fleet_device``): the scan of
+    ``lidar_scan_device`` plus one round body per (centres [j], radius [j]), the scanning robot's own body self0 + b
+    left out.  owner (B, R) int32 = the body a ray ended on, -2 the static world, -1 nothing; static_ranges (B, R) =
+    the hit distances of the static world alone."""
+    a = lidar_args(pose, points, boxes, circles, angle_min, angle_max, max_range, offset, height, ranges)
+    f = lidar_bodies_args(centres, radius, self0, owner, static_ranges)
+    _grid_call("rmpc_lidar_scan_fleet_device", int(points.shape[0]), C.byref(a), C.byref(f), _stream_arg(stream))
 
 
 def plan_points_device(pose, points, z_prev=None, exitflag=None, offset=(0.4, 0.0), height: float = 0.02, stream=None):

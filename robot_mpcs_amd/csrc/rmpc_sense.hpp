@@ -24,25 +24,15 @@ __device__ __forceinline__ void sense_origin(double x, double y, double c, doubl
   py = y + ox * s + oy * c;
 }
 
-// One lane per (robot, ray): lane g = b * R + i, so with R = 64 one wavefront is one robot.  The shapes are read at
-// wave-uniform addresses (every lane of a wave tests the same shape at the same time): the loads become scalar loads
-// into SGPRs that the vector ALU reads directly.  Per box: two subtractions and two products per axis against the
-// ray's reciprocal direction, min / max, no division.
-__global__ __launch_bounds__(256) void k_lidar(const double *__restrict__ pose, int stride, int B, int R, double amin,
-                                               double step, double range, double offx, double offy, double height,
+// The least hit distance of the ray (o, d) in the static world, range when nothing is hit within range.  The shapes
+// are read at wave-uniform addresses (every lane of a wave tests the same shape at the same time): the loads become
+// scalar loads into SGPRs that the vector ALU reads directly.  Per box: two subtractions and two products per axis
+// against the ray's reciprocal direction, min / max, no division.  One copy for k_lidar and k_lidar_fleet: the fleet
+// scan's static_ranges are the plain scan's ranges bit for bit.
+__device__ __forceinline__ double lidar_static(double ox, double oy, double dx, double dy, double range,
                                                const double *__restrict__ boxes, int nbox,
-                                               const double *__restrict__ circles, int ncircle,
-                                               double *__restrict__ points, double *__restrict__ ranges) {
+                                               const double *__restrict__ circles, int ncircle) {
 #pragma clang fp contract(off)
-  const int g = blockIdx.x * 256 + threadIdx.x;
-  if (g >= B * R) return;
-  const int b = g / R, i = g - b * R;
-  const double *const p = pose + (size_t)b * stride;
-  const double x = p[0], y = p[1], th = p[2];
-  double ox, oy;
-  sense_origin(x, y, cos(th), sin(th), offx, offy, ox, oy);
-  const double ang = (th + amin) + (double)i * step;
-  const double dx = cos(ang), dy = sin(ang);
   const bool zx = dx == 0.0, zy = dy == 0.0;
   const double ix = zx ? 0.0 : 1.0 / dx, iy = zy ? 0.0 : 1.0 / dy;
   const double inf = __builtin_inf();
@@ -70,11 +60,125 @@ __global__ __launch_bounds__(256) void k_lidar(const double *__restrict__ pose, 
       if (tc > 0.0 && tc < t) t = tc;
     }
   }
+  return t;
+}
+
+// One lane per (robot, ray): lane g = b * R + i, so with R = 64 one wavefront is one robot.
+__global__ __launch_bounds__(256) void k_lidar(const double *__restrict__ pose, int stride, int B, int R, double amin,
+                                               double step, double range, double offx, double offy, double height,
+                                               const double *__restrict__ boxes, int nbox,
+                                               const double *__restrict__ circles, int ncircle,
+                                               double *__restrict__ points, double *__restrict__ ranges) {
+#pragma clang fp contract(off)
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= B * R) return;
+  const int b = g / R, i = g - b * R;
+  const double *const p = pose + (size_t)b * stride;
+  const double x = p[0], y = p[1], th = p[2];
+  double ox, oy;
+  sense_origin(x, y, cos(th), sin(th), offx, offy, ox, oy);
+  const double ang = (th + amin) + (double)i * step;
+  const double dx = cos(ang), dy = sin(ang);
+  const double t = lidar_static(ox, oy, dx, dy, range, boxes, nbox, circles, ncircle);
   double *const o = points + (size_t)g * 3;
   o[0] = ox + t * dx;
   o[1] = oy + t * dy;
   o[2] = height;
   if (ranges) ranges[g] = t;
+}
+
+// ---- the fleet in the scan: the static world of k_lidar plus P round bodies, one per robot --------
+// One workgroup per scanning robot b, its lanes sharing the rays (a batch of blockDim.x rays at a time).  A ray first
+// takes its static hit ts from lidar_static.  The bodies then pass in chunks of blockDim.x: each lane holds one body
+// against the cull (not the robot's own, radius > 0, |o - c|^2 <= (range + r)^2 with a relative margin of 1e-6, about
+// 1e10 rounding errors: a body outside it has tc > range for every ray); a 64-bit ballot and a popcount compact the
+// survivors of a wave, the waves' counts meet in LDS, and the survivors go to an LDS list of (cx, cy, r, j).  When the
+// next chunk might not fit, every lane tests its ray against the list (all lanes read the same entry at the same time: a
+// broadcast) and the list starts again, so there is no limit on the bodies in range.  The ray keeps the least (tc, j)
+// with tc < ts strictly: a minimum with an index tie-break, so the result does not depend on the order in which the
+// bodies are met.  A NaN centre or radius fails the cull as it would fail the rule.
+constexpr int kFleetListMax = 512;   // entries of the LDS list; >= the largest block (256)
+
+__global__ __launch_bounds__(256) void k_lidar_fleet(const double *__restrict__ pose, int stride, int R, double amin,
+                                                     double step, double range, double offx, double offy, double height,
+                                                     const double *__restrict__ boxes, int nbox,
+                                                     const double *__restrict__ circles, int ncircle,
+                                                     const double *__restrict__ centres, int cstride,
+                                                     const double *__restrict__ radius, int P, int self0,
+                                                     double *__restrict__ points, double *__restrict__ ranges,
+                                                     double *__restrict__ static_ranges, int *__restrict__ owner) {
+#pragma clang fp contract(off)
+  __shared__ double lx[kFleetListMax], ly[kFleetListMax], lr[kFleetListMax];
+  __shared__ int lj[kFleetListMax];
+  __shared__ int wc[4];
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int wave = tid >> 6, lane = tid & 63, nw = nt >> 6;
+  const double *const p = pose + (size_t)b * stride;
+  const double x = p[0], y = p[1], th = p[2];
+  double ox, oy;
+  sense_origin(x, y, cos(th), sin(th), offx, offy, ox, oy);
+  const long long self = (long long)self0 + b;
+  for (int i0 = 0; i0 < R; i0 += nt) {
+    const int i = i0 + tid;
+    const double ang = (th + amin) + (double)i * step;
+    const double dx = cos(ang), dy = sin(ang);
+    const double ts = lidar_static(ox, oy, dx, dy, range, boxes, nbox, circles, ncircle);
+    double t = ts;
+    int own = -1;
+    // the ray against the n entries of the list
+    auto drain = [&](int n) {
+      for (int e = 0; e < n; e++) {
+        const double r = lr[e];
+        const int j = lj[e];
+        const double ux = ox - lx[e], uy = oy - ly[e];
+        const double bb = dx * ux + dy * uy;
+        const double cc = (ux * ux + uy * uy) - r * r;
+        const double disc = bb * bb - cc;
+        if (cc > 0.0 && disc >= 0.0) {
+          const double tc = -bb - sqrt(disc);
+          if (tc > 0.0 && (tc < t || (tc == t && own >= 0 && j < own))) { t = tc; own = j; }
+        }
+      }
+    };
+    int count = 0;   // the same in every lane of the block
+    for (int j0 = 0; j0 < P; j0 += nt) {
+      if (count + nt > kFleetListMax) { drain(count); count = 0; }
+      const int j = j0 + tid;
+      double cx = 0.0, cy = 0.0, r = 0.0;
+      bool keep = false;
+      if (j < P && (long long)j != self) {
+        const double *const c = centres + (size_t)j * cstride;
+        cx = c[0]; cy = c[1]; r = radius[j];
+        const double ux = ox - cx, uy = oy - cy, lim = range + r;
+        keep = r > 0.0 && ux * ux + uy * uy <= (lim * lim) * 1.000001;
+      }
+      const unsigned long long m = __ballot(keep);
+      if (lane == 0) wc[wave] = __popcll(m);
+      __syncthreads();
+      int at = count;
+      for (int w = 0; w < nw; w++) {
+        const int n = wc[w];
+        if (w < wave) at += n;
+        count += n;
+      }
+      if (keep) {
+        at += __popcll(m & ((1ull << lane) - 1ull));
+        lx[at] = cx; ly[at] = cy; lr[at] = r; lj[at] = j;
+      }
+      __syncthreads();
+    }
+    drain(count);
+    if (i < R) {
+      const size_t g = (size_t)b * R + i;
+      double *const o = points + g * 3;
+      o[0] = ox + t * dx;
+      o[1] = oy + t * dy;
+      o[2] = height;
+      if (ranges) ranges[g] = t;
+      if (static_ranges) static_ranges[g] = ts;
+      if (owner) owner[g] = own >= 0 ? own : (ts < range ? -2 : -1);
+    }
+  }
 }
 
 // One lane per (robot, stage): the sensor origin of q = z_prev [b][k][0 .. 2] (x_{k+1} of the previous plan, the

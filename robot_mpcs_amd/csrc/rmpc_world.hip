@@ -256,7 +256,7 @@ int rmpc_follow_path_device(int B, const int32_t *d_path, const int32_t *d_len, 
 }
 
 /* the lidar (rmpc_sense.hpp): no handle; each call runs on the device its first pointer lives on */
-int rmpc_lidar_scan_device(int B, const rmpc_lidar *l, void *stream) {
+static int lidar_scan_check(int B, const rmpc_lidar *l) {
   if (!l) return fail("null argument");
   if (l->struct_size != (int)sizeof(rmpc_lidar)) return fail("rmpc_lidar.struct_size mismatch");
   if (B < 1 || l->rays < 1) return fail("lidar: need B >= 1 and rays >= 1");
@@ -266,12 +266,35 @@ int rmpc_lidar_scan_device(int B, const rmpc_lidar *l, void *stream) {
     return fail("lidar: B*rays, B*pose_stride, nbox*4 and ncircle*3 must not exceed INT_MAX");
   if (!(l->range > 0.0) || std::isinf(l->range)) return fail("lidar: range must be positive and finite");
   if (!l->pose || !l->points || (l->nbox > 0 && !l->boxes) || (l->ncircle > 0 && !l->circles)) return fail("null argument");
-  if (use_device_of(l->pose)) return -1;
+  return 0;
+}
+
+int rmpc_lidar_scan_device(int B, const rmpc_lidar *l, void *stream) {
+  if (lidar_scan_check(B, l) || use_device_of(l->pose)) return -1;
   const int n = B * l->rays;
   const double step = (l->angle_max - l->angle_min) / (double)l->rays;
   hipLaunchKernelGGL(k_lidar, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, l->pose, l->pose_stride, B,
                      l->rays, l->angle_min, step, l->range, l->offset_x, l->offset_y, l->height, l->boxes, l->nbox,
                      l->circles, l->ncircle, l->points, l->ranges);
+  return launch_status();
+}
+
+/* the fleet in the scan (k_lidar_fleet): one workgroup per robot, as wide as its rays need (64 .. 256) */
+int rmpc_lidar_scan_fleet_device(int B, const rmpc_lidar *l, const rmpc_lidar_bodies *f, void *stream) {
+  if (!f) return fail("null argument");
+  if (f->struct_size != (int)sizeof(rmpc_lidar_bodies)) return fail("rmpc_lidar_bodies.struct_size mismatch");
+  if (lidar_scan_check(B, l)) return -1;
+  if (f->P < 0) return fail("lidar fleet: negative body count");
+  if (f->centre_stride < 2) return fail("lidar fleet: centre_stride must be >= 2 (cx, cy)");
+  if (!grid_fits(f->P, f->centre_stride)) return fail("lidar fleet: P*centre_stride must not exceed INT_MAX");
+  if (f->P > 0 && (!f->centres || !f->radius)) return fail("null argument");
+  if (use_device_of(l->pose)) return -1;
+  const double step = (l->angle_max - l->angle_min) / (double)l->rays;
+  const int threads = l->rays <= 64 ? 64 : l->rays <= 128 ? 128 : 256;
+  hipLaunchKernelGGL(k_lidar_fleet, dim3(B), dim3(threads), 0, (hipStream_t)stream, l->pose, l->pose_stride, l->rays,
+                     l->angle_min, step, l->range, l->offset_x, l->offset_y, l->height, l->boxes, l->nbox, l->circles,
+                     l->ncircle, f->centres, f->centre_stride, f->radius, f->P, f->self0, l->points, l->ranges,
+                     f->static_ranges, (int *)f->owner);
   return launch_status();
 }
 

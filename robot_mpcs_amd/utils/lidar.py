@@ -6,7 +6,8 @@ planes to ``setLinearConstraints``; its comment asks for "a preprocessor class".
 B robots: scan -> plan points -> FSD, three launches on one stream (``rmpc_lidar_scan_device``,
 ``rmpc_plan_points_device``, ``rmpc_free_space_device``), writing the ``lin_constrs`` array a scene points at.
 ``boxes_from_grid`` turns an occupancy map into the boxes the scan sees, so that the lidar and the global planner see
-one world.  There is no CPU path.
+one world.  With ``body_radius`` the scan also sees the fleet's own robots (``rmpc_lidar_scan_fleet_device``).  There is
+no CPU path.
 """
 from __future__ import annotations
 
@@ -51,10 +52,19 @@ class LidarPlanes:
     the array a scene's ``lin_constrs`` points at.  ``step(xinit, z_prev, exitflag)`` enqueues the three launches on the
     current (or the given) stream and never synchronises.  The defaults are the boxer's: the sensor 0.4 m ahead of the
     base at height 0.02, ``max_radius`` 5 (the reference's FreeSpaceDecomposition), a full circle of 64 rays (the
-    FSD kernel takes at most 64 points)."""
+    FSD kernel takes at most 64 points).
+
+    With ``body_radius`` (a scalar or (B,)) the robots see each other: the block's own robots are round
+    bodies of that radius centred at ``body_offset`` in the body frame (default: the sensor offset; ``heading`` = 0
+    for a robot without one, whose body sits at (x, y)), robot b being body b.  ``step`` then takes the centres from
+    the poses (``rmpc_fleet_points_device``, N = 1, into ``centres`` (B, 1, 3)) and runs the fleet scan
+    (``rmpc_lidar_scan_fleet_device``) into ``owner`` (B, rays) int32 and ``static_ranges`` (B, rays) as well: four
+    launches.  ``step(..., bodies=(centres, radius, self0))`` scans those bodies instead (other blocks' robots, a mixed
+    fleet), with or without ``body_radius``."""
 
     def __init__(self, B, N, K, boxes=None, circles=None, rays=64, angle_min=-math.pi, angle_max=math.pi, max_range=10.0,
-                 max_radius=5.0, offset=(0.4, 0.0), height=0.02, device=None):
+                 max_radius=5.0, offset=(0.4, 0.0), height=0.02, device=None, body_radius=None, body_offset=None,
+                 heading=1):
         import torch
         if not 1 <= int(rays) <= 64:
             raise ValueError("LidarPlanes: 1 <= rays <= 64 (the free-space decomposition reads at most 64 points)")
@@ -73,13 +83,41 @@ class LidarPlanes:
         self.ranges = torch.zeros((self.B, self.rays), **f64)
         self.seeds = torch.zeros((self.B, self.N, 3), **f64)
         self.planes = torch.zeros((self.B, self.N, self.K, 4), **f64)
+        self.body_radius = self.centres = self.owner = self.static_ranges = None
+        self.heading = int(heading)
+        self.body_offset = self.offset if body_offset is None else (float(body_offset[0]), float(body_offset[1]))
+        if body_radius is not None:
+            self.body_radius = torch.as_tensor(body_radius, dtype=torch.float64).reshape(-1).to(dev).expand(self.B) \
+                .contiguous()
+            self.centres = torch.zeros((self.B, 1, 3), **f64)
+            self._fleet_buffers()
 
-    def step(self, xinit, z_prev=None, exitflag=None, stream=None):
+    def _fleet_buffers(self):
+        import torch
+        self.owner = torch.zeros((self.B, self.rays), dtype=torch.int32, device=self.device)
+        self.static_ranges = torch.zeros((self.B, self.rays), dtype=torch.float64, device=self.device)
+
+    def _scan_fleet(self, xinit, bodies, st):
+        if self.owner is None:          # bodies handed to a block built without body_radius: on their first use
+            self._fleet_buffers()
+        if bodies is None:
+            _lib.fleet_points_device(xinit, self.centres, None, None, self.heading, self.body_offset, 0.0, stream=st)
+            bodies = (self.centres, self.body_radius, 0)
+        centres, radius, self0 = bodies
+        _lib.lidar_scan_fleet_device(xinit, self.points, centres, radius, self.boxes, self.circles, self.angle_min,
+                                     self.angle_max, self.max_range, self.offset, self.height, self0=self0,
+                                     owner=self.owner, static_ranges=self.static_ranges, ranges=self.ranges, stream=st)
+
+    def step(self, xinit, z_prev=None, exitflag=None, stream=None, bodies=None):
         """xinit (B, stride >= 3) poses; z_prev (B, N, nvar) the previous plan or None (first step); exitflag (B,) int32
-        or None.  Returns ``planes``."""
+        or None; bodies (centres (P, stride >= 2) or (P, 1, 3), radius (P,), self0) device tensors or None.  Returns
+        ``planes``."""
         st = _lib.stream_handle(stream, self.device)
-        _lib.lidar_scan_device(xinit, self.points, self.boxes, self.circles, self.angle_min, self.angle_max,
-                               self.max_range, self.offset, self.height, ranges=self.ranges, stream=st)
+        if bodies is not None or self.body_radius is not None:
+            self._scan_fleet(xinit, bodies, st)
+        else:
+            _lib.lidar_scan_device(xinit, self.points, self.boxes, self.circles, self.angle_min, self.angle_max,
+                                   self.max_range, self.offset, self.height, ranges=self.ranges, stream=st)
         _lib.plan_points_device(xinit, self.seeds, z_prev, exitflag, self.offset, self.height, stream=st)
         _lib.free_space_decomposition_device(self.points, self.seeds, self.planes, self.max_radius, stream=st)
         return self.planes

@@ -77,14 +77,21 @@ class ObstacleTracker:
         _lib.lidar_tracks_device(self.args, self.B, stream=st)
         return self.obst_dyn
 
-    def step(self, xinit, circles, stream=None):
-        """xinit (B, stride >= 3) the poses, circles (P, 3) = (cx, cy, r) what moves in the world now (device tensors).
-        Scans the boxes and the circles, scans the boxes alone (skipped without boxes), takes the sensor origins and
-        runs the tracker.  Returns ``obst_dyn``."""
+    def step(self, xinit, circles, stream=None, bodies=None):
+        """xinit (B, stride >= 3) the poses, circles (P, 3) = (cx, cy, r) what moves in the world now or None, bodies
+        (centres, radius, self0) the fleet's robots as ``LidarPlanes.step`` takes them or None (device tensors).
+        Scans the boxes and the circles (with bodies: and the other robots, ``rmpc_lidar_scan_fleet_device``), scans the
+        boxes alone (skipped without boxes), takes the sensor origins and runs the tracker.  Returns ``obst_dyn``."""
         st = _lib.stream_handle(stream, self.device)
         self.args.ranges = self.ranges.data_ptr()
-        _lib.lidar_scan_device(xinit, self.points, self.boxes, circles, self.angle_min, self.angle_max, self.max_range,
-                               self.offset, self.height, ranges=self.ranges, stream=st)
+        if bodies is None:
+            _lib.lidar_scan_device(xinit, self.points, self.boxes, circles, self.angle_min, self.angle_max,
+                                   self.max_range, self.offset, self.height, ranges=self.ranges, stream=st)
+        else:
+            centres, radius, self0 = bodies
+            _lib.lidar_scan_fleet_device(xinit, self.points, centres, radius, self.boxes, circles, self.angle_min,
+                                         self.angle_max, self.max_range, self.offset, self.height, self0=self0,
+                                         ranges=self.ranges, stream=st)
         return self._track(xinit, st)
 
     def step_ranges(self, pose, ranges, stream=None):
