@@ -61,7 +61,7 @@ extern "C" {
  *              RMPC_MATCH_MAX_RAYS, rmpc_scan_match, rmpc_grid_edge_distance_device, rmpc_lidar_project_device,
  *              rmpc_scan_match_device; moving obstacles, RMPC_TRACK_MAX_RAYS, RMPC_TRACK_MAX_TRACKS,
  *              RMPC_TRACK_MAX_DET, rmpc_tracks, rmpc_lidar_tracks_device; the fleet in the scan, rmpc_lidar_bodies,
- *              rmpc_lidar_scan_fleet_device. */
+ *              rmpc_lidar_scan_fleet_device; the test hook rmpc_last_solve_path (RMPC_PATH_*). */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -926,6 +926,26 @@ const char *rmpc_spec_for(const rmpc_desc *desc);   /* the view rmpc_create woul
 /* Test aid: overwrites the LDS of every CU of the handle's device with NaN patterns (tests/test_gpu_parity.py:
  * a solve must not depend on what a previous kernel left in LDS). */
 int rmpc_debug_poison_lds(rmpc_handle *h);
+
+/* Test aid: which kernels the host loop enqueued for the last solve of this handle, so that a test of a batch regime can
+ * assert that it ran in it.  Host only: filled in as the solve is enqueued, no device read, no synchronisation.
+ *   out[0]  passes enqueued when the survivors moved to the compact workspace (k_migrate), -1: they did not
+ *   out[1]  survivors moved, -1: none
+ *   out[2]  recursion kernel of the first pass, RMPC_PATH_RIC_*
+ *   out[3]  recursion kernel of the last pass enqueued.  k_riccati's grouped and one-wave blocks are both launched
+ *           for a list of at least 512 columns and the list's length on the device picks one: GROUPED is reported
+ *           until a look of the host loop has found that length below 512 (it never grows), WAVE from then on; a
+ *           solve under a pass budget takes no looks and reports what it launched
+ *   out[4]  list builder run on the whole batch, RMPC_PATH_COMPACT_* (after a migration the survivors' list is built
+ *           by k_compact_wave whatever the batch)
+ *   out[5]  1: the solve was one fused launch, out[0 .. 4] are -1
+ * Before the first solve out[0 .. 4] are -1. */
+#define RMPC_PATH_RIC_WAVE 0      /* k_riccati<C, 1>: one wavefront per instance */
+#define RMPC_PATH_RIC_GROUPED 1   /* k_riccati<C, IPB>: several instances per block, half a wavefront each for small models */
+#define RMPC_PATH_RIC_LANE 2      /* k_riccati_lane: one lane per instance */
+#define RMPC_PATH_COMPACT_WAVE 0  /* k_compact_wave */
+#define RMPC_PATH_COMPACT_BLOCK 1 /* k_compact */
+int rmpc_last_solve_path(const rmpc_handle *h, int32_t out[6]);
 
 /* Test aid: the whole-horizon reductions of the kernels (sums, maxima, minima over the lpi = 32 or 64 consecutive lanes of
  * an instance) run by one wavefront on device `device` over caller-supplied lane values, once with the shuffle exchanges

@@ -175,7 +175,7 @@ class TimedPlanArgs(C.Structure):
 EXPORTED_SYMBOLS = [
     "rmpc_version", "rmpc_source_hash", "rmpc_last_error", "rmpc_desc_size", "rmpc_create", "rmpc_destroy", "rmpc_solve_batch",
     "rmpc_solve_batch_device", "rmpc_workspace_bytes", "rmpc_set_warm_start", "rmpc_set_pass_budget", "rmpc_is_fused", "rmpc_fused_kernel_name", "rmpc_is_async", "rmpc_set_profiling", "rmpc_get_profile",
-    "rmpc_kernel_name", "rmpc_last_passes", "rmpc_debug_sweep", "rmpc_debug_step", "rmpc_debug_step_curv", "rmpc_spec_source", "rmpc_spec_name", "rmpc_spec_for", "rmpc_debug_poison_lds",
+    "rmpc_kernel_name", "rmpc_last_passes", "rmpc_last_solve_path", "rmpc_debug_sweep", "rmpc_debug_step", "rmpc_debug_step_curv", "rmpc_spec_source", "rmpc_spec_name", "rmpc_spec_for", "rmpc_debug_poison_lds",
     "rmpc_debug_fused_stamps", "rmpc_debug_wave_reduce", "rmpc_pack_scene_device", "rmpc_solve_batch_scene_device", "rmpc_pack_scene_workspace", "rmpc_solve_batch_packed_device", "rmpc_advance_device", "rmpc_advance_device_flags", "rmpc_retarget_device", "rmpc_advance_obstacles_device", "rmpc_free_space_device",
     "rmpc_grid_inflate_device", "rmpc_grid_fields_device", "rmpc_grid_paths_device", "rmpc_grid_cells_device",
     "rmpc_follow_path_device", "rmpc_lidar_scan_device", "rmpc_plan_points_device", "rmpc_fleet_points_device",
@@ -287,6 +287,8 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_is_async.argtypes = [C.c_void_p]
     L.rmpc_last_passes.restype = C.c_int
     L.rmpc_last_passes.argtypes = [C.c_void_p]
+    L.rmpc_last_solve_path.restype = C.c_int
+    L.rmpc_last_solve_path.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.rmpc_debug_sweep.restype = C.c_int
     L.rmpc_debug_sweep.argtypes = [C.c_void_p, C.c_int] + [dp] * 9
     L.rmpc_debug_step.restype = C.c_int
@@ -1076,6 +1078,18 @@ class Solver:
 
     def last_passes(self) -> int:
         return int(self._L.rmpc_last_passes(self._h))
+
+    def last_solve_path(self) -> dict:
+        """Test aid (``rmpc_last_solve_path``): the kernels the host loop enqueued for the last solve, noted on the host as
+        it enqueued them.  ``migrated_at`` (passes enqueued before k_migrate, -1: no migration), ``survivors`` (columns
+        moved, -1), ``ric_first`` / ``ric_last`` (``"wave"``, ``"grouped"``, ``"lane"``: recursion kernel of the first
+        and of the last pass enqueued), ``compact`` (``"wave"`` or ``"block"``: list builder run on the whole batch) and
+        ``fused``; a fused solve, or a handle that has not solved yet, has None for the kernel names."""
+        out = (C.c_int32 * 6)()
+        self._check(self._L.rmpc_last_solve_path(self._h, out), "rmpc_last_solve_path")
+        ric = {0: "wave", 1: "grouped", 2: "lane"}
+        return dict(migrated_at=int(out[0]), survivors=int(out[1]), ric_first=ric.get(out[2]), ric_last=ric.get(out[3]),
+                    compact={0: "wave", 1: "block"}.get(out[4]), fused=bool(out[5]))
 
     def debug_sweep(self, xinit, x0, params):
         xinit = np.ascontiguousarray(xinit, dtype=np.float64).reshape(-1, self.nx)

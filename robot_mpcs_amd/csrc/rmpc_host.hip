@@ -284,6 +284,8 @@ static int solve_device(rmpc_handle *h, int B, const double *d_xinit, const doub
     // (k_fused leaves the multipliers in the warm-start arrays only for a handle in warm-start mode; k_fused_arm always)
     h->have_duals = h->warm_mode || h->ops->arm_fused; h->duals_B = B;
     h->last_passes = -1;   // on the device (rmpc_last_passes fetches it)
+    for (int i = 0; i < 5; i++) h->path[i] = -1;
+    h->path[5] = 1;
     if (h->profiling) {
       HIPCHK(hipStreamSynchronize(st));
       prof_collect(h);
@@ -314,10 +316,19 @@ static int solve_device(rmpc_handle *h, int B, const double *d_xinit, const doub
   // counter every few passes (it cannot know how many passes to enqueue) and moves the survivors to the compact
   // workspace.
   const bool async = h->pass_budget > 0 && max_passes_override <= 0;
+  // rmpc_last_solve_path: what this loop enqueues, noted as it does (no device read beyond the looks it takes anyway)
+  int *const path = h->path;
+  path[0] = -1; path[1] = -1; path[2] = -1; path[3] = -1; path[5] = 0;
+  path[4] = B <= kCompactWaveMax ? RMPC_PATH_COMPACT_WAVE : RMPC_PATH_COMPACT_BLOCK;
+  int seen = B;   // length of the list (*W.n_act) as of the last host look; it never grows
   for (; pass < cap; pass++) {
     const int first = pass == 0;
     { ProfScope ps(h, st, K_SWEEP); h->ops->pass(h, ph, first, pass, st, K_SWEEP); }
     { ProfScope ps(h, st, K_RICCATI); h->ops->pass(h, ph, first, pass, st, K_RICCATI); }
+    // (grouped: both instantiations were launched and the list length picks one on the device -- below kGroupedMin at
+    //  the last look means the one-wave blocks from then on)
+    path[3] = (h->ric_sel == RMPC_PATH_RIC_GROUPED && seen < kGroupedMin) ? RMPC_PATH_RIC_WAVE : h->ric_sel;
+    if (first) path[2] = path[3];
     if (ph.B <= kCompactWaveMax) hipLaunchKernelGGL(k_compact_wave, dim3(1), dim3(64), 0, st, ph.W, ph.B, pass);
     else hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, st, ph.W, ph.B, pass);
     { ProfScope ps(h, st, K_STEP); h->ops->pass(h, ph, first, pass, st, K_STEP); }
@@ -327,12 +338,15 @@ static int solve_device(rmpc_handle *h, int B, const double *d_xinit, const doub
       HIPCHK(hipStreamSynchronize(st));
       const int n = *h->h_active;
       if (n == 0) { pass++; break; }
+      seen = n * kDenseDiv > ph.B ? ph.B : n;   // (k_compact: the identity list while most of the columns iterate)
       if (may_migrate && !migrated && n * kDenseDiv <= B) {
         // k_compact has just left the compacted list of the n survivors in the batch's workspace
         hipLaunchKernelGGL(k_migrate, dim3((n + 63) / 64, M.N), dim3(64), 0, st, h->W, h->Wc, n, M.nv, M.m, M.nx, M.npar,
                            M.nh, M.nfk * M.n);
         ph = Phase{h->Wc, n};
         migrated = true;
+        path[0] = pass + 1; path[1] = n;
+        seen = n;
       }
       next_check += (may_migrate && !migrated) ? 2 : 4;  // look more often while the migration is still ahead
     }
@@ -584,6 +598,7 @@ int rmpc_create(const rmpc_desc *desc_in, int max_batch, rmpc_handle **out) {
   const size_t big = carve(h->M, rs, h->Bp, h->max_passes, nullptr, tmp);
   const size_t small = h->Bpc ? carve(h->M, rs, h->Bpc, 0, nullptr, tmp) : 0;
   h->fused = fused_supported(h->ops, h->M, h->T) && !getenv("RMPC_NO_FUSED");   // (debugging switch: pass kernels only)
+  h->path[5] = h->fused ? 1 : 0;
   FusedWs ftmp;
   h->ws_bytes = big + small + (h->fused ? carve_fused(h->M, *h->ops, fused_columns(max_batch), nullptr, ftmp) : 0);
   e = hipMalloc(&h->ws_base, h->ws_bytes);
@@ -819,6 +834,14 @@ int rmpc_get_profile(rmpc_handle *h, double *total_ms, int64_t *launches, double
                              : (i == K_RICCATI || i == K_FUSED) ? (int64_t)h->max_batch * h->lane_bytes[i]
                                                                 : h->lane_bytes[i];
   }
+  return 0;
+}
+
+/* test aid: see include/rmpc.h */
+int rmpc_last_solve_path(const rmpc_handle *h, int32_t out[6]) {
+  if (!h) return fail("null handle");
+  if (!out) return fail("rmpc_last_solve_path: out is NULL");
+  for (int i = 0; i < 6; i++) out[i] = h->path[i];
   return 0;
 }
 

@@ -43,6 +43,9 @@ struct rmpc_handle {
   int *h_active = nullptr;  // pinned
   int last_passes = 0;
   int last_cap = 0;             // passes enqueued by the last solve of the pass kernels
+  // rmpc_last_solve_path (test aid): what solve_device enqueued for the last solve, kept on the host as it enqueues
+  int ric_sel = -1;             // recursion launch_pass selected last (RMPC_PATH_RIC_*; grouped: both launched, the list decides)
+  int path[6] = {-1, -1, -1, -1, -1, 0};
   // profiling
   bool profiling = false;
   std::vector<hipEvent_t> ev;   // pool, reused across solves

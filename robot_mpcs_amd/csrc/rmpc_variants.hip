@@ -31,9 +31,11 @@ void launch_pass(rmpc_handle *h, const Phase &ph, int first, int pass, hipStream
       // lane-per-instance recursion for large lists (h->ric_lane: 0 never, 1 from kLaneMin instances on, 2 always)
       if (h->ric_lane == 2 || (h->ric_lane == 1 && B >= kLaneMin)) {
         hipLaunchKernelGGL((k_riccati_lane<C>), dim3((B + 63) / 64), dim3(64), 0, st, h->M, ph.W, B, first);
+        h->ric_sel = RMPC_PATH_RIC_LANE;
         return;
       }
     }
+    h->ric_sel = (C::IPB > 1 && B >= kGroupedMin) ? RMPC_PATH_RIC_GROUPED : RMPC_PATH_RIC_WAVE;
     if (C::IPB > 1 && B >= kGroupedMin)
     {
       constexpr int per_block = C::IPB * (64 / C::RIC_LPI);   // instances per block

@@ -51,6 +51,21 @@ def test_debug_step_hooks_are_exported_and_refuse_a_null_handle(lib):
     assert b"null" in L.rmpc_last_error()
 
 
+def test_last_solve_path_is_exported_and_refuses_a_null_handle(lib):
+    """rmpc_last_solve_path (which kernels the host loop enqueued for the last solve) is part of the exported set and fails
+    cleanly without a handle, leaving the caller's words alone; the codes it returns are the header's."""
+    L = lib.load_library()
+    assert "rmpc_last_solve_path" in lib.EXPORTED_SYMBOLS
+    out = (C.c_int32 * 6)(*([77] * 6))
+    assert L.rmpc_last_solve_path(None, out) != 0
+    assert b"null" in L.rmpc_last_error()
+    assert list(out) == [77] * 6
+    hdr = open(os.path.join(ROOT, "include", "rmpc.h")).read()
+    codes = dict(re.findall(r"#define (RMPC_PATH_[A-Z_]+) (\d+)", hdr))
+    assert codes == {"RMPC_PATH_RIC_WAVE": "0", "RMPC_PATH_RIC_GROUPED": "1", "RMPC_PATH_RIC_LANE": "2",
+                     "RMPC_PATH_COMPACT_WAVE": "0", "RMPC_PATH_COMPACT_BLOCK": "1"}   # (what Solver.last_solve_path decodes)
+
+
 def test_workspace_bytes_is_host_only_and_scales(lib):
     from robot_mpcs_amd.scenarios import make_scenario
     L = lib.load_library()

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from gpu_support import TOL, check_plan
+from pass_batch_cases import MIGRATION_CASES, case_id
 
 pytestmark = pytest.mark.gpu
 
@@ -193,42 +194,81 @@ def test_solve_does_not_depend_on_stale_lds(rt, name, B, kw):
     assert np.isin(clean["exitflag"], (1, 2)).mean() > 0.95
 
 
-@pytest.mark.parametrize("name,B,seed", [("cfg2", 2048, 7), ("cfg3", 1280, 8)])
-def test_survivor_migration_is_transparent(rt, name, B, seed):
-    """Batches of >= 1024 instances move their last survivors to the compact workspace
-    (k_migrate).  Same arithmetic in other columns: results must be bit-identical to a solve with
-    migration switched off, and match the oracle like any other batch."""
-    sc = rt["make_scenario"](name, B=B, seed=seed)
-    s = rt["Solver"](sc.desc, max_batch=B)
+def _migrating_pair(rt, monkeypatch, desc, B, env):
+    """Two handles of the pass kernels for one batch size: one as shipped, one created under RMPC_NO_MIGRATE (debugging
+    switch, read once when a handle is created)."""
+    monkeypatch.delenv("RMPC_NO_MIGRATE", raising=False)
+    monkeypatch.delenv("RMPC_RIC_LANE", raising=False)
+    monkeypatch.delenv("RMPC_NO_FUSED", raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    s = rt["Solver"](desc, max_batch=B)
+    monkeypatch.setenv("RMPC_NO_MIGRATE", "1")
+    s2 = rt["Solver"](desc, max_batch=B)
+    monkeypatch.delenv("RMPC_NO_MIGRATE")
+    assert not s.is_fused() and not s2.is_fused()
+    return s, s2
+
+
+@pytest.mark.parametrize("name,B,seed,kw,env", MIGRATION_CASES, ids=[case_id(c) for c in MIGRATION_CASES])
+def test_survivor_migration_is_transparent(rt, name, B, seed, kw, env, monkeypatch):
+    """Batches of >= 1024 instances on the pass kernels move their last survivors to the compact workspace (k_migrate: a
+    hand-kept list of the per-instance words and per-stage arrays that cross the pass boundary).  Same arithmetic in other
+    columns: results must be bit-identical to a solve with migration switched off, and match the oracle like any other
+    batch.  A word k_migrate forgets is a word the survivors read from the compact workspace as it was found -- filled
+    with NaN patterns here (all bytes 0xff: -1 as an int) -- while their twins in the unmigrated solve read the live
+    one: the bit-for-bit comparison of the two is what notices.
+    That both handles ran where the test means them to is asserted through rmpc_last_solve_path: pass kernels, a
+    migration of at least 8 survivors on one side and none on the other (pass_batch_cases.py: the seeds are those for
+    which the oracle's pass counts predict it).
+    B stays below 4096 here: above it the migrated list (n_act = the survivors) and the unmigrated one (n_act = the
+    batch while more than an eighth of it iterates, the instances still iterating afterwards) can sit on different
+    sides of kGroupedMin = 512, the two solves then run different k_riccati blocks and bit-identity is not owed."""
+    assert B < 4096
+    sc = rt["make_scenario"](name, B=B, seed=seed, **kw)
+    s, s2 = _migrating_pair(rt, monkeypatch, sc.desc, B, env)
+    s.poison_lds()     # (the compact workspace too: a word k_migrate does not bring along is a NaN pattern, or -1, there)
     gpu = s.solve(sc.xinit, sc.x0, sc.params)
+    path = s.last_solve_path()
     s.close()
-    os.environ["RMPC_NO_MIGRATE"] = "1"   # debugging switch, read once when a handle is created
-    try:
-        s2 = rt["Solver"](sc.desc, max_batch=B)
-    finally:
-        del os.environ["RMPC_NO_MIGRATE"]
     ref = s2.solve(sc.xinit, sc.x0, sc.params)
+    path2 = s2.last_solve_path()
     s2.close()
+    print("migration %s B %d: %s | twin %s | iters max %d" % (name, B, path, path2, gpu["iters"].max()))
+    assert not path["fused"] and path["migrated_at"] >= 8 and 8 <= path["survivors"] <= B // 8, path
+    assert not path2["fused"] and path2["migrated_at"] == -1 and path2["survivors"] == -1, path2
     for key in ("z", "exitflag", "iters", "obj", "kkt"):
         assert np.array_equal(gpu[key], ref[key]), key
-    assert gpu["iters"].max() > 16   # some instances did outlive the migration point
     cpu = rt["Oracle"](sc.desc).solve_batch(sc.xinit, sc.x0, sc.params)
+    print("migration %s B %d: iteration counts equal to the oracle's %.4f" % (name, B, (gpu["iters"] == cpu["iters"]).mean()))
     check_plan(gpu, cpu, sc.desc["nx"] + sc.desc["ns"])
 
 
-def test_handle_reuse_after_migration(rt):
-    """A handle that has just run a migrating batch solves a small batch exactly like a fresh handle."""
-    big = rt["make_scenario"]("cfg2", B=2048, seed=21)
-    small = rt["make_scenario"]("cfg2", B=100, seed=22)
-    s = rt["Solver"](big.desc, max_batch=2048)
+def test_handle_reuse_after_migration(rt, monkeypatch):
+    """A handle of the pass kernels that has just run a migrating batch solves a small batch exactly like a fresh handle
+    (and like a handle that went through the same big batch without migrating)."""
+    name, B, seed, kw, env = MIGRATION_CASES[0]
+    big = rt["make_scenario"](name, B=B, seed=seed, **kw)
+    small = rt["make_scenario"](name, B=100, seed=22, **kw)
+    s, s2 = _migrating_pair(rt, monkeypatch, big.desc, B, env)
     s.solve(big.xinit, big.x0, big.params)
+    path = s.last_solve_path()
+    assert path["migrated_at"] >= 8 and path["survivors"] >= 8, path
     a = s.solve(small.xinit, small.x0, small.params)
+    after = s.last_solve_path()
+    assert not after["fused"] and after["migrated_at"] == -1 and after["ric_first"] == "wave", after
     s.close()
-    f = rt["Solver"](small.desc, max_batch=100)
+    s2.solve(big.xinit, big.x0, big.params)
+    assert s2.last_solve_path()["migrated_at"] == -1
+    c = s2.solve(small.xinit, small.x0, small.params)
+    s2.close()
+    f = rt["Solver"](small.desc, max_batch=100)     # (created under the same switches: pass kernels)
+    assert not f.is_fused()
     b = f.solve(small.xinit, small.x0, small.params)
     f.close()
     for key in ("z", "exitflag", "iters", "obj", "kkt"):
         assert np.array_equal(a[key], b[key]), key
+        assert np.array_equal(c[key], b[key]), key
 
 
 @pytest.mark.parametrize("name", ["cfg1", "cfg2", "cfg3", "cfg4", "boxer", "pointRobot", "panda"])

@@ -3,9 +3,36 @@
 import numpy as np
 import pytest
 
+from pass_batch_cases import NO_FUSED, strided_sample
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-6
+LANE = {"RMPC_RIC_LANE": "2"}
+
+
+def _set_env(monkeypatch, env):
+    """The switches a handle reads once, at rmpc_create: those of the case and no others."""
+    for k in ("RMPC_NO_FUSED", "RMPC_RIC_LANE", "RMPC_NO_MIGRATE"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def _ids(cases, n):
+    # (the first n entries of a case, then the overrides and switches that tell it from its neighbours)
+    return ["-".join([str(v) for v in c[:n]] + ["%s%s" % (k[0].upper(), v) for k, v in sorted(c[n].items())]
+                     + [k[5:].lower() + v for k, v in sorted(c[n + 1].items())]) for c in cases]
+
+
+# (name, B, steps, make_scenario overrides, environment at rmpc_create, fused): the fused handles, and the pass kernels --
+# k_sweep's warm first pass and k_save_duals behind every solve -- through the models that are there anyway (4 and 8
+# joints: ric_backward; a horizon of 40 stages), the arm's and the boxer's own recursions and the lane-per-instance one
+CLOSED_LOOP_CASES = [
+    ("cfg2", 24, 8, {}, {}, True), ("cfg3", 24, 8, {}, {}, True), ("cfg4", 8, 6, {}, {}, True), ("wc_boxer", 16, 6, {}, {}, True),
+    ("chain4", 16, 6, {}, {}, False), ("chain8", 8, 5, {}, {}, False), ("cfg2", 24, 6, {"time_horizon": 40}, {}, False),
+    ("cfg4", 8, 6, {}, NO_FUSED, False), ("cfg3", 24, 6, {}, NO_FUSED, False), ("cfg2", 24, 6, {}, dict(NO_FUSED, **LANE), False),
+]
 
 
 @pytest.fixture(scope="module")
@@ -18,15 +45,18 @@ def rt():
     return dict(Oracle=Oracle, Solver=Solver, make_scenario=make_scenario)
 
 
-@pytest.mark.parametrize("name,B,steps", [("cfg2", 24, 8), ("cfg3", 24, 8), ("cfg4", 8, 6), ("wc_boxer", 16, 6)])
-def test_warm_started_closed_loop_matches_oracle(rt, name, B, steps):
+@pytest.mark.parametrize("name,B,steps,kw,env,fused", CLOSED_LOOP_CASES, ids=_ids(CLOSED_LOOP_CASES, 3))
+def test_warm_started_closed_loop_matches_oracle(rt, name, B, steps, kw, env, fused, monkeypatch):
     """previous_plan initialisation + multiplier warm start, plant = the model's ERK2 map.  Every step: same exit
     flags (1 <-> 2 flips only at the tolerance), applied control within 1e-6, and the warm start pays:
-    fewer iterations than the cold first step."""
+    fewer iterations than the cold first step.  Fused handles and handles of the pass kernels (there the multipliers of
+    a finished solve reach the next one through k_save_duals and the warm first pass of k_sweep)."""
     from robot_mpcs_amd.fleet import flags_consistent
-    sc = rt["make_scenario"](name, B=B, seed=41)
+    _set_env(monkeypatch, env)
+    sc = rt["make_scenario"](name, B=B, seed=41, **kw)
     o = rt["Oracle"](sc.desc)
     s = rt["Solver"](sc.desc, max_batch=B)
+    assert s.is_fused() == fused
     s.set_warm_start(True)
     nx, nv, N, nxs = o.nx, o.nv, o.N, o.nx + o.ns
     x = sc.xinit.copy()
@@ -48,6 +78,8 @@ def test_warm_started_closed_loop_matches_oracle(rt, name, B, steps):
         us = np.maximum(1.0, np.abs(cz[:, 0, nxs:]).max(axis=1))
         assert np.all(du[ok] <= TOL * us[ok]), (t, du.max())
         assert (g["iters"] == ci).mean() >= 0.9, (t, g["iters"], ci)
+        path = s.last_solve_path()
+        assert path["fused"] == fused and (fused or path["ric_first"] == ("lane" if "RMPC_RIC_LANE" in env else "wave")), path
         if t == 0:
             it_first = g["iters"].mean()
         else:
@@ -79,14 +111,21 @@ def test_warm_start_is_per_instance_and_forgets_on_mode_change(rt):
     s.close()
 
 
-@pytest.mark.parametrize("name,B", [("cfg2", 64), ("cfg3", 64), ("cfg4", 32)])
-def test_warm_start_recovers_after_a_poisoned_solve(rt, name, B):
+RECOVERY_CASES = [("cfg2", 64, {}, {}), ("cfg3", 64, {}, {}), ("cfg4", 32, {}, {}),
+                  # the pass kernels: k_save_duals fills the rows of a failed instance with zeros and its mu with mu0
+                  ("cfg2", 64, {}, NO_FUSED), ("cfg4", 32, {}, NO_FUSED)]
+
+
+@pytest.mark.parametrize("name,B,kw,env", RECOVERY_CASES, ids=_ids(RECOVERY_CASES, 2))
+def test_warm_start_recovers_after_a_poisoned_solve(rt, name, B, kw, env, monkeypatch):
     """A warm-started handle whose instance 4 gets a NaN start state for ONE control step: that solve fails (flag < 0), its
     multipliers are not kept, and the next solve from clean inputs converges again to the cold solve's objective; every other
     instance goes through the three steps bit for bit like a twin handle that never saw the NaN."""
-    sc = rt["make_scenario"](name, B=B, seed=15)
+    _set_env(monkeypatch, env)
+    sc = rt["make_scenario"](name, B=B, seed=15, **kw)
     a = rt["Solver"](sc.desc, max_batch=B); a.set_warm_start(True)
     b = rt["Solver"](sc.desc, max_batch=B); b.set_warm_start(True)
+    assert a.is_fused() == b.is_fused() == (not env)
     cold = a.solve(sc.xinit, sc.x0, sc.params)
     b.solve(sc.xinit, sc.x0, sc.params)
     xi = sc.xinit.copy(); xi[4, 1] = np.nan
@@ -103,6 +142,55 @@ def test_warm_start_recovers_after_a_poisoned_solve(rt, name, B):
     assert abs(rec["obj"][4] - cold["obj"][4]) <= 1e-5 * max(1.0, abs(cold["obj"][4]))
     for k in ("z", "exitflag", "iters"):
         assert np.array_equal(rec[k][others], twin3[k][others]), k
+
+
+def test_warm_loop_across_a_migration(rt, monkeypatch):
+    """Three warm-started control steps of 1024 point robots on the pass kernels, each step's inputs taken from the plan
+    of the step before, through a handle that migrates and a twin created under RMPC_NO_MIGRATE: every step bit for bit
+    the same.  After a migration the survivors' multipliers are saved by a second k_save_duals, out of the compact
+    workspace and through `orig` over the stale rows the first launch left for them: a row saved from the wrong column or
+    the wrong buffer changes step 1 of exactly the survivors of step 0.  The oracle's solve_warm follows a strided sample
+    of 32 instances through the same steps (the applied-control bar of the closed-loop test); pass_batch_cases.py says
+    how the seed was chosen (oracle, cold step: 258 instances iterating after 14 passes, 78 after 16 -> they move)."""
+    from robot_mpcs_amd.fleet import flags_consistent
+    B, steps = 1024, 3
+    _set_env(monkeypatch, NO_FUSED)
+    sc = rt["make_scenario"]("cfg2", B=B, seed=7)
+    a = rt["Solver"](sc.desc, max_batch=B); a.set_warm_start(True)
+    monkeypatch.setenv("RMPC_NO_MIGRATE", "1")     # (read once, at rmpc_create)
+    b = rt["Solver"](sc.desc, max_batch=B); b.set_warm_start(True)
+    assert not a.is_fused() and not b.is_fused()
+    o = rt["Oracle"](sc.desc)
+    nx, nxs, N = o.nx, o.nx + o.ns, o.N
+    idx = strided_sample(B, 32)
+    duals = {int(i): None for i in idx}
+    x = sc.xinit.copy(); x0 = sc.x0.copy()
+    for t in range(steps):
+        ra = a.solve(x, x0, sc.params); rb = b.solve(x, x0, sc.params)
+        pa, pb = a.last_solve_path(), b.last_solve_path()
+        print("warm loop step %d: %s | twin %s | iters mean %.2f max %d" % (t, pa, pb, ra["iters"].mean(), ra["iters"].max()))
+        assert not pa["fused"] and not pb["fused"] and pb["migrated_at"] == -1, (t, pa, pb)
+        if t == 0:
+            assert pa["migrated_at"] >= 8 and pa["survivors"] >= 8, pa
+        for k in ("z", "exitflag", "iters"):
+            assert np.array_equal(ra[k], rb[k]), (t, k, np.flatnonzero((ra[k] != rb[k]).reshape(B, -1).any(axis=1)))
+        cz = np.zeros((len(idx),) + ra["z"].shape[1:]); cf = np.zeros(len(idx), dtype=np.int32); ci = np.zeros(len(idx), dtype=np.int32)
+        for j, i in enumerate(idx):
+            r = o.solve_warm(x[i], x0[i], sc.params[i], duals[int(i)])
+            cz[j] = r["z"]; cf[j] = r["exitflag"]; ci[j] = r["iters"]
+            duals[int(i)] = r["duals"] if r["exitflag"] >= 0 else (np.zeros((N, o.m)), np.zeros((N, nx)), sc.desc["options"]["mu0"] / 1000.0)
+        assert flags_consistent(ra["exitflag"][idx], cf, ra["kkt"][idx], 1e-6), (t, ra["exitflag"][idx], cf)
+        ok = np.isin(cf, (1, 2))
+        du = np.abs(ra["z"][idx, 0, nxs:] - cz[:, 0, nxs:]).max(axis=1)
+        us = np.maximum(1.0, np.abs(cz[:, 0, nxs:]).max(axis=1))
+        assert np.all(du[ok] <= TOL * us[ok]), (t, du.max())
+        print("warm loop step %d: iteration counts equal to the oracle's %.4f" % (t, (ra["iters"][idx] == ci).mean()))
+        assert (ra["iters"][idx] == ci).mean() >= 0.9, (t, ra["iters"][idx], ci)
+        good = ra["exitflag"] >= 0
+        z = ra["z"]
+        x0 = np.where(good[:, None, None], np.concatenate([z[:, 1:], z[:, -1:]], axis=1), x0)
+        x = np.where(good[:, None], z[:, 1, :nx], x)
+    a.close(); b.close()
 
 
 def test_mixed_fleet_shard_closed_loop(rt):
