@@ -100,6 +100,41 @@ __device__ __forceinline__ double frcp(double x) {
   return fma(r, e, r);
 }
 
+// x is formed where this statement stands, not later: an empty statement that reads x from a vector register.  The
+// compiler keeps the statement in program order among the loads, stores and scheduling barriers around it, so a long
+// accumulation chain (a sum or a maximum over the rows of a stage) advances row by row and only the accumulator stays
+// alive, not every row's operands up to the point where the chain is finally run.  x is an input only: what the
+// compiler knows of the value (that the result of an fmax is already canonical, say) is kept, and no instruction is
+// emitted.  Empty in the host build (the constraint is the device's).
+template <class T>
+__device__ __forceinline__ void formed_here(const T &x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : : "v"(x));
+#else
+  (void)x;
+#endif
+}
+
+// "some test of this lane has failed", gathered test by test where the tests stand.  An int that is or-ed with
+// comparisons lives as a lane mask in scalar registers anyway; formed_here() would force it into a vector register
+// (a select per test).  Here the mask is the variable: each test is the comparison and one scalar or, held in place
+// as a scalar operand, and any() is one select at the end.  A lane reads only its own bit, so the lanes a call leaves
+// out do not matter.  The host build keeps the int.
+struct LaneTests {
+#if defined(__HIP_DEVICE_COMPILE__)
+  unsigned long long m = 0;
+  __device__ __forceinline__ void add(const bool failed) {
+    m |= __builtin_amdgcn_ballot_w64(failed);
+    asm volatile("" : : "s"(m));
+  }
+  __device__ __forceinline__ int any() const { return (int)__builtin_amdgcn_inverse_ballot_w64(m); }
+#else
+  int m = 0;
+  __device__ __forceinline__ void add(const bool failed) { m |= (int)failed; }
+  __device__ __forceinline__ int any() const { return m; }
+#endif
+};
+
 // compile-time loop: fn(integral_constant<int, L>) ... fn(integral_constant<int, H-1>)
 template <int L, class F, int... I>
 __device__ __forceinline__ void for_range_impl(F &&fn, std::integer_sequence<int, I...>) {

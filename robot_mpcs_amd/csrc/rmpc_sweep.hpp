@@ -371,6 +371,13 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
   }
   // trial slack / multiplier of row i and their bookkeeping; returns sigma, ca, cb, lv
   struct RowW { double sig, ca, cb, lv; };
+  // (ROWSUMS, the scope of FINROWS below -- the chain without slack in its own order under a generated view: the sums,
+  //  maxima and the positivity test over the rows advance at each row.  They are long serial chains whose only use is
+  //  `out`, and the compiler ran them all at the end of the stage, with tv, lv and g - tv of every row alive until
+  //  then: a third of the later-pass call's register copies.  Same operations in the same order; the defect's terms
+  //  are left free, holding them costs registers: DESIGN.md 5.1)
+  constexpr bool ROWSUMS = (C::ROBOT == RMPC_ROBOT_CHAIN) && NQ <= 3 && NS == 0 && V::SPEC;
+  LaneTests rowbad;
   // (gold, gdz: row value at the current iterate and J_i dz -- the slack / multiplier steps of the row are
   //  recomputed with the very expressions k_step took its step lengths from)
   auto row_core = [&](int i, double g, double tcv, double lcv, double gold, double gdz) __attribute__((always_inline)) -> RowW {
@@ -392,7 +399,9 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
     ln[IDXL(i)] = lv;
     const double rg = g - tv;
     theta += fabs(rg);
-    bad |= (int)!(tv > 0.0);   // (cannot happen: fraction to the boundary; keeps the product's sign meaningful.  |=: no branch)
+    // (cannot happen: fraction to the boundary; keeps the product's sign meaningful.  |=: no branch)
+    if constexpr (ROWSUMS) rowbad.add(!(tv > 0.0));
+    else bad |= (int)!(tv > 0.0);
     {
       int ex;
       lprod *= frexp(tv, &ex);
@@ -403,6 +412,10 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
     rcomp = fmax(rcomp, cmp);
     sumc += cmp;
     minc = fmin(minc, cmp);
+    if constexpr (ROWSUMS) {
+      formed_here(theta); formed_here(lprod); formed_here(lexp); formed_here(rineq); formed_here(rcomp);
+      formed_here(sumc); formed_here(minc);
+    }
     const double it = frcp(tv);
     return {lv * it, lv * rg * it, it, lv};
   };
@@ -940,6 +953,7 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
   }
   rec[C::R_ZERO] = 0.0;
   const double logsum = log(lprod) + 0.6931471805599453094 * (double)lexp;
+  if constexpr (ROWSUMS) bad |= rowbad.any();
   bad |= (int)(!isfinite(f) | !isfinite(theta) | !isfinite(logsum));
   st(3);
   st.put(out, 0, 4);
