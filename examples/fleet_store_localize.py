@@ -12,11 +12,20 @@ starts at the truth: ``OdometryDrift.advance`` integrates the noisy wheel odomet
 ``--dead-reckoning`` skips the matcher, ``--true-pose`` feeds the follower the truth (the loop of fleet_store_lidar.py).
 Nothing crosses PCIe between control steps; the statistics stay on the device until the end.
 
+``--kidnap N --kidnap-step S`` displaces the estimates of N robots by up to 1.5 m and 0.4 rad at step S, as if they had
+been lifted and set down elsewhere.  From then on a robot whose matched scan still lies far from the map,
+``score > used * lost_per_ray`` (compared on the device into ``active``, no host read), relocalises:
+``ScanSearcher.relocalize`` searches 81 x 81 x 41 poses around its estimate (``rmpc_scan_search_device``)
+and matches again at the pose found.
+
     python examples/fleet_store_localize.py [--robots 64] [--steps 1200] [--seed 0] [--dead-reckoning | --true-pose]
+                                            [--kidnap N --kidnap-step S]
 
 Prints one JSON line: the report of the other store examples (routes, arrivals, failed solves, clearances, ms per
 control step), the mean, p95 and max of the estimate's position [m] and heading [rad] error over all robot-steps and
-the mean position error after the last step, and ms of ``ScanMatcher.step`` alone (median of 20 event-timed calls).
+the mean position error after the last step, and ms of ``ScanMatcher.step`` alone (median of 20 event-timed calls);
+with ``--kidnap`` each kidnapped robot's position error [m] before and after step S and after the last step, how many
+of them ended step S within two fine cells (0.1125 m) of the truth, and ms of ``ScanSearcher.step`` alone.
 """
 import argparse
 import json
@@ -34,15 +43,18 @@ if ROOT not in sys.path:
 MODES = ("match", "dead-reckoning", "true-pose")
 
 
-def run(B=64, steps=1200, seed=0, dev="cuda:0", K=4, rays=64, mode="match", threshold=1.3, occ_threshold=0.5):
+def run(B=64, steps=1200, seed=0, dev="cuda:0", K=4, rays=64, mode="match", threshold=1.3, occ_threshold=0.5, kidnap=0,
+        kidnap_step=None, lost_per_ray=32.0):
     import torch
     from robot_mpcs_amd.fleet import Arrivals, MixedFleetShard, dev_f64, event_ms
     from robot_mpcs_amd.global_planner import plan_batch
     from robot_mpcs_amd.store import STORE as S, BoxerStore, clear_routes, store_map
-    from robot_mpcs_amd.utils.localization import OdometryDrift, ScanMatcher
+    from robot_mpcs_amd.utils.localization import OdometryDrift, ScanMatcher, ScanSearcher
 
     if mode not in MODES:
         raise ValueError("mode: one of %s" % (MODES,))
+    if kidnap and (mode != "match" or not 0 < kidnap <= B or kidnap_step is None or not 0 <= kidnap_step < steps):
+        raise ValueError("kidnap: needs mode match, 0 < kidnap <= B and 0 <= kidnap_step < steps")
     rng = np.random.default_rng(seed)
     g_inf, starts, goals = clear_routes(store_map(seed), B, rng, dev)
     fleet = BoxerStore(B, seed, dev, K, rays, starts, rng)
@@ -57,6 +69,13 @@ def run(B=64, steps=1200, seed=0, dev="cuda:0", K=4, rays=64, mode="match", thre
     matcher.set_map(dev_f64(fleet.raw, dev), occ_threshold)
     drift = OdometryDrift(B, steps, seed)
     est = fleet.x[:, :3].clone()
+    if kidnap:
+        searcher = ScanSearcher(matcher, nxy=40, step_xy=0.0375, nth=20, step_th=0.02)
+        searcher.set_map()
+        kid = torch.arange(kidnap, device=dev) * (B // kidnap)
+        shift = dev_f64(np.random.default_rng(seed + 1000).uniform(-1, 1, (kidnap, 3)) * [1.5, 1.5, 0.4], dev)
+        kid_err = torch.zeros((3, kidnap), dtype=torch.float64, device=dev)       # before, after step S, after the last step
+        err_of = lambda: (est[kid, :2] - fleet.x[kid, :2]).norm(dim=1)
     x_prev = torch.empty_like(fleet.x)
     e_pos = torch.zeros((steps, B), dtype=torch.float64, device=dev)
     e_th = torch.zeros((steps, B), dtype=torch.float64, device=dev)
@@ -65,8 +84,17 @@ def run(B=64, steps=1200, seed=0, dev="cuda:0", K=4, rays=64, mode="match", thre
     t_loop = time.perf_counter()
     for step in range(steps):
         fleet.scan()
+        if kidnap and step == kidnap_step:
+            est[kid] += shift
+            kid_err[0] = err_of()
         if mode == "match":
             est.copy_(matcher.step(est, lp.ranges))
+        if kidnap and step >= kidnap_step:
+            lost = matcher.score.double() > matcher.used.double() * lost_per_ray
+            found = searcher.relocalize(est, lp.ranges, lost.to(torch.int32))
+            est.copy_(torch.where(lost[:, None], found, est))
+            if step == kidnap_step:
+                kid_err[1] = err_of()
         e_pos[step] = (est[:, :2] - fleet.x[:, :2]).norm(dim=1)
         e_th[step] = (torch.remainder(est[:, 2] - fleet.x[:, 2] + math.pi, 2.0 * math.pi) - math.pi).abs()
         follower.step(fleet.x if mode == "true-pose" else est, fleet.goal)
@@ -78,6 +106,14 @@ def run(B=64, steps=1200, seed=0, dev="cuda:0", K=4, rays=64, mode="match", thre
     ms = 1e3 * (time.perf_counter() - t_loop) / steps
 
     match_ms = event_ms(lambda: matcher.step(est, lp.ranges), 20)
+    extra = {}
+    if kidnap:
+        kid_err[2] = err_of()
+        e = kid_err.cpu().numpy()
+        extra = dict(kidnap=kidnap, kidnap_step=kidnap_step, lost_per_ray=lost_per_ray, kidnapped=kid.tolist(),
+                     kidnap_err_before_m=np.round(e[0], 3).tolist(), kidnap_err_after_m=np.round(e[1], 3).tolist(),
+                     kidnap_err_final_m=np.round(e[2], 3).tolist(), kidnap_recovered=int((e[1] <= 2 * S.cell / 8).sum()),
+                     search_step_ms=round(event_ms(lambda: searcher.step(est, lp.ranges), 20), 4))
     q = lambda e, p: float(e.flatten().quantile(p).item())
     out = dict(fleet.report(), steps=steps, mode=mode, routes=int((lens > 0).sum().item()), **arrivals.summary(),
                pos_err_mean_m=float(e_pos.mean().item()), pos_err_p95_m=q(e_pos, 0.95), pos_err_max_m=float(e_pos.max().item()),
@@ -85,7 +121,7 @@ def run(B=64, steps=1200, seed=0, dev="cuda:0", K=4, rays=64, mode="match", thre
                heading_err_mean_rad=float(e_th.mean().item()), heading_err_p95_rad=q(e_th, 0.95),
                heading_err_max_rad=float(e_th.max().item()),
                matched_share=float((matcher.best >= 0).double().mean().item()) if mode == "match" else None,
-               ms_per_step=round(ms, 3), match_step_ms=round(match_ms, 4), arrive_tol_m=tol)
+               ms_per_step=round(ms, 3), match_step_ms=round(match_ms, 4), arrive_tol_m=tol, **extra)
     fleet.close()
     return out
 
@@ -101,11 +137,15 @@ def main():
     how = ap.add_mutually_exclusive_group()
     how.add_argument("--dead-reckoning", action="store_true")
     how.add_argument("--true-pose", action="store_true")
+    ap.add_argument("--kidnap", type=int, default=0)
+    ap.add_argument("--kidnap-step", type=int, default=None)
+    ap.add_argument("--lost-per-ray", type=float, default=32.0)
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build()
     mode = "dead-reckoning" if a.dead_reckoning else "true-pose" if a.true_pose else "match"
-    print(json.dumps(run(a.robots, a.steps, a.seed, K=a.K, rays=a.rays, mode=mode, threshold=a.threshold)))
+    print(json.dumps(run(a.robots, a.steps, a.seed, K=a.K, rays=a.rays, mode=mode, threshold=a.threshold, kidnap=a.kidnap,
+                         kidnap_step=a.kidnap_step, lost_per_ray=a.lost_per_ray)))
 
 
 if __name__ == "__main__":

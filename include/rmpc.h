@@ -61,7 +61,9 @@ extern "C" {
  *              RMPC_MATCH_MAX_RAYS, rmpc_scan_match, rmpc_grid_edge_distance_device, rmpc_lidar_project_device,
  *              rmpc_scan_match_device; moving obstacles, RMPC_TRACK_MAX_RAYS, RMPC_TRACK_MAX_TRACKS,
  *              RMPC_TRACK_MAX_DET, rmpc_tracks, rmpc_lidar_tracks_device; the fleet in the scan, rmpc_lidar_bodies,
- *              rmpc_lidar_scan_fleet_device; the test hook rmpc_last_solve_path (RMPC_PATH_*). */
+ *              rmpc_lidar_scan_fleet_device; the test hook rmpc_last_solve_path (RMPC_PATH_*); wide-window
+ *              localisation, RMPC_SEARCH_MAX_N, rmpc_scan_search, rmpc_grid_min_pyramid_device,
+ *              rmpc_scan_search_work_bytes, rmpc_scan_search_device. */
 #define RMPC_VERSION 201
 
 #define RMPC_MAX_JOINTS 8
@@ -679,6 +681,74 @@ int rmpc_grid_edge_distance_device(int H, int W, const double *d_grid, double oc
                                    int32_t *d_d2, void *stream);
 int rmpc_lidar_project_device(int B, const rmpc_lidar *l, void *stream);
 int rmpc_scan_match_device(int B, const rmpc_scan_match *m, void *stream);
+
+/* Wide-window localisation: the pose of rmpc_scan_match_device over a lattice of up to 255 x 255 x 255,
+ * found by branch and bound (Olson 2009, the multi-resolution half) instead of by scoring every candidate.  Needs no
+ * handle; every pointer is a device pointer, each call runs on the device of its first pointer (d_d2, s->pose), takes
+ * a stream and never synchronises.  Bounds are int32 sums of table entries that no candidate below a node undercuts,
+ * so the result is the exhaustive rule's bit for bit, on every run and whatever the order of the search.
+ *
+ * rmpc_grid_min_pyramid_device: from d_d2 [FH][FW] (FH = H sub, FW = W sub; the table of
+ * rmpc_grid_edge_distance_device) d_pyr [levels][FH][FW] int32, level major: pyr [l][R][C] = the least d2 over the
+ * window [R, R + 2^l) x [C, C + 2^l) intersected with the map; level 0 is d2 itself.  One launch per level.  Refused:
+ * NULL pointers, H or W < 1, H W > RMPC_GRID_MAX_CELLS, sub outside [1, 8], levels outside [1, 12].
+ *
+ * rmpc_scan_search_device: rules 1 to 5 of rmpc_scan_match_device over the lattice nxy, nth <= RMPC_SEARCH_MAX_N, with
+ * the same used rays, the same expressions for qx, qy, C, R in the same order, the same cap outside the map and the
+ * same order (score, m, k), compared as the tuple (k < 2^24 and m < 2^16 no longer fit one word beside a 31-bit
+ * score); pose_out, best, score, score0 (always the centre candidate's exact score) and used are those of that rule.
+ * A robot with active [b] == 0 (active may be NULL: every robot is active) gets rule 1's outputs, pose_out = the
+ * prior, best -1, score = score0 = 0, and used = its count of used rays.  rot comes from the caller as before.
+ *
+ * The bound.  A node is one rotation jth and a block of translations jx in [a, a1], jy in [b, b1], a and b multiples
+ * of 2^h and a1 = min(a + 2^h, 2 nxy + 1) - 1 (b1 likewise), h = top_log2 at the top level, one less per level and 0 at
+ * a leaf, which is one candidate and is scored by rule 4.  Of a node with h > 0, per used ray, with rule 4's
+ * expressions as doubles: Ca, Cb = the fine columns at jx = a and jx = a1, Ra, Rb = the fine rows at jy = b and
+ * jy = b1.  Any of the four not finite: the term is 0.  Else Cb < 0 or Ca >= FW or Rb < 0 or Ra >= FH: the term is
+ * cap.  Else all four are clipped into the map, e = max(Cb - Ca, Rb - Ra) + 1, l = the least level with 2^l >= e, and
+ * the term is pyr [l][Ra][Ca], or 0 when l >= levels.  The bound is the int32 sum of the terms; the node's key is
+ * (bound, m_min, 0) with m_min the least m of its block, and a node is dropped only when its key is greater than the
+ * full key (score, m, k) of the best candidate scored so far.
+ *
+ * The top-level nodes are numbered t = (jth nb + b / 2^top_log2) nb + a / 2^top_log2, nb = ceil((2 nxy + 1) / 2^top_log2),
+ * ntop = (2 nth + 1) nb nb.  top_bound [B][ntop] (may be NULL) receives their bounds, of the robots that were searched
+ * only: the rows of the others are not written.  leaves [B] (may be NULL) = the number of candidates scored exactly, a
+ * diagnostic that may depend on the schedule (0 for a robot that was not searched; the centre candidate's extra
+ * scoring for score0 is not counted).  work holds the bound table when top_bound is NULL: the kernel writes at most
+ * 4 B ntop bytes of it, rmpc_scan_search_work_bytes (B, nxy, nth, top_log2) says how many (-1 on arguments out of
+ * range); the nodes being searched live in a store of fixed size on the chip that cannot overflow.
+ * struct_size must equal sizeof(rmpc_scan_search); refused (-1, rmpc_last_error) as by rmpc_scan_match_device, with
+ * nxy or nth outside [0, RMPC_SEARCH_MAX_N], and: top_log2 outside [0, 7], levels outside [1, 12], a NULL pyr or work,
+ * work_bytes below the query's value, B ntop beyond INT_MAX. */
+#define RMPC_SEARCH_MAX_N 127
+typedef struct rmpc_scan_search {
+  int32_t struct_size;                 /* sizeof(rmpc_scan_search) */
+  int32_t rays;                        /* R in [1, RMPC_MATCH_MAX_RAYS] */
+  const double *pose;                  /* [B][pose_stride]: the priors, x, y, heading at 0, 1, 2 */
+  const double *points;                /* [B][R][3]: the scan projected at the priors */
+  const double *ranges;                /* [B][R] */
+  double range;                        /* the scan's range (> 0): t < range is a hit */
+  int32_t pose_stride, min_hits;       /* >= 3; >= 1 */
+  const int32_t *d2;                   /* [H sub][W sub] */
+  int32_t H, W, sub, cap;
+  double x0, y0, cell;
+  int32_t nxy, nth;                    /* the lattice: (2 nxy + 1)^2 (2 nth + 1) candidates, each n <= 127 */
+  double step_xy, step_th;
+  const double *rot;                   /* [2 nth + 1][2] */
+  double *pose_out;                    /* [B][3] out */
+  int32_t *best, *score;               /* [B] out */
+  int32_t *score0, *used;              /* [B] out, may be NULL */
+  const int32_t *pyr;                  /* [levels][H sub][W sub]: rmpc_grid_min_pyramid_device of d2 */
+  int32_t levels, top_log2;            /* [1, 12]; [0, 7] */
+  const int32_t *active;               /* [B], may be NULL: 0 = leave this robot at its prior */
+  void *work;                          /* work_bytes >= rmpc_scan_search_work_bytes(B, nxy, nth, top_log2) */
+  int64_t work_bytes;
+  int32_t *leaves;                     /* [B] out, may be NULL */
+  int32_t *top_bound;                  /* [B][ntop] out, may be NULL */
+} rmpc_scan_search;
+int rmpc_grid_min_pyramid_device(int H, int W, int sub, const int32_t *d_d2, int levels, int32_t *d_pyr, void *stream);
+int64_t rmpc_scan_search_work_bytes(int B, int nxy, int nth, int top_log2);
+int rmpc_scan_search_device(int B, const rmpc_scan_search *s, void *stream);
 
 /* Moving obstacles: a multi-target tracker per robot, from one lidar scan to the obst_dyn array a scene
  * points at (rmpc_scene.obst_dyn, predicted by the solver per stage at dt k).  Needs no handle; every pointer is a

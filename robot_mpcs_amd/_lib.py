@@ -139,6 +139,17 @@ class ScanMatchArgs(C.Structure):
     ]
 
 
+class ScanSearchArgs(C.Structure):
+    """Mirror of ``rmpc_scan_search`` (include/rmpc.h): the fields of ``rmpc_scan_match``, then the pyramid, the
+    workspace and the search's own outputs, device pointers."""
+    _fields_ = ScanMatchArgs._fields_ + [
+        ("pyr", C.c_void_p), ("levels", C.c_int32), ("top_log2", C.c_int32),
+        ("active", C.c_void_p),
+        ("work", C.c_void_p), ("work_bytes", C.c_int64),
+        ("leaves", C.c_void_p), ("top_bound", C.c_void_p),
+    ]
+
+
 class TracksArgs(C.Structure):
     """Mirror of ``rmpc_tracks`` (include/rmpc.h): one scan of B robots through the moving-obstacle tracker, device
     pointers."""
@@ -185,6 +196,7 @@ EXPORTED_SYMBOLS = [
     "rmpc_grid_edge_distance_device", "rmpc_lidar_project_device", "rmpc_scan_match_device",
     "rmpc_lidar_tracks_device", "rmpc_timed_plan_work_bytes", "rmpc_timed_plan_device", "rmpc_timed_follow_device",
     "rmpc_lidar_scan_fleet_device",
+    "rmpc_grid_min_pyramid_device", "rmpc_scan_search_work_bytes", "rmpc_scan_search_device",
 ]
 
 _lib = None
@@ -368,6 +380,12 @@ def load_library(path: str = LIB_PATH):
     L.rmpc_lidar_project_device.argtypes = [i, C.POINTER(LidarArgs), vp]
     L.rmpc_scan_match_device.restype = C.c_int
     L.rmpc_scan_match_device.argtypes = [i, C.POINTER(ScanMatchArgs), vp]
+    L.rmpc_grid_min_pyramid_device.restype = C.c_int
+    L.rmpc_grid_min_pyramid_device.argtypes = [i, i, i, vp, i, vp, vp]
+    L.rmpc_scan_search_work_bytes.restype = C.c_int64
+    L.rmpc_scan_search_work_bytes.argtypes = [i, i, i, i]
+    L.rmpc_scan_search_device.restype = C.c_int
+    L.rmpc_scan_search_device.argtypes = [i, C.POINTER(ScanSearchArgs), vp]
     L.rmpc_lidar_tracks_device.restype = C.c_int
     L.rmpc_lidar_tracks_device.argtypes = [i, C.POINTER(TracksArgs), vp]
     L.rmpc_timed_plan_work_bytes.restype = C.c_int64
@@ -810,6 +828,58 @@ def scan_match_args(pose, points, ranges, d2, rot, pose_out, best, score, H: int
 def scan_match_device(args: ScanMatchArgs, B: int, stream=None):
     """Correlative scan matching of B robots (``rmpc_scan_match_device``) with the ``scan_match_args`` of the call."""
     _grid_call("rmpc_scan_match_device", int(B), C.byref(args), _stream_arg(stream))
+
+
+# limits of the wide-window search (include/rmpc.h)
+SEARCH_MAX_N, SEARCH_MAX_TOP, SEARCH_MAX_LEVELS = 127, 7, 12
+
+
+def grid_min_pyramid_device(d2, pyr, sub: int, stream=None):
+    """d2 (H sub, W sub) int32 -> pyr (levels, H sub, W sub) int32: per level l and fine cell the least d2 over the
+    window of side 2^l that starts there, cut at the map's edge (``rmpc_grid_min_pyramid_device``)."""
+    FH, FW, sub = int(d2.shape[0]), int(d2.shape[1]), int(sub)
+    if sub < 1 or FH % sub or FW % sub or pyr.dim() != 3 or tuple(pyr.shape[1:]) != (FH, FW):
+        raise ValueError(f"grid_min_pyramid_device: need d2 (H sub, W sub) and pyr (levels, {FH}, {FW})")
+    _grid_call("rmpc_grid_min_pyramid_device", FH // sub, FW // sub, sub, _ptr(d2), int(pyr.shape[0]), _ptr(pyr),
+               _stream_arg(stream))
+
+
+def scan_search_top_nodes(nxy: int, nth: int, top_log2: int) -> int:
+    """the top-level nodes of one robot: (2 nth + 1) nb nb, nb = ceil((2 nxy + 1) / 2^top_log2)"""
+    nb = -(-(2 * int(nxy) + 1) // (1 << int(top_log2)))
+    return (2 * int(nth) + 1) * nb * nb
+
+
+def scan_search_work_bytes(B: int, nxy: int, nth: int, top_log2: int) -> int:
+    """bytes of workspace of ``scan_search_device`` (``rmpc_scan_search_work_bytes``)"""
+    L = load_library()
+    n = L.rmpc_scan_search_work_bytes(int(B), int(nxy), int(nth), int(top_log2))
+    if n < 0:
+        raise RmpcError("rmpc_scan_search_work_bytes failed: " + L.rmpc_last_error().decode())
+    return int(n)
+
+
+def scan_search_args(match: ScanMatchArgs, pyr, top_log2: int, work, active=None, leaves=None,
+                     top_bound=None) -> ScanSearchArgs:
+    """The ``rmpc_scan_search`` of one scan: the ``scan_match_args`` of the call (nxy, nth up to ``SEARCH_MAX_N``), pyr
+    (levels, H sub, W sub) int32, work a uint8 tensor of ``scan_search_work_bytes``, and, when given, active, leaves (B,)
+    and top_bound (B, ``scan_search_top_nodes``) int32 -- contiguous device tensors."""
+    a = ScanSearchArgs()
+    for name, _ in ScanMatchArgs._fields_:
+        setattr(a, name, getattr(match, name))
+    a.struct_size = C.sizeof(ScanSearchArgs)
+    a.pyr, a.levels, a.top_log2 = pyr.data_ptr(), int(pyr.shape[0]), int(top_log2)
+    a.active = None if active is None else active.data_ptr()
+    a.work, a.work_bytes = work.data_ptr(), int(work.numel()) * int(work.element_size())
+    a.leaves = None if leaves is None else leaves.data_ptr()
+    a.top_bound = None if top_bound is None else top_bound.data_ptr()
+    return a
+
+
+def scan_search_device(args: ScanSearchArgs, B: int, stream=None):
+    """Branch-and-bound scan matching of B robots (``rmpc_scan_search_device``) with the ``scan_search_args`` of the
+    call."""
+    _grid_call("rmpc_scan_search_device", int(B), C.byref(args), _stream_arg(stream))
 
 
 # limits of the moving-obstacle tracker (include/rmpc.h)

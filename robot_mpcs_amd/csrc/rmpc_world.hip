@@ -93,6 +93,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_map.hpp"
 #include "rmpc_assign.hpp"
 #include "rmpc_locate.hpp"
+#include "rmpc_search.hpp"
 #include "rmpc_timed.hpp"
 #include "rmpc_track.hpp"
 
@@ -482,32 +483,87 @@ int rmpc_lidar_project_device(int B, const rmpc_lidar *l, void *stream) {
   return launch_status();
 }
 
-int rmpc_scan_match_device(int B, const rmpc_scan_match *m, void *stream) {
-  const char *who = "scan match";
-  if (!m) return fail("null argument");
-  if (m->struct_size != (int)sizeof(rmpc_scan_match)) return fail("rmpc_scan_match.struct_size mismatch");
-  if (B < 1) return fail("scan match: need B >= 1");
+// the fields rmpc_scan_match and rmpc_scan_search share, in the order rmpc_scan_match_device has always checked them
+extern "C++" template <class M>
+static int scan_lattice_check(const std::string &who, int B, const M *m, int max_n) {
+  if (B < 1) return fail(who + ": need B >= 1");
   if (m->rays < 1 || m->rays > RMPC_MATCH_MAX_RAYS)
-    return fail("scan match: need 1 <= rays <= RMPC_MATCH_MAX_RAYS = " + std::to_string(RMPC_MATCH_MAX_RAYS));
-  if (m->pose_stride < 3) return fail("scan match: pose_stride must be >= 3 (x, y, heading)");
-  if (m->min_hits < 1) return fail("scan match: need min_hits >= 1");
+    return fail(who + ": need 1 <= rays <= RMPC_MATCH_MAX_RAYS = " + std::to_string(RMPC_MATCH_MAX_RAYS));
+  if (m->pose_stride < 3) return fail(who + ": pose_stride must be >= 3 (x, y, heading)");
+  if (m->min_hits < 1) return fail(who + ": need min_hits >= 1");
   if (!grid_fits((long long)B * m->rays, 3) || !grid_fits(B, m->pose_stride))
-    return fail("scan match: B*rays*3 and B*pose_stride must not exceed INT_MAX");
-  if (!(m->range > 0.0) || std::isinf(m->range)) return fail("scan match: range must be positive and finite");
+    return fail(who + ": B*rays*3 and B*pose_stride must not exceed INT_MAX");
+  if (!(m->range > 0.0) || std::isinf(m->range)) return fail(who + ": range must be positive and finite");
   if (edge_table_check(who, m->H, m->W, m->sub, m->cap)) return -1;
-  if (!grid_fits(m->rays, m->cap)) return fail("scan match: rays*cap must not exceed INT_MAX");
+  if (!grid_fits(m->rays, m->cap)) return fail(who + ": rays*cap must not exceed INT_MAX");
   if (!(m->cell > 0.0) || std::isinf(m->cell) || !std::isfinite(m->x0) || !std::isfinite(m->y0))
-    return fail("scan match: cell must be positive and finite, x0 and y0 finite");
-  if (m->nxy < 0 || m->nxy > kMatchMaxN || m->nth < 0 || m->nth > kMatchMaxN)
-    return fail("scan match: nxy and nth must lie in [0, 15]");
+    return fail(who + ": cell must be positive and finite, x0 and y0 finite");
+  if (m->nxy < 0 || m->nxy > max_n || m->nth < 0 || m->nth > max_n)
+    return fail(who + ": nxy and nth must lie in [0, " + std::to_string(max_n) + "]");
   if (!(m->step_xy >= 0.0) || std::isinf(m->step_xy) || !(m->step_th >= 0.0) || std::isinf(m->step_th))
-    return fail("scan match: step_xy and step_th must be finite and >= 0");
+    return fail(who + ": step_xy and step_th must be finite and >= 0");
   if ((m->nxy > 0 && m->step_xy == 0.0) || (m->nth > 0 && m->step_th == 0.0))
-    return fail("scan match: a step of 0 needs nxy or nth of 0");
+    return fail(who + ": a step of 0 needs nxy or nth of 0");
   if (!m->pose || !m->points || !m->ranges || !m->d2 || !m->rot || !m->pose_out || !m->best || !m->score)
     return fail("null argument");
+  return 0;
+}
+
+int rmpc_scan_match_device(int B, const rmpc_scan_match *m, void *stream) {
+  if (!m) return fail("null argument");
+  if (m->struct_size != (int)sizeof(rmpc_scan_match)) return fail("rmpc_scan_match.struct_size mismatch");
+  if (scan_lattice_check("scan match", B, m, kMatchMaxN)) return -1;
   if (use_device_of(m->pose)) return -1;
   hipLaunchKernelGGL(k_scan_match, dim3(B), dim3(kMatchThreads), 0, (hipStream_t)stream, *m);
+  return launch_status();
+}
+
+/* wide-window localisation (rmpc_search.hpp) */
+int rmpc_grid_min_pyramid_device(int H, int W, int sub, const int32_t *d_d2, int levels, int32_t *d_pyr, void *stream) {
+  if (!d_d2 || !d_pyr) return fail("null argument");
+  if (edge_table_check("grid min pyramid", H, W, sub, 1)) return -1;
+  if (levels < 1 || levels > kSearchMaxLevels) return fail("grid min pyramid: levels must lie in [1, 12]");
+  if (use_device_of(d_d2)) return -1;
+  const int FH = H * sub, FW = W * sub, n = FH * FW;                   // <= 2^14 * 64
+  for (int l = 0; l < levels; l++) {
+    const int *const src = l == 0 ? (const int *)d_d2 : (const int *)d_pyr + (size_t)(l - 1) * n;
+    hipLaunchKernelGGL(k_min_pyramid, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, src,
+                       (int *)d_pyr + (size_t)l * n, FH, FW, l == 0 ? 0 : 1 << (l - 1));
+  }
+  return launch_status();
+}
+
+// the top-level nodes of one robot (include/rmpc.h), 0 on arguments out of range
+static long long search_top_nodes(int nxy, int nth, int top_log2) {
+  if (nxy < 0 || nxy > kSearchMaxN || nth < 0 || nth > kSearchMaxN || top_log2 < 0 || top_log2 > kSearchMaxTop) return 0;
+  const long long nb = ((2 * nxy + 1) + (1 << top_log2) - 1) >> top_log2;
+  return (2 * nth + 1) * nb * nb;                                     // <= 255^3
+}
+
+int64_t rmpc_scan_search_work_bytes(int B, int nxy, int nth, int top_log2) {
+  const long long ntop = search_top_nodes(nxy, nth, top_log2);
+  if (B < 1 || ntop == 0) {
+    fail("scan search work bytes: need B >= 1, nxy and nth in [0, 127], top_log2 in [0, 7]");
+    return -1;
+  }
+  return (int64_t)B * ntop * (int64_t)sizeof(int32_t);
+}
+
+int rmpc_scan_search_device(int B, const rmpc_scan_search *s, void *stream) {
+  const std::string who = "scan search";
+  if (!s) return fail("null argument");
+  if (s->struct_size != (int)sizeof(rmpc_scan_search)) return fail("rmpc_scan_search.struct_size mismatch");
+  if (scan_lattice_check(who, B, s, kSearchMaxN)) return -1;
+  if (s->top_log2 < 0 || s->top_log2 > kSearchMaxTop) return fail(who + ": top_log2 must lie in [0, 7]");
+  if (s->levels < 1 || s->levels > kSearchMaxLevels) return fail(who + ": levels must lie in [1, 12]");
+  if (!s->pyr || !s->work) return fail("null argument");
+  const long long ntop = search_top_nodes(s->nxy, s->nth, s->top_log2);
+  if (!grid_fits(B, ntop)) return fail(who + ": B*ntop must not exceed INT_MAX");
+  if (s->work_bytes < rmpc_scan_search_work_bytes(B, s->nxy, s->nth, s->top_log2))
+    return fail(who + ": work_bytes is below rmpc_scan_search_work_bytes");
+  if (use_device_of(s->pose)) return -1;
+  const int nb = ((2 * s->nxy + 1) + (1 << s->top_log2) - 1) >> s->top_log2;
+  hipLaunchKernelGGL(k_scan_search, dim3(B), dim3(kSearchThreads), 0, (hipStream_t)stream, *s, (int)ntop, nb);
   return launch_status();
 }
 

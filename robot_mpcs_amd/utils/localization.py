@@ -1,8 +1,10 @@
 """Where a robot believes it is: ``ScanMatcher`` corrects a pose prior by correlative scan matching of the robot's own
 lidar ranges against a map (``rmpc_grid_edge_distance_device``, ``rmpc_lidar_project_device``,
 ``rmpc_scan_match_device``), and ``OdometryDrift`` is the wheel odometry that makes the prior drift.  The
-other fleet features read the pose off the simulator's state; a robot on a shop floor has these two.  There is no CPU
-path for the matcher; the odometry is plain torch element-wise arithmetic.
+other fleet features read the pose off the simulator's state; a robot on a shop floor has these two.  ``ScanSearcher``
+finds the matcher's pose over a window of metres instead of centimetres, for a robot whose estimate is lost
+(``rmpc_grid_min_pyramid_device``, ``rmpc_scan_search_device``).  There is no CPU path for the matcher or
+the searcher; the odometry is plain torch element-wise arithmetic.
 """
 from __future__ import annotations
 
@@ -71,6 +73,65 @@ class ScanMatcher:
                                  self.nth, self.step_th, self.max_range, self.min_hits, self.score0, self.used)
         _lib.scan_match_device(a, self.B, stream=st)
         return self.pose_out
+
+
+class ScanSearcher:
+    """Wide-window scan matching beside a ``ScanMatcher``: the pose that ``rmpc_scan_match``'s rule picks from a lattice
+    of (2 nxy + 1)^2 (2 nth + 1) poses, nxy and nth up to 127, found by branch and bound on the minimum pyramid of the
+    matcher's ``d2``.  Shares the matcher's map, lidar, frame and ``min_hits``; owns ``pyr`` (levels, H sub, W sub) int32,
+    ``rot``, ``points``, the workspace and ``pose_out`` (B, 3), ``best``, ``score``, ``score0``, ``used``, ``leaves`` (B,)
+    int32.  ``levels`` defaults to what the window of a top-level block of 2^top_log2 steps needs.  ``set_map()`` (after
+    the matcher's) is one launch per level, ``step`` two (project, search); neither reads the device."""
+
+    def __init__(self, matcher, nxy, step_xy, nth, step_th, top_log2=3, levels=None):
+        import math
+        import torch
+        if not 0 <= int(nxy) <= _lib.SEARCH_MAX_N or not 0 <= int(nth) <= _lib.SEARCH_MAX_N:
+            raise ValueError(f"ScanSearcher: 0 <= nxy, nth <= {_lib.SEARCH_MAX_N}")
+        if not 0 <= int(top_log2) <= _lib.SEARCH_MAX_TOP:
+            raise ValueError(f"ScanSearcher: 0 <= top_log2 <= {_lib.SEARCH_MAX_TOP}")
+        m = self.matcher = matcher
+        if levels is None:
+            levels = min(_lib.SEARCH_MAX_LEVELS,
+                         math.ceil(math.log2((1 << int(top_log2)) * float(step_xy) * m.sub / m.cell + 2.0)) + 1)
+        if not 1 <= int(levels) <= _lib.SEARCH_MAX_LEVELS:
+            raise ValueError(f"ScanSearcher: 1 <= levels <= {_lib.SEARCH_MAX_LEVELS}")
+        dev = self.device = m.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.B = m.B
+        self.nxy, self.step_xy, self.nth, self.step_th = int(nxy), float(step_xy), int(nth), float(step_th)
+        self.top_log2, self.levels = int(top_log2), int(levels)
+        self.pyr = torch.full((self.levels, m.H * m.sub, m.W * m.sub), m.cap, **i32)
+        self.rot = torch.from_numpy(rotation_table(self.nth, self.step_th)).to(dev)
+        self.points = torch.zeros((m.B, m.rays, 3), dtype=torch.float64, device=dev)
+        nbytes = 4 * m.B * _lib.scan_search_top_nodes(self.nxy, self.nth, self.top_log2)
+        self.work = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.pose_out = torch.zeros((m.B, 3), dtype=torch.float64, device=dev)
+        self.best, self.score = torch.zeros(m.B, **i32), torch.zeros(m.B, **i32)
+        self.score0, self.used, self.leaves = torch.zeros(m.B, **i32), torch.zeros(m.B, **i32), torch.zeros(m.B, **i32)
+
+    def set_map(self, stream=None):
+        """the pyramid of the matcher's ``d2``: call after ``matcher.set_map`` (on the same stream)"""
+        _lib.grid_min_pyramid_device(self.matcher.d2, self.pyr, self.matcher.sub,
+                                     stream=_lib.stream_handle(stream, self.device))
+
+    def step(self, pose, ranges, active=None, stream=None):
+        """pose (B, stride >= 3) the priors, ranges (B, rays) the scan, active (B,) int32 or None: robots with 0 keep
+        their prior (``best`` -1).  Returns ``pose_out`` (B, 3), the least pose of the wide lattice by the matcher's rule."""
+        m, st = self.matcher, _lib.stream_handle(stream, self.device)
+        _lib.lidar_project_device(pose, ranges, self.points, m.angle_min, m.angle_max, m.max_range, m.offset, m.height,
+                                  stream=st)
+        a = _lib.scan_match_args(pose, self.points, ranges, m.d2, self.rot, self.pose_out, self.best, self.score, m.H, m.W,
+                                 m.sub, m.cap, m.x0, m.y0, m.cell, self.nxy, self.step_xy, self.nth, self.step_th,
+                                 m.max_range, m.min_hits, self.score0, self.used)
+        s = _lib.scan_search_args(a, self.pyr, self.top_log2, self.work, active=active, leaves=self.leaves)
+        _lib.scan_search_device(s, self.B, stream=st)
+        return self.pose_out
+
+    def relocalize(self, pose, ranges, active=None, stream=None):
+        """the search, then the matcher's fine lattice at the search's result: returns the matcher's ``pose_out``.  A
+        robot with active 0 is matched at its prior."""
+        return self.matcher.step(self.step(pose, ranges, active, stream), ranges, stream)
 
 
 class OdometryDrift:
