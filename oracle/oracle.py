@@ -18,6 +18,10 @@ _LIB_PATH = os.path.join(_HERE, "librmpc_oracle.so")
 MAX_JOINTS, MAX_LINKS, MAX_PAIRS, MAX_MODULES, NV_MAX = 8, 8, 4, 8, 24
 MAX_XROWS = 32
 TRACE_W = 8
+# branch census of a solve (rmpc_oracle.h ORC_CEN_*, same order)
+CENSUS = ("gn_backtrack", "ls_memory", "ls_max", "curv_halved", "curv_ls_fail", "fact_fail", "cs_retry", "cs_kept",
+          "cs_doubled", "skip", "back_max", "latch_set", "latch_released", "restart", "rho_raised", "stall_max",
+          "stall_reset", "exit", "cs_exhausted")
 
 
 class OrcDesc(C.Structure):
@@ -98,6 +102,9 @@ def lib():
         L.orc_solve_batch.argtypes = [C.POINTER(OrcDesc), C.c_int, dp, dp, dp, dp, C.POINTER(OrcStats), C.c_int]
         L.orc_debug_step.restype = C.c_int
         L.orc_debug_step.argtypes = [C.POINTER(OrcDesc), dp, dp, dp, dp, dp, C.c_double] + [dp] * 10 + [C.POINTER(C.c_int), C.c_double, dp]
+        L.orc_last_passes.restype = C.c_int
+        L.orc_last_census.restype = C.c_int
+        L.orc_last_census.argtypes = [C.POINTER(C.c_int32)]
         L.orc_dynamics.restype = C.c_int
         L.orc_dynamics.argtypes = [C.POINTER(OrcDesc), dp, dp, dp]
         assert L.orc_desc_size() == C.sizeof(OrcDesc), "orc_desc layout mismatch"
@@ -154,6 +161,16 @@ def make_desc(d: dict) -> OrcDesc:
 
 def _p(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def last_census():
+    """Branch census of the calling thread's last solve: ``{"census": {name: count or maximum}, "first": {name: iteration
+    at which the counter first moved, -1 = never}, "passes": orc_last_passes()}`` (names: CENSUS)."""
+    buf = (C.c_int32 * (2 * len(CENSUS)))()
+    n = lib().orc_last_census(buf)
+    assert n == len(CENSUS), "census layout mismatch"
+    return dict(census={k: int(buf[i]) for i, k in enumerate(CENSUS)},
+                first={k: int(buf[n + i]) for i, k in enumerate(CENSUS)}, passes=int(lib().orc_last_passes()))
 
 
 class Oracle:
@@ -226,6 +243,7 @@ class Oracle:
         assert rc == 0, rc
         out = dict(z=z.reshape(self.N, self.nv), exitflag=st.exitflag, iters=st.iters, res_stat=st.res_stat,
                    res_eq=st.res_eq, res_ineq=st.res_ineq, res_comp=st.res_comp, obj=st.obj, mu=st.mu)
+        out.update(last_census())
         if trace:
             out["trace"] = tr[: st.iters + 1]
         return out
@@ -249,7 +267,18 @@ class Oracle:
         assert rc == 0, rc
         return dict(z=z.reshape(self.N, self.nv), exitflag=st.exitflag, iters=st.iters, res_stat=st.res_stat,
                     res_eq=st.res_eq, res_ineq=st.res_ineq, res_comp=st.res_comp, obj=st.obj, mu=st.mu,
-                    duals=(lam_out, nu_out, st.mu))
+                    duals=(lam_out, nu_out, st.mu), **last_census())
+
+    def solve_each(self, xinit, x0, params, duals=None):
+        """``solve_warm`` of every instance of a batch, one after the other on the calling thread (``duals``: a list with
+        one entry per instance, or None: all cold).  Returns stacked ``z``, ``exitflag``, ``iters``, ``passes`` and the
+        per-instance lists ``census``, ``first`` and ``duals``."""
+        B = len(xinit)
+        rs = [self.solve_warm(xinit[b], x0[b], params[b], None if duals is None else duals[b]) for b in range(B)]
+        return dict(z=np.array([r["z"] for r in rs]), exitflag=np.array([r["exitflag"] for r in rs], dtype=np.int32),
+                    iters=np.array([r["iters"] for r in rs], dtype=np.int32),
+                    passes=np.array([r["passes"] for r in rs], dtype=np.int32),
+                    census=[r["census"] for r in rs], first=[r["first"] for r in rs], duals=[r["duals"] for r in rs])
 
     def debug_step(self, xinit, x0, params, duals=None, curv=0.0):
         """One instance: the first pass of a solve (``duals`` as in ``solve_warm``, None = cold) and one step computation

@@ -1061,6 +1061,24 @@ static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, 
  * one more per step recomputed with the Gauss-Newton blocks) */
 static __thread int tl_passes;
 int orc_last_passes(void) { return tl_passes; }
+/* branch census of the calling thread's last solve (rmpc_oracle.h, ORC_CEN_*): counts or maxima, and the iteration at
+ * which each counter first moved (-1: never).  Counting only: no decision reads it. */
+static __thread int32_t tl_census[ORC_CEN_N], tl_census_first[ORC_CEN_N];
+static void cen_hit(int c, int it) {
+  tl_census[c]++;
+  if (tl_census_first[c] < 0) tl_census_first[c] = it;
+}
+static void cen_max(int c, int v, int it) {
+  if (v > tl_census[c]) {
+    tl_census[c] = v;
+    if (tl_census_first[c] < 0) tl_census_first[c] = it;
+  }
+}
+int orc_last_census(int32_t *out) {
+  memcpy(out, tl_census, sizeof tl_census);
+  memcpy(out + ORC_CEN_N, tl_census_first, sizeof tl_census_first);
+  return ORC_CEN_N;
+}
 static int orc_trace_stderr(void) {
   return getenv("ORC_TRACE") != 0;
 }
@@ -1241,6 +1259,8 @@ static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, 
   int ls_start = 0; /* step-length memory: halvings the next Gauss-Newton line search starts from */
   double obj_prev = 0.0;
   tl_passes = 1;
+  memset(tl_census, 0, sizeof tl_census);
+  for (int c = 0; c < ORC_CEN_N; c++) tl_census_first[c] = -1;
   int ev = eval_all(d, w, params);
   if (ev != 0) { exitflag = (ev == ORC_EVAL_BAD_AVOID) ? -7 : -10; goto done; }
   mu = first_duals(d, w, lam_w, nu_w, mu_w);
@@ -1299,15 +1319,18 @@ static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, 
     if (it >= 1 && res_eq <= ORC_ACC_FEAS && res_ineq <= ORC_ACC_FEAS && res_comp <= ORC_ACC_FEAS &&
         fabs(obj - obj_prev) <= d->acc_obj_tol * fmax(1.0, fabs(obj)))
       stall++;
-    else
+    else {
+      if (stall > 0) cen_hit(ORC_CEN_STALL_RESET, it);
       stall = 0;
+    }
+    cen_max(ORC_CEN_STALL_MAX, stall, it);
     obj_prev = obj;
     if (d->acc_iters > 0 && stall >= d->acc_iters) { exitflag = 2; break; }
     if (it >= d->max_iter) { exitflag = 0; break; }
     /* ---- step computation: exact constraint curvature first (when the model
      * qualifies and no fallback is latched), Gauss-Newton blocks otherwise ---- */
     int use_curv = curv_ok && !gn_sticky && mu <= ORC_CURV_MU;
-    if (use_curv && backoff_model(d) && curv_skip > 0) { curv_skip--; use_curv = 0; }
+    if (use_curv && backoff_model(d) && curv_skip > 0) { curv_skip--; use_curv = 0; cen_hit(ORC_CEN_SKIP, it); }
     double alpha = 0.0, ad = 1.0;
     int ls = 0, accepted = 0, fatal = 0;
     double theta_c = cscale ? theta_mem : 1.0;
@@ -1315,11 +1338,13 @@ static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, 
     for (;;) {
       stage_blocks(d, w, nh, mu, use_curv, theta_c);
       if (riccati(w) != 0) {
-        if (use_curv && cscale && theta_c > ORC_CS_MIN) { theta_c *= 0.5; theta_retry = 1; tl_passes++; continue; }
+        if (use_curv && cscale && theta_c > ORC_CS_MIN) { theta_c *= 0.5; theta_retry = 1; tl_passes++; cen_hit(ORC_CEN_CS_RETRY, it); continue; }
         if (use_curv) {
           use_curv = 0;
           tl_passes++;
-          if (backoff_model(d)) { curv_back = curv_back ? (curv_back < 16 ? 2 * curv_back : 16) : 1; curv_skip = curv_back; }
+          cen_hit(ORC_CEN_FACT_FAIL, it);
+          if (theta_retry) cen_hit(ORC_CEN_CS_EXHAUSTED, it);
+          if (backoff_model(d)) { curv_back = curv_back ? (curv_back < 16 ? 2 * curv_back : 16) : 1; curv_skip = curv_back; cen_max(ORC_CEN_BACK_MAX, curv_back, it); }
           continue; /* this iteration only */
         }
         fatal = 1;
@@ -1346,7 +1371,7 @@ static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, 
       /* ---- l1 merit, Armijo backtracking ---- */
       if (theta > 1e-13) {
         double need = gphi / (0.9 * theta);
-        if (rho < need) rho = need + 1.0;
+        if (rho < need) { rho = need + 1.0; cen_hit(ORC_CEN_RHO_RAISED, it); }
       }
       double D = gphi - rho * theta;
       double phi0 = obj - mu * logsum + rho * theta;
@@ -1355,6 +1380,7 @@ static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, 
       /* step-length memory: a Gauss-Newton line search starts one halving above the one accepted last;
        * a step with the exact curvature is tried at full length first */
       const int ls_begin = use_curv ? 0 : ls_start;
+      if (ls_begin > 0) cen_hit(ORC_CEN_LS_MEMORY, it);
       alpha = ldexp(ap, -ls_begin);
       for (ls = ls_begin; ls <= ls_cap; ls++) {
         for (size_t i = 0; i < (size_t)N * nv; i++) w->zt[i] = w->z[i] + alpha * w->dz[i];
@@ -1369,22 +1395,34 @@ static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, 
       }
       if (!accepted && use_curv) {
         /* Gauss-Newton fallback for this iteration; latched after repeated failures (the unicycle: backed off instead) */
-        if (backoff_model(d)) { curv_back = curv_back ? (curv_back < 16 ? 2 * curv_back : 16) : 1; curv_skip = curv_back; }
-        else if (++curv_fail >= ORC_CURV_FAIL_MAX) gn_sticky = 1;
+        cen_hit(ORC_CEN_CURV_LS_FAIL, it);
+        if (backoff_model(d)) { curv_back = curv_back ? (curv_back < 16 ? 2 * curv_back : 16) : 1; curv_skip = curv_back; cen_max(ORC_CEN_BACK_MAX, curv_back, it); }
+        else if (++curv_fail >= ORC_CURV_FAIL_MAX) { if (!gn_sticky) cen_hit(ORC_CEN_LATCH_SET, it); gn_sticky = 1; }
         tl_passes++;
         use_curv = 0;
         continue;
       }
       if (accepted && use_curv) { curv_fail = 0; curv_back = 0; }
+      if (accepted) {
+        cen_max(ORC_CEN_LS_MAX, ls, it);
+        if (!use_curv && ls > ls_begin) cen_hit(ORC_CEN_GN_BACKTRACK, it);
+        if (use_curv && ls > 0) cen_hit(ORC_CEN_CURV_HALVED, it);
+      }
       if (cscale) {
         if (accepted && use_curv) {
-          if (theta_retry) { theta_mem = theta_c; theta_clean = 0; }
-          else if (++theta_clean >= ORC_CS_CLEAN) { theta_mem = theta_c < 0.75 ? 2.0 * theta_c : 1.0; theta_clean = 0; }
-        } else if (accepted && theta_retry) { theta_mem = theta_c; theta_clean = 0; }
+          if (theta_retry) { theta_mem = theta_c; theta_clean = 0; cen_hit(ORC_CEN_CS_KEPT, it); }
+          else if (++theta_clean >= ORC_CS_CLEAN) {
+            if (theta_c < 1.0) cen_hit(ORC_CEN_CS_DOUBLED, it);
+            theta_mem = theta_c < 0.75 ? 2.0 * theta_c : 1.0; theta_clean = 0;
+          }
+        } else if (accepted && theta_retry) { theta_mem = theta_c; theta_clean = 0; cen_hit(ORC_CEN_CS_KEPT, it); }
       }
       /* the arms: a Gauss-Newton step accepted at full length releases the latch (the failures that set it
        * belong to the first iterations of a warm start, where the fraction to the boundary cuts the steps) */
-      if (accepted && !use_curv && ls == 0 && arm_curv(d)) { gn_sticky = 0; curv_fail = 0; }
+      if (accepted && !use_curv && ls == 0 && arm_curv(d)) {
+        if (gn_sticky) cen_hit(ORC_CEN_LATCH_RELEASED, it);
+        gn_sticky = 0; curv_fail = 0;
+      }
       if (accepted) ls_start = ls > ORC_LS_GROW ? ls - ORC_LS_GROW : 0;
       break;
     }
@@ -1418,7 +1456,7 @@ static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, 
     /* ---- barrier restart on stalled steps ---- */
     {
       small_steps = (it >= ORC_RS_IT && alpha < ORC_RS_ALPHA) ? small_steps + 1 : 0;
-      if (small_steps >= ORC_RS_N && mu < ORC_RS_MU && !(mu_hold > 0.0)) { mu_hold = ORC_RS_MU; small_steps = 0; }
+      if (small_steps >= ORC_RS_N && mu < ORC_RS_MU && !(mu_hold > 0.0)) { mu_hold = ORC_RS_MU; small_steps = 0; cen_hit(ORC_CEN_RESTART, it); }
       if (mu_hold > 0.0) {
         if (mu < mu_hold) mu = mu_hold;
         mu_hold *= ORC_RS_DECAY;
@@ -1430,6 +1468,8 @@ static int solve_impl(const orc_desc *d, const double *xinit, const double *x0, 
     if (ev != 0) { exitflag = (ev == ORC_EVAL_BAD_AVOID) ? -7 : -10; break; }
   }
 done:
+  tl_census[ORC_CEN_EXIT] = exitflag;
+  tl_census_first[ORC_CEN_EXIT] = it;
   st->exitflag = exitflag;
   st->iters = it;
   st->mu = mu;

@@ -128,6 +128,52 @@ int orc_num_rows(const orc_desc *d, int *nh, int *m);
 int orc_fk(const orc_desc *d, const double *q, int frame, double *pos, double *Jp);
 /* Cacc [n*n] += sum_c F_c d2 pos_c / dq dq (holonomic chain) */
 int orc_last_passes(void);
+
+/* Branch census of the calling thread's last solve (orc_solve, orc_solve_warm): which branches of the decision logic
+ * around the step the solve took.  Counting only -- no decision reads a counter, results are bit for bit those of a
+ * build without it (tests/test_decision_census_cpu.py against tests/golden).  Each counter against the sentence of
+ * DESIGN.md section 3 it witnesses ("count": events of the solve; "max": largest value seen):
+ *   GN_BACKTRACK   count  a Gauss-Newton step accepted after at least one halving of its own line search
+ *                         (ls > ls_begin)                          -- "Armijo (1e-4) backtracking by halving"
+ *   LS_MEMORY      count  a Gauss-Newton line search started below full length (ls_begin > 0)
+ *                                                                  -- "step-length memory"
+ *   LS_MAX         max    halvings of an accepted step             -- "at most ls_max = 25 halvings"
+ *   CURV_HALVED    count  a step with the curvature terms accepted at its second trial
+ *                                                                  -- "its (2-trial) line search"
+ *   CURV_LS_FAIL   count  both trials of a curvature step rejected: null pass, Gauss-Newton step for the iteration
+ *                                                                  -- "the curvature step fails its (2-trial) line search"
+ *   FACT_FAIL      count  factorisation with the curvature terms failed and the iteration fell back to Gauss-Newton
+ *                         (no retry for the model, or retries used up)
+ *                                                                  -- "when the reduced Hessian is not positive definite"
+ *   CS_RETRY       count  factorisation failed, retried with the curvature scaled by 1/2 (null pass)
+ *                                                                  -- "retried at theta = 1/2, then 1/4"
+ *   CS_KEPT        count  an accepted step stored the scale a retry reached (theta_mem = theta_c)
+ *                                                                  -- "the scale that worked is where the next iteration starts"
+ *   CS_DOUBLED     count  three clean curvature steps doubled a scale below 1
+ *                                                                  -- "three accepted curvature steps ... double it again"
+ *   SKIP           count  an iteration skipped its curvature step because of the back-off
+ *   BACK_MAX       max    the back-off count curv_back             -- "1, 2, 4 ... 16 iterations"
+ *   LATCH_SET      count  the second failed curvature line search in a row latched Gauss-Newton
+ *                                                                  -- "two consecutive failures latch Gauss-Newton"
+ *   LATCH_RELEASED count  a full Gauss-Newton step released a set latch
+ *                                                                  -- "the arms release the latch after a Gauss-Newton step
+ *                                                                      accepted at full length"
+ *   RESTART        count  the barrier restart fired                -- "restart on stalled steps"
+ *   RHO_RAISED     count  the penalty of the l1 merit was raised   -- "l1 merit"
+ *   STALL_MAX      max    iterations in a row that met the acceptable test
+ *   STALL_RESET    count  that series was broken after it had counted   -- "for 8 consecutive iterations"
+ *   EXIT           value  the exit flag (which stopping rule fired); its "first" entry is the iteration count
+ *   CS_EXHAUSTED   count  FACT_FAIL after the scaled retries       -- "before the iteration gives the curvature up"
+ * orc_last_census writes 2 * ORC_CEN_N words: the counters, then for each the iteration at which it first moved
+ * (-1: never); returns ORC_CEN_N. */
+enum {
+  ORC_CEN_GN_BACKTRACK = 0, ORC_CEN_LS_MEMORY, ORC_CEN_LS_MAX, ORC_CEN_CURV_HALVED, ORC_CEN_CURV_LS_FAIL,
+  ORC_CEN_FACT_FAIL, ORC_CEN_CS_RETRY, ORC_CEN_CS_KEPT, ORC_CEN_CS_DOUBLED, ORC_CEN_SKIP, ORC_CEN_BACK_MAX,
+  ORC_CEN_LATCH_SET, ORC_CEN_LATCH_RELEASED, ORC_CEN_RESTART, ORC_CEN_RHO_RAISED, ORC_CEN_STALL_MAX,
+  ORC_CEN_STALL_RESET, ORC_CEN_EXIT, ORC_CEN_CS_EXHAUSTED, ORC_CEN_N
+};
+int orc_last_census(int32_t *out);
+
 int orc_stage_curvature(const orc_desc *d, const double *z, const double *p, const double *lam, int fixed_state,
                         double *Cout);
 int orc_fk_curv(const orc_desc *d, const double *q, int frame, const double *F, double *Cacc);
