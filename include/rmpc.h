@@ -31,6 +31,11 @@
  *   <0 failure (-5 factorisation, -6 non-finite, -7 infeasible/diverged,
  *      -8 line search) -- the planner only tests the sign (mpcPlanner.py:263,
  *      examples/boxer_example.py:194).
+ *
+ * The Python binding is derived from the declarations in this file (robot_mpcs_amd/_abi.py reads the structs, the
+ * prototypes and the integer macros as written here, and refuses a form it does not know: DESIGN.md 1.1).  Parameters
+ * that take a device pointer are named d_*: the binding passes those, and void *, as plain addresses, and every other
+ * pointer parameter as a typed host array.
  */
 #ifndef RMPC_H
 #define RMPC_H

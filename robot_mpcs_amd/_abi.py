@@ -1,0 +1,123 @@
+"""The ctypes view of ``include/rmpc.h``, read from the header itself: ``constants``, ``structs``, ``prototypes``.
+
+Not a C parser.  After comments and preprocessor lines are taken out, the header may hold only
+  * ``#define RMPC_X <integer>`` or ``(-<integer>)`` (other macros are not constants and are passed over),
+  * ``typedef struct NAME { ... } NAME;`` whose members are ``[const] T [*]name[[extent]...]``, several declarators per
+    declaration allowed, T one of int32_t, int64_t, double, int (void and char behind a pointer), an extent a literal
+    or a constant; every pointer member is a ``c_void_p``,
+  * ``typedef struct rmpc_handle rmpc_handle;`` and the ``extern "C"`` braces,
+  * prototypes ``T [*]name(parameters);`` over any number of lines, with (long long too)
+      ``const char *`` / ``char *`` -> ``c_char_p``; ``rmpc_handle *`` -> ``c_void_p``, ``**`` -> ``POINTER(c_void_p)``;
+      a pointer to one of the structs -> ``POINTER(that Structure)``;
+      ``void *`` and any pointer named ``d_*`` (a device pointer: the wrappers pass ``data_ptr()``) -> ``c_void_p``;
+      every other ``T *p`` or ``T p[n]`` (a host array: the wrappers pass typed numpy pointers) -> ``POINTER(T)``.
+Anything else -- unsigned, a union, a bit-field, a function pointer, an unknown type or extent, a stray declaration --
+raises ``RmpcError`` with the text that was not understood; nothing is skipped.
+"""
+import ctypes as C
+import os
+import re
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "rmpc.h")
+
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "int": C.c_int, "long long": C.c_longlong}
+_DECLARATION = re.compile(r"(?:const\s+)?(long long|\w+)(\s+|\s*(?:\*\s*)+)(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)")
+_DECLARATOR = re.compile(r"((?:\*\s*)*)(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)")
+
+
+class RmpcError(RuntimeError):
+    pass
+
+
+def _extents(text, constants, where):
+    out = []
+    for e in re.findall(r"\w+", text):
+        if not e.isdigit() and e not in constants:
+            raise RmpcError(f"rmpc.h: unknown array extent {e!r} in {where!r}")
+        out.append(int(e) if e.isdigit() else constants[e])
+    return out
+
+
+def _members(body, constants):
+    """the ``_fields_`` of a struct body"""
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        first, *more = (p.strip() for p in decl.split(","))
+        m = _DECLARATION.fullmatch(first)
+        if not m or m.group(1) not in (*_SCALARS, "void", "char"):
+            raise RmpcError(f"rmpc.h: cannot type the member {decl!r}")
+        base, parts = m.group(1), [m.groups()[1:]]
+        for p in more:
+            d = _DECLARATOR.fullmatch(p)
+            if not d:
+                raise RmpcError(f"rmpc.h: cannot type the member {decl!r}")
+            parts.append(d.groups())
+        for stars, name, ext in parts:
+            if "*" not in stars and base not in _SCALARS:
+                raise RmpcError(f"rmpc.h: cannot type the member {decl!r}")
+            t = C.c_void_p if "*" in stars else _SCALARS[base]
+            for n in reversed(_extents(ext, constants, decl)):      # double m[8][3] is (c_double * 3) * 8
+                t = t * n
+            fields.append((name, t))
+    return fields
+
+
+def _ctype(text, structs, constants, returns=False):
+    """(name, ctypes type) of one parameter, or with ``returns`` a function's name and its return type"""
+    m = _DECLARATION.fullmatch(text.strip())
+    if not m:
+        raise RmpcError(f"rmpc.h: cannot type {text.strip()!r}")
+    base, name = m.group(1), m.group(3)
+    depth = m.group(2).count("*") + len(_extents(m.group(4), constants, text))     # T p[n] is T *p
+    if depth == 0 and base in _SCALARS:
+        return name, _SCALARS[base]
+    if depth == 1 and base == "char":
+        return name, C.c_char_p
+    if returns:
+        if depth == 0 and base == "void":
+            return name, None
+    elif base == "rmpc_handle" and depth in (1, 2):
+        return name, C.c_void_p if depth == 1 else C.POINTER(C.c_void_p)
+    elif depth == 1 and base in structs:
+        return name, C.POINTER(structs[base])
+    elif depth == 1 and (base == "void" or base in _SCALARS):
+        return name, C.c_void_p if base == "void" or name.startswith("d_") else C.POINTER(_SCALARS[base])
+    raise RmpcError(f"rmpc.h: cannot type {text.strip()!r}")
+
+
+def parse(text):
+    """(constants, structs, prototypes) of a header's text"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {k: int(a or b) for k, a, b in
+                 re.findall(r"^[ \t]*#[ \t]*define[ \t]+(RMPC_\w+)[ \t]+(?:(\d+)|\((-\d+)\))[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text, braces = re.subn(r'\bextern\s+"C"\s*\{', "", text)
+    structs = {}
+
+    def take_struct(m):
+        if m.group(1) != m.group(3):
+            raise RmpcError(f"rmpc.h: struct {m.group(1)} is given the other name {m.group(3)}")
+        structs[m.group(1)] = type(m.group(1), (C.Structure,), {"_fields_": _members(m.group(2), constants)})
+        return ""
+
+    text = re.sub(r"\btypedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;", take_struct, text)
+    prototypes = {}
+    *statements, rest = text.split(";")
+    for s in (s.strip() for s in statements):
+        m = re.fullmatch(r"([^()]*)\((.*)\)", s, flags=re.S)
+        if m:
+            name, restype = _ctype(m.group(1), structs, constants, returns=True)
+            args = [] if m.group(2).strip() == "void" else m.group(2).split(",")
+            prototypes[name] = (restype, [_ctype(a, structs, constants)[1] for a in args])
+        elif s.split() != "typedef struct rmpc_handle rmpc_handle".split():
+            raise RmpcError(f"rmpc.h: not a form the binding knows: {s!r}")
+    if rest.split() != ["}"] * braces:
+        raise RmpcError(f"rmpc.h: not a form the binding knows: {rest.strip()!r}")
+    return constants, structs, prototypes
+
+
+try:
+    with open(HEADER) as _f:
+        constants, structs, prototypes = parse(_f.read())
+except OSError as _e:
+    raise RmpcError(f"{HEADER} not found: the binding is derived from it ({_e})") from None

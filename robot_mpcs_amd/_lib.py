@@ -12,192 +12,35 @@ import os
 
 import numpy as np
 
+from . import _abi
+from ._abi import RmpcError
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RMPC_LIB_PATH") or os.path.join(_HERE, "csrc", "librmpc_hip.so")
 
-MAX_JOINTS, MAX_LINKS, MAX_PAIRS, MAX_MODULES, NV_MAX = 8, 8, 4, 8, 24
-MAX_XROWS = 32
-NUM_KERNELS = 6
+
+def _k(*names):
+    """the values of the header's RMPC_<name> macros"""
+    return tuple(_abi.constants["RMPC_" + n] for n in names)
 
 
-class RmpcError(RuntimeError):
-    pass
+MAX_JOINTS, MAX_LINKS, MAX_PAIRS, MAX_MODULES, NV_MAX = _k("MAX_JOINTS", "MAX_LINKS", "MAX_PAIRS", "MAX_MODULES", "NV_MAX")
+MAX_XROWS, NUM_KERNELS = _k("MAX_XROWS", "NUM_KERNELS")
 
-
-class RmpcDesc(C.Structure):
-    """Mirror of ``rmpc_desc`` (include/rmpc.h)."""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("device", C.c_int32),
-        ("robot", C.c_int32), ("N", C.c_int32),
-        ("n", C.c_int32), ("nx", C.c_int32), ("nu", C.c_int32), ("ns", C.c_int32), ("npar", C.c_int32),
-        ("dt", C.c_double),
-        ("n_modules", C.c_int32), ("module_kind", C.c_int32 * MAX_MODULES),
-        ("nobst", C.c_int32),
-        ("n_links", C.c_int32), ("link_frame", C.c_int32 * MAX_LINKS),
-        ("n_pairs", C.c_int32), ("pair_frame", (C.c_int32 * 2) * MAX_PAIRS),
-        ("end_frame", C.c_int32),
-        ("n_joints", C.c_int32), ("joint_type", C.c_int32 * MAX_JOINTS), ("joint_dof", C.c_int32 * MAX_JOINTS),
-        ("joint_xyz", (C.c_double * 3) * MAX_JOINTS), ("joint_rot", (C.c_double * 9) * MAX_JOINTS),
-        ("joint_axis", (C.c_double * 3) * MAX_JOINTS),
-        ("off_r_body", C.c_int32), ("off_obst", C.c_int32), ("off_lin", C.c_int32),
-        ("off_lower", C.c_int32), ("off_upper", C.c_int32), ("off_lower_u", C.c_int32),
-        ("off_upper_u", C.c_int32), ("off_lower_vel", C.c_int32), ("off_upper_vel", C.c_int32),
-        ("off_wu", C.c_int32), ("off_goal", C.c_int32), ("off_wgoal", C.c_int32),
-        ("off_wconstr", C.c_int32), ("off_ws", C.c_int32),
-        ("has_goal", C.c_int32), ("has_avoid", C.c_int32),
-        ("lb", C.c_double * NV_MAX), ("ub", C.c_double * NV_MAX),
-        ("max_iter", C.c_int32),
-        ("tol_stat", C.c_double), ("tol_eq", C.c_double), ("tol_ineq", C.c_double), ("tol_comp", C.c_double),
-        ("mu0", C.c_double),
-        ("acc_iters", C.c_int32), ("acc_obj_tol", C.c_double), ("ls_max", C.c_int32),
-        # rows of the row-described modules (include/rmpc.h RMPC_MOD_ROWS)
-        ("n_xrows", C.c_int32), ("xrow_mod", C.c_int32 * MAX_XROWS), ("xrow_kind", C.c_int32 * MAX_XROWS),
-        ("xrow_a", C.c_int32 * MAX_XROWS), ("xrow_b", C.c_int32 * MAX_XROWS), ("xrow_poff", C.c_int32 * MAX_XROWS),
-    ]
-
-
-class RmpcScene(C.Structure):
-    """Mirror of ``rmpc_scene`` (include/rmpc.h): device pointers + broadcast weights."""
-    _fields_ = [
-        ("struct_size", C.c_int32),
-        ("goal", C.c_void_p), ("r_body", C.c_void_p), ("obst", C.c_void_p), ("obst_dyn", C.c_void_p),
-        ("dyn_radius", C.c_double),
-        ("lower_limits", C.c_void_p), ("upper_limits", C.c_void_p),
-        ("lower_limits_u", C.c_void_p), ("upper_limits_u", C.c_void_p),
-        ("lower_limits_vel", C.c_void_p), ("upper_limits_vel", C.c_void_p),
-        ("lin_constrs", C.c_void_p),
-        ("w", C.c_double), ("wu", C.c_double), ("ws", C.c_double),
-        ("wconstr", C.c_double * MAX_MODULES),
-    ]
-
-
-class RetargetArgs(C.Structure):
-    """Mirror of ``rmpc_retarget`` (include/rmpc.h): the steady loop's goal hand-over, device pointers."""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("pool_len", C.c_int32),
-        ("xinit", C.c_void_p), ("x0", C.c_void_p), ("exitflag", C.c_void_p), ("iters", C.c_void_p), ("goal", C.c_void_p),
-        ("goal_pool", C.c_void_p), ("x_start", C.c_void_p), ("lower_limits", C.c_void_p), ("upper_limits", C.c_void_p), ("cursor", C.c_void_p), ("dwell", C.c_void_p), ("failrun", C.c_void_p),
-        ("tol", C.c_double), ("settle_vel", C.c_double), ("mu_regoal", C.c_double),
-        ("settle_min_dwell", C.c_int32), ("max_dwell", C.c_int32), ("fail_reset_after", C.c_int32), ("reserved", C.c_int32),
-        ("counts", C.c_void_p),
-    ]
-
-
-class LidarArgs(C.Structure):
-    """Mirror of ``rmpc_lidar`` (include/rmpc.h): one scan of B robots in a shared world, device pointers."""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("rays", C.c_int32),
-        ("angle_min", C.c_double), ("angle_max", C.c_double), ("range", C.c_double),
-        ("offset_x", C.c_double), ("offset_y", C.c_double), ("height", C.c_double),
-        ("pose", C.c_void_p), ("pose_stride", C.c_int32),
-        ("nbox", C.c_int32), ("boxes", C.c_void_p),
-        ("ncircle", C.c_int32), ("circles", C.c_void_p),
-        ("points", C.c_void_p), ("ranges", C.c_void_p),
-    ]
-
-
-class LidarBodiesArgs(C.Structure):
-    """Mirror of ``rmpc_lidar_bodies`` (include/rmpc.h): the fleet's bodies a scan sees besides its world, device
-    pointers."""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("P", C.c_int32),
-        ("centres", C.c_void_p), ("centre_stride", C.c_int32),
-        ("radius", C.c_void_p),
-        ("self0", C.c_int32),
-        ("owner", C.c_void_p), ("static_ranges", C.c_void_p),
-    ]
-
-
-class GridMarkArgs(C.Structure):
-    """Mirror of ``rmpc_grid_mark`` (include/rmpc.h): one scan of B robots added to the evidence grids, device pointers."""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("rays", C.c_int32),
-        ("origins", C.c_void_p), ("points", C.c_void_p), ("ranges", C.c_void_p),
-        ("range", C.c_double), ("hit_depth", C.c_double),
-        ("H", C.c_int32), ("W", C.c_int32),
-        ("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double),
-        ("hits", C.c_void_p), ("misses", C.c_void_p), ("skipped", C.c_void_p),
-    ]
-
-
-class ScanMatchArgs(C.Structure):
-    """Mirror of ``rmpc_scan_match`` (include/rmpc.h): one scan of B robots matched against the edge-distance table,
-    device pointers."""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("rays", C.c_int32),
-        ("pose", C.c_void_p), ("points", C.c_void_p), ("ranges", C.c_void_p),
-        ("range", C.c_double),
-        ("pose_stride", C.c_int32), ("min_hits", C.c_int32),
-        ("d2", C.c_void_p),
-        ("H", C.c_int32), ("W", C.c_int32), ("sub", C.c_int32), ("cap", C.c_int32),
-        ("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double),
-        ("nxy", C.c_int32), ("nth", C.c_int32),
-        ("step_xy", C.c_double), ("step_th", C.c_double),
-        ("rot", C.c_void_p),
-        ("pose_out", C.c_void_p), ("best", C.c_void_p), ("score", C.c_void_p),
-        ("score0", C.c_void_p), ("used", C.c_void_p),
-    ]
-
-
-class ScanSearchArgs(C.Structure):
-    """Mirror of ``rmpc_scan_search`` (include/rmpc.h): the fields of ``rmpc_scan_match``, then the pyramid, the
-    workspace and the search's own outputs, device pointers."""
-    _fields_ = ScanMatchArgs._fields_ + [
-        ("pyr", C.c_void_p), ("levels", C.c_int32), ("top_log2", C.c_int32),
-        ("active", C.c_void_p),
-        ("work", C.c_void_p), ("work_bytes", C.c_int64),
-        ("leaves", C.c_void_p), ("top_bound", C.c_void_p),
-    ]
-
-
-class TracksArgs(C.Structure):
-    """Mirror of ``rmpc_tracks`` (include/rmpc.h): one scan of B robots through the moving-obstacle tracker, device
-    pointers."""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("rays", C.c_int32), ("closed", C.c_int32), ("min_rays", C.c_int32),
-        ("points", C.c_void_p), ("ranges", C.c_void_p), ("static_ranges", C.c_void_p), ("origin", C.c_void_p),
-        ("range", C.c_double), ("margin", C.c_double), ("gap", C.c_double), ("radius", C.c_double),
-        ("max_extent", C.c_double),
-        ("gate", C.c_double), ("dt", C.c_double), ("alpha", C.c_double), ("beta", C.c_double), ("v_max", C.c_double),
-        ("park_x", C.c_double), ("park_y", C.c_double),
-        ("confirm", C.c_int32), ("max_miss", C.c_int32), ("n_tracks", C.c_int32), ("n_out", C.c_int32),
-        ("track", C.c_void_p), ("age", C.c_void_p), ("miss", C.c_void_p),
-        ("obst_dyn", C.c_void_p), ("det", C.c_void_p), ("counts", C.c_void_p),
-    ]
-
-
-class TimedPlanArgs(C.Structure):
-    """Mirror of ``rmpc_timed_plan`` (include/rmpc.h): one prioritised space-time plan of B robots for G orders, device
-    pointers."""
-    _fields_ = [
-        ("struct_size", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("movement", C.c_int32),
-        ("grid", C.c_void_p), ("occ_threshold", C.c_double),
-        ("B", C.c_int32), ("Gf", C.c_int32),
-        ("start_cell", C.c_void_p), ("goal_index", C.c_void_p), ("fields", C.c_void_p), ("goal_cells", C.c_void_p),
-        ("T", C.c_int32), ("sep2", C.c_int32), ("lag", C.c_int32), ("G", C.c_int32),
-        ("orders", C.c_void_p),
-        ("work", C.c_void_p), ("work_bytes", C.c_int64),
-        ("paths", C.c_void_p), ("status", C.c_void_p), ("arrive", C.c_void_p),
-        ("key", C.c_void_p), ("best", C.c_void_p),
-    ]
-
+# The structs of include/rmpc.h, with the header's field names (_abi.py derives them from it).
+RmpcDesc = _abi.structs["rmpc_desc"]                  # the model descriptor
+RmpcScene = _abi.structs["rmpc_scene"]                # device pointers + broadcast weights
+RetargetArgs = _abi.structs["rmpc_retarget"]          # the steady loop's goal hand-over, device pointers
+LidarArgs = _abi.structs["rmpc_lidar"]                # one scan of B robots in a shared world, device pointers
+LidarBodiesArgs = _abi.structs["rmpc_lidar_bodies"]   # the fleet's bodies a scan sees besides its world, device pointers
+GridMarkArgs = _abi.structs["rmpc_grid_mark"]         # one scan of B robots added to the evidence grids, device pointers
+ScanMatchArgs = _abi.structs["rmpc_scan_match"]       # one scan of B robots matched against the edge-distance table
+ScanSearchArgs = _abi.structs["rmpc_scan_search"]     # rmpc_scan_match's fields, then the pyramid, workspace and outputs
+TracksArgs = _abi.structs["rmpc_tracks"]              # one scan of B robots through the moving-obstacle tracker
+TimedPlanArgs = _abi.structs["rmpc_timed_plan"]       # one prioritised space-time plan of B robots for G orders
 
 # every symbol include/rmpc.h declares
-EXPORTED_SYMBOLS = [
-    "rmpc_version", "rmpc_source_hash", "rmpc_last_error", "rmpc_desc_size", "rmpc_create", "rmpc_destroy", "rmpc_solve_batch",
-    "rmpc_solve_batch_device", "rmpc_workspace_bytes", "rmpc_set_warm_start", "rmpc_set_pass_budget", "rmpc_is_fused", "rmpc_fused_kernel_name", "rmpc_is_async", "rmpc_set_profiling", "rmpc_get_profile",
-    "rmpc_kernel_name", "rmpc_last_passes", "rmpc_last_solve_path", "rmpc_debug_sweep", "rmpc_debug_step", "rmpc_debug_step_curv", "rmpc_spec_source", "rmpc_spec_name", "rmpc_spec_for", "rmpc_debug_poison_lds",
-    "rmpc_debug_fused_stamps", "rmpc_debug_wave_reduce", "rmpc_pack_scene_device", "rmpc_solve_batch_scene_device", "rmpc_pack_scene_workspace", "rmpc_solve_batch_packed_device", "rmpc_advance_device", "rmpc_advance_device_flags", "rmpc_retarget_device", "rmpc_advance_obstacles_device", "rmpc_free_space_device",
-    "rmpc_grid_inflate_device", "rmpc_grid_fields_device", "rmpc_grid_paths_device", "rmpc_grid_cells_device",
-    "rmpc_follow_path_device", "rmpc_lidar_scan_device", "rmpc_plan_points_device", "rmpc_fleet_points_device",
-    "rmpc_fleet_planes_device", "rmpc_grid_mark_device", "rmpc_grid_occupancy_device",
-    "rmpc_grid_frontier_device", "rmpc_grid_fields_seeded_device", "rmpc_grid_descend_device",
-    "rmpc_grid_targets_device", "rmpc_grid_route_costs_device", "rmpc_assign_greedy_device",
-    "rmpc_grid_edge_distance_device", "rmpc_lidar_project_device", "rmpc_scan_match_device",
-    "rmpc_lidar_tracks_device", "rmpc_timed_plan_work_bytes", "rmpc_timed_plan_device", "rmpc_timed_follow_device",
-    "rmpc_lidar_scan_fleet_device",
-    "rmpc_grid_min_pyramid_device", "rmpc_scan_search_work_bytes", "rmpc_scan_search_device",
-]
+EXPORTED_SYMBOLS = list(_abi.prototypes)
 
 _lib = None
 
@@ -266,134 +109,9 @@ def load_library(path: str = LIB_PATH):
     except ImportError:
         pass
     L = C.CDLL(path)
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    L.rmpc_version.restype = C.c_int
-    L.rmpc_source_hash.restype = C.c_char_p
-    L.rmpc_last_error.restype = C.c_char_p
-    L.rmpc_desc_size.restype = C.c_int
-    L.rmpc_create.restype = C.c_int
-    L.rmpc_create.argtypes = [C.POINTER(RmpcDesc), C.c_int, C.POINTER(C.c_void_p)]
-    L.rmpc_destroy.restype = None
-    L.rmpc_destroy.argtypes = [C.c_void_p]
-    L.rmpc_solve_batch.restype = C.c_int
-    L.rmpc_solve_batch.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, dp, ip, ip, dp, dp]
-    L.rmpc_solve_batch_device.restype = C.c_int
-    L.rmpc_solve_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
-    L.rmpc_workspace_bytes.restype = C.c_int64
-    L.rmpc_workspace_bytes.argtypes = [C.POINTER(RmpcDesc), C.c_int]
-    L.rmpc_set_warm_start.restype = C.c_int
-    L.rmpc_set_warm_start.argtypes = [C.c_void_p, C.c_int]
-    L.rmpc_set_profiling.restype = C.c_int
-    L.rmpc_set_profiling.argtypes = [C.c_void_p, C.c_int]
-    L.rmpc_get_profile.restype = C.c_int
-    L.rmpc_get_profile.argtypes = [C.c_void_p, dp, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64)]
-    L.rmpc_kernel_name.restype = C.c_char_p
-    L.rmpc_kernel_name.argtypes = [C.c_int]
-    L.rmpc_set_pass_budget.restype = C.c_int
-    L.rmpc_set_pass_budget.argtypes = [C.c_void_p, C.c_int]
-    L.rmpc_is_fused.restype = C.c_int
-    L.rmpc_is_fused.argtypes = [C.c_void_p]
-    L.rmpc_fused_kernel_name.restype = C.c_char_p
-    L.rmpc_fused_kernel_name.argtypes = [C.c_void_p]
-    L.rmpc_is_async.restype = C.c_int
-    L.rmpc_is_async.argtypes = [C.c_void_p]
-    L.rmpc_last_passes.restype = C.c_int
-    L.rmpc_last_passes.argtypes = [C.c_void_p]
-    L.rmpc_last_solve_path.restype = C.c_int
-    L.rmpc_last_solve_path.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-    L.rmpc_debug_sweep.restype = C.c_int
-    L.rmpc_debug_sweep.argtypes = [C.c_void_p, C.c_int] + [dp] * 9
-    L.rmpc_debug_step.restype = C.c_int
-    L.rmpc_debug_step.argtypes = [C.c_void_p, C.c_int] + [dp] * 15 + [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]
-    L.rmpc_debug_step_curv.restype = C.c_int
-    L.rmpc_debug_step_curv.argtypes = L.rmpc_debug_step.argtypes + [C.c_double, dp]
-    L.rmpc_spec_source.restype = C.c_int64
-    L.rmpc_spec_source.argtypes = [C.POINTER(RmpcDesc), C.c_char_p, C.c_char_p, C.c_int64]
-    L.rmpc_spec_name.restype = C.c_char_p
-    L.rmpc_spec_name.argtypes = [C.c_void_p]
-    L.rmpc_debug_poison_lds.restype = C.c_int
-    L.rmpc_debug_poison_lds.argtypes = [C.c_void_p]
-    L.rmpc_spec_for.restype = C.c_char_p
-    L.rmpc_spec_for.argtypes = [C.POINTER(RmpcDesc)]
-    L.rmpc_debug_wave_reduce.restype = C.c_int
-    L.rmpc_debug_wave_reduce.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp]
-    L.rmpc_debug_fused_stamps.restype = C.c_int
-    L.rmpc_debug_fused_stamps.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.c_int]
-    L.rmpc_pack_scene_device.restype = C.c_int
-    L.rmpc_pack_scene_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(RmpcScene), C.c_void_p, C.c_void_p]
-    L.rmpc_pack_scene_workspace.restype = C.c_int
-    L.rmpc_pack_scene_workspace.argtypes = [C.c_void_p, C.c_int, C.POINTER(RmpcScene), C.c_void_p]
-    L.rmpc_solve_batch_packed_device.restype = C.c_int
-    L.rmpc_solve_batch_packed_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
-    L.rmpc_solve_batch_scene_device.restype = C.c_int
-    L.rmpc_solve_batch_scene_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(RmpcScene)] + [C.c_void_p] * 8
-    L.rmpc_advance_device.restype = C.c_int
-    L.rmpc_advance_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.rmpc_advance_device_flags.restype = C.c_int
-    L.rmpc_advance_device_flags.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.rmpc_retarget_device.restype = C.c_int
-    L.rmpc_retarget_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(RetargetArgs), C.c_void_p]
-    L.rmpc_advance_obstacles_device.restype = C.c_int
-    L.rmpc_advance_obstacles_device.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
-    L.rmpc_free_space_device.restype = C.c_int
-    L.rmpc_free_space_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    vp, i, d = C.c_void_p, C.c_int, C.c_double
-    L.rmpc_grid_inflate_device.restype = C.c_int
-    L.rmpc_grid_inflate_device.argtypes = [i, i, d, d, d, vp, vp, vp]
-    L.rmpc_grid_fields_device.restype = C.c_int
-    L.rmpc_grid_fields_device.argtypes = [i, i, vp, i, vp, i, d, d, vp, vp, vp, vp]
-    L.rmpc_grid_paths_device.restype = C.c_int
-    L.rmpc_grid_paths_device.argtypes = [i, i, vp, i, vp, vp, i, vp, vp, i, d, d, i, vp, vp, vp]
-    L.rmpc_grid_cells_device.restype = C.c_int
-    L.rmpc_grid_cells_device.argtypes = [i, vp, i, i, i, d, d, d, vp, vp]
-    L.rmpc_follow_path_device.restype = C.c_int
-    L.rmpc_follow_path_device.argtypes = [i, vp, vp, i, vp, vp, i, i, d, d, d, d, vp, vp]
-    L.rmpc_lidar_scan_device.restype = C.c_int
-    L.rmpc_lidar_scan_device.argtypes = [i, C.POINTER(LidarArgs), vp]
-    L.rmpc_lidar_scan_fleet_device.restype = C.c_int
-    L.rmpc_lidar_scan_fleet_device.argtypes = [i, C.POINTER(LidarArgs), C.POINTER(LidarBodiesArgs), vp]
-    L.rmpc_plan_points_device.restype = C.c_int
-    L.rmpc_plan_points_device.argtypes = [i, i, vp, i, vp, vp, i, d, d, d, vp, vp]
-    L.rmpc_fleet_points_device.restype = C.c_int
-    L.rmpc_fleet_points_device.argtypes = [i, i, vp, i, vp, vp, i, i, d, d, d, vp, vp]
-    L.rmpc_fleet_planes_device.restype = C.c_int
-    L.rmpc_fleet_planes_device.argtypes = [i, i, vp, vp, i, d, i, i, vp, vp]
-    L.rmpc_grid_mark_device.restype = C.c_int
-    L.rmpc_grid_mark_device.argtypes = [i, C.POINTER(GridMarkArgs), vp]
-    L.rmpc_grid_occupancy_device.restype = C.c_int
-    L.rmpc_grid_occupancy_device.argtypes = [i, i, vp, vp, i, i, i, d, d, d, vp, vp]
-    L.rmpc_grid_frontier_device.restype = C.c_int
-    L.rmpc_grid_frontier_device.argtypes = [i, i, vp, vp, vp, d, i, d, vp, vp, vp, vp]
-    L.rmpc_grid_fields_seeded_device.restype = C.c_int
-    L.rmpc_grid_fields_seeded_device.argtypes = [i, i, vp, i, vp, i, d, d, vp, vp, vp, vp]
-    L.rmpc_grid_descend_device.restype = C.c_int
-    L.rmpc_grid_descend_device.argtypes = [i, i, vp, i, vp, vp, i, vp, vp, i, d, d, i, vp, vp, vp]
-    L.rmpc_grid_targets_device.restype = C.c_int
-    L.rmpc_grid_targets_device.argtypes = [i, i, vp, i, vp, vp, vp]
-    L.rmpc_grid_route_costs_device.restype = C.c_int
-    L.rmpc_grid_route_costs_device.argtypes = [i, i, vp, i, vp, i, vp, i, d, d, vp, vp]
-    L.rmpc_assign_greedy_device.restype = C.c_int
-    L.rmpc_assign_greedy_device.argtypes = [i, i, vp, vp, vp, vp]
-    L.rmpc_grid_edge_distance_device.restype = C.c_int
-    L.rmpc_grid_edge_distance_device.argtypes = [i, i, vp, d, i, i, vp, vp]
-    L.rmpc_lidar_project_device.restype = C.c_int
-    L.rmpc_lidar_project_device.argtypes = [i, C.POINTER(LidarArgs), vp]
-    L.rmpc_scan_match_device.restype = C.c_int
-    L.rmpc_scan_match_device.argtypes = [i, C.POINTER(ScanMatchArgs), vp]
-    L.rmpc_grid_min_pyramid_device.restype = C.c_int
-    L.rmpc_grid_min_pyramid_device.argtypes = [i, i, i, vp, i, vp, vp]
-    L.rmpc_scan_search_work_bytes.restype = C.c_int64
-    L.rmpc_scan_search_work_bytes.argtypes = [i, i, i, i]
-    L.rmpc_scan_search_device.restype = C.c_int
-    L.rmpc_scan_search_device.argtypes = [i, C.POINTER(ScanSearchArgs), vp]
-    L.rmpc_lidar_tracks_device.restype = C.c_int
-    L.rmpc_lidar_tracks_device.argtypes = [i, C.POINTER(TracksArgs), vp]
-    L.rmpc_timed_plan_work_bytes.restype = C.c_int64
-    L.rmpc_timed_plan_work_bytes.argtypes = [i, i, i, i]
-    L.rmpc_timed_plan_device.restype = C.c_int
-    L.rmpc_timed_plan_device.argtypes = [C.POINTER(TimedPlanArgs), vp]
-    L.rmpc_timed_follow_device.restype = C.c_int
-    L.rmpc_timed_follow_device.argtypes = [i, i, vp, vp, vp, vp, i, i, d, d, d, d, i, i, vp, vp, vp]
+    for name, (restype, argtypes) in _abi.prototypes.items():    # the declarations of include/rmpc.h, nothing else
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
         raise RmpcError("rmpc_desc layout mismatch between _lib.py and librmpc_hip.so")
     want = _source_hash()
@@ -522,13 +240,14 @@ def free_space_decomposition_device(points, seeds, planes_out, max_radius: float
 
 
 # status codes of the global planner (include/rmpc.h)
-GRID_MAX_CELLS = 16384
-GRID_OK, GRID_START_OCCUPIED, GRID_GOAL_OCCUPIED, GRID_OUTSIDE, GRID_TOO_LONG = 0, -1, -2, -3, -4
-GRID_BAD_MAP, GRID_NO_FIXED_POINT, GRID_BAD_SEED = -5, -6, -7
+GRID_MAX_CELLS, GRID_OK, GRID_START_OCCUPIED, GRID_GOAL_OCCUPIED, GRID_OUTSIDE, GRID_TOO_LONG = _k(
+    "GRID_MAX_CELLS", "GRID_OK", "GRID_START_OCCUPIED", "GRID_GOAL_OCCUPIED", "GRID_OUTSIDE", "GRID_TOO_LONG")
+GRID_BAD_MAP, GRID_NO_FIXED_POINT, GRID_BAD_SEED = _k("GRID_BAD_MAP", "GRID_NO_FIXED_POINT", "GRID_BAD_SEED")
 # limits of the assignment (include/rmpc.h)
-ASSIGN_MAX_ROBOTS, ASSIGN_MAX_TARGETS = 4096, 1024
-# limits of the scan match (include/rmpc.h)
-MATCH_MAX_RAYS, MATCH_MAX_N = 2048, 15
+ASSIGN_MAX_ROBOTS, ASSIGN_MAX_TARGETS = _k("ASSIGN_MAX_ROBOTS", "ASSIGN_MAX_TARGETS")
+# limits of the scan match: the rays (include/rmpc.h) and nxy, nth (kMatchMaxN, csrc/rmpc_locate.hpp)
+MATCH_MAX_RAYS, = _k("MATCH_MAX_RAYS")
+MATCH_MAX_N = 15
 
 
 def _grid_call(name, *args):
@@ -830,8 +549,10 @@ def scan_match_device(args: ScanMatchArgs, B: int, stream=None):
     _grid_call("rmpc_scan_match_device", int(B), C.byref(args), _stream_arg(stream))
 
 
-# limits of the wide-window search (include/rmpc.h)
-SEARCH_MAX_N, SEARCH_MAX_TOP, SEARCH_MAX_LEVELS = 127, 7, 12
+# limits of the wide-window search: nxy, nth (include/rmpc.h), top_log2 and the pyramid's levels (kSearchMaxTop,
+# kSearchMaxLevels, csrc/rmpc_search.hpp)
+SEARCH_MAX_N, = _k("SEARCH_MAX_N")
+SEARCH_MAX_TOP, SEARCH_MAX_LEVELS = 7, 12
 
 
 def grid_min_pyramid_device(d2, pyr, sub: int, stream=None):
@@ -883,7 +604,7 @@ def scan_search_device(args: ScanSearchArgs, B: int, stream=None):
 
 
 # limits of the moving-obstacle tracker (include/rmpc.h)
-TRACK_MAX_RAYS, TRACK_MAX_TRACKS, TRACK_MAX_DET = 2048, 16, 16
+TRACK_MAX_RAYS, TRACK_MAX_TRACKS, TRACK_MAX_DET = _k("TRACK_MAX_RAYS", "TRACK_MAX_TRACKS", "TRACK_MAX_DET")
 
 
 def tracks_args(points, ranges, origin, track, age, miss, obst_dyn, radius: float, dt: float, static_ranges=None,
@@ -916,8 +637,8 @@ def lidar_tracks_device(args: TracksArgs, B: int, stream=None):
 
 
 # limits and the status of the timed routes (include/rmpc.h)
-TIMED_MAX_ROBOTS, TIMED_MAX_T, TIMED_MAX_ORDERS, TIMED_MAX_SEP2, TIMED_MAX_LAG = 1024, 1023, 1024, 4096, 4
-TIMED_BAD_ORDER = -8
+TIMED_MAX_ROBOTS, TIMED_MAX_T, TIMED_MAX_ORDERS, TIMED_MAX_SEP2, TIMED_MAX_LAG, TIMED_BAD_ORDER = _k(
+    "TIMED_MAX_ROBOTS", "TIMED_MAX_T", "TIMED_MAX_ORDERS", "TIMED_MAX_SEP2", "TIMED_MAX_LAG", "TIMED_BAD_ORDER")
 
 
 def timed_plan_work_bytes(H: int, W: int, T: int, G: int) -> int:
@@ -1157,9 +878,10 @@ class Solver:
         ``fused``; a fused solve, or a handle that has not solved yet, has None for the kernel names."""
         out = (C.c_int32 * 6)()
         self._check(self._L.rmpc_last_solve_path(self._h, out), "rmpc_last_solve_path")
-        ric = {0: "wave", 1: "grouped", 2: "lane"}
+        ric = dict(zip(_k("PATH_RIC_WAVE", "PATH_RIC_GROUPED", "PATH_RIC_LANE"), ("wave", "grouped", "lane")))
+        compact = dict(zip(_k("PATH_COMPACT_WAVE", "PATH_COMPACT_BLOCK"), ("wave", "block")))
         return dict(migrated_at=int(out[0]), survivors=int(out[1]), ric_first=ric.get(out[2]), ric_last=ric.get(out[3]),
-                    compact={0: "wave", 1: "block"}.get(out[4]), fused=bool(out[5]))
+                    compact=compact.get(out[4]), fused=bool(out[5]))
 
     def debug_sweep(self, xinit, x0, params):
         xinit = np.ascontiguousarray(xinit, dtype=np.float64).reshape(-1, self.nx)
