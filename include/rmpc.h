@@ -394,7 +394,8 @@ int rmpc_grid_inflate_device(int H, int W, double cell, double size_robot, doubl
  * D(u) = min_v (delta(u,v) + cost_factor data[v] + D(v)), +inf on occupied and unreachable cells -- the exact fixed
  * point, bitwise the same on every run.  d_status [G]: RMPC_GRID_OK, _GOAL_OCCUPIED, _OUTSIDE, _BAD_MAP or
  * _NO_FIXED_POINT (field all +inf).  cost_factor must be finite and >= 0 (prices may not be negative: refused).
- * d_sweeps [G] (may be NULL): the sweeps the field took.  H W <= RMPC_GRID_MAX_CELLS, larger maps are refused. */
+ * d_sweeps [G] (may be NULL): the sweeps the field took.  H W <= RMPC_GRID_MAX_CELLS, larger maps are refused
+ * (rmpc_grid_large.h has the entries that take them). */
 int rmpc_grid_fields_device(int H, int W, const double *d_grid, int G, const int32_t *d_goal_cells, int movement,
                             double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status,
                             int32_t *d_sweeps, void *stream);

@@ -19,6 +19,8 @@ import os
 import re
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "rmpc.h")
+# the fields on large maps: a header of its own, read into tables of its own
+LARGE_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_grid_large.h")
 
 _SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "int": C.c_int, "long long": C.c_longlong}
 _DECLARATION = re.compile(r"(?:const\s+)?(long long|\w+)(\s+|\s*(?:\*\s*)+)(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)")
@@ -116,8 +118,13 @@ def parse(text):
     return constants, structs, prototypes
 
 
-try:
-    with open(HEADER) as _f:
-        constants, structs, prototypes = parse(_f.read())
-except OSError as _e:
-    raise RmpcError(f"{HEADER} not found: the binding is derived from it ({_e})") from None
+def _read(path):
+    try:
+        with open(path) as f:
+            return parse(f.read())
+    except OSError as e:
+        raise RmpcError(f"{path} not found: the binding is derived from it ({e})") from None
+
+
+constants, structs, prototypes = _read(HEADER)
+large_constants, _, large_prototypes = _read(LARGE_HEADER)

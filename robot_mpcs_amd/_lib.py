@@ -41,6 +41,8 @@ TimedPlanArgs = _abi.structs["rmpc_timed_plan"]       # one prioritised space-ti
 
 # every symbol include/rmpc.h declares
 EXPORTED_SYMBOLS = list(_abi.prototypes)
+# and every symbol include/rmpc_grid_large.h declares
+GRID_LARGE_SYMBOLS = list(_abi.large_prototypes)
 
 _lib = None
 
@@ -109,7 +111,8 @@ def load_library(path: str = LIB_PATH):
     except ImportError:
         pass
     L = C.CDLL(path)
-    for name, (restype, argtypes) in _abi.prototypes.items():    # the declarations of include/rmpc.h, nothing else
+    # the declarations of include/rmpc.h and include/rmpc_grid_large.h, nothing else
+    for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
@@ -298,6 +301,31 @@ def grid_fields_seeded_device(grid, seeds, fields, status, movement: int = 8, oc
     _grid_call("rmpc_grid_fields_seeded_device", H, W, _ptr(grid), int(seeds.shape[0]), _ptr(seeds), int(movement),
                float(occ_threshold), float(cost_factor), _ptr(fields), _ptr(status),
                None if sweeps is None else _ptr(sweeps), _stream_arg(stream))
+
+
+# limits of the fields on large maps (include/rmpc_grid_large.h)
+GRID_LARGE_MAX_CELLS, GRID_LARGE_MAX_SIDE, GRID_TILE = (
+    _abi.large_constants["RMPC_" + n] for n in ("GRID_LARGE_MAX_CELLS", "GRID_LARGE_MAX_SIDE", "GRID_TILE"))
+
+
+def grid_fields_large_device(grid, goal_cells, fields, status, movement: int = 8, occ_threshold: float = 0.8,
+                             cost_factor: float = 3.0, visits=None, stream=None):
+    """As ``grid_fields_device`` on maps up to ``GRID_LARGE_MAX_CELLS`` cells, the same fields bit for bit; visits (G,)
+    int32 or None: the tile visits each field took (``rmpc_grid_fields_large_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    _grid_call("rmpc_grid_fields_large_device", H, W, _ptr(grid), int(goal_cells.shape[0]), _ptr(goal_cells),
+               int(movement), float(occ_threshold), float(cost_factor), _ptr(fields), _ptr(status),
+               None if visits is None else _ptr(visits), _stream_arg(stream))
+
+
+def grid_fields_seeded_large_device(grid, seeds, fields, status, movement: int = 8, occ_threshold: float = 0.8,
+                                    cost_factor: float = 3.0, visits=None, stream=None):
+    """As ``grid_fields_seeded_device`` on maps up to ``GRID_LARGE_MAX_CELLS`` cells, the same fields bit for bit;
+    visits (G,) int32 or None: the tile visits each field took (``rmpc_grid_fields_seeded_large_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    _grid_call("rmpc_grid_fields_seeded_large_device", H, W, _ptr(grid), int(seeds.shape[0]), _ptr(seeds),
+               int(movement), float(occ_threshold), float(cost_factor), _ptr(fields), _ptr(status),
+               None if visits is None else _ptr(visits), _stream_arg(stream))
 
 
 def grid_descend_device(grid, fields, seeds, start_cell, field_index, path, length, movement: int = 8,

@@ -12,6 +12,7 @@
 #include <string>
 
 #include "../../include/rmpc.h"
+#include "../../include/rmpc_grid_large.h"
 #include "rmpc_err.hpp"
 
 namespace rmpc {
@@ -89,6 +90,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 }  // namespace rmpc
 
 #include "rmpc_grid.hpp"
+#include "rmpc_grid_large.hpp"
 #include "rmpc_sense.hpp"
 #include "rmpc_map.hpp"
 #include "rmpc_assign.hpp"
@@ -155,6 +157,30 @@ static int grid_fields(Kernel kernel, int H, int W, const double *d_grid, int G,
   return launch_status();
 }
 
+// rmpc_grid_fields_large_device and rmpc_grid_fields_seeded_large_device (include/rmpc_grid_large.h; both speak as
+// "grid fields large"): every refusal comes before the first HIP call
+template <bool kSeeded>
+static int grid_fields_large(int H, int W, const double *d_grid, int G, const int *d_goal_cells, const double *d_seeds,
+                             int movement, double occ_threshold, double cost_factor, double *d_fields,
+                             int32_t *d_status, int32_t *d_visits, void *stream) {
+  const std::string who = "grid fields large";
+  if (!d_grid || !(kSeeded ? (const void *)d_seeds : (const void *)d_goal_cells) || !d_fields || !d_status)
+    return fail("null argument");
+  if (H < 1 || W < 1) return fail(who + ": need H, W >= 1");
+  if (movement != 4 && movement != 8) return fail(who + ": movement must be 4 or 8");
+  if (H > RMPC_GRID_LARGE_MAX_SIDE || W > RMPC_GRID_LARGE_MAX_SIDE)
+    return fail(who + ": " + std::to_string(H) + "x" + std::to_string(W) + " map has a side above RMPC_GRID_LARGE_MAX_SIDE = " +
+                std::to_string(RMPC_GRID_LARGE_MAX_SIDE));
+  if ((long long)H * W > RMPC_GRID_LARGE_MAX_CELLS)
+    return fail(who + ": " + std::to_string(H) + "x" + std::to_string(W) + " map exceeds RMPC_GRID_LARGE_MAX_CELLS = " +
+                std::to_string(RMPC_GRID_LARGE_MAX_CELLS) + " cells");
+  if (grid_fields_check(who, G, H, W) || grid_cost_check(who, cost_factor) || use_device_of(d_grid)) return -1;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid_fields_large<kSeeded>), dim3(G), dim3(kLargeThreads), 0, (hipStream_t)stream,
+                     d_grid, H, W, d_goal_cells, d_seeds, movement, occ_threshold, cost_factor, d_fields, (int *)d_status,
+                     (int *)d_visits);
+  return launch_status();
+}
+
 // rmpc_grid_paths_device and rmpc_grid_descend_device: `d_ends` the goal cells or the seed grids of `kernel`
 template <class Kernel, class T>
 static int grid_descent(const char *who, Kernel kernel, int H, int W, const double *d_grid, int G, const double *d_fields,
@@ -215,6 +241,20 @@ int rmpc_grid_fields_seeded_device(int H, int W, const double *d_grid, int G, co
                                    int32_t *d_sweeps, void *stream) {
   return grid_fields(k_grid_fields_seeded, H, W, d_grid, G, d_seeds, movement, occ_threshold, cost_factor, d_fields,
                      d_status, d_sweeps, stream);
+}
+
+int rmpc_grid_fields_large_device(int H, int W, const double *d_grid, int G, const int32_t *d_goal_cells, int movement,
+                                  double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status,
+                                  int32_t *d_visits, void *stream) {
+  return grid_fields_large<false>(H, W, d_grid, G, (const int *)d_goal_cells, nullptr, movement, occ_threshold, cost_factor,
+                                  d_fields, d_status, d_visits, stream);
+}
+
+int rmpc_grid_fields_seeded_large_device(int H, int W, const double *d_grid, int G, const double *d_seeds, int movement,
+                                         double occ_threshold, double cost_factor, double *d_fields, int32_t *d_status,
+                                         int32_t *d_visits, void *stream) {
+  return grid_fields_large<true>(H, W, d_grid, G, nullptr, d_seeds, movement, occ_threshold, cost_factor, d_fields,
+                                 d_status, d_visits, stream);
 }
 
 int rmpc_grid_paths_device(int H, int W, const double *d_grid, int G, const double *d_fields, const int32_t *d_goal_cells,

@@ -1,5 +1,6 @@
 """``a_star`` with the reference's signature and return format (``robotmpcs/global_planner/a_star.py``), computed on the
-device: the cost-to-go field of the goal (``rmpc_grid_fields_device``) and its descent from the start
+device: the cost-to-go field of the goal (``rmpc_grid_fields_device``, on a map of more than ``_lib.GRID_MAX_CELLS``
+cells ``rmpc_grid_fields_large_device``) and its descent from the start
 (``rmpc_grid_paths_device``).  The path has the least cost delta + occupancy_cost_factor data over its cells, the cost
 the reference's A* sums (its doubled potential term in the priority can make that A* return a dearer path on graded
 maps; on binary maps both costs agree).  The map's ``visited`` array is left untouched."""
@@ -31,7 +32,8 @@ def a_star(start_m, goal_m, gmap, movement='8N', occupancy_cost_factor=3):
     path = torch.empty((1, H * W), dtype=torch.int32, device=dev)
     length = torch.empty(1, dtype=torch.int32, device=dev)
     th, f = float(gmap.occupancy_threshold), float(occupancy_cost_factor)
-    _lib.grid_fields_device(grid, goal_c, fields, status, MOVES[movement], th, f)
+    fields_device = _lib.grid_fields_large_device if H * W > _lib.GRID_MAX_CELLS else _lib.grid_fields_device
+    fields_device(grid, goal_c, fields, status, MOVES[movement], th, f)
     _lib.grid_paths_device(grid, fields, goal_c, start_c, i32([0]), path, length, MOVES[movement], th, f)
     n = int(length.item())
     if n < 0:

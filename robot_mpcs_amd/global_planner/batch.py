@@ -23,7 +23,8 @@ def plan_batch(grid, starts, goal_cells, movement="8N", occupancy_threshold=0.8,
     """grid (H, W) occupancy (numpy or device tensor), starts (B,) and goal_cells (B,) cell indices row * W + col ->
     (paths (B, max_len) int32, lens (B,) int32) on the device; lens as ``rmpc_grid_paths_device`` (> 0 cells, 0
     unreachable, < 0 an error code of ``_lib.GRID_*``).  Each distinct goal gets one field.  max_len defaults to
-    4 (H + W), at most H W.  With return_fields, also (fields (G, H, W), status (G,), goal_index (B,))."""
+    4 (H + W), at most H W.  Maps of more than ``_lib.GRID_MAX_CELLS`` cells, up to ``_lib.GRID_LARGE_MAX_CELLS``, take
+    ``rmpc_grid_fields_large_device``.  With return_fields, also (fields (G, H, W), status (G,), goal_index (B,))."""
     import torch
     if movement not in MOVES:
         raise ValueError("Unknown movement")
@@ -43,7 +44,9 @@ def plan_batch(grid, starts, goal_cells, movement="8N", occupancy_threshold=0.8,
     paths = torch.empty((s.shape[0], max_len), dtype=torch.int32, device=dev)
     lens = torch.empty(s.shape[0], dtype=torch.int32, device=dev)
     st = _lib.stream_handle(stream, dev)
-    _lib.grid_fields_device(g, uniq, fields, status, MOVES[movement], occupancy_threshold, occupancy_cost_factor, stream=st)
+    # a map beyond one workgroup's LDS takes the tiled entry: the same fields, bit for bit
+    fields_device = _lib.grid_fields_large_device if H * W > _lib.GRID_MAX_CELLS else _lib.grid_fields_device
+    fields_device(g, uniq, fields, status, MOVES[movement], occupancy_threshold, occupancy_cost_factor, stream=st)
     _lib.grid_paths_device(g, fields, uniq, s, inv, paths, lens, MOVES[movement], occupancy_threshold,
                            occupancy_cost_factor, stream=st)
     if return_fields:
