@@ -138,6 +138,7 @@ typedef const __attribute__((address_space(4))) ArmBlock cArmBlock;
 struct FusedHalf {
   double gphi_sum;
   int b, valid, retired, first, ipass, nextslot;
+  int recurse, usec;   // what the half's decision of this pass said: they wait through the sweep call of an early hand-over
 };
 // The view a phase FUNCTION reads the problem's structure through: a generated view is a set of constants; the runtime
 // tables come through uniform pointers in the constant address space (GView: tables in front of the pointer block,
@@ -367,6 +368,8 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
   int ipass = 0;                // passes of the instance so far
   int nextslot = blockIdx.x * IPW + half;   // queue position of the half's first instance (-1: ask the counter)
   double gphi_sum = 0.0;   // merit slope of the current step (sum over the stages; step phase)
+  bool recurse = false;    // the decision of this pass asked for a recursion ...
+  bool usec = false;       // ... with the curvature terms
   // (every lane of an instance holds the same words: its lane 0 parks them, all lanes take them back)
   auto park = [&]() __attribute__((always_inline)) {
     if (k == 0) {
@@ -374,6 +377,7 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
       FusedHalf hw;
       hw.gphi_sum = gphi_sum; hw.b = bi; hw.ipass = ipass; hw.nextslot = nextslot;
       hw.valid = valid ? 1 : 0; hw.retired = retired ? 1 : 0; hw.first = first ? 1 : 0;
+      hw.recurse = recurse ? 1 : 0; hw.usec = usec ? 1 : 0;
       shalf[half] = hw;
     }
   };
@@ -385,239 +389,262 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
     const FusedHalf hw = shalf[half];
     gphi_sum = hw.gphi_sum; bi = hw.b; ipass = hw.ipass; nextslot = hw.nextslot;
     valid = hw.valid != 0; retired = hw.retired != 0; first = hw.first != 0;
+    recurse = hw.recurse != 0; usec = hw.usec != 0;
   };
 
+  // Generated views with LDS records: the step lengths of a fresh step are formed inside the sweep call (MERGE2).
+  // (The same reordering for the runtime tables, inline, is bit-identical too and no faster: boxer 0.48 vs 0.50 M.)
+  constexpr bool MERGE2 = V::SPEC && REC_LDS;
   PassStamps ps;
   ps.start();
   for (;;) {
-    // ---- finished instances leave, idle halves take the next instance of the queue -----------------------------------
-    ps.hand_begin();
-    {
-      const bool over = valid && (s.status == ST_ACTIVE) && ipass >= max_passes;   // deadline (rmpc_set_pass_budget) or cap
-      const bool done = valid && (s.status != ST_ACTIVE || over);
-      if (__ballot(done || (!valid && !retired)) != 0ull) {
-        cArmBlock *const A = blk();
-        // The half asks the queue FIRST: the counter's answer travels while the epilogue runs and is looked at behind
-        // the epilogue's stores (positions beyond the grid's own; the counter is zeroed before the launch).
-        const bool take = (done || !valid) && !retired;   // the half wants the next instance
-        bool took = false;
-        int qt = 0;
-        if (take && nextslot < 0 && k == 0) qt = atomicAdd(A->F.passes + 1, 1);
-        if (done) {
-          // epilogue: plan in the ABI layout, statistics (the trial point and the step were made visible to the whole
-          // wavefront by the ordering points of the pass that ended the solve)
-          const size_t b = (size_t)bi;
-          const bool c1 = s.cur != 0;
-          const bool okd = (s.status == ST_ACTIVE || s.status >= 0) && isfinite(s.mu) && s.mu > 0.0;
-          if (stage) {
-            const gdouble *zf = (const gdouble *)(c1 ? A->F.z[1] : A->F.z[0]) + b * A->F.nv * S;
-            double *zr = zout + (b * N + k) * NV;
-            double zv[NV];
+    // A pass of the wavefront is hand-over, sweep, decision -- up to twice -- and then ONE recursion call for both halves.
+    // Round 0 is the pass of every half that holds an instance.  A half whose instance stops at that decision would sit
+    // out the partner's recursion (half of the pass) and meet its next instance only at the top of the next pass: round 1
+    // runs the hand-over for it at once -- epilogue, dequeue, prologue --, then the first sweep and the first decision of
+    // the instance it took, so that this instance's first recursion shares the call with the partner's.  The rounds are
+    // two trips through one copy of the code (the hand-over is a large part of the kernel's body); an instance keeps its
+    // order of sweep, decision, recursion and step, and what a partner does changes nothing in it.
+    bool idle = false;
+    recurse = false;
+    usec = false;
+#pragma nounroll
+    for (int round = 0;; round = 1) {
+      // ---- finished instances leave, idle halves take the next instance of the queue -----------------------------------
+      ps.hand_begin();
+      bool took = false;
+      {
+        // deadline (rmpc_set_pass_budget) or cap: looked at at the top of a pass only, behind the instance's recursion
+        const bool over = round == 0 && valid && (s.status == ST_ACTIVE) && ipass >= max_passes;
+        const bool done = valid && (s.status != ST_ACTIVE || over);
+        if (__ballot(done || (!valid && !retired)) != 0ull) {
+          cArmBlock *const A = blk();
+          // The half asks the queue FIRST: the counter's answer travels while the epilogue runs and is looked at behind
+          // the epilogue's stores (positions beyond the grid's own; the counter is zeroed before the launch).
+          const bool take = (done || !valid) && !retired;   // the half wants the next instance
+          int qt = 0;
+          if (take && nextslot < 0 && k == 0) qt = atomicAdd(A->F.passes + 1, 1);
+          if (done) {
+            // epilogue: plan in the ABI layout, statistics (the trial point and the step were made visible to the whole
+            // wavefront by the ordering points of the pass that ended the solve)
+            const size_t b = (size_t)bi;
+            const bool c1 = s.cur != 0;
+            const bool okd = (s.status == ST_ACTIVE || s.status >= 0) && isfinite(s.mu) && s.mu > 0.0;
+            if (stage) {
+              const gdouble *zf = (const gdouble *)(c1 ? A->F.z[1] : A->F.z[0]) + b * A->F.nv * S;
+              double *zr = zout + (b * N + k) * NV;
+              double zv[NV];
 #pragma unroll
-            for (int j = 0; j < NV; j++) zv[j] = zf[j * S + k];
-            if (save_duals) {
-              // multipliers for a warm start of the next solve of this instance (a failed solve leaves zeros and mu0):
-              // every word of the stage is requested before the first is stored (sets of kDualSet rows: the point
-              // robot's 33 rows and 6 costates are one set; slots beyond the last row repeat it -- same address, same
-              // value: no tail loop, no branch)
-              const int m = A->F.m;
-              const gdouble *lf = (const gdouble *)(c1 ? A->F.lam[1] : A->F.lam[0]) + b * m * S;
-              const gdouble *nf = (const gdouble *)(c1 ? A->F.nu[1] : A->F.nu[0]) + b * A->F.nx * S;
-              gdouble *wl = (gdouble *)A->F.wlam + b * m * S, *wn = (gdouble *)A->F.wnu + b * A->F.nx * S;
-              double nv6[NX];
+              for (int j = 0; j < NV; j++) zv[j] = zf[j * S + k];
+              if (save_duals) {
+                // multipliers for a warm start of the next solve of this instance (a failed solve leaves zeros and mu0):
+                // every word of the stage is requested before the first is stored (sets of kDualSet rows: the point
+                // robot's 33 rows and 6 costates are one set; slots beyond the last row repeat it -- same address, same
+                // value: no tail loop, no branch)
+                const int m = A->F.m;
+                const gdouble *lf = (const gdouble *)(c1 ? A->F.lam[1] : A->F.lam[0]) + b * m * S;
+                const gdouble *nf = (const gdouble *)(c1 ? A->F.nu[1] : A->F.nu[0]) + b * A->F.nx * S;
+                gdouble *wl = (gdouble *)A->F.wlam + b * m * S, *wn = (gdouble *)A->F.wnu + b * A->F.nx * S;
+                double nv6[NX];
 #pragma unroll
-              for (int j = 0; j < NX; j++) nv6[j] = nf[j * S + k];
-              constexpr int kDualSet = 36;
-              for (int i0 = 0; i0 < m; i0 += kDualSet) {
-                double lv[kDualSet];
+                for (int j = 0; j < NX; j++) nv6[j] = nf[j * S + k];
+                constexpr int kDualSet = 36;
+                for (int i0 = 0; i0 < m; i0 += kDualSet) {
+                  double lv[kDualSet];
 #pragma unroll
-                for (int u = 0; u < kDualSet; u++) lv[u] = lf[min(i0 + u, m - 1) * S + k];
-                if (i0 == 0) {
+                  for (int u = 0; u < kDualSet; u++) lv[u] = lf[min(i0 + u, m - 1) * S + k];
+                  if (i0 == 0) {
+#pragma unroll
+                    for (int j = 0; j < NV; j++) zr[j] = zv[j];
+#pragma unroll
+                    for (int j = 0; j < NX; j++) wn[j * S + k] = okd ? nv6[j] : 0.0;
+                  }
+#pragma unroll
+                  for (int u = 0; u < kDualSet; u++) wl[min(i0 + u, m - 1) * S + k] = okd ? lv[u] : 0.0;
+                }
+                if (m <= 0) {
 #pragma unroll
                   for (int j = 0; j < NV; j++) zr[j] = zv[j];
 #pragma unroll
                   for (int j = 0; j < NX; j++) wn[j * S + k] = okd ? nv6[j] : 0.0;
                 }
-#pragma unroll
-                for (int u = 0; u < kDualSet; u++) wl[min(i0 + u, m - 1) * S + k] = okd ? lv[u] : 0.0;
-              }
-              if (m <= 0) {
+              } else {
 #pragma unroll
                 for (int j = 0; j < NV; j++) zr[j] = zv[j];
-#pragma unroll
-                for (int j = 0; j < NX; j++) wn[j * S + k] = okd ? nv6[j] : 0.0;
               }
-            } else {
-#pragma unroll
-              for (int j = 0; j < NV; j++) zr[j] = zv[j];
             }
-          }
-          if (k == 0) {
-            exitflag[b] = (s.status == ST_ACTIVE) ? 0 : s.status;
-            iters_out[b] = s.iters;
-            kkt[b] = fmax(fmax(s.res_stat, s.res_eq), fmax(s.res_ineq, s.res_comp));
-            obj[b] = s.obj;
-            if (save_duals) {   // (read by a warm-started launch, k_order_t and rmpc_retarget_device only)
-              A->F.wmu[b] = okd ? s.mu : A->M.mu0;
-              A->F.lastp[b] = ipass;
-            }
-            atomicMax(A->F.passes, ipass);
-          }
-          valid = false;
-          s.status = 0;
-        }
-        if (take) {
-          int pos = nextslot;
-          if (pos < 0) pos = (int)gridDim.x * IPW + __shfl(qt, half * LPI, 64);
-          nextslot = -1;
-          if (pos < B) {
-            bi = use_order ? A->F.order[pos] : pos;
-            const size_t b = (size_t)bi;
-            valid = true;
-            took = true;
-            // prologue: ABI rows of this stage -> the instance's block (x_1 := xinit, mpcModel.py:108).  One set of
-            // requests: the stage's row of x0, xinit (lane 0) and every parameter word, then the stores.
-            if (stage) {
-              gdouble *const pz0 = (gdouble *)A->F.z[0] + b * A->F.nv * S;
-              const double *zr = x0 + (b * N + k) * NV;
-              double zv[NV];
-#pragma unroll
-              for (int j = 0; j < NV; j++) zv[j] = zr[j];
-              if (k == 0) {
-#pragma unroll
-                for (int j = 0; j < NX; j++) zv[j] = xinit[b * NX + j];
+            if (k == 0) {
+              exitflag[b] = (s.status == ST_ACTIVE) ? 0 : s.status;
+              iters_out[b] = s.iters;
+              kkt[b] = fmax(fmax(s.res_stat, s.res_eq), fmax(s.res_ineq, s.res_comp));
+              obj[b] = s.obj;
+              if (save_duals) {   // (read by a warm-started launch, k_order_t and rmpc_retarget_device only)
+                A->F.wmu[b] = okd ? s.mu : A->M.mu0;
+                A->F.lastp[b] = ipass;
               }
-              if (params) {
-                // 16-byte requests from the first 16-byte boundary of the stage's row on (one word in front of it when
-                // the row starts between two: odd npar and odd stage index, or a caller's array at an odd word), a
-                // last single word when one is left.  Sets of kParSet pairs; slots beyond the row repeat its last pair
-                // (same address, same value: no tail loop, no branch).
-                const int npar = A->M.npar;
-                gdouble *const pp = (gdouble *)A->F.p + b * A->F.npar * S;
-                const double *pr = params + (b * N + k) * npar;
-                const int head = (int)(((unsigned long long)pr >> 3) & 1ull);
-                const int np2 = (npar - head) >> 1;           // whole pairs
-                const bool tail = ((npar - head) & 1) != 0;
-                const double h0 = head ? pr[0] : 0.0, t0 = tail ? pr[npar - 1] : 0.0;
-                const double2 *pq = (const double2 *)(pr + head);
-                constexpr int kParSet = 20;
-                for (int j0 = 0; j0 < np2; j0 += kParSet) {
-                  double2 pv[kParSet];
+              atomicMax(A->F.passes, ipass);
+            }
+            valid = false;
+            s.status = 0;
+          }
+          if (take) {
+            int pos = nextslot;
+            if (pos < 0) pos = (int)gridDim.x * IPW + __shfl(qt, half * LPI, 64);
+            nextslot = -1;
+            if (pos < B) {
+              bi = use_order ? A->F.order[pos] : pos;
+              const size_t b = (size_t)bi;
+              valid = true;
+              took = true;
+              // prologue: ABI rows of this stage -> the instance's block (x_1 := xinit, mpcModel.py:108).  One set of
+              // requests: the stage's row of x0, xinit (lane 0) and every parameter word, then the stores.
+              if (stage) {
+                gdouble *const pz0 = (gdouble *)A->F.z[0] + b * A->F.nv * S;
+                const double *zr = x0 + (b * N + k) * NV;
+                double zv[NV];
 #pragma unroll
-                  for (int u = 0; u < kParSet; u++) pv[u] = pq[min(j0 + u, np2 - 1)];
-                  if (j0 == 0) {
+                for (int j = 0; j < NV; j++) zv[j] = zr[j];
+                if (k == 0) {
+#pragma unroll
+                  for (int j = 0; j < NX; j++) zv[j] = xinit[b * NX + j];
+                }
+                if (params) {
+                  // 16-byte requests from the first 16-byte boundary of the stage's row on (one word in front of it when
+                  // the row starts between two: odd npar and odd stage index, or a caller's array at an odd word), a
+                  // last single word when one is left.  Sets of kParSet pairs; slots beyond the row repeat its last pair
+                  // (same address, same value: no tail loop, no branch).
+                  const int npar = A->M.npar;
+                  gdouble *const pp = (gdouble *)A->F.p + b * A->F.npar * S;
+                  const double *pr = params + (b * N + k) * npar;
+                  const int head = (int)(((unsigned long long)pr >> 3) & 1ull);
+                  const int np2 = (npar - head) >> 1;           // whole pairs
+                  const bool tail = ((npar - head) & 1) != 0;
+                  const double h0 = head ? pr[0] : 0.0, t0 = tail ? pr[npar - 1] : 0.0;
+                  const double2 *pq = (const double2 *)(pr + head);
+                  constexpr int kParSet = 20;
+                  for (int j0 = 0; j0 < np2; j0 += kParSet) {
+                    double2 pv[kParSet];
+#pragma unroll
+                    for (int u = 0; u < kParSet; u++) pv[u] = pq[min(j0 + u, np2 - 1)];
+                    if (j0 == 0) {
+#pragma unroll
+                      for (int j = 0; j < NV; j++) pz0[j * S + k] = zv[j];
+                    }
+#pragma unroll
+                    for (int u = 0; u < kParSet; u++) {
+                      const int j = head + 2 * min(j0 + u, np2 - 1);
+                      pp[j * S + k] = pv[u].x; pp[(j + 1) * S + k] = pv[u].y;
+                    }
+                  }
+                  if (np2 <= 0) {
 #pragma unroll
                     for (int j = 0; j < NV; j++) pz0[j * S + k] = zv[j];
                   }
-#pragma unroll
-                  for (int u = 0; u < kParSet; u++) {
-                    const int j = head + 2 * min(j0 + u, np2 - 1);
-                    pp[j * S + k] = pv[u].x; pp[(j + 1) * S + k] = pv[u].y;
-                  }
-                }
-                if (np2 <= 0) {
+                  if (head) pp[k] = h0;
+                  if (tail) pp[(npar - 1) * S + k] = t0;
+                } else {
 #pragma unroll
                   for (int j = 0; j < NV; j++) pz0[j * S + k] = zv[j];
                 }
-                if (head) pp[k] = h0;
-                if (tail) pp[(npar - 1) * S + k] = t0;
-              } else {
+                if constexpr (REC_LDS) {   // the step slots are read (and discarded) by the first sweep: keep them finite
 #pragma unroll
-                for (int j = 0; j < NV; j++) pz0[j * S + k] = zv[j];
+                  for (int j = 0; j < NV + NX; j++) slots[k * GS + DZ_OFF + j] = 0.0;
+                }
               }
-              if constexpr (REC_LDS) {   // the step slots are read (and discarded) by the first sweep: keep them finite
-#pragma unroll
-                for (int j = 0; j < NV + NX; j++) slots[k * GS + DZ_OFF + j] = 0.0;
+              {
+                const double mu0 = A->M.mu0;
+                inst_init(s, warm ? warm_mu(A->F.wmu[b], mu0) : mu0);
               }
+              first = true;
+              ipass = 0;
+              gphi_sum = 0.0;
+            } else {
+              retired = true;
+              bi = B - 1;
             }
-            {
-              const double mu0 = A->M.mu0;
-              inst_init(s, warm ? warm_mu(A->F.wmu[b], mu0) : mu0);
-            }
-            first = true;
-            ipass = 0;
-            gphi_sum = 0.0;
-          } else {
-            retired = true;
-            bi = B - 1;
           }
+          GSYNC();   // the new instance's block is complete before any lane reads another lane's part
+          ps.hand_events(done && k == 0, took && k == 0, round);
         }
-        GSYNC();   // the new instance's block is complete before any lane reads another lane's part
-        ps.hand_events(done && k == 0, took && k == 0);
       }
-    }
-    const bool act = valid && (s.status == ST_ACTIVE);
-    ps.hand_end();
-    if (__ballot(act) == 0ull) break;   // both halves are idle and the queue is empty
-    if (act) ipass++;
-    // which copy of the sweep the lane runs this pass (first pass of its instance or not): the two halves of the
-    // wavefront may differ (both copies then run, one after the other); an idle half follows its partner
-    const bool v1 = act ? first : (__ballot(act && first) != 0ull);
-    ps.pass_begin(act && k == 0, v1);
-    ps.mark();
-    // ---- sweep: trial point, model functions, condensing, stage partials -------------------------------
-    Partials q = {0, 0, 0, 0, 0, 0, 0, 0, 1e300, 0};
-    // Generated views with LDS records: the step lengths of a fresh step are formed inside the sweep call (MERGE2).
-    // (The same reordering for the runtime tables, inline, is bit-identical too and no faster: boxer 0.48 vs 0.50 M.)
-    constexpr bool MERGE2 = V::SPEC && REC_LDS;
-    park();
-    bool fresh = false;
-    if constexpr (MERGE2) {
-      const bool nostep = first || (s.redo != 0);
-      fresh = act && !nostep && (s.newstep != 0);
-      const FusedWs *const Fp = (const FusedWs *)(Tp + 1);
-      __attribute__((address_space(3))) SweepStepOut *const so = (__attribute__((address_space(3))) SweepStepOut *)&sres[half];
-      cArmBlock *const A = blk();
-      const double dt = A->M.dt;
-      const int use_curv = A->M.use_curv;
-      if (v1) fused_sweep_step_call<C, V, 1>(so, Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, act && stage, nostep, fresh, s.ls, s.amin_p, s.amin_d, gphi_sum, s.mu, warm ? 1 : 0);
-      else fused_sweep_step_call<C, V, 0>(so, Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, act && stage, nostep, fresh, s.ls, s.amin_p, s.amin_d, gphi_sum, s.mu, warm ? 1 : 0);
-    } else {
-      // the sweep is a call (scalars in, partials out): a generated view, or the runtime tables through GView
-      if (act && stage) {
+      // who sweeps and decides in this round: every half with an instance; in round 1 the halves that have just taken one
+      // (the partner's instance waits between its decision and its recursion)
+      const bool act = valid && (s.status == ST_ACTIVE) && (round == 0 || took);
+      ps.hand_end();
+      if (__ballot(act) == 0ull) {   // round 0: both halves are idle and the queue is empty; round 1: it was empty
+        idle = round == 0;
+        break;
+      }
+      if (act) ipass++;
+      // which copy of the sweep the lane runs this pass (first pass of its instance or not): the two halves of the
+      // wavefront may differ (both copies then run, one after the other); an idle half follows its partner
+      const bool v1 = act ? first : (__ballot(act && first) != 0ull);
+      ps.pass_begin(act && k == 0, v1, round);
+      ps.mark();
+      // ---- sweep: trial point, model functions, condensing, stage partials -------------------------------
+      Partials q = {0, 0, 0, 0, 0, 0, 0, 0, 1e300, 0};
+      park();
+      bool fresh = false;
+      if constexpr (MERGE2) {
         const bool nostep = first || (s.redo != 0);
-        double alpha = 0.0, adual = 0.0;
-        if (!nostep) {
-          alpha = ldexp(s.amin_p, -s.ls);
-          adual = s.amin_d;
-        }
-        const FusedWs *const Fp = (const FusedWs *)(Tp + 1);   // (the pointer block behind the row tables)
+        fresh = act && !nostep && (s.newstep != 0);
+        const FusedWs *const Fp = (const FusedWs *)(Tp + 1);
+        __attribute__((address_space(3))) SweepStepOut *const so = (__attribute__((address_space(3))) SweepStepOut *)&sres[half];
         cArmBlock *const A = blk();
         const double dt = A->M.dt;
         const int use_curv = A->M.use_curv;
-        if (first) q = fused_sweep_call<C, VC, 1, REC_LDS>(Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, nostep, alpha, adual, s.mu, warm ? 1 : 0);
-        else q = fused_sweep_call<C, VC, 0, REC_LDS>(Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, nostep, alpha, adual, s.mu, warm ? 1 : 0);
+        if (v1) fused_sweep_step_call<C, V, 1>(so, Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, act && stage, nostep, fresh, s.ls, s.amin_p, s.amin_d, gphi_sum, s.mu, warm ? 1 : 0);
+        else fused_sweep_step_call<C, V, 0>(so, Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, act && stage, nostep, fresh, s.ls, s.amin_p, s.amin_d, gphi_sum, s.mu, warm ? 1 : 0);
+      } else {
+        // the sweep is a call (scalars in, partials out): a generated view, or the runtime tables through GView
+        if (act && stage) {
+          const bool nostep = first || (s.redo != 0);
+          double alpha = 0.0, adual = 0.0;
+          if (!nostep) {
+            alpha = ldexp(s.amin_p, -s.ls);
+            adual = s.amin_d;
+          }
+          const FusedWs *const Fp = (const FusedWs *)(Tp + 1);   // (the pointer block behind the row tables)
+          cArmBlock *const A = blk();
+          const double dt = A->M.dt;
+          const int use_curv = A->M.use_curv;
+          if (first) q = fused_sweep_call<C, VC, 1, REC_LDS>(Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, nostep, alpha, adual, s.mu, warm ? 1 : 0);
+          else q = fused_sweep_call<C, VC, 0, REC_LDS>(Fp, N, dt, use_curv, (size_t)bi, s.cur, k, slots, nostep, alpha, adual, s.mu, warm ? 1 : 0);
+        }
       }
+      ps.sweep_returned();
+      unpark();
+      Reduced r;
+      if constexpr (MERGE2) {
+        // (the call has reduced over the stages and left the instance's words in LDS: unpark's fence orders the reads)
+        const SweepStepOut o = sres[half];
+        if (fresh) { s.amin_p = o.amin_p; s.amin_d = o.amin_d; gphi_sum = o.gphi; }
+        r.f = o.f; r.th = o.th; r.lgs = o.lgs; r.sumc = o.sumc; r.badf = o.badf;
+        r.rstat = o.rstat; r.req = o.req; r.rineq = o.rineq; r.rcomp = o.rcomp; r.minc = o.minc;
+        ps.sections(sres[half]);
+      } else {
+        ps.sections(q);
+        // (outside `act && stage`: the whole wavefront reduces, idle lanes with the neutral elements)
+        double rs5[5] = {q.f, q.th, q.logs, q.sumc, q.bad}, rm4[4] = {q.rstat, q.req, q.rineq, q.rcomp}, rn1[1] = {q.minc};
+        wave_reduce_many<LPI>(rs5, rm4, rn1);
+        r.f = rs5[0]; r.th = rs5[1]; r.lgs = rs5[2]; r.sumc = rs5[3]; r.badf = rs5[4];
+        r.rstat = rm4[0]; r.req = rm4[1]; r.rineq = rm4[2]; r.rcomp = rm4[3]; r.minc = rn1[0];
+      }
+      r.gphi = first ? 0.0 : gphi_sum;
+      ps.sweep_reduced();
+      GSYNC();   // trial point and records are complete before any lane reads another lane's part
+      ps.sweep_end();
+      // ---- decisions, then a new step when the trial was accepted --------------------------------------
+      // (the tolerances and caps of the decision: scalar loads from the model's copy behind the row tables)
+      if (act) recurse = inst_decide<C>(*(const DevModel *)&blk()->M, s, r, first, usec);   // (sets both of its half)
+      if (act) first = false;
+      ps(PH_DEC);
+      // Round 1 only for a half that holds an instance this decision has stopped (a retired half holds none).  At most two
+      // rounds: an instance that stops at its first decision inside round 1 leaves at the top of the next pass.
+      if (round != 0 || __ballot(valid && s.status != ST_ACTIVE) == 0ull) break;
     }
-    ps.sweep_returned();
-    unpark();
-    Reduced r;
-    if constexpr (MERGE2) {
-      // (the call has reduced over the stages and left the instance's words in LDS: unpark's fence orders the reads)
-      const SweepStepOut o = sres[half];
-      if (fresh) { s.amin_p = o.amin_p; s.amin_d = o.amin_d; gphi_sum = o.gphi; }
-      r.f = o.f; r.th = o.th; r.lgs = o.lgs; r.sumc = o.sumc; r.badf = o.badf;
-      r.rstat = o.rstat; r.req = o.req; r.rineq = o.rineq; r.rcomp = o.rcomp; r.minc = o.minc;
-      ps.sections(sres[half]);
-    } else {
-      ps.sections(q);
-      // (outside `act && stage`: the whole wavefront reduces, idle lanes with the neutral elements)
-      double rs5[5] = {q.f, q.th, q.logs, q.sumc, q.bad}, rm4[4] = {q.rstat, q.req, q.rineq, q.rcomp}, rn1[1] = {q.minc};
-      wave_reduce_many<LPI>(rs5, rm4, rn1);
-      r.f = rs5[0]; r.th = rs5[1]; r.lgs = rs5[2]; r.sumc = rs5[3]; r.badf = rs5[4];
-      r.rstat = rm4[0]; r.req = rm4[1]; r.rineq = rm4[2]; r.rcomp = rm4[3]; r.minc = rn1[0];
-    }
-    r.gphi = first ? 0.0 : gphi_sum;
-    ps.sweep_reduced();
-    GSYNC();   // trial point and records are complete before any lane reads another lane's part
-    ps.sweep_end();
-    // ---- decisions, then a new step when the trial was accepted --------------------------------------
-    bool usec = false;
-    bool recurse = false;
-    // (the tolerances and caps of the decision: scalar loads from the model's copy behind the row tables)
-    if (act) recurse = inst_decide<C>(*(const DevModel *)&blk()->M, s, r, first, usec);
-    if (act) first = false;
-    ps(PH_DEC);
+    if (idle) break;
+    ps.mark();   // (a round 1 that ended in its hand-over: those cycles are the hand-over's, not the recursion's)
     park();
     const double mu_r = s.mu;
     const double cw_r = usec ? (C::CSCALE ? s.theta_c : 1.0) : 0.0;   // weight of the curvature terms in this recursion
@@ -647,7 +674,8 @@ __global__ __launch_bounds__(64, 1) __attribute__((amdgpu_waves_per_eu(1, 1), di
     // (MERGE2: formed inside the next sweep call -- nothing to park, call or reduce here)
     if constexpr (!MERGE2) {
       double ap = 1.0, ad = 1.0, gp = 0.0;
-      const bool stepping = act && (s.status == ST_ACTIVE) && (s.newstep != 0);
+      // (an instance that is active here has swept and decided in one of this pass's rounds)
+      const bool stepping = valid && (s.status == ST_ACTIVE) && (s.newstep != 0);
       park();
       if (stepping && stage) {
         const FusedWs *const Fp = (const FusedWs *)(Tp + 1);

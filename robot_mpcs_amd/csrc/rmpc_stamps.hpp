@@ -58,25 +58,30 @@ struct SecStamps {
 // FusedWs::stamps (read by scripts/fused_stamps.py and tests/tools/dev_arm_fused_stamps.py).
 struct PassStamps {
   long long ph[4], sec[8], hand, t_start, t_a, t_top, t_sub;
-  int pass, ipass, nhand, both;
+  int pass, ipass, nhand, both, nearly;
   __device__ __forceinline__ void start() {
     for (int i = 0; i < 4; i++) ph[i] = 0;
     for (int i = 0; i < 8; i++) sec[i] = 0;
     hand = 0;
-    pass = ipass = nhand = both = 0;
+    pass = ipass = nhand = both = nearly = 0;
     t_start = t_a = __builtin_amdgcn_s_memtime();
   }
-  // hand-over: from the top of the pass loop to the test that ends it; events = epilogues + prologues (their lane 0)
+  // hand-over: from the top of a round of the pass loop to the test that ends the round (k_fused: both sites, the top of
+  // the pass and the early one behind the decision, round 1); events = epilogues + prologues (their lane 0); early
+  // hand-overs = the epilogues of round 1
   __device__ __forceinline__ void hand_begin() { t_top = __builtin_amdgcn_s_memtime(); }
-  __device__ __forceinline__ void hand_events(const bool left, const bool took) {
+  __device__ __forceinline__ void hand_events(const bool left, const bool took, const int round = 0) {
     nhand += __popcll(__ballot(left)) + __popcll(__ballot(took));
+    if (round != 0) nearly += __popcll(__ballot(left));
   }
   __device__ __forceinline__ void hand_end() { hand += __builtin_amdgcn_s_memtime() - t_top; }
   // a pass of the wavefront.  inst: lane 0 of every instance that takes the pass; v1: the lane runs the first-pass copy
-  // of the sweep call (both copies run when the two halves of k_fused differ)
-  __device__ __forceinline__ void pass_begin(const bool inst, const bool v1) {
-    pass++;
+  // of the sweep call (both copies run when the two halves of k_fused differ).  Round 1 of k_fused (the first sweep behind
+  // an early hand-over) belongs to the pass round 0 began: its instance passes count, its cycles go to the same phases.
+  __device__ __forceinline__ void pass_begin(const bool inst, const bool v1, const int round = 0) {
     ipass += __popcll(__ballot(inst));
+    if (round != 0) return;
+    pass++;
     both += (__ballot(v1) != 0ull && __ballot(!v1) != 0ull) ? 1 : 0;
   }
   __device__ __forceinline__ void mark() { t_a = __builtin_amdgcn_s_memtime(); }
@@ -105,7 +110,8 @@ struct PassStamps {
     (*this)(PH_SWEEP);
     sec[7] += t_a - t_sub;
   }
-  // Record of the wavefront: [0 .. 3] phases, [4] total, [5] passes | passes with both sweep copies << 32,
+  // Record of the wavefront: [0 .. 3] phases, [4] total, [5] passes | passes with both sweep copies << 32 | early
+  // hand-overs << 48 (16 bits each for the two counts: a development aid, launches of some hundred passes per wavefront),
   // [7] instance passes | hand-over events << 32.  k_fused (two = true): [6] hand-over cycles, and the sections as a
   // second record at gridDim.x + blockIdx.x; k_fused_arm: [6] the start time.
   __device__ __forceinline__ void store(long long *const stamps, const bool two) {
@@ -117,7 +123,7 @@ struct PassStamps {
       }
       for (int i = 0; i < 4; i++) o[i] = ph[i];
       o[4] = __builtin_amdgcn_s_memtime() - t_start;
-      o[5] = (long long)pass | ((long long)both << 32);
+      o[5] = (long long)pass | ((long long)(both & 0xffff) << 32) | ((long long)(nearly & 0xffff) << 48);
       o[6] = two ? hand : t_start;
       o[7] = (long long)ipass | ((long long)nhand << 32);
     }
@@ -127,9 +133,9 @@ struct PassStamps {
 struct PassStamps {
   __device__ __forceinline__ void start() {}
   __device__ __forceinline__ void hand_begin() {}
-  __device__ __forceinline__ void hand_events(bool, bool) {}
+  __device__ __forceinline__ void hand_events(bool, bool, int = 0) {}
   __device__ __forceinline__ void hand_end() {}
-  __device__ __forceinline__ void pass_begin(bool, bool) {}
+  __device__ __forceinline__ void pass_begin(bool, bool, int = 0) {}
   __device__ __forceinline__ void mark() {}
   __device__ __forceinline__ void operator()(int) {}
   template <class O> __device__ __forceinline__ void sections(O) {}
