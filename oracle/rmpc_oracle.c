@@ -993,7 +993,10 @@ static int trial_merit(const orc_desc *d, orc_work *w, const double *params, dou
 /* Second-order terms of the distance rows are used when they are the exact
  * constraint Hessians: holonomic chain, no slack, n <= 3, and every frame a row
  * refers to moves affinely with q (prismatic joints, or a revolute joint at the
- * frame itself) -- the point robot.  DESIGN.md, section "Algorithm". */
+ * frame itself) -- the point robot.  With a goal cost the end frame has to be
+ * affine as well: the goal's kinematic second-order term exists only for the
+ * arms (with_fk_curv), and without it the matrix would be exact in the rows and
+ * Gauss-Newton in the goal.  DESIGN.md, section "Algorithm". */
 static int frame_is_affine(const orc_desc *d, int f) {
   for (int j = 0; j <= f; j++)
     if (d->joint_type[j] == ORC_JOINT_REVOLUTE && j != f) return 0;
@@ -1030,6 +1033,7 @@ static int model_uses_curvature(const orc_desc *d) {
   if (dd_curv(d)) return 1;
   if (d->robot != ORC_ROBOT_CHAIN || d->ns != 0) return 0;
   if (with_fk_curv(d)) return 1;   /* the kinematics' own second derivatives are part of the terms */
+  if (d->has_goal && !frame_is_affine(d, d->end_frame)) return 0;   /* (n <= 3: the goal cost carries no such term) */
   for (int mi = 0; mi < d->n_modules; mi++) {
     if (d->module_kind[mi] == ORC_MOD_RADIAL)
       for (int l = 0; l < d->n_links; l++) if (!frame_is_affine(d, d->link_frame[l])) return 0;

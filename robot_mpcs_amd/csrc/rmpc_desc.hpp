@@ -283,7 +283,9 @@ static int build_model(const rmpc_desc &d, DevModel &M, std::string &err) {
   M.acc_obj_tol = d.acc_obj_tol > 0 ? d.acc_obj_tol : 1e-8;
   M.ls_max = d.ls_max > 0 ? d.ls_max : kDescLsMax;
   // exact curvature of the distance rows: holonomic chain, no slack, and for n <= 3 every frame a
-  // distance row refers to moves affinely with q (prismatic joints, or revolute at the frame itself)
+  // distance row refers to moves affinely with q (prismatic joints, or revolute at the frame itself) -- and the
+  // goal's frame too when the model has a goal cost: its kinematic term exists only under Cfg::FKCURV (n > 3), so
+  // with a goal on a frame that turns the terms would be those of a hybrid matrix, not of the exact Hessian
   auto affine = [&](int f) {
     for (int j = 0; j <= f; j++)
       if (d.joint_type[j] == RMPC_JOINT_REVOLUTE && j != f) return false;
@@ -296,6 +298,7 @@ static int build_model(const rmpc_desc &d, DevModel &M, std::string &err) {
     if (M.row_kind[r] == ROW_RADIAL) curv = curv && affine(M.row_a[r]);
     if (M.row_kind[r] == ROW_SELF) curv = curv && affine(M.row_a[r]) && affine(M.row_b[r]);
   }
+  if (curv && d.n <= 3 && d.has_goal) curv = affine(d.end_frame);
   if (d.robot == RMPC_ROBOT_DIFFDRIVE) curv = true;   // exact second-order terms of the unicycle (Cfg::DDCURV)
   M.use_curv = curv ? 1 : 0;
   return 0;

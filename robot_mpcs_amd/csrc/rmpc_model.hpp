@@ -52,7 +52,7 @@ struct DevModel {
   double lb_val[RMPC_NV_MAX], ub_val[RMPC_NV_MAX];
   int max_iter;
   double tol_stat, tol_eq, tol_ineq, tol_comp, mu0;
-  int use_curv;      // exact curvature of the distance rows (affine kinematics, no slack, n <= 3)
+  int use_curv;      // exact curvature of the distance rows (n <= 3: rows' and goal's frames affine in q, no slack)
   int acc_iters;     // acceptable termination window (0 = off)
   double acc_obj_tol;
   int ls_max;        // step halvings allowed in one line search
@@ -222,8 +222,9 @@ struct Cfg {
   static constexpr int NQ2 = NQ_ * (NQ_ + 1) / 2;
   static constexpr int NR = 5;  // reduced diff-drive state (x, y, theta, v, omega)
   // exact curvature of the distance rows / inverse-barrier objective (Cqq block of the stage record): holonomic
-  // chains without slack.  Three joints: only when every frame moves affinely with q (decided per descriptor,
-  // DevModel::use_curv).  The arms: always, with the second derivatives of the kinematics themselves (FKCURV:
+  // chains without slack.  Three joints or fewer: only when every frame a distance row refers to, and the goal's
+  // frame when there is a goal cost, moves affinely with q (decided per descriptor, DevModel::use_curv: otherwise
+  // CURV is compiled in and the terms are off at run time).  The arms: always, with the second derivatives of the kinematics themselves (FKCURV:
   // distance rows, inverse-barrier objective and the goal cost) -- without them a warm-started arm crawls to the
   // tolerance at a linear rate of 0.6 per iteration.
   static constexpr bool CURV = (ROBOT_ == RMPC_ROBOT_CHAIN) && (NS_ == 0);

@@ -37,7 +37,8 @@ REL = 8.0 * REL_MEASURED
 H = lambda N: {"time_horizon": N}
 
 # (config, scenario overrides) -> draw of the class: 0 unless the first draw misses a condition of (c) on the oracle
-SALT = {("cfg3", ()): 4, ("boxer", ()): 4}   # (the first draw keeps one cold instance of four in both)
+SALT = {("cfg3", ()): 4, ("boxer", ()): 4,   # (the first draw keeps one cold instance of four in both)
+        ("aff3g", ()): 1}                    # (chain_cases.py; the same)
 
 
 def key_of(name, kw):

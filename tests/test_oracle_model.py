@@ -4,6 +4,7 @@ differences, and a sympy derivation of the panda kinematics.  CPU only."""
 import numpy as np
 import pytest
 
+import chain_cases
 from oracle import nlp_numpy as ref
 from oracle.oracle import Oracle
 from robot_mpcs_amd.scenarios import make_scenario
@@ -11,7 +12,13 @@ from robot_mpcs_amd.scenarios import make_scenario
 CASES = ["cfg1", "cfg2", "cfg3", "cfg4", "boxer",
          # VelLimitConstraints rows; ConstraintAvoidance weight non-zero on every module (Linear, SelfCollision,
          # Joint / Vel / Input limits as "first row of a module")
-         "wc_point", "wc_boxer", "wc_boxer_slack", "wc_panda"]
+         "wc_point", "wc_boxer", "wc_boxer_slack", "wc_panda",
+         # the cuts of the shipped chains, and the chains that mix revolute and prismatic joints (chain_cases.py)
+         "chain2", "chain4", "chain5", "chain6", "chain8"] + list(chain_cases.NAMES)
+
+
+def _scenario(name, **kw):
+    return (chain_cases.make_chain_scenario if name in chain_cases.CLASSES else make_scenario)(name, **kw)
 
 
 def _random_points(sc, o, rng, k=6):
@@ -31,7 +38,7 @@ def _random_points(sc, o, rng, k=6):
 
 @pytest.mark.parametrize("name", CASES)
 def test_values_match_numpy(name, oracle_lib):
-    sc = make_scenario(name, B=4, seed=3)
+    sc = _scenario(name, B=4, seed=3)
     o = Oracle(sc.desc)
     rng = np.random.default_rng(0)
     for z, p in _random_points(sc, o, rng):
@@ -45,7 +52,7 @@ def test_values_match_numpy(name, oracle_lib):
 
 @pytest.mark.parametrize("name", CASES)
 def test_derivatives_match_finite_differences(name, oracle_lib):
-    sc = make_scenario(name, B=4, seed=4)
+    sc = _scenario(name, B=4, seed=4)
     o = Oracle(sc.desc)
     d = sc.desc
     rng = np.random.default_rng(1)
