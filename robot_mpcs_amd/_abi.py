@@ -13,6 +13,10 @@ Not a C parser.  After comments and preprocessor lines are taken out, the header
       every other ``T *p`` or ``T p[n]`` (a host array: the wrappers pass typed numpy pointers) -> ``POINTER(T)``.
 Anything else -- unsigned, a union, a bit-field, a function pointer, an unknown type or extent, a stray declaration --
 raises ``RmpcError`` with the text that was not understood; nothing is skipped.
+
+The headers beside it are read the same way into tables of their own: ``include/rmpc_grid_large.h`` into
+``large_constants`` / ``large_prototypes``, ``include/rmpc_assign_opt.h`` into ``assign_constants`` /
+``assign_prototypes``.
 """
 import ctypes as C
 import os
@@ -21,6 +25,8 @@ import re
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "rmpc.h")
 # the fields on large maps: a header of its own, read into tables of its own
 LARGE_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_grid_large.h")
+# the minimum-cost assignment: likewise
+ASSIGN_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_assign_opt.h")
 
 _SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "int": C.c_int, "long long": C.c_longlong}
 _DECLARATION = re.compile(r"(?:const\s+)?(long long|\w+)(\s+|\s*(?:\*\s*)+)(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)")
@@ -128,3 +134,4 @@ def _read(path):
 
 constants, structs, prototypes = _read(HEADER)
 large_constants, _, large_prototypes = _read(LARGE_HEADER)
+assign_constants, _, assign_prototypes = _read(ASSIGN_HEADER)

@@ -43,6 +43,8 @@ TimedPlanArgs = _abi.structs["rmpc_timed_plan"]       # one prioritised space-ti
 EXPORTED_SYMBOLS = list(_abi.prototypes)
 # and every symbol include/rmpc_grid_large.h declares
 GRID_LARGE_SYMBOLS = list(_abi.large_prototypes)
+# and every symbol include/rmpc_assign_opt.h declares
+ASSIGN_OPT_SYMBOLS = list(_abi.assign_prototypes)
 
 _lib = None
 
@@ -111,8 +113,9 @@ def load_library(path: str = LIB_PATH):
     except ImportError:
         pass
     L = C.CDLL(path)
-    # the declarations of include/rmpc.h and include/rmpc_grid_large.h, nothing else
-    for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items()):
+    # the declarations of include/rmpc.h, include/rmpc_grid_large.h and include/rmpc_assign_opt.h, nothing else
+    for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items(),
+                                      *_abi.assign_prototypes.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
@@ -531,6 +534,46 @@ def assign_greedy_device(cost, assign, passes=None, stream=None):
         raise ValueError(f"assign_greedy_device: need assign and passes ({B},)")
     _grid_call("rmpc_assign_greedy_device", B, T, _ptr(cost), _ptr(assign), None if passes is None else _ptr(passes),
                _stream_arg(stream))
+
+
+# the greatest integer cost of a takeable pair (include/rmpc_assign_opt.h)
+ASSIGN_OPT_MAX_Q = _abi.assign_constants["RMPC_ASSIGN_OPT_MAX_Q"]
+
+
+def assign_optimal_work_bytes(G: int, B: int, T: int) -> int:
+    """The bytes of workspace ``assign_optimal_device`` needs for G problems of B x T
+    (``rmpc_assign_optimal_work_bytes``; host only)."""
+    L = load_library()
+    n = L.rmpc_assign_optimal_work_bytes(int(G), int(B), int(T))
+    if n < 0:
+        raise RmpcError("rmpc_assign_optimal_work_bytes failed: " + L.rmpc_last_error().decode())
+    return int(n)
+
+
+def assign_optimal_device(cost, assign, scale: float = 1024.0, total=None, count=None, steps=None, work=None, stream=None):
+    """cost (B, T) or (G, B, T) fp64 -> assign (B,) or (G, B) int32, the target of every robot or -1: per problem the
+    matching with the most takeable pairs and among those the least sum of q = rint(cost scale), by shortest augmenting
+    paths on integers (``rmpc_assign_optimal_device``).  total (G,) int64, count (G,) int32, steps (G,) int32 or None:
+    the sum of q, the number of pairs, the steps of the search.  work: a contiguous device tensor of at least
+    ``assign_optimal_work_bytes(G, B, T)`` bytes, allocated here when None."""
+    import torch
+    if cost.dim() not in (2, 3) or cost.dtype != torch.float64 or not cost.is_contiguous():
+        raise ValueError("assign_optimal_device: need cost (B, T) or (G, B, T), contiguous fp64")
+    G = 1 if cost.dim() == 2 else int(cost.shape[0])
+    B, T = int(cost.shape[-2]), int(cost.shape[-1])
+    if tuple(assign.shape) != tuple(cost.shape[:-1]) or assign.dtype != torch.int32 or not assign.is_contiguous():
+        raise ValueError(f"assign_optimal_device: need assign {tuple(cost.shape[:-1])} contiguous int32")
+    for name, t, dt in (("total", total, torch.int64), ("count", count, torch.int32), ("steps", steps, torch.int32)):
+        if t is not None and (t.numel() != G or t.dtype != dt or not t.is_contiguous()):
+            raise ValueError(f"assign_optimal_device: need {name} ({G},) contiguous {dt}")
+    need = assign_optimal_work_bytes(G, B, T)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=cost.device)
+    if not work.is_contiguous():
+        raise ValueError("assign_optimal_device: need a contiguous workspace")
+    opt = lambda t: None if t is None else _ptr(t)
+    _grid_call("rmpc_assign_optimal_device", G, B, T, _ptr(cost), float(scale), _ptr(assign), opt(total), opt(count),
+               opt(steps), _ptr(work), int(work.numel() * work.element_size()), _stream_arg(stream))
 
 
 def grid_edge_distance_device(grid, d2, occ_threshold: float, sub: int, cap: int, stream=None):

@@ -1,7 +1,8 @@
 // rmpc_world.hip -- the world around the solver, on the device: the moving obstacles between two control steps, the
 // free-space decomposition, the global planner (rmpc_grid.hpp), the lidar and the fleet's separating planes
 // (rmpc_sense.hpp), the map built from the scans (rmpc_map.hpp), the assignment of robots to frontier targets
-// (rmpc_assign.hpp), localisation by scan matching (rmpc_locate.hpp), the fleet's timed routes (rmpc_timed.hpp), with
+// (rmpc_assign.hpp), the minimum-cost assignment of robots to goals (rmpc_assign_opt.hpp, include/rmpc_assign_opt.h),
+// localisation by scan matching (rmpc_locate.hpp), the fleet's timed routes (rmpc_timed.hpp), with
 // their entries of the C ABI.  None of them
 // takes a handle: each call runs on the device its first pointer lives on, on the stream it is given.  A translation
 // unit of its own, which needs rmpc.h, the HIP runtime and the error channel only -- nothing of the solver.
@@ -13,6 +14,7 @@
 
 #include "../../include/rmpc.h"
 #include "../../include/rmpc_grid_large.h"
+#include "../../include/rmpc_assign_opt.h"
 #include "rmpc_err.hpp"
 
 namespace rmpc {
@@ -94,6 +96,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_sense.hpp"
 #include "rmpc_map.hpp"
 #include "rmpc_assign.hpp"
+#include "rmpc_assign_opt.hpp"
 #include "rmpc_locate.hpp"
 #include "rmpc_search.hpp"
 #include "rmpc_timed.hpp"
@@ -481,6 +484,44 @@ int rmpc_assign_greedy_device(int B, int T, const double *d_cost, int32_t *d_ass
   if (assign_sizes_check("assign greedy", B, T) || use_device_of(d_cost)) return -1;
   hipLaunchKernelGGL(k_assign_greedy, dim3(1), dim3(kAssignThreads), 0, (hipStream_t)stream, B, T, d_cost,
                      (int *)d_assign, (int *)d_pass);
+  return launch_status();
+}
+
+/* minimum-cost assignment (rmpc_assign_opt.hpp, include/rmpc_assign_opt.h) */
+static int assign_opt_sizes_check(const std::string &who, int G, int B, int T) {
+  if (assign_sizes_check(who, B, T)) return -1;
+  return G < 1 || !grid_fits(G, (long long)B * T) ? fail(who + ": need 1 <= G and G*B*T <= INT_MAX") : 0;
+}
+
+int64_t rmpc_assign_optimal_work_bytes(int G, int B, int T) {
+  if (assign_opt_sizes_check("assign optimal work bytes", G, B, T)) return -1;
+  return (int64_t)assign_opt_matrix_offset(G) + (int64_t)G * B * T * (int64_t)sizeof(int32_t);
+}
+
+int rmpc_assign_optimal_device(int G, int B, int T, const double *d_cost, double scale, int32_t *d_assign,
+                               int64_t *d_total, int32_t *d_count, int32_t *d_steps, void *d_work,
+                               int64_t work_bytes, void *stream) {
+  const std::string who = "assign optimal";
+  if (!d_cost || !d_assign || !d_work) return fail("null argument");
+  if (assign_opt_sizes_check(who, G, B, T)) return -1;
+  if (!(scale > 0.0) || std::isinf(scale)) return fail(who + ": scale must be finite and > 0");
+  const int64_t need = rmpc_assign_optimal_work_bytes(G, B, T);
+  if (work_bytes < need)
+    return fail(who + ": the workspace holds " + std::to_string(work_bytes) + " bytes, " + std::to_string(need) +
+                " are needed (rmpc_assign_optimal_work_bytes)");
+  if (use_device_of(d_cost)) return -1;
+  int *const qmax = (int *)d_work, *const Q = (int *)((char *)d_work + assign_opt_matrix_offset(G));
+  const long long total = (long long)G * B * T;
+  const int n = B <= T ? T : B;
+  HIPCHK(hipMemsetAsync(qmax, 0, (size_t)G * sizeof(int), (hipStream_t)stream));
+  hipLaunchKernelGGL(k_assign_quantise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, T,
+                     total, d_cost, scale, qmax, Q);
+  // a thread per column up to 1024 columns, whole wavefronts; beyond that 2 or 4 columns per thread
+  const int threads = n > 1024 ? 1024 : (n + 63) / 64 * 64;
+  auto solve = n <= 64 ? k_assign_optimal<64, 1> : n <= 1024 ? k_assign_optimal<1024, 1>
+               : n <= 2048 ? k_assign_optimal<1024, 2> : k_assign_optimal<1024, 4>;
+  hipLaunchKernelGGL(solve, dim3(G), dim3(threads), 0, (hipStream_t)stream, B, T, (const int *)qmax, (const int *)Q,
+                     (int *)d_assign, (long long *)d_total, (int *)d_count, (int *)d_steps);
   return launch_status();
 }
 

@@ -3,7 +3,8 @@
 Mirrors ``robotmpcs.global_planner`` (``gridmap.OccupancyGridMap``, ``a_star.a_star``, ``globalPlanner.GlobalPlanner``:
 same module, class and method names, so that a port of ``examples/boxer_example_global.py`` changes only its imports)
 and adds the batched, device-resident fleet API (``plan_batch``, ``RouteFollower``, ``replan``, ``shelf_map``) and the
-fleet's conflict-free timed routes (``TimedRoutes``, ``TimedFollower``).  The work is done
+fleet's conflict-free timed routes (``TimedRoutes``, ``TimedFollower``) and the pairing of robots with goals at the least
+sum of route costs (``GoalAssigner``).  The work is done
 by the ``rmpc_grid_*_device`` / ``rmpc_follow_path_device`` / ``rmpc_timed_*_device`` kernels (include/rmpc.h); there is no CPU path.  Importing
 the package needs no GPU.
 """
@@ -11,7 +12,8 @@ from .gridmap import OccupancyGridMap
 from .a_star import a_star
 from .globalPlanner import FREE, OCC, GlobalPlanner, png_values
 from .batch import RouteFollower, cell_xy, cells_from_positions, pick_routes, plan_batch, replan, shelf_map, store_routes
+from .dispatch import GoalAssigner
 from .timed import TimedFollower, TimedRoutes, pick_spaced_routes, priority_orders
 
-__all__ = ["FREE", "OCC", "OccupancyGridMap", "a_star", "GlobalPlanner", "RouteFollower", "TimedFollower", "TimedRoutes", "cell_xy", "cells_from_positions",
+__all__ = ["FREE", "OCC", "OccupancyGridMap", "a_star", "GlobalPlanner", "GoalAssigner", "RouteFollower", "TimedFollower", "TimedRoutes", "cell_xy", "cells_from_positions",
            "pick_routes", "pick_spaced_routes", "plan_batch", "png_values", "priority_orders", "replan", "shelf_map", "store_routes"]
