@@ -16,7 +16,7 @@ raises ``RmpcError`` with the text that was not understood; nothing is skipped.
 
 The headers beside it are read the same way into tables of their own: ``include/rmpc_grid_large.h`` into
 ``large_constants`` / ``large_prototypes``, ``include/rmpc_assign_opt.h`` into ``assign_constants`` /
-``assign_prototypes``.
+``assign_prototypes``, ``include/rmpc_tours.h`` into ``tours_constants`` / ``tours_prototypes``.
 """
 import ctypes as C
 import os
@@ -27,6 +27,8 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 LARGE_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_grid_large.h")
 # the minimum-cost assignment: likewise
 ASSIGN_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_assign_opt.h")
+# the tours and the follower that stops: likewise
+TOURS_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_tours.h")
 
 _SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "int": C.c_int, "long long": C.c_longlong}
 _DECLARATION = re.compile(r"(?:const\s+)?(long long|\w+)(\s+|\s*(?:\*\s*)+)(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)")
@@ -135,3 +137,4 @@ def _read(path):
 constants, structs, prototypes = _read(HEADER)
 large_constants, _, large_prototypes = _read(LARGE_HEADER)
 assign_constants, _, assign_prototypes = _read(ASSIGN_HEADER)
+tours_constants, _, tours_prototypes = _read(TOURS_HEADER)

@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = list(_abi.prototypes)
 GRID_LARGE_SYMBOLS = list(_abi.large_prototypes)
 # and every symbol include/rmpc_assign_opt.h declares
 ASSIGN_OPT_SYMBOLS = list(_abi.assign_prototypes)
+# and every symbol include/rmpc_tours.h declares
+TOURS_SYMBOLS = list(_abi.tours_prototypes)
 
 _lib = None
 
@@ -113,9 +115,10 @@ def load_library(path: str = LIB_PATH):
     except ImportError:
         pass
     L = C.CDLL(path)
-    # the declarations of include/rmpc.h, include/rmpc_grid_large.h and include/rmpc_assign_opt.h, nothing else
+    # the declarations of include/rmpc.h, include/rmpc_grid_large.h, include/rmpc_assign_opt.h and
+    # include/rmpc_tours.h, nothing else
     for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items(),
-                                      *_abi.assign_prototypes.items()):
+                                      *_abi.assign_prototypes.items(), *_abi.tours_prototypes.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
@@ -574,6 +577,68 @@ def assign_optimal_device(cost, assign, scale: float = 1024.0, total=None, count
     opt = lambda t: None if t is None else _ptr(t)
     _grid_call("rmpc_assign_optimal_device", G, B, T, _ptr(cost), float(scale), _ptr(assign), opt(total), opt(count),
                opt(steps), _ptr(work), int(work.numel() * work.element_size()), _stream_arg(stream))
+
+
+# limits of the tours (include/rmpc_tours.h)
+TOURS_MAX_ROBOTS, TOURS_MAX_TASKS = (_abi.tours_constants["RMPC_TOURS_MAX_" + n] for n in ("ROBOTS", "TASKS"))
+TOURS_MODES = {"sum": 0, "span": 1, 0: 0, 1: 1}
+
+
+def tours_work_bytes(G: int, B: int, T: int) -> int:
+    """The bytes of workspace ``tours_device`` needs for G problems of B robots and T tasks (``rmpc_tours_work_bytes``;
+    host only)."""
+    L = load_library()
+    n = L.rmpc_tours_work_bytes(int(G), int(B), int(T))
+    if n < 0:
+        raise RmpcError("rmpc_tours_work_bytes failed: " + L.rmpc_last_error().decode())
+    return int(n)
+
+
+def tours_device(start_cost, task_cost, tours, lens, cost, mode="span", scale: float = 1024.0, max_rounds: int = 1 << 30,
+                 owner=None, count=None, total=None, span=None, build_steps=None, rounds=None, work=None, stream=None):
+    """start_cost (B, T) or (G, B, T), task_cost (T, T) or (G, T, T) fp64 -> tours (.., B, K) int32 (every robot's tasks
+    in order, padded with -1), lens (.., B) int32, cost (.., B) int64: cheapest insertion, then the best relocation or
+    exchange per round, at most ``max_rounds`` of them, on q = rint(cost scale) (``rmpc_tours_device``,
+    include/rmpc_tours.h).  mode "sum" (0) or "span" (1).  owner (.., T) int32, count (G,) int32, total, span (G,) int64,
+    build_steps, rounds (G,) int32, or None.  work: a contiguous device tensor of at least ``tours_work_bytes(G, B, T)``
+    bytes, allocated here when None."""
+    import torch
+    if start_cost.dim() not in (2, 3) or task_cost.dim() != start_cost.dim() or tours.dim() != start_cost.dim():
+        raise ValueError("tours_device: need start_cost (B, T) or (G, B, T), task_cost and tours of as many dimensions")
+    G = 1 if start_cost.dim() == 2 else int(start_cost.shape[0])
+    lead = tuple(start_cost.shape[:-2])
+    B, T, K = int(start_cost.shape[-2]), int(start_cost.shape[-1]), int(tours.shape[-1])
+    if mode not in TOURS_MODES:
+        raise ValueError("tours_device: mode must be 'sum' or 'span'")
+    for name, t, shape, dt in (("start_cost", start_cost, lead + (B, T), torch.float64),
+                               ("task_cost", task_cost, lead + (T, T), torch.float64),
+                               ("tours", tours, lead + (B, K), torch.int32), ("lens", lens, lead + (B,), torch.int32),
+                               ("cost", cost, lead + (B,), torch.int64), ("owner", owner, lead + (T,), torch.int32)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
+            raise ValueError(f"tours_device: need {name} {shape} contiguous {dt}")
+    for name, t, dt in (("count", count, torch.int32), ("total", total, torch.int64), ("span", span, torch.int64),
+                        ("build_steps", build_steps, torch.int32), ("rounds", rounds, torch.int32)):
+        if t is not None and (t.numel() != G or t.dtype != dt or not t.is_contiguous()):
+            raise ValueError(f"tours_device: need {name} ({G},) contiguous {dt}")
+    need = tours_work_bytes(G, B, T)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=start_cost.device)
+    if not work.is_contiguous():
+        raise ValueError("tours_device: need a contiguous workspace")
+    opt = lambda t: None if t is None else _ptr(t)
+    _grid_call("rmpc_tours_device", G, B, T, K, _ptr(start_cost), _ptr(task_cost), TOURS_MODES[mode], float(scale),
+               int(max_rounds), _ptr(tours), _ptr(lens), _ptr(cost), opt(owner), opt(count), opt(total), opt(span),
+               opt(build_steps), opt(rounds), _ptr(work), int(work.numel() * work.element_size()), _stream_arg(stream))
+
+
+def follow_tour_device(path, length, idx, pos, goal, W: int, x0: float, y0: float, cell: float, threshold: float,
+                       stop_at, leg, served, now: int, stop_tol: float, stream=None):
+    """``follow_path_device`` with stops: stop_at (B, K) int32 ascending path indices (-1 unused), leg (B,) int32 the
+    stops served (in and out), served (B, K) int32 takes ``now`` where a stop is served (``rmpc_follow_tour_device``)."""
+    _grid_call("rmpc_follow_tour_device", int(path.shape[0]), _ptr(path), _ptr(length), int(path.shape[1]), _ptr(idx),
+               _ptr(pos), int(pos.stride(0)), int(W), float(x0), float(y0), float(cell), float(threshold), _ptr(goal),
+               int(stop_at.shape[1]), _ptr(stop_at), _ptr(leg), _ptr(served), int(now), float(stop_tol),
+               _stream_arg(stream))
 
 
 def grid_edge_distance_device(grid, d2, occ_threshold: float, sub: int, cap: int, stream=None):

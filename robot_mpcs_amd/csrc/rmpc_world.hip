@@ -2,6 +2,7 @@
 // free-space decomposition, the global planner (rmpc_grid.hpp), the lidar and the fleet's separating planes
 // (rmpc_sense.hpp), the map built from the scans (rmpc_map.hpp), the assignment of robots to frontier targets
 // (rmpc_assign.hpp), the minimum-cost assignment of robots to goals (rmpc_assign_opt.hpp, include/rmpc_assign_opt.h),
+// tours of several tasks per robot and the follower that stops at them (rmpc_tours.hpp, include/rmpc_tours.h),
 // localisation by scan matching (rmpc_locate.hpp), the fleet's timed routes (rmpc_timed.hpp), with
 // their entries of the C ABI.  None of them
 // takes a handle: each call runs on the device its first pointer lives on, on the stream it is given.  A translation
@@ -15,6 +16,7 @@
 #include "../../include/rmpc.h"
 #include "../../include/rmpc_grid_large.h"
 #include "../../include/rmpc_assign_opt.h"
+#include "../../include/rmpc_tours.h"
 #include "rmpc_err.hpp"
 
 namespace rmpc {
@@ -97,6 +99,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_map.hpp"
 #include "rmpc_assign.hpp"
 #include "rmpc_assign_opt.hpp"
+#include "rmpc_tours.hpp"
 #include "rmpc_locate.hpp"
 #include "rmpc_search.hpp"
 #include "rmpc_timed.hpp"
@@ -522,6 +525,66 @@ int rmpc_assign_optimal_device(int G, int B, int T, const double *d_cost, double
                : n <= 2048 ? k_assign_optimal<1024, 2> : k_assign_optimal<1024, 4>;
   hipLaunchKernelGGL(solve, dim3(G), dim3(threads), 0, (hipStream_t)stream, B, T, (const int *)qmax, (const int *)Q,
                      (int *)d_assign, (long long *)d_total, (int *)d_count, (int *)d_steps);
+  return launch_status();
+}
+
+/* tours of several tasks per robot (rmpc_tours.hpp, include/rmpc_tours.h) */
+static int tours_sizes_check(const std::string &who, int G, int B, int T) {
+  if (B < 1 || B > RMPC_TOURS_MAX_ROBOTS || T < 1 || T > RMPC_TOURS_MAX_TASKS)
+    return fail(who + ": need 1 <= B <= RMPC_TOURS_MAX_ROBOTS = " + std::to_string(RMPC_TOURS_MAX_ROBOTS) +
+                " and 1 <= T <= RMPC_TOURS_MAX_TASKS = " + std::to_string(RMPC_TOURS_MAX_TASKS));
+  return G < 1 || !grid_fits(G, (long long)T * T) || !grid_fits(G, (long long)B * T)
+             ? fail(who + ": need 1 <= G, G*T*T <= INT_MAX and G*B*T <= INT_MAX") : 0;
+}
+
+int64_t rmpc_tours_work_bytes(int G, int B, int T) {
+  if (tours_sizes_check("tours work bytes", G, B, T)) return -1;
+  return (int64_t)tours_work_ints(G, B, T) * (int64_t)sizeof(int32_t);
+}
+
+int rmpc_tours_device(int G, int B, int T, int K, const double *d_start_cost, const double *d_task_cost, int mode,
+                      double scale, int max_rounds, int32_t *d_tours, int32_t *d_len, int64_t *d_cost, int32_t *d_owner,
+                      int32_t *d_count, int64_t *d_total, int64_t *d_span, int32_t *d_build_steps, int32_t *d_rounds,
+                      void *d_work, int64_t work_bytes, void *stream) {
+  const std::string who = "tours";
+  if (!d_start_cost || !d_task_cost || !d_tours || !d_len || !d_cost || !d_work) return fail("null argument");
+  if (tours_sizes_check(who, G, B, T)) return -1;
+  if (K < 1 || K > T) return fail(who + ": need 1 <= K <= T");
+  if (mode != 0 && mode != 1) return fail(who + ": mode must be 0 (least sum) or 1 (least makespan)");
+  if (!(scale > 0.0) || std::isinf(scale)) return fail(who + ": scale must be finite and > 0");
+  if (max_rounds < 0) return fail(who + ": max_rounds must be >= 0");
+  const int64_t need = rmpc_tours_work_bytes(G, B, T);
+  if (work_bytes < need)
+    return fail(who + ": the workspace holds " + std::to_string(work_bytes) + " bytes, " + std::to_string(need) +
+                " are needed (rmpc_tours_work_bytes)");
+  if (use_device_of(d_start_cost)) return -1;
+  const long long nstart = (long long)G * B * T, ntask = (long long)G * T * T, total = nstart + ntask;
+  int *const qs = (int *)d_work, *const qt = qs + nstart, *const qtT = qt + ntask, *const ins = qtT + ntask,
+            *const pos = ins + nstart;
+  hipLaunchKernelGGL(k_tours_quantise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, T, nstart,
+                     total, d_start_cost, d_task_cost, scale, qs, qt, qtT, ins, pos);
+  // a thread per task, whole wavefronts; up to 64 tasks the workgroup is one wave
+  auto solve = T <= 64 ? k_tours<64> : k_tours<1024>;
+  hipLaunchKernelGGL(solve, dim3(G), dim3((T + 63) / 64 * 64), 0, (hipStream_t)stream, B, T, K, mode, max_rounds,
+                     (const int *)qs, (const int *)qt, (const int *)qtT, ins, pos, (int *)d_tours, (int *)d_len, (long long *)d_cost,
+                     (int *)d_owner, (int *)d_count, (long long *)d_total, (long long *)d_span, (int *)d_build_steps,
+                     (int *)d_rounds);
+  return launch_status();
+}
+
+int rmpc_follow_tour_device(int B, const int32_t *d_path, const int32_t *d_len, int max_len, int32_t *d_idx,
+                            const double *d_pos, int stride, int W, double x0, double y0, double cell, double threshold,
+                            double *d_goal, int K, const int32_t *d_stop_at, int32_t *d_leg, int32_t *d_served, int now,
+                            double stop_tol, void *stream) {
+  if (!d_path || !d_len || !d_idx || !d_pos || !d_goal || !d_stop_at || !d_leg || !d_served) return fail("null argument");
+  if (grid_paths_check("follow tour", B, max_len)) return -1;
+  if (K < 1 || !grid_fits(B, K)) return fail("follow tour: need K >= 1 and B*K <= INT_MAX");
+  if (stride < 2 || !grid_fits(B, stride) || W < 1) return fail("follow tour: need stride >= 2, W >= 1");
+  if (!(stop_tol >= 0.0)) return fail("follow tour: stop_tol must be >= 0");
+  if (use_device_of(d_path)) return -1;
+  hipLaunchKernelGGL(k_follow_tour, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int *)d_path,
+                     (const int *)d_len, max_len, (int *)d_idx, d_pos, stride, B, W, x0, y0, cell, threshold, d_goal, K,
+                     (const int *)d_stop_at, (int *)d_leg, (int *)d_served, now, stop_tol);
   return launch_status();
 }
 

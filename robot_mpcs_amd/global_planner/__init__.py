@@ -4,7 +4,8 @@ Mirrors ``robotmpcs.global_planner`` (``gridmap.OccupancyGridMap``, ``a_star.a_s
 same module, class and method names, so that a port of ``examples/boxer_example_global.py`` changes only its imports)
 and adds the batched, device-resident fleet API (``plan_batch``, ``RouteFollower``, ``replan``, ``shelf_map``) and the
 fleet's conflict-free timed routes (``TimedRoutes``, ``TimedFollower``) and the pairing of robots with goals at the least
-sum of route costs (``GoalAssigner``).  The work is done
+sum of route costs (``GoalAssigner``) and tours of several goals per robot with a follower that stops at them
+(``TourPlanner``, ``TourFollower``; ``rmpc_tours_device`` / ``rmpc_follow_tour_device``, include/rmpc_tours.h).  The work is done
 by the ``rmpc_grid_*_device`` / ``rmpc_follow_path_device`` / ``rmpc_timed_*_device`` kernels (include/rmpc.h); there is no CPU path.  Importing
 the package needs no GPU.
 """
@@ -14,6 +15,7 @@ from .globalPlanner import FREE, OCC, GlobalPlanner, png_values
 from .batch import RouteFollower, cell_xy, cells_from_positions, pick_routes, plan_batch, replan, shelf_map, store_routes
 from .dispatch import GoalAssigner
 from .timed import TimedFollower, TimedRoutes, pick_spaced_routes, priority_orders
+from .tours import TourFollower, TourPlanner
 
-__all__ = ["FREE", "OCC", "OccupancyGridMap", "a_star", "GlobalPlanner", "GoalAssigner", "RouteFollower", "TimedFollower", "TimedRoutes", "cell_xy", "cells_from_positions",
+__all__ = ["FREE", "OCC", "OccupancyGridMap", "a_star", "GlobalPlanner", "GoalAssigner", "RouteFollower", "TimedFollower", "TimedRoutes", "TourFollower", "TourPlanner", "cell_xy", "cells_from_positions",
            "pick_routes", "pick_spaced_routes", "plan_batch", "png_values", "priority_orders", "replan", "shelf_map", "store_routes"]
