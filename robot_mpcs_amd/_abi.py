@@ -16,7 +16,8 @@ raises ``RmpcError`` with the text that was not understood; nothing is skipped.
 
 The headers beside it are read the same way into tables of their own: ``include/rmpc_grid_large.h`` into
 ``large_constants`` / ``large_prototypes``, ``include/rmpc_assign_opt.h`` into ``assign_constants`` /
-``assign_prototypes``, ``include/rmpc_tours.h`` into ``tours_constants`` / ``tours_prototypes``.
+``assign_prototypes``, ``include/rmpc_tours.h`` into ``tours_constants`` / ``tours_prototypes``,
+``include/rmpc_timed_tours.h`` into ``timed_tours_constants`` / ``timed_tours_structs`` / ``timed_tours_prototypes``.
 """
 import ctypes as C
 import os
@@ -29,6 +30,8 @@ LARGE_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_grid_large.h")
 ASSIGN_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_assign_opt.h")
 # the tours and the follower that stops: likewise
 TOURS_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_tours.h")
+# the timed tours: likewise, with a struct of its own
+TIMED_TOURS_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_timed_tours.h")
 
 _SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "int": C.c_int, "long long": C.c_longlong}
 _DECLARATION = re.compile(r"(?:const\s+)?(long long|\w+)(\s+|\s*(?:\*\s*)+)(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)")
@@ -138,3 +141,4 @@ constants, structs, prototypes = _read(HEADER)
 large_constants, _, large_prototypes = _read(LARGE_HEADER)
 assign_constants, _, assign_prototypes = _read(ASSIGN_HEADER)
 tours_constants, _, tours_prototypes = _read(TOURS_HEADER)
+timed_tours_constants, timed_tours_structs, timed_tours_prototypes = _read(TIMED_TOURS_HEADER)

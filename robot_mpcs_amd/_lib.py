@@ -38,6 +38,7 @@ ScanMatchArgs = _abi.structs["rmpc_scan_match"]       # one scan of B robots mat
 ScanSearchArgs = _abi.structs["rmpc_scan_search"]     # rmpc_scan_match's fields, then the pyramid, workspace and outputs
 TracksArgs = _abi.structs["rmpc_tracks"]              # one scan of B robots through the moving-obstacle tracker
 TimedPlanArgs = _abi.structs["rmpc_timed_plan"]       # one prioritised space-time plan of B robots for G orders
+TimedToursArgs = _abi.timed_tours_structs["rmpc_timed_tours"]     # the same through every robot's stops (rmpc_timed_tours.h)
 
 # every symbol include/rmpc.h declares
 EXPORTED_SYMBOLS = list(_abi.prototypes)
@@ -47,6 +48,8 @@ GRID_LARGE_SYMBOLS = list(_abi.large_prototypes)
 ASSIGN_OPT_SYMBOLS = list(_abi.assign_prototypes)
 # and every symbol include/rmpc_tours.h declares
 TOURS_SYMBOLS = list(_abi.tours_prototypes)
+# and every symbol include/rmpc_timed_tours.h declares
+TIMED_TOURS_SYMBOLS = list(_abi.timed_tours_prototypes)
 
 _lib = None
 
@@ -115,10 +118,11 @@ def load_library(path: str = LIB_PATH):
     except ImportError:
         pass
     L = C.CDLL(path)
-    # the declarations of include/rmpc.h, include/rmpc_grid_large.h, include/rmpc_assign_opt.h and
-    # include/rmpc_tours.h, nothing else
+    # the declarations of include/rmpc.h, include/rmpc_grid_large.h, include/rmpc_assign_opt.h, include/rmpc_tours.h
+    # and include/rmpc_timed_tours.h, nothing else
     for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items(),
-                                      *_abi.assign_prototypes.items(), *_abi.tours_prototypes.items()):
+                                      *_abi.assign_prototypes.items(), *_abi.tours_prototypes.items(),
+                                      *_abi.timed_tours_prototypes.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
@@ -819,6 +823,61 @@ def timed_follow_device(paths, idx_in, idx_out, pos, goal, W: int, x0: float, y0
     _grid_call("rmpc_timed_follow_device", int(paths.shape[0]), int(paths.shape[1]) - 1, _ptr(paths), _ptr(idx_in),
                _ptr(idx_out), _ptr(pos), int(pos.stride(0)), int(W), float(x0), float(y0), float(cell), float(threshold),
                int(sep2), int(lag), _ptr(goal), None if blocked is None else _ptr(blocked), _stream_arg(stream))
+
+
+# limits of the timed tours (include/rmpc_timed_tours.h)
+TIMED_TOURS_MAX_STOPS, TIMED_TOURS_MAX_DWELL = (_abi.timed_tours_constants["RMPC_TIMED_TOURS_MAX_" + n]
+                                                for n in ("STOPS", "DWELL"))
+
+
+def timed_tours_work_bytes(H: int, W: int, T: int, G: int) -> int:
+    """bytes of workspace of ``timed_tours_plan_device`` (``rmpc_timed_tours_work_bytes``)"""
+    L = load_library()
+    n = L.rmpc_timed_tours_work_bytes(int(H), int(W), int(T), int(G))
+    if n < 0:
+        raise RmpcError("rmpc_timed_tours_work_bytes failed: " + L.rmpc_last_error().decode())
+    return int(n)
+
+
+def timed_tours_args(grid, start_cell, stops, lens, park_index, fields, goal_cells, orders, work, paths, status, arrive, key,
+                     best, serve_at, served, unserved, dwell: int = 0, movement: int = 4, occ_threshold: float = 0.8,
+                     sep2: int = 9, lag: int = 1) -> TimedToursArgs:
+    """The ``rmpc_timed_tours`` of one plan: ``timed_plan_args`` with stops (B, K), lens, park_index (B,) int32 in place
+    of goal_index, and the outputs serve_at (G, B, K), served (G, B), unserved (G,) int32 -- contiguous device tensors."""
+    a = TimedToursArgs()
+    a.struct_size = C.sizeof(TimedToursArgs)
+    a.H, a.W, a.movement = int(grid.shape[0]), int(grid.shape[1]), int(movement)
+    a.grid, a.occ_threshold = grid.data_ptr(), float(occ_threshold)
+    a.B, a.Gf = int(start_cell.shape[0]), int(fields.shape[0])
+    a.start_cell, a.K, a.dwell = start_cell.data_ptr(), int(stops.shape[1]), int(dwell)
+    a.stops, a.len, a.park_index = stops.data_ptr(), lens.data_ptr(), park_index.data_ptr()
+    a.fields, a.goal_cells = fields.data_ptr(), goal_cells.data_ptr()
+    a.T, a.sep2, a.lag, a.G = int(paths.shape[2]) - 1, int(sep2), int(lag), int(orders.shape[0])
+    a.orders = orders.data_ptr()
+    a.work, a.work_bytes = work.data_ptr(), int(work.numel() * work.element_size())
+    a.paths, a.status, a.arrive, a.key, a.best = (paths.data_ptr(), status.data_ptr(), arrive.data_ptr(), key.data_ptr(),
+                                                  best.data_ptr())
+    a.serve_at, a.served, a.unserved = serve_at.data_ptr(), served.data_ptr(), unserved.data_ptr()
+    a._keep = (grid, start_cell, stops, lens, park_index, fields, goal_cells, orders, work, paths, status, arrive, key, best,
+               serve_at, served, unserved)
+    return a
+
+
+def timed_tours_plan_device(args: TimedToursArgs, stream=None):
+    """One prioritised space-time plan through every robot's stops per order (``rmpc_timed_tours_plan_device``)."""
+    _grid_call("rmpc_timed_tours_plan_device", C.byref(args), _stream_arg(stream))
+
+
+def timed_tours_follow_device(paths, idx_in, idx_out, pos, goal, W: int, x0: float, y0: float, cell: float, threshold: float,
+                              sep2: int, lag: int, serve_at, leg, served, now: int, stop_tol: float, blocked=None,
+                              stream=None):
+    """``timed_follow_device`` with stops: serve_at (B, K) int32 (one order's), leg (B,) int32 in and out, served (B, K)
+    int32; one simultaneous step of the follower that serves a stop only within ``stop_tol`` of it
+    (``rmpc_timed_tours_follow_device``)."""
+    _grid_call("rmpc_timed_tours_follow_device", int(paths.shape[0]), int(paths.shape[1]) - 1, _ptr(paths), _ptr(idx_in),
+               _ptr(idx_out), _ptr(pos), int(pos.stride(0)), int(W), float(x0), float(y0), float(cell), float(threshold),
+               int(sep2), int(lag), _ptr(goal), None if blocked is None else _ptr(blocked), int(serve_at.shape[1]),
+               _ptr(serve_at), _ptr(leg), _ptr(served), int(now), float(stop_tol), _stream_arg(stream))
 
 
 class Solver:

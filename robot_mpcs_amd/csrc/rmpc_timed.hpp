@@ -55,6 +55,122 @@ __device__ __forceinline__ void timed_disc_count(int *__restrict__ cnt, int H, i
   }
 }
 
+// The four parts of a robot's plan, shared by k_timed_plan and k_timed_tours_plan (rmpc_timed_tours.hpp).  Every one is
+// called by the whole workgroup under uniform control flow.
+
+// later[w] = the cells with cnt > 0: those that conflict with the start of a robot not yet planned
+__device__ __forceinline__ void timed_later_mask(const int *__restrict__ cnt, timed_word *__restrict__ later, int W, int Wd,
+                                                 int L, int tid, int nt) {
+  for (int w = tid; w < L; w += nt) {
+    const int r = w / Wd, c0 = (w - r * Wd) * 64;
+    timed_word word = 0;
+    for (int bb = 0; bb < 64 && c0 + bb < W; bb++)
+      if (cnt[r * W + c0 + bb] > 0) word |= 1ull << bb;
+    later[w] = word;
+  }
+}
+
+// layer t of the history = {cell (sr, sc)}: where a robot stands when a sweep begins
+__device__ __forceinline__ void timed_seed_layer(timed_word *__restrict__ layer, int Wd, int L, int sr, int sc, int tid, int nt) {
+  for (int w = tid; w < L; w += nt) layer[w] = w == sr * Wd + (sc >> 6) ? 1ull << (sc & 63) : 0ull;
+}
+
+// reach[t] (cur) from reach[t - 1] (prev) and res[t] (rs); true when this thread wrote a word that is not empty.  The
+// caller's __syncthreads_or is the layer's one barrier.
+__device__ __forceinline__ bool timed_sweep_layer(const timed_word *prev, timed_word *cur, const timed_word *rs,
+                                                  const timed_word *freeb, const timed_word *later, bool early, int H,
+                                                  int Wd, int L, int movement, int tid, int nt) {
+  bool any = false;
+  for (int w = tid; w < L; w += nt) {
+    const int r = Wd == 1 ? w : w / Wd, j = w - r * Wd;
+    const bool up = r > 0, dn = r < H - 1;
+    const timed_word P = prev[w];
+    const timed_word V = P | (up ? prev[w - Wd] : 0ull) | (dn ? prev[w + Wd] : 0ull);
+    timed_word S = P, Sl = 0, Sr = 0;         // what moves by one column: the row itself, with 8 moves its neighbours too
+    if (j > 0) Sl = prev[w - 1];
+    if (j < Wd - 1) Sr = prev[w + 1];
+    if (movement == 8) {
+      S = V;
+      if (j > 0) Sl |= (up ? prev[w - 1 - Wd] : 0ull) | (dn ? prev[w - 1 + Wd] : 0ull);
+      if (j < Wd - 1) Sr |= (up ? prev[w + 1 - Wd] : 0ull) | (dn ? prev[w + 1 + Wd] : 0ull);
+    }
+    timed_word n = V | (S << 1) | (Sl >> 63) | (S >> 1) | (Sr << 63);
+    n &= freeb[w] & ~__hip_atomic_load(rs + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (early) n &= ~later[w];
+    cur[w] = n;
+    any = any || n != 0ull;
+  }
+  return any;
+}
+
+// the end cell: the least (F(c), c) over the layer E; an F that is not below +inf ranks as +inf.  nt is a power of two;
+// ends behind a barrier, so every thread gets the cell (INT_MAX for an empty layer).
+__device__ __forceinline__ int timed_end_cell(const double *__restrict__ F, const timed_word *E, int W, int Wd, int L,
+                                              double *red_d, int *red_c, int tid, int nt) {
+  double bd = __builtin_inf();
+  int bc = INT_MAX;
+  for (int w = tid; w < L; w += nt) {
+    const int r = w / Wd, c0 = r * W + (w - r * Wd) * 64;
+    timed_word word = E[w];
+    while (word) {
+      const int c = c0 + __ffsll((long long)word) - 1;
+      word &= word - 1;
+      double d = F[c];
+      d = d < __builtin_inf() ? d : __builtin_inf();
+      if (d < bd || (d == bd && c < bc)) { bd = d; bc = c; }
+    }
+  }
+  red_d[tid] = bd; red_c[tid] = bc;
+  __syncthreads();
+  for (int h = nt >> 1; h > 0; h >>= 1) {
+    if (tid < h) {
+      const double d = red_d[tid + h];
+      const int c = red_c[tid + h];
+      if (d < red_d[tid] || (d == red_d[tid] && c < red_c[tid])) { red_d[tid] = d; red_c[tid] = c; }
+    }
+    __syncthreads();
+  }
+  return red_c[0];
+}
+
+// backwards from (te, c) down to layer t0 (one thread): path[t - 1] for t = te .. t0 + 1, wait first, else the first move
+// in move order whose origin was reachable
+__device__ __forceinline__ void timed_backtrack(const timed_word *hist, int L, int H, int W, int Wd, int movement,
+                                                int *__restrict__ path, int c, int te, int t0) {
+  for (int t = te; t > t0; t--) {
+    const timed_word *const prev = hist + (size_t)(t - 1) * L;
+    const int r = c / W, col = c - r * W;
+    if (!timed_bit(prev, Wd, r, col)) {
+      for (int m = 0; m < movement; m++) {
+        const int rr = r - grid_dr(m), cc = col - grid_dc(m);
+        if (rr >= 0 && rr < H && cc >= 0 && cc < W && timed_bit(prev, Wd, rr, cc)) { c = rr * W + cc; break; }
+      }
+    }
+    path[t - 1] = c;
+  }
+}
+
+// stamping: the cells that conflict with path[t] into res[s], |s - t| <= lag, one (t, disc row, s) per thread and pass
+__device__ __forceinline__ void timed_stamp(timed_word *res, const int *__restrict__ path, int H, int W, int Wd, int L, int T,
+                                            int lag, int rad, int sep2, int tid, int nt) {
+  const int side = 2 * rad + 1, nl = 2 * lag + 1;
+  const long long total = (long long)(T + 1) * side * nl;
+  for (long long i = tid; i < total; i += nt) {
+    const int t = (int)(i / (side * nl)), rem = (int)(i - (long long)t * side * nl);
+    const int dr = rem / nl - rad, sl = t - lag + (rem - (rem / nl) * nl);
+    if (sl < 0 || sl > T) continue;
+    const int c = path[t], r = c / W + dr, col = c % W;
+    if (r < 0 || r >= H) continue;
+    const int h = timed_half_width(dr, rad, sep2);
+    const int lo = col - h > 0 ? col - h : 0, hi = col + h < W - 1 ? col + h : W - 1;
+    for (int j = lo >> 6; j <= hi >> 6; j++) {
+      const int a = (lo > j * 64 ? lo : j * 64) - j * 64, e = (hi < j * 64 + 63 ? hi : j * 64 + 63) - j * 64;
+      const timed_word mask = (e == 63 ? ~0ull : (1ull << (e + 1)) - 1ull) & ~((1ull << a) - 1ull);
+      __hip_atomic_fetch_or(res + (size_t)sl * L + r * Wd + j, mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 // One workgroup per priority order, its robots in rank order.  res is written with atomic ORs (the discs of different
 // layers of a path overlap) and read with atomic loads, so that no reader is served a line from before the ORs.
 template <bool kLds>
@@ -125,90 +241,24 @@ __global__ __launch_bounds__(kTimedThreads) void k_timed_plan(rmpc_timed_plan p,
     const int sr = s / W, sc = s - sr * W;
     timed_disc_count(cnt, H, W, sr, sc, rad, sep2, -1, tid, nt);
     __syncthreads();
-    for (int w = tid; w < L; w += nt) {
-      const int r = w / Wd, c0 = (w - r * Wd) * 64;
-      timed_word word = 0;
-      for (int bb = 0; bb < 64 && c0 + bb < W; bb++)
-        if (cnt[r * W + c0 + bb] > 0) word |= 1ull << bb;
-      later[w] = word;
-      hist[w] = w == sr * Wd + (sc >> 6) ? 1ull << (sc & 63) : 0ull;
-    }
+    timed_later_mask(cnt, later, W, Wd, L, tid, nt);
+    timed_seed_layer(hist, Wd, L, sr, sc, tid, nt);
     __syncthreads();
 
     // the layers: reach[t] from reach[t - 1]; one barrier per layer, which also tells whether the layer is empty
     int f = 0;
     for (int t = 1; t <= T; t++) {
-      const timed_word *const prev = hist + (size_t)(t - 1) * L;
-      timed_word *const cur = hist + (size_t)t * L;
-      const timed_word *const rs = res + (size_t)t * L;
-      bool any = false;
-      for (int w = tid; w < L; w += nt) {
-        const int r = Wd == 1 ? w : w / Wd, j = w - r * Wd;
-        const bool up = r > 0, dn = r < H - 1;
-        const timed_word P = prev[w];
-        const timed_word V = P | (up ? prev[w - Wd] : 0ull) | (dn ? prev[w + Wd] : 0ull);
-        timed_word S = P, Sl = 0, Sr = 0;         // what moves by one column: the row itself, with 8 moves its neighbours too
-        if (j > 0) Sl = prev[w - 1];
-        if (j < Wd - 1) Sr = prev[w + 1];
-        if (p.movement == 8) {
-          S = V;
-          if (j > 0) Sl |= (up ? prev[w - 1 - Wd] : 0ull) | (dn ? prev[w - 1 + Wd] : 0ull);
-          if (j < Wd - 1) Sr |= (up ? prev[w + 1 - Wd] : 0ull) | (dn ? prev[w + 1 + Wd] : 0ull);
-        }
-        timed_word n = V | (S << 1) | (Sl >> 63) | (S >> 1) | (Sr << 63);
-        n &= freeb[w] & ~__hip_atomic_load(rs + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (t <= lag) n &= ~later[w];
-        cur[w] = n;
-        any = any || n != 0ull;
-      }
+      const bool any = timed_sweep_layer(hist + (size_t)(t - 1) * L, hist + (size_t)t * L, res + (size_t)t * L, freeb, later,
+                                         t <= lag, H, Wd, L, p.movement, tid, nt);
       if (!__syncthreads_or(any)) { f = t; break; }
     }
     const int te = f ? f - 1 : T;
 
-    // the end cell: the least (D_goal(c), c) over reach[te]; a D that is not below +inf ranks as +inf
-    {
-      const double *const F = p.fields + (size_t)gi * HW;
-      const timed_word *const E = hist + (size_t)te * L;
-      double bd = __builtin_inf();
-      int bc = INT_MAX;
-      for (int w = tid; w < L; w += nt) {
-        const int r = w / Wd, c0 = r * W + (w - r * Wd) * 64;
-        timed_word word = E[w];
-        while (word) {
-          const int c = c0 + __ffsll((long long)word) - 1;
-          word &= word - 1;
-          double d = F[c];
-          d = d < __builtin_inf() ? d : __builtin_inf();
-          if (d < bd || (d == bd && c < bc)) { bd = d; bc = c; }
-        }
-      }
-      red_d[tid] = bd; red_c[tid] = bc;
-      __syncthreads();
-      for (int h = nt >> 1; h > 0; h >>= 1) {      // (nt is a power of two)
-        if (tid < h) {
-          const double d = red_d[tid + h];
-          const int c = red_c[tid + h];
-          if (d < red_d[tid] || (d == red_d[tid] && c < red_c[tid])) { red_d[tid] = d; red_c[tid] = c; }
-        }
-        __syncthreads();
-      }
-    }
-    const int end = red_c[0];
+    // the end cell: the least (D_goal(c), c) over reach[te]
+    const int end = timed_end_cell(p.fields + (size_t)gi * HW, hist + (size_t)te * L, W, Wd, L, red_d, red_c, tid, nt);
     for (int t = te + tid; t <= T; t += nt) path[t] = end;
     if (tid == 0) {
-      // backwards from te: wait first, else the first move in move order whose origin was reachable
-      int c = end;
-      for (int t = te; t >= 1; t--) {
-        const timed_word *const prev = hist + (size_t)(t - 1) * L;
-        const int r = c / W, col = c - r * W;
-        if (!timed_bit(prev, Wd, r, col)) {
-          for (int m = 0; m < p.movement; m++) {
-            const int rr = r - grid_dr(m), cc = col - grid_dc(m);
-            if (rr >= 0 && rr < H && cc >= 0 && cc < W && timed_bit(prev, Wd, rr, cc)) { c = rr * W + cc; break; }
-          }
-        }
-        path[t - 1] = c;
-      }
+      timed_backtrack(hist, L, H, W, Wd, p.movement, path, end, te, 0);
       int a = T + 1;
       if (end == p.goal_cells[gi]) {
         a = te;
@@ -218,26 +268,7 @@ __global__ __launch_bounds__(kTimedThreads) void k_timed_plan(rmpc_timed_plan p,
       fails += f > 0; late += a > T; sum += a;
     }
     __syncthreads();
-
-    // stamping: the cells that conflict with p[t] into res[s], |s - t| <= lag, one (t, disc row, s) per thread and pass
-    {
-      const int side = 2 * rad + 1, nl = 2 * lag + 1;
-      const long long total = (long long)(T + 1) * side * nl;
-      for (long long i = tid; i < total; i += nt) {
-        const int t = (int)(i / (side * nl)), rem = (int)(i - (long long)t * side * nl);
-        const int dr = rem / nl - rad, sl = t - lag + (rem - (rem / nl) * nl);
-        if (sl < 0 || sl > T) continue;
-        const int c = path[t], r = c / W + dr, col = c % W;
-        if (r < 0 || r >= H) continue;
-        const int h = timed_half_width(dr, rad, sep2);
-        const int lo = col - h > 0 ? col - h : 0, hi = col + h < W - 1 ? col + h : W - 1;
-        for (int j = lo >> 6; j <= hi >> 6; j++) {
-          const int a = (lo > j * 64 ? lo : j * 64) - j * 64, e = (hi < j * 64 + 63 ? hi : j * 64 + 63) - j * 64;
-          const timed_word mask = (e == 63 ? ~0ull : (1ull << (e + 1)) - 1ull) & ~((1ull << a) - 1ull);
-          __hip_atomic_fetch_or(res + (size_t)sl * L + r * Wd + j, mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-    }
+    timed_stamp(res, path, H, W, Wd, L, T, lag, rad, sep2, tid, nt);
     __syncthreads();
   }
   if (tid == 0) p.key[g] = (int64_t)((fails << 44) | (late << 32) | sum);

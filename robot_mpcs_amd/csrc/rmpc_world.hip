@@ -3,7 +3,8 @@
 // (rmpc_sense.hpp), the map built from the scans (rmpc_map.hpp), the assignment of robots to frontier targets
 // (rmpc_assign.hpp), the minimum-cost assignment of robots to goals (rmpc_assign_opt.hpp, include/rmpc_assign_opt.h),
 // tours of several tasks per robot and the follower that stops at them (rmpc_tours.hpp, include/rmpc_tours.h),
-// localisation by scan matching (rmpc_locate.hpp), the fleet's timed routes (rmpc_timed.hpp), with
+// localisation by scan matching (rmpc_locate.hpp), the fleet's timed routes (rmpc_timed.hpp), timed tours through
+// every robot's stops (rmpc_timed_tours.hpp, include/rmpc_timed_tours.h), with
 // their entries of the C ABI.  None of them
 // takes a handle: each call runs on the device its first pointer lives on, on the stream it is given.  A translation
 // unit of its own, which needs rmpc.h, the HIP runtime and the error channel only -- nothing of the solver.
@@ -17,6 +18,7 @@
 #include "../../include/rmpc_grid_large.h"
 #include "../../include/rmpc_assign_opt.h"
 #include "../../include/rmpc_tours.h"
+#include "../../include/rmpc_timed_tours.h"
 #include "rmpc_err.hpp"
 
 namespace rmpc {
@@ -103,6 +105,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_locate.hpp"
 #include "rmpc_search.hpp"
 #include "rmpc_timed.hpp"
+#include "rmpc_timed_tours.hpp"
 #include "rmpc_track.hpp"
 
 using namespace rmpc;
@@ -812,6 +815,79 @@ int rmpc_timed_follow_device(int B, int T, const int32_t *d_paths, const int32_t
   hipLaunchKernelGGL(k_timed_follow, dim3(B), dim3(256), 0, (hipStream_t)stream, (const int *)d_paths, B, T,
                      (const int *)d_idx_in, (int *)d_idx_out, d_pos, stride, W, x0, y0, cell, threshold, sep2, lag, d_goal,
                      (int *)d_blocked);
+  return launch_status();
+}
+
+/* timed tours (rmpc_timed_tours.hpp, include/rmpc_timed_tours.h) */
+int64_t rmpc_timed_tours_work_bytes(int H, int W, int T, int G) {
+  if (grid_cells_check("timed tours", H, W, false)) return -1;
+  if (T < 1 || T > RMPC_TIMED_MAX_T || G < 1 || G > RMPC_TIMED_MAX_ORDERS)
+    return fail("timed tours: need 1 <= T <= RMPC_TIMED_MAX_T and 1 <= G <= RMPC_TIMED_MAX_ORDERS");
+  return (int64_t)G * timed_order_words(H, W, T) * (int64_t)sizeof(timed_word);
+}
+
+static int timed_tours_stops_check(const std::string &who, int K) {
+  if (K < 1 || K > RMPC_TIMED_TOURS_MAX_STOPS)
+    return fail(who + ": need 1 <= K <= RMPC_TIMED_TOURS_MAX_STOPS = " + std::to_string(RMPC_TIMED_TOURS_MAX_STOPS));
+  return 0;
+}
+
+int rmpc_timed_tours_plan_device(const rmpc_timed_tours *p, void *stream) {
+  const char *who = "timed tours";
+  if (!p) return fail("null argument");
+  if (p->struct_size != (int)sizeof(rmpc_timed_tours)) return fail("rmpc_timed_tours.struct_size mismatch");
+  if (!p->grid || !p->start_cell || !p->stops || !p->len || !p->park_index || !p->fields || !p->goal_cells || !p->orders ||
+      !p->work || !p->paths || !p->status || !p->arrive || !p->key || !p->best || !p->serve_at || !p->served || !p->unserved)
+    return fail("null argument");
+  if (grid_check(p->H, p->W, p->movement) || grid_cells_check(who, p->H, p->W, false) ||
+      timed_common_check(who, p->B, p->T, p->sep2, p->lag) || grid_fields_check(who, p->Gf, p->H, p->W) ||
+      timed_tours_stops_check(who, p->K))
+    return -1;
+  if (p->dwell < 0 || p->dwell > RMPC_TIMED_TOURS_MAX_DWELL)
+    return fail("timed tours: need 0 <= dwell <= RMPC_TIMED_TOURS_MAX_DWELL = " + std::to_string(RMPC_TIMED_TOURS_MAX_DWELL));
+  if (p->G < 1 || p->G > RMPC_TIMED_MAX_ORDERS)
+    return fail("timed tours: need 1 <= G <= RMPC_TIMED_MAX_ORDERS = " + std::to_string(RMPC_TIMED_MAX_ORDERS));
+  if (!grid_fits((long long)p->G * p->B, p->T + 1)) return fail("timed tours: G*B*(T+1) must not exceed INT_MAX");
+  if (!grid_fits((long long)p->G * p->B, p->K)) return fail("timed tours: G*B*K must not exceed INT_MAX");
+  const int64_t need = rmpc_timed_tours_work_bytes(p->H, p->W, p->T, p->G);
+  if (need < 0) return -1;
+  if (p->work_bytes < need)
+    return fail("timed tours: the workspace holds " + std::to_string(p->work_bytes) + " bytes, " + std::to_string(need) +
+                " are needed (rmpc_timed_tours_work_bytes)");
+  if (use_device_of(p->grid)) return -1;
+  TimedGeom q;
+  q.Wd = (p->W + 63) / 64;
+  q.L = p->H * q.Wd;
+  q.rad = 0;
+  while ((q.rad + 1) * (q.rad + 1) < p->sep2) q.rad++;
+  q.per_order = timed_order_words(p->H, p->W, p->T);
+  const size_t hist = (size_t)(p->T + 1) * q.L * sizeof(timed_word);
+  const int nt = q.L <= 64 ? 64 : (q.L <= 128 ? 128 : kTimedThreads);      // a power of two: the end cell's reduction
+  if (hist <= (size_t)kTimedHistLds)
+    hipLaunchKernelGGL(k_timed_tours_plan<true>, dim3(p->G), dim3(nt), hist, (hipStream_t)stream, *p, q, (timed_word *)p->work);
+  else
+    hipLaunchKernelGGL(k_timed_tours_plan<false>, dim3(p->G), dim3(nt), 0, (hipStream_t)stream, *p, q, (timed_word *)p->work);
+  hipLaunchKernelGGL(k_timed_tours_best, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int64_t *)p->key,
+                     (const int *)p->unserved, p->G, (int *)p->best);
+  return launch_status();
+}
+
+int rmpc_timed_tours_follow_device(int B, int T, const int32_t *d_paths, const int32_t *d_idx_in, int32_t *d_idx_out,
+                                   const double *d_pos, int stride, int W, double x0, double y0, double cell,
+                                   double threshold, int sep2, int lag, double *d_goal, int32_t *d_blocked, int K,
+                                   const int32_t *d_serve_at, int32_t *d_leg, int32_t *d_served, int now, double stop_tol,
+                                   void *stream) {
+  const char *who = "timed tours follow";
+  if (!d_paths || !d_idx_in || !d_idx_out || !d_pos || !d_goal || !d_serve_at || !d_leg || !d_served)
+    return fail("null argument");
+  if (d_idx_in == d_idx_out) return fail("timed tours follow: d_idx_out must not be d_idx_in");
+  if (timed_common_check(who, B, T, sep2, lag) || timed_tours_stops_check(who, K)) return -1;
+  if (stride < 2 || !grid_fits(B, stride) || W < 1) return fail("timed tours follow: need stride >= 2, W >= 1");
+  if (!(stop_tol >= 0.0)) return fail("timed tours follow: stop_tol must be >= 0");
+  if (use_device_of(d_paths)) return -1;
+  hipLaunchKernelGGL(k_timed_tours_follow, dim3(B), dim3(256), 0, (hipStream_t)stream, (const int *)d_paths, B, T,
+                     (const int *)d_idx_in, (int *)d_idx_out, d_pos, stride, W, x0, y0, cell, threshold, sep2, lag, d_goal,
+                     (int *)d_blocked, K, (const int *)d_serve_at, (int *)d_leg, (int *)d_served, now, stop_tol);
   return launch_status();
 }
 

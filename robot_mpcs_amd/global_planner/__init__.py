@@ -5,7 +5,8 @@ same module, class and method names, so that a port of ``examples/boxer_example_
 and adds the batched, device-resident fleet API (``plan_batch``, ``RouteFollower``, ``replan``, ``shelf_map``) and the
 fleet's conflict-free timed routes (``TimedRoutes``, ``TimedFollower``) and the pairing of robots with goals at the least
 sum of route costs (``GoalAssigner``) and tours of several goals per robot with a follower that stops at them
-(``TourPlanner``, ``TourFollower``; ``rmpc_tours_device`` / ``rmpc_follow_tour_device``, include/rmpc_tours.h).  The work is done
+(``TourPlanner``, ``TourFollower``; ``rmpc_tours_device`` / ``rmpc_follow_tour_device``, include/rmpc_tours.h) and the two
+together, timed tours through every robot's stops (``TimedTours``, ``TimedTourFollower``; include/rmpc_timed_tours.h).  The work is done
 by the ``rmpc_grid_*_device`` / ``rmpc_follow_path_device`` / ``rmpc_timed_*_device`` kernels (include/rmpc.h); there is no CPU path.  Importing
 the package needs no GPU.
 """
@@ -16,6 +17,7 @@ from .batch import RouteFollower, cell_xy, cells_from_positions, pick_routes, pl
 from .dispatch import GoalAssigner
 from .timed import TimedFollower, TimedRoutes, pick_spaced_routes, priority_orders
 from .tours import TourFollower, TourPlanner
+from .timed_tours import TimedTourFollower, TimedTours, pick_spaced_tours
 
-__all__ = ["FREE", "OCC", "OccupancyGridMap", "a_star", "GlobalPlanner", "GoalAssigner", "RouteFollower", "TimedFollower", "TimedRoutes", "TourFollower", "TourPlanner", "cell_xy", "cells_from_positions",
-           "pick_routes", "pick_spaced_routes", "plan_batch", "png_values", "priority_orders", "replan", "shelf_map", "store_routes"]
+__all__ = ["FREE", "OCC", "OccupancyGridMap", "a_star", "GlobalPlanner", "GoalAssigner", "RouteFollower", "TimedFollower", "TimedRoutes", "TimedTourFollower", "TimedTours", "TourFollower", "TourPlanner", "cell_xy", "cells_from_positions",
+           "pick_routes", "pick_spaced_routes", "pick_spaced_tours", "plan_batch", "png_values", "priority_orders", "replan", "shelf_map", "store_routes"]

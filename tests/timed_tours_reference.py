@@ -1,0 +1,300 @@
+"""The timed tours' rules restated on the CPU from include/rmpc_timed_tours.h (rmpc_timed_tours_plan_device,
+rmpc_timed_tours_follow_device): ``plan_ref`` works on boolean layers and a reservation table, ``plan_walk`` a cell at a
+time on sets against the paths already planned (no table), ``follow_ref`` is the follower's simultaneous step.
+tests/test_timed_tours_cpu.py holds the two against each other and against hand-worked cases,
+tests/test_gpu_timed_tours.py holds the device against ``plan_ref`` and ``follow_ref`` bit for bit.  Grids, cells and
+moves are those of tests/timed_reference.py."""
+import numpy as np
+
+from global_planner_reference import MOVES
+from timed_reference import BAD_ORDER, INT64_MAX, OUTSIDE, _d2, _end_cell, _is_permutation
+
+INT32_MAX = (1 << 31) - 1
+
+
+def _skipped(s, n, stops, park, HW, K, Gf):
+    """rule 1"""
+    if not (0 <= s < HW and 0 <= n <= K and 0 <= park < Gf):
+        return True
+    return any(not 0 <= int(v) < Gf for v in stops[:n])
+
+
+def _blank(G, B, T, K):
+    return dict(paths=np.full((G, B, T + 1), -1, dtype=np.int32), status=np.full((G, B), BAD_ORDER, dtype=np.int32),
+                arrive=np.full((G, B), T + 1, dtype=np.int32), serve_at=np.full((G, B, K), -1, dtype=np.int32),
+                served=np.zeros((G, B), dtype=np.int32), unserved=np.full(G, INT32_MAX, dtype=np.int32))
+
+
+def _finish(out, valid, lens, K, T):
+    """key, unserved and best of the valid rows from status, arrive and served"""
+    G = len(valid)
+    out["key"] = np.full(G, INT64_MAX, dtype=np.int64)
+    n = np.array([int(v) if 0 <= int(v) <= K else 0 for v in lens])
+    best = None
+    for g in range(G):
+        if not valid[g]:
+            continue
+        st, ar = out["status"][g], out["arrive"][g]
+        out["key"][g] = (int((st > 0).sum()) << 44) | (int((ar > T).sum()) << 32) | int(ar.sum())
+        out["unserved"][g] = int((n - out["served"][g]).sum())
+        rank = (int(out["unserved"][g]), int(out["key"][g]), g)
+        best = rank if best is None or rank < best else best
+    out["best"] = np.array([-1 if best is None else best[2]], dtype=np.int32)
+    return out
+
+
+def _problem(grid, start, stops, lens, park_index, fields, orders):
+    grid = np.asarray(grid, dtype=float)
+    stops = np.asarray(stops, dtype=np.int64).reshape(len(start), -1)
+    orders = np.atleast_2d(np.asarray(orders))
+    return grid, stops, orders, grid.shape[0], grid.shape[1], len(start), stops.shape[1], len(fields), orders.shape[0]
+
+
+def plan_ref(grid, start, stops, lens, park_index, fields, goal_cells, orders, T, sep2, lag=1, dwell=0, movement=4, occ=0.8):
+    """The rule of rmpc_timed_tours_plan_device on boolean layers and a reservation table: dict(paths (G, B, T + 1),
+    status, arrive, served (G, B), serve_at (G, B, K), unserved (G,), best (1,) int32, key (G,) int64).  stops (B, K),
+    lens, park_index (B,)."""
+    grid, stops, orders, H, W, B, K, Gf, G = _problem(grid, start, stops, lens, park_index, fields, orders)
+    HW = H * W
+    free = ~(grid >= occ)
+    rows, cols = np.mgrid[0:H, 0:W]
+    disc = lambda c: (rows - c // W) ** 2 + (cols - c % W) ** 2 < sep2
+    moves = [(dc, dr) for dc, dr, _ in MOVES[movement]]
+    skip = [_skipped(int(start[b]), int(lens[b]), stops[b], int(park_index[b]), HW, K, Gf) for b in range(B)]
+    out = _blank(G, B, T, K)
+    valid = [_is_permutation(orders[g], B) for g in range(G)]
+    for g in range(G):
+        if not valid[g]:
+            continue
+        res = np.zeros((T + 1, H, W), dtype=bool)
+        order = [int(b) for b in orders[g]]
+        for k, b in enumerate(order):
+            if skip[b]:
+                out["status"][g, b] = OUTSIDE
+                continue
+            later = np.zeros((H, W), dtype=bool)
+            for j in order[k + 1:]:
+                if not skip[j]:
+                    later |= disc(int(start[j]))
+            reach = np.zeros((T + 1, H, W), dtype=bool)
+            p = np.full(T + 1, -1, dtype=np.int32)
+
+            def sweep(t):
+                pad = np.pad(reach[t - 1], 1)
+                n = reach[t - 1].copy()
+                for dc, dr in moves:
+                    n |= pad[1 - dr:1 - dr + H, 1 - dc:1 - dc + W]
+                n &= free & ~res[t]
+                if t <= lag:
+                    n &= ~later
+                reach[t] = n
+                return n.any()
+
+            def back(c, te, t0):
+                """p[t0 .. te - 1] from (te, c)"""
+                for t in range(te, t0, -1):
+                    r, col = divmod(c, W)
+                    if not reach[t - 1, r, col]:
+                        for dc, dr in moves:
+                            rr, cc = r - dr, col - dc
+                            if 0 <= rr < H and 0 <= cc < W and reach[t - 1, rr, cc]:
+                                c = rr * W + cc
+                                break
+                    p[t - 1] = c
+
+            def end_leg(D, t0, f):
+                te = f - 1 if f else T
+                end = _end_cell(np.flatnonzero(reach[te].ravel()), np.asarray(D).ravel())
+                p[te:] = end
+                back(end, te, t0)
+                return te, end
+
+            t0, at, n = 0, int(start[b]), int(lens[b])
+            status = arrive = None
+            for j in range(n):
+                gi = int(stops[b, j])
+                s = int(goal_cells[gi])
+                inside = 0 <= s < HW
+                reach[t0:] = False
+                reach[t0, at // W, at % W] = True
+                a, f, t = None, 0, t0
+                while True:
+                    if inside and reach[t, s // W, s % W] and t + dwell <= T and not any(
+                            res[u, s // W, s % W] or (u <= lag and later[s // W, s % W]) for u in range(t + 1, t + dwell + 1)):
+                        a = t
+                        break
+                    if t == T:
+                        break
+                    t += 1
+                    if not sweep(t):
+                        f = t
+                        break
+                if a is None:
+                    end_leg(fields[gi], t0, f)
+                    status, arrive = f, T + 1
+                    break
+                p[a:a + dwell + 1] = s
+                back(s, a, t0)
+                out["serve_at"][g, b, j] = a
+                out["served"][g, b] += 1
+                t0, at = a + dwell, s
+            if status is None:
+                reach[t0:] = False
+                reach[t0, at // W, at % W] = True
+                f = 0
+                for t in range(t0 + 1, T + 1):
+                    if not sweep(t):
+                        f = t
+                        break
+                te, end = end_leg(fields[int(park_index[b])], t0, f)
+                status, arrive = f, T + 1
+                if end == int(goal_cells[int(park_index[b])]):
+                    arrive = te
+                    while arrive > t0 and p[arrive - 1] == end:
+                        arrive -= 1
+            out["paths"][g, b], out["status"][g, b], out["arrive"][g, b] = p, status, arrive
+            for t in range(T + 1):
+                res[max(0, t - lag):min(T, t + lag) + 1] |= disc(int(p[t]))
+    return _finish(out, valid, lens, K, T)
+
+
+def plan_walk(grid, start, stops, lens, park_index, fields, goal_cells, orders, T, sep2, lag=1, dwell=0, movement=4, occ=0.8):
+    """The same rule a cell at a time: layers are sets of cells, and a cell is reserved at t when it conflicts with a
+    cell that a robot planned earlier holds within lag layers of t (no reservation table)."""
+    grid, stops, orders, H, W, B, K, Gf, G = _problem(grid, start, stops, lens, park_index, fields, orders)
+    HW = H * W
+    moves = [(dc, dr) for dc, dr, _ in MOVES[movement]]
+    skipped = lambda b: _skipped(int(start[b]), int(lens[b]), stops[b], int(park_index[b]), HW, K, Gf)
+    out = _blank(G, B, T, K)
+    valid = [_is_permutation(orders[g], B) for g in range(G)]
+    for g in range(G):
+        if not valid[g]:
+            continue
+        order, planned = [int(b) for b in orders[g]], []
+        for k, b in enumerate(order):
+            if skipped(b):
+                out["status"][g, b] = OUTSIDE
+                continue
+            later = [int(start[j]) for j in order[k + 1:] if not skipped(j)]
+
+            def reserved(c, t):
+                """what rule 3 and the held test ask beyond the grid"""
+                if t <= lag and any(_d2(c, sj, W) < sep2 for sj in later):
+                    return True
+                return any(_d2(c, int(q[u]), W) < sep2 for q in planned for u in range(max(0, t - lag), min(T, t + lag) + 1))
+
+            def grow(layer, t):
+                cand = set()
+                for c in layer:
+                    r, col = divmod(c, W)
+                    cand.add(c)
+                    for dc, dr in moves:
+                        if 0 <= r + dr < H and 0 <= col + dc < W:
+                            cand.add((r + dr) * W + col + dc)
+                return {c for c in cand if not grid[c // W, c % W] >= occ and not reserved(c, t)}
+
+            def trace(layers, t0, c):
+                """the cells from layer t0 to the last one, ending on c: wait first, else the first move"""
+                cells = [c]
+                for layer in reversed(layers[:-1]):
+                    if c not in layer:
+                        r, col = divmod(c, W)
+                        for dc, dr in moves:
+                            rr, cc = r - dr, col - dc
+                            if 0 <= rr < H and 0 <= cc < W and rr * W + cc in layer:
+                                c = rr * W + cc
+                                break
+                    cells.append(c)
+                return cells[::-1]
+
+            p, serve, at, status, arrive = [], [], int(start[b]), None, T + 1
+            todo = [int(goal_cells[int(v)]) for v in stops[b, :int(lens[b])]] + [None]        # None: the parking leg
+            for j, s in enumerate(todo):
+                t0 = len(p) - 1 if p else 0                 # (the last cell written is where the robot stands)
+                layers, f, a = [{at}], 0, None
+                while True:
+                    t = t0 + len(layers) - 1
+                    if s is not None and s in layers[-1] and t + dwell <= T and not any(
+                            reserved(s, u) for u in range(t + 1, t + dwell + 1)):
+                        a = t
+                        break
+                    if t == T:
+                        break
+                    nxt = grow(layers[-1], t + 1)
+                    if not nxt:
+                        f = t + 1
+                        break
+                    layers.append(nxt)
+                if a is not None:
+                    p = p[:t0] + trace(layers, t0, s) + [s] * dwell
+                    serve.append(a)
+                    at = s
+                    continue
+                gi = int(park_index[b]) if s is None else int(stops[b, j])
+                end = _end_cell(np.array(sorted(layers[-1])), np.asarray(fields[gi]).ravel())
+                p = p[:t0] + trace(layers, t0, end)
+                te = len(p) - 1
+                p += [end] * (T - te)
+                status = f
+                if s is None and end == int(goal_cells[gi]):
+                    arrive = te
+                    while arrive > t0 and p[arrive - 1] == end:
+                        arrive -= 1
+                break
+            out["paths"][g, b], out["status"][g, b], out["arrive"][g, b] = p, status, arrive
+            out["serve_at"][g, b, :len(serve)], out["served"][g, b] = serve, len(serve)
+            planned.append(p)
+    return _finish(out, valid, lens, K, T)
+
+
+def follow_ref(paths, idx_in, pos, goal, W, x0, y0, cell, threshold, sep2, lag, serve_at, leg, served, now, stop_tol):
+    """One step of rmpc_timed_tours_follow_device: (idx_out, goal, blocked, leg, served); pos (B, >= 2); goal (B, 3), leg
+    (B,) and served (B, K) are copied."""
+    paths, serve_at = np.asarray(paths), np.asarray(serve_at)
+    B, T, K = paths.shape[0], paths.shape[1] - 1, serve_at.shape[1]
+    idx_out, blocked, goal = np.array(idx_in, dtype=np.int32), np.full(B, -1, dtype=np.int32), np.array(goal, dtype=float)
+    leg, served = np.array(leg, dtype=np.int32), np.array(served, dtype=np.int32)
+    centre = lambda c: (x0 + float(c % W) * cell, y0 + float(c // W) * cell)
+    for b in range(B):
+        p = paths[b]
+        if p[0] < 0:
+            continue
+        i = min(max(int(idx_in[b]), 0), T)
+        cx, cy = centre(int(p[i]))
+        dx, dy = cx - pos[b, 0], cy - pos[b, 1]
+        dist = np.sqrt(dx * dx + dy * dy)
+        n = max(int(leg[b]), 0)
+        if n < K and serve_at[b, n] == i and dist <= stop_tol:
+            served[b, n] = now
+            n += 1
+            leg[b] = n
+        pending = n < K and serve_at[b, n] == i
+        tol = stop_tol if i in serve_at[b].tolist() else threshold
+        if i < T and not pending and dist <= tol:
+            for j in range(B):
+                if j == b or paths[j, 0] < 0:
+                    continue
+                if any(_d2(int(paths[j, s]), int(p[i + 1]), W) < sep2 and not int(idx_in[j]) >= s + lag
+                       for s in range(0, i - lag + 1)):
+                    blocked[b] = j
+                    break
+            if blocked[b] < 0:
+                i += 1
+        idx_out[b] = i
+        goal[b] = centre(int(p[i])) + (0.0,)
+    return idx_out, goal, blocked, leg, served
+
+
+# ---- the store case ----------------------------------------------------------------------------------------------------
+def store_tours_case(B=16, picks=24, seed=0, sep2=9, start_sep2=25):
+    """(raw, g_inf, starts, pick_cells): B starts and ``picks`` pick cells among the cells ``clear_cells(raw, 2)`` that
+    the planning grid calls free, drawn by ``pick_spaced_tours`` from ``default_rng(seed)``: picks pairwise at least sep2
+    (squared cells) apart, starts start_sep2 -- what examples/fleet_store_timed_tours.py draws"""
+    from robot_mpcs_amd.global_planner import pick_spaced_tours
+    from robot_mpcs_amd.store import STORE, clear_cells
+    from timed_reference import store_grid
+    raw, g_inf = store_grid(seed)
+    ok = clear_cells(raw, STORE.clear_cells) & (g_inf < 0.8)
+    starts, goals = pick_spaced_tours(raw > 0.5, ok, B, picks, np.random.default_rng(seed), STORE.x0, STORE.y0, STORE.cell, sep2,
+                                      start_sep2)
+    return raw, g_inf, starts, goals
