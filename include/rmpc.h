@@ -244,8 +244,12 @@ int rmpc_last_passes(rmpc_handle *h);
 
 /* ---- next rows of the hot path: inputs produced on the device ---------- */
 
-/* Compact scene of B instances; every pointer is a DEVICE pointer and may be NULL (field left at
- * zero).  Device counterpart of MPCPlanner.reset() + setGoalReaching / setRadialConstraints /
+/* Compact scene of B instances; every pointer is a DEVICE pointer and may be NULL.  A NULL field is left at zero, with
+ * one exception, the obstacle words of a model that has them: when BOTH obst and obst_dyn are NULL every obstacle word
+ * (position and radius of all nobst slots) is -100, the reference's EmptyObstacle (mpcPlanner.py:18-26,127-133), as the
+ * host packer's setRadialConstraints writes them for obstacles not given.  When both are given obst_dyn wins: the
+ * predicted obstacles are written and obst is not read.  A field the model has no parameter for is not read.
+ * Device counterpart of MPCPlanner.reset() + setGoalReaching / setRadialConstraints /
  * setLinearConstraints / setJointLimits / setInputLimits / setVelLimits / setConstraintAvoidance /
  * updateDynamicObstacles (robotmpcs/planner/mpcPlanner.py:83-210). */
 typedef struct rmpc_scene {

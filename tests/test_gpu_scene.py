@@ -5,6 +5,8 @@ the closed-loop advance equal to the oracle's plant + the host warm-start shift.
 import numpy as np
 import pytest
 
+from scene_cases import _scene_tensors
+
 pytestmark = pytest.mark.gpu
 
 
@@ -17,24 +19,6 @@ def rt():
     from robot_mpcs_amd._lib import Solver
     from robot_mpcs_amd.scenarios import LIMITS, make_scenario
     return dict(torch=torch, Oracle=Oracle, Solver=Solver, make_scenario=make_scenario, limits=LIMITS)
-
-
-def _scene_tensors(rt, sc):
-    torch = rt["torch"]
-    dev = torch.device("cuda:0")
-    B = sc.B
-    robot = sc.setup["mpc"]["model_name"]
-    lim, limu = rt["limits"][robot]
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-    ten = dict(goal=t(sc.extra["goal"]), r_body=t(np.full(B, sc.extra["r_body"])),
-               lower_limits=t(np.tile(lim[0], (B, 1))), upper_limits=t(np.tile(lim[1], (B, 1))),
-               lower_limits_u=t(np.tile(limu[0], (B, 1))), upper_limits_u=t(np.tile(limu[1], (B, 1))))
-    if "obst_dyn" in sc.extra:
-        ten["obst_dyn"] = t(sc.extra["obst_dyn"])
-    elif "obst_pos" in sc.extra:
-        rad = sc.extra.get("obst_radius", np.full(sc.extra["obst_pos"].shape[:2], 0.1))
-        ten["obst"] = t(np.concatenate([sc.extra["obst_pos"], rad[:, :, None]], axis=2))
-    return ten
 
 
 @pytest.mark.parametrize("name,B", [("cfg2", 300), ("cfg3", 130), ("cfg4", 70)])
@@ -89,8 +73,8 @@ def test_fused_scene_solve_equals_plain_solve(rt, name, B):
     assert np.array_equal(it.cpu().numpy(), plain["iters"])
     # the two halves of the scene solve, for callers that pack the scenes of several handles before the first solve
     z2 = torch.full_like(z, float("nan")); ef2 = torch.zeros_like(ef); it2 = torch.zeros_like(it)
-    with pytest.raises(Exception):    # nothing packed for this batch size yet
-        s.solve(sc.xinit, sc.x0, sc.params)          # (a plain solve overwrites the workspace parameters)
+    s.solve(sc.xinit, sc.x0, sc.params)              # (a plain solve overwrites the workspace parameters)
+    with pytest.raises(Exception):    # nothing packed for this batch size any more
         s.solve_packed_device(B, tx, t0, z2, ef2, it2, kkt, obj)
     s.pack_scene_workspace(B, scene)
     s.solve_packed_device(B, tx, t0, z2, ef2, it2, kkt, obj)

@@ -12,6 +12,7 @@ from robot_mpcs_amd.models.mpcModel import DESCRIPTOR_FILE, load_descriptor, nor
 from robot_mpcs_amd.planner.mpcPlanner import _stage_key, solver_directory
 from robot_mpcs_amd.planner.packing import ParamPacker
 from robot_mpcs_amd.scenarios import CONFIG_DIR, build_model, make_scenario
+from scene_reference import reference_style_pack as _reference_style_pack
 
 
 def test_unknown_or_missing_config_keys_raise_type_error():
@@ -56,52 +57,6 @@ def test_stage_keys_follow_horizon_digits():
     assert _stage_key(100, 7) == "x007"
 
 
-def _reference_style_pack(pm, npar, N, cfg, calls):
-    """Per-element loops exactly as the reference planner writes them."""
-    p = np.zeros(npar * N)
-    for i in range(N):
-        if "wgoal" in pm:
-            p[[npar * i + v for v in pm["wgoal"]]] = cfg.weights["w"]
-        p[[npar * i + v for v in pm["wu"]]] = cfg.weights["wu"]
-        if cfg.slack:
-            p[[npar * i + v for v in pm["ws"]]] = cfg.weights["ws"]
-    for name, args in calls:
-        for i in range(N):
-            if name == "radial":
-                pos, rad, r_body = args
-                p[npar * i + pm["r_body"][0]] = r_body
-                for j in range(cfg.number_obstacles):
-                    pj, rj = (pos[j], rad[j]) if j < len(pos) else ([-100, -100, -100], -100)
-                    for m_i in range(3):
-                        p[npar * i + pm["obst"][j * 4 + m_i]] = pj[m_i]
-                    p[npar * i + pm["obst"][j * 4 + 3]] = rj
-            elif name == "joint":
-                for j in range(cfg.n):
-                    p[npar * i + pm["lower_limits"][j]] = args[0][j]
-                    p[npar * i + pm["upper_limits"][j]] = args[1][j]
-            elif name == "input":
-                for j in range(len(pm["lower_limits_u"])):
-                    p[npar * i + pm["lower_limits_u"][j]] = args[0][j]
-                    p[npar * i + pm["upper_limits_u"][j]] = args[1][j]
-            elif name == "goal":
-                for j in range(3):
-                    p[npar * i + pm["goal"][j]] = args[j] if j < len(args) else 0
-            elif name == "avoid":
-                p[[npar * i + v for v in pm["wconstr"]]] = cfg.weights["wconstr"]
-            elif name == "dyn":
-                obst, dt, r = args
-                nb = obst.size // 9
-                for j in range(cfg.number_obstacles):
-                    if j < nb:
-                        pos, vel, acc = obst[9 * j: 9 * j + 3], obst[9 * j + 3: 9 * j + 6], obst[9 * j + 6: 9 * j + 9]
-                    else:
-                        pos, vel, acc = np.ones(3) * -100, np.zeros(3), np.zeros(3)
-                    for m_i in range(3):
-                        p[npar * i + pm["obst"][j * 4 + m_i]] = pos[m_i] + vel[m_i] * dt * i + 0.5 * (dt * i) ** 2 * acc[m_i]
-                    p[npar * i + pm["obst"][j * 4 + 3]] = r
-    return p
-
-
 def test_packer_matches_reference_loops_point_robot():
     model, setup = build_model(os.path.join(CONFIG_DIR, "cfg2_pointRobotMpc.yaml"))
     cfg = MpcConfiguration(**setup["mpc"])
@@ -134,7 +89,7 @@ def test_packer_dynamic_obstacles_and_slack_weight():
     for b in range(B):
         ref = _reference_style_pack(model._paramMap, model._npar, cfg.time_horizon, cfg, [
             ("radial", ([], [], 0.6)), ("dyn", (dyn[b], cfg.time_step, 0.1))])
-        np.testing.assert_allclose(pk.params[b], ref, rtol=0, atol=1e-15)
+        assert np.array_equal(pk.params[b], ref)     # (bit for bit: Python's precedence is the packer's association)
     assert np.all(pk.p3[:, :, model._paramMap["ws"][0]] == 1e10)
 
 
