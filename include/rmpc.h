@@ -135,15 +135,20 @@ typedef struct rmpc_desc {
       off_wconstr, off_ws;
   int32_t has_goal, has_avoid;
   double lb[RMPC_NV_MAX], ub[RMPC_NV_MAX]; /* z bounds, +-inf allowed (mpcModel.py:91-104) */
-  /* solver options */
-  int32_t max_iter;
-  double tol_stat, tol_eq, tol_ineq, tol_comp;
-  double mu0;
-  int32_t acc_iters;    /* acceptable termination: consecutive stagnant feasible iterations (0 = off, default 8) */
-  double acc_obj_tol;   /* ... relative objective change (default 1e-8) */
-  int32_t ls_max;       /* step halvings allowed in one line search (default 25); an instance that exhausts them
-                           stops with exitflag -8 and its current iterate.  Small values bound the number of passes
-                           of a real-time solve (examples/fleet_loop.py) */
+  /* solver options.  A zeroed field means its default -- with ONE exception, acc_iters, where zero means off.  The stop
+   * tests of an iteration come in this order: converged (exitflag 1), acceptable (2), iteration limit (0); an instance
+   * that converges at iteration max_iter returns 1. */
+  int32_t max_iter;     /* iteration limit, default 200; <= 0 means the default (NOT zero iterations) */
+  double tol_stat, tol_eq, tol_ineq, tol_comp;  /* converged: stationarity, dynamics, inequality and complementarity
+                           residuals (defaults 1e-6, 1e-8, 1e-8, 1e-6); each <= 0 or NaN means its default.  tol_comp
+                           also sets the floor of the barrier parameter, 0.1 tol_comp */
+  double mu0;           /* initial barrier parameter of a cold start (default 1.0); <= 0 or NaN means the default */
+  int32_t acc_iters;    /* acceptable termination: consecutive stagnant feasible iterations (0 = off, default 8).  A
+                           zeroed field is OFF, not 8: ask for the default by writing 8.  Negative values are off too */
+  double acc_obj_tol;   /* ... relative objective change (default 1e-8); <= 0 or NaN means the default */
+  int32_t ls_max;       /* step halvings allowed in one line search (default 25; <= 0 means the default); an instance
+                           that exhausts them stops with exitflag -8 and its current iterate.  Small values bound the
+                           number of passes of a real-time solve (examples/fleet_loop.py) */
   /* ---- 0.2.1: rows of the RMPC_MOD_ROWS modules, in row order; xrow_mod = index into module_kind.  The rows of one
    * module must all be on states (RADIAL / LINEAR / SELF, VAR with a < nx) or all on inputs (VAR with a >= nx + ns): the
    * stage-1 neutralisation and the inverse-barrier objective are per module (InequalityManager.py:25-33).  RADIAL and

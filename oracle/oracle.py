@@ -271,13 +271,16 @@ class Oracle:
 
     def solve_each(self, xinit, x0, params, duals=None):
         """``solve_warm`` of every instance of a batch, one after the other on the calling thread (``duals``: a list with
-        one entry per instance, or None: all cold).  Returns stacked ``z``, ``exitflag``, ``iters``, ``passes`` and the
+        one entry per instance, or None: all cold).  Returns stacked ``z``, ``exitflag``, ``iters``, ``passes``, ``obj``, ``kkt`` and the
         per-instance lists ``census``, ``first`` and ``duals``."""
         B = len(xinit)
         rs = [self.solve_warm(xinit[b], x0[b], params[b], None if duals is None else duals[b]) for b in range(B)]
         return dict(z=np.array([r["z"] for r in rs]), exitflag=np.array([r["exitflag"] for r in rs], dtype=np.int32),
                     iters=np.array([r["iters"] for r in rs], dtype=np.int32),
                     passes=np.array([r["passes"] for r in rs], dtype=np.int32),
+                    obj=np.array([r["obj"] for r in rs]),
+                    # (the residual a caller is told: rmpc_solve_batch's kkt_res)
+                    kkt=np.array([max(r["res_stat"], r["res_eq"], r["res_ineq"], r["res_comp"]) for r in rs]),
                     census=[r["census"] for r in rs], first=[r["first"] for r in rs], duals=[r["duals"] for r in rs])
 
     def debug_step(self, xinit, x0, params, duals=None, curv=0.0):

@@ -31,6 +31,18 @@ query.  Oracle, instances iterating after the looks around the migration:
       (181 against a bar of 192: should a few instances of the device take two passes longer, 88 move after 20)
   cfg2   B 1024 seed 7        look 14: 258 (25.2 %)   look 16:  78 (7.6 %)  ->  78 move after 16 passes
       (the cold first step of test_gpu_warm_start.py::test_warm_loop_across_a_migration)
+
+The stall counter of the acceptable stop across a migration (STALL_MIGRATION below).  In a cold batch the feasible,
+stagnant end game comes long after the migration: over cfg2 B 1024 and cfg3 B 1280, seeds 7 .. 12, windows of 3, 5 and
+8 at acc_obj_tol 1e-4 and 1e-3, every survivor that ends with flag 2 begins its last stagnant run 17 passes or more after
+the move, and the survivors that are stagnant at the move converge one pass later, where the converged test comes
+before the counter is read.  In the WARM second step the batch is feasible from the start and migrates at the first
+look, after 8 passes:
+  cfg3   B 1280 seed 10, acc_iters 3, acc_obj_tol 1e-4, step 1   look 8: 87   -> 87 move after 8 passes; 19 of them
+      end with flag 2, and for at least six (181, 571, 780, 912, 919, 1273) the run of three stagnant iterations that
+      ends the solve began at iteration 4, evaluated by pass 7: the counter crosses k_migrate at 1 or more and is what
+      decides the flag-2 exit at iteration 6.  (decision_cases.ACC itself, acc_iters = 1, cannot show this: the first
+      stagnant iteration ends the solve.)
 """
 import numpy as np
 
@@ -47,6 +59,25 @@ MIGRATION_CASES = [
     # a horizon beyond the fused kernel's 32 stages: the production route to these kernels, no switch
     ("cfg2", 1536, 11, {"time_horizon": 40}, {}),
 ]
+
+
+# (name, B, seed, option overrides, environment at rmpc_create): see above
+STALL_MIGRATION = ("cfg3", 1280, 10, {"acc_iters": 3, "acc_obj_tol": 1e-4}, NO_FUSED)
+
+
+def carried_stall_decides(o, desc, x, x0, params, duals, migrated_at):
+    """Oracle census of one instance of a batch that migrated after ``migrated_at`` passes: True when the instance is a
+    survivor (needs more passes), ends with flag 2, and the unbroken run of acc_iters stagnant iterations that ends it
+    began at an iteration evaluated within those passes -- so the counter is non-zero when the survivors move, is not
+    reset afterwards, and its carried value decides the exit.  (The passes an instance has used when it reaches
+    iteration i are those of its solve under max_iter = i.)  Returns (verdict, the oracle's result)."""
+    k = desc["options"]["acc_iters"]
+    r = o.solve_warm(x, x0, params, duals)
+    if r["exitflag"] != 2 or r["passes"] <= migrated_at:
+        return False, r
+    began = r["iters"] - k + 1      # (stall >= k at the exit: the last k iterations were stagnant in a row)
+    cut = type(o)(dict(desc, options=dict(desc["options"], max_iter=began))).solve_warm(x, x0, params, duals)
+    return bool(cut["exitflag"] == 0 and cut["iters"] == began and cut["passes"] <= migrated_at), r
 
 
 def case_id(case):

@@ -5,7 +5,19 @@
     (flag, iterations, passes and census unchanged under eight relative perturbations of 1e-8 of its inputs) -- a
     later change of the algorithm that un-reaches a branch fails here and names the case;
   * the table branch x model class is complete: every pair has a witness, is excluded by a Cfg flag, or is one of at
-    most three pairs listed as unreached.
+    most three pairs listed as unreached;
+  * the witnesses under option sets off the defaults (decision_cases.OPTION_SETS) end with the flag, iteration and pass
+    counts pinned in decision_cases.EXPECT, and every class -- each recursion family of the arms, and the horizon of 40
+    stages -- has its flag 2, flag 0, flag -8 and loose-tolerance witness;
+  * the edge witnesses (decision_cases.EDGES) are what the rule derives from the cases, hold the rule and reproduce
+    their pinned results under every option variant, rounding filter included;
+  * KKT_REL_MEASURED is the oracle's own movement of the reported residual over the comparison points of
+    test_gpu_decision_branches.py.
+The pins are what notices a change of the stop tests' order or of the acceptable window in the oracle (tried on a
+scratch copy of oracle/rmpc_oracle.c): ``stall >= acc_iters`` made ``>`` fails test_option_witness_results_are_pinned
+(every ACC witness) and test_edge_variants_reproduce_on_the_oracle; the iteration-limit test moved before the
+acceptable test fails test_edge_variants_reproduce_on_the_oracle (the flag-2 max_iter edges: flag 0 at max_iter = n);
+the res_comp test of the acceptable window dropped fails test_option_witness_results_are_pinned.
 """
 import json
 import os
@@ -83,9 +95,14 @@ def test_witness_takes_its_branches_and_is_insensitive_to_rounding(rt, case):
     b = case.witness
     census = cpu["census"][b]
     print(dc.case_id(case), "flag", cpu["exitflag"][b], "iterations", cpu["iters"][b], "passes", cpu["passes"][b], census)
+    o_def = dc.default_oracle(rt["Oracle"], sc, case) if dc.is_loose(case.opts) else None
+    view = dc.census_view(o, sc, case, loop[-1], b, o_def)
     for k in case.branches:
-        assert dc.BRANCHES[k](census), (k, census)
-    assert cpu["exitflag"][b] != 0 and cpu["passes"][b] <= dc.MAX_PASSES
+        assert dc.BRANCHES[k](view), (k, view)
+    assert (cpu["exitflag"][b] != 0 or "flag0" in case.branches) and cpu["passes"][b] <= dc.MAX_PASSES
+    if o_def is not None:
+        print("    at the default tolerances: %d iterations" % view["default_iters"])
+        assert dc.rounding_insensitive(o_def, sc, case, loop[-1])
     again = dc.witness_solve(o, sc, case, loop[-1])     # (alone, as the filter solves it)
     assert dc.signature(again) == (cpu["exitflag"][b], cpu["iters"][b], cpu["passes"][b], tuple(sorted(census.items())))
     assert dc.rounding_insensitive(o, sc, case, loop[-1])
@@ -104,3 +121,78 @@ def test_branch_by_class_table_is_complete():
     assert not missing, sorted(missing)
     # the flags that exclude pairs are those of the model classes: a class's scenarios qualify for what its witnesses take
     assert {cls for cls, _ in have} == set(dc.CLASSES)
+
+
+OPTION_CASES = [c for c in dc.CASES if set(c.opts) - {"mu0"}]
+
+
+def test_option_witnesses_cover_every_class():
+    """Per class, per recursion family of the arms and at the horizon of 40 stages: flag 2 under ACC or BENCH, flag 0
+    under BENCH, flag -8 under LS and the loose-tolerance flag 1."""
+    assert set(dc.EXPECT) == {dc.case_id(c) for c in OPTION_CASES}
+    groups = {"chain3": lambda c: c.kw.get("time_horizon", 0) <= 32, "chain3+N40": lambda c: c.kw.get("time_horizon", 0) > 32,
+              "point_slack": lambda c: True, "unicycle": lambda c: True,
+              "arm": lambda c: c.name in ("cfg4", "chain5", "chain6"), "arm+dense": lambda c: c.name in ("chain4", "chain8")}
+    for g, member in groups.items():
+        mine = [c for c in OPTION_CASES if c.cls == g.split("+")[0] and member(c)]
+        for k, sets in dc.OPTION_BRANCHES.items():
+            hit = [c for c in mine if k in c.branches and any(c.opts == dc.OPTION_SETS[s] for s in sets)]
+            assert hit, (g, k)
+    # about twenty: a case per group and exit (24), the cold flag-2 ones of the edges (3), a flag -8 after an accepted step
+    # per class (4)
+    assert len(OPTION_CASES) <= 31
+    later = [c for c in OPTION_CASES if "flag-8" in c.branches and dc.EXPECT[dc.case_id(c)][1] >= 1]
+    assert {c.cls for c in later} == set(dc.CLASSES)
+
+
+@pytest.mark.parametrize("case", OPTION_CASES, ids=dc.case_id)
+def test_option_witness_results_are_pinned(rt, case):
+    sc, o, loop = dc.loop_of(rt["make_scenario"], rt["Oracle"], case)
+    got = dc.result_of(loop[-1]["cpu"], case.witness)
+    print(dc.case_id(case), "flag, iterations, passes", got, "pinned", dc.EXPECT[dc.case_id(case)])
+    assert got == dc.EXPECT[dc.case_id(case)]
+
+
+def test_edges_are_what_the_rule_derives(rt):
+    derived = dc.derive_edges(rt["make_scenario"], rt["Oracle"])
+    assert derived == dc.EDGES
+    have = {(dc.CASES[e.case].cls, e.kind, e.flag) for e in dc.EDGES}
+    want = {(cls, kind, flag) for cls in dc.CLASSES for kind, flag in (("max_iter", 1), ("max_iter", 2), ("acc_iters", 2))}
+    assert want - have == set(dc.EDGES_MISSING), sorted(want - have)
+    # every class has both edges; the flag-2 max_iter edge (acceptable before the iteration limit) where a cold case ends so
+    assert {(cls, k) for cls, k, _ in have} == {(cls, k) for cls in dc.CLASSES for k in ("max_iter", "acc_iters")}
+
+
+@pytest.mark.parametrize("edge", dc.EDGES, ids=dc.edge_id)
+def test_edge_variants_reproduce_on_the_oracle(rt, edge):
+    (sc, o, loop), variants = dc.edge_loops(rt["make_scenario"], rt["Oracle"], edge)
+    c = dc.CASES[edge.case]
+    assert dc.edge_holds(edge, loop, variants), (edge, [dc.result_of(lp[-1]["cpu"], c.witness) for _, _, _, _, lp in variants])
+    for (label, cv, scv, ov, lp), want in zip(variants, edge.expect):
+        got = dc.result_of(lp[-1]["cpu"], c.witness)
+        print(dc.edge_id(edge), label, cv.opts, "flag, iterations, passes", got, "pinned", want, lp[-1]["cpu"]["census"][c.witness])
+        assert got == want and got[2] <= dc.MAX_PASSES
+        again = dc.witness_solve(ov, scv, cv, lp[-1])
+        assert dc.signature(again) == got + (tuple(sorted(lp[-1]["cpu"]["census"][c.witness].items())),)
+        assert dc.rounding_insensitive(ov, scv, cv, lp[-1])
+    if edge.kind == "acc_iters":
+        assert edge.expect[0][0] != 2     # (off means off)
+
+
+def test_kkt_rel_is_the_oracles_own_movement(rt):
+    """The bar of the reported residual in test_gpu_decision_branches.py: see decision_cases.KKT_REL_MEASURED."""
+    pts = dc.comparison_points(rt["make_scenario"], rt["Oracle"])
+    worst, compared = 0.0, 0
+    for label, o, sc, c, step in pts:
+        k0, rel = dc.kkt_movement(o, sc, c, step)
+        skipped = k0 < dc.KKT_FLOOR
+        print("%-90s kkt %.3e  movement %.3e%s" % (label, k0, rel, "  (below the floor: not compared)" if skipped else ""))
+        if not skipped:
+            worst, compared = max(worst, rel), compared + 1
+    print("comparison points %d, compared %d, worst relative movement of the oracle's residual %.3e (pinned %.3e)"
+          % (len(pts), compared, worst, dc.KKT_REL_MEASURED))
+    assert len(pts) >= 20 and compared >= 0.75 * len(pts), (len(pts), compared)
+    assert worst <= dc.KKT_REL_MEASURED <= 1.05 * worst, (worst, dc.KKT_REL_MEASURED)
+    assert dc.KKT_REL == 8 * dc.KKT_REL_MEASURED
+    # the perturbation is 1e-8: a bar that a stage missing from a maximum (O(1)) would pass has lost its meaning
+    assert dc.KKT_REL < 0.1

@@ -15,7 +15,17 @@ loop steps from the oracle's plan, as test_warm_started_closed_loop_matches_orac
     Every path counts passes as the oracle does (one per horizon evaluation: first sweep, trial points, null passes):
     no path needed a convention of its own;
   * cold witnesses: for each iteration at which one of the case's branches first fired (census), both sides solve with
-    max_iter one past it: flag 0, that iteration count, the witness's iterate within check_plan's bars of the oracle's.
+    max_iter one past it: flag 0, that iteration count, the witness's iterate within check_plan's bars of the oracle's;
+  * the witnesses under option sets off the defaults (decision_cases.OPTION_SETS: the acceptable window, the benchmark's
+    options, a small line-search cap, loose tolerances) go through the same two tests; where the witness ends the last step
+    with flag 0 or -8 its returned iterate is compared like a cut's (a line search that runs out returns the current
+    iterate on both sides);
+  * the edge witnesses (decision_cases.EDGES), one handle per option variant: max_iter equal to the iteration at which
+    the witness converges (or reaches the acceptable level) ends with that flag, one less with flag 0 -- the order of
+    the stop tests in inst_decide; the acceptable window switched off and one iteration longer;
+  * wherever a witness is compared at flag 0, -8 or a cut: the reported objective to OBJ_RTOL and the reported residual
+    kkt against the oracle's max(res_stat, res_eq, res_ineq, res_comp) to decision_cases.KKT_REL, eight times the
+    oracle's own movement under the rounding filter's perturbations (measured on the CPU).
 Each case prints path, flags, iterations and passes of both sides, and the measured differences.
 """
 import numpy as np
@@ -100,6 +110,16 @@ def _run(s, sc, loop, budget=0):
     return out
 
 
+def _check_reported(label, g, b, obj, kkt):
+    """The numbers a caller is told beside the plan: objective and KKT residual of the returned iterate."""
+    dobj = abs(g["obj"][b] - obj) / abs(obj)
+    dk = abs(g["kkt"][b] - kkt) / kkt if kkt >= dc.KKT_FLOOR else None
+    print("    %s: obj gpu %.12e cpu %.12e (relative %.2e, bar %.0e); kkt gpu %.6e cpu %.6e (relative %s, bar %.2e)" % (
+        label, g["obj"][b], obj, dobj, dc.OBJ_RTOL, g["kkt"][b], kkt, "below the floor, not compared" if dk is None else "%.2e" % dk, dc.KKT_REL))
+    assert dobj <= dc.OBJ_RTOL, (label, dobj)
+    assert dk is None or dk <= dc.KKT_REL, (label, dk)
+
+
 def _plan_diff(gz, cz, nxs):
     """(whole plan, applied control) differences over check_plan's scales."""
     return (np.abs(gz - cz).max() / max(1.0, np.abs(cz).max()),
@@ -125,6 +145,11 @@ def test_decisions_match_oracle_on_witness(rt, case, path, monkeypatch):
             dz, du = _plan_diff(g["z"][b], cpu["z"][b], nxs)
             print("    plan difference %.2e, applied control %.2e (bar %.0e)" % (dz, du, TOL))
             assert dz <= TOL and du <= TOL, (t, dz, du)
+        if t == last and cpu["exitflag"][b] in (0, -8):     # (the returned iterate, like a cut's, and what is reported of it)
+            dz, du = _plan_diff(g["z"][b], cpu["z"][b], nxs)
+            print("    iterate difference %.2e, first control %.2e (bar %.0e)" % (dz, du, TOL))
+            assert dz <= TOL and du <= TOL, (t, dz, du)
+            _check_reported("step %d" % t, g, b, cpu["obj"][b], cpu["kkt"][b])
     pool = lambda side, key: np.concatenate([r[key][others] for r in side])
     cpus = [step["cpu"] for step in loop]
     check_plan({k: pool(got, k) for k in ("exitflag", "iters", "z", "kkt")}, {k: pool(cpus, k) for k in ("exitflag", "iters", "z")}, nxs)
@@ -135,10 +160,14 @@ def test_decisions_match_oracle_on_witness(rt, case, path, monkeypatch):
     below = _run(s, sc, loop, budget=p - 1)[last] if p >= 2 else None
     print("    passes: finished with a budget of %d (flag %d); with %d: flag %s" % (p, at["exitflag"][b], p - 1, None if below is None else below["exitflag"][b]))
     assert below is None or below["exitflag"][b] == 0, (p, below["exitflag"][b])
+    if flag == 0 and below is not None:
+        # (a witness that ends with flag 0 by itself: one pass short it has not reached its last iteration either)
+        print("    iterations with a budget of %d: %d (with %d: %d)" % (p - 1, below["iters"][b], p, at["iters"][b]))
+        assert below["iters"][b] < iters, (p, below["iters"][b], iters)
     s.close()
 
 
-COLD = [(c, p) for c, p in PARAMS if c.mode == "cold"]
+COLD = [(c, p) for c, p in PARAMS if dc.has_cuts(c)]     # (cold, and a branch that is not dated by the exit)
 
 
 @pytest.mark.parametrize("case,path", COLD, ids=["%s-%s" % (dc.case_id(c), p) for c, p in COLD])
@@ -148,8 +177,7 @@ def test_iterate_after_the_branch_matches_oracle(rt, case, path, monkeypatch):
     sc, o, loop = dc.loop_of(rt["make_scenario"], rt["Oracle"], case)
     nxs, b = o.nx + o.ns, case.witness
     first, iters = loop[0]["cpu"]["first"][b], int(loop[0]["cpu"]["iters"][b])
-    cuts = sorted({first[dc.FIRST_OF.get(k, k)] + 1 for k in case.branches} - {0})
-    cuts = [f for f in cuts if f < iters]    # (at its last iteration the solve stops by itself: the loop test above)
+    cuts = dc.cut_iterations(case, first, iters)    # (at its last iteration the solve stops by itself: the loop test above)
     assert cuts, (case, first)
     for f in cuts:
         desc = dict(sc.desc, options=dict(sc.desc["options"], max_iter=f))
@@ -165,3 +193,57 @@ def test_iterate_after_the_branch_matches_oracle(rt, case, path, monkeypatch):
         assert r["exitflag"] == 0 and r["iters"] == f
         assert g["exitflag"][b] == 0 and g["iters"][b] == f
         assert dz <= TOL and du <= TOL, (f, dz, du)
+        _check_reported("cut at %d" % f, g, b, r["obj"], dc.kkt_of(r))
+
+
+def _edge_params(kind):
+    return [(e, p) for e in dc.EDGES if e.kind == kind for p in paths_of(dc.CASES[e.case])]
+
+
+def _check_edge(rt, edge, path, monkeypatch):
+    """Every option variant of the edge through a handle of its own on the path, fed the case's inputs step by step:
+    flag and iterations of the witness equal to the oracle's at every step, plan (flag 1, 2) within TOL, and at the last
+    step -- the solve the rounding filter vouches for -- the iterate and the reported numbers where the oracle stops
+    with 0 or -8."""
+    _set_env(monkeypatch, PATHS[path][0])
+    (sc, o, loop), variants = dc.edge_loops(rt["make_scenario"], rt["Oracle"], edge)
+    case = dc.CASES[edge.case]
+    nxs, b = o.nx + o.ns, case.witness
+    results = {}
+    for (label, cv, scv, ov, lp), want in zip(variants, edge.expect):
+        s = _handle(rt, scv, cv, path)
+        got = _run(s, scv, lp)
+        lpath = s.last_solve_path()
+        s.close()
+        assert lpath["fused"] == PATHS[path][1] and (PATHS[path][3] is None or lpath["ric_first"] == PATHS[path][3]), lpath
+        for t, (g, step) in enumerate(zip(got, lp)):
+            cpu = step["cpu"]
+            dz, du = _plan_diff(g["z"][b], cpu["z"][b], nxs)
+            print("%s %s %s %s step %d witness: flag gpu %d cpu %d, iterations gpu %d cpu %d, passes cpu %d, plan or iterate difference %.2e, first control %.2e (bar %.0e)" % (
+                dc.edge_id(edge), path, label, cv.opts, t, g["exitflag"][b], cpu["exitflag"][b], g["iters"][b], cpu["iters"][b], cpu["passes"][b], dz, du, TOL))
+            assert g["exitflag"][b] == cpu["exitflag"][b] and g["iters"][b] == cpu["iters"][b], (label, t, g["exitflag"], cpu["exitflag"], g["iters"], cpu["iters"])
+            if cpu["exitflag"][b] in (1, 2) or (t == len(lp) - 1 and cpu["exitflag"][b] in (0, -8)):
+                assert dz <= TOL and du <= TOL, (label, t, dz, du)
+            if t == len(lp) - 1 and cpu["exitflag"][b] in (0, -8):
+                _check_reported("%s step %d" % (label, t), g, b, cpu["obj"][b], cpu["kkt"][b])
+        last = dc.result_of(lp[-1]["cpu"], b)
+        assert last == want, (label, last, want)      # (the oracle's side is what the CPU test pinned)
+        results[label] = (int(got[-1]["exitflag"][b]), int(got[-1]["iters"][b]))
+    return results
+
+
+@pytest.mark.parametrize("edge,path", _edge_params("max_iter"), ids=["%s-%s" % (dc.edge_id(e), p) for e, p in _edge_params("max_iter")])
+def test_stop_order_at_the_iteration_limit(rt, edge, path, monkeypatch):
+    """max_iter = n, the iteration at which the witness converges (flag 1) or reaches the acceptable level (flag 2): that
+    flag and n iterations, not flag 0 -- converged, then acceptable, then the iteration limit; max_iter = n - 1: flag 0 and
+    n - 1 iterations."""
+    res = _check_edge(rt, edge, path, monkeypatch)
+    assert res["at"] == (edge.flag, edge.n) and res["below"] == (0, edge.n - 1), res
+
+
+@pytest.mark.parametrize("edge,path", _edge_params("acc_iters"), ids=["%s-%s" % (dc.edge_id(e), p) for e, p in _edge_params("acc_iters")])
+def test_acceptable_window_edges(rt, edge, path, monkeypatch):
+    """A witness that ends with flag 2 under acc_iters = k: with acc_iters = 0 the window is off (never flag 2), with
+    k + 1 it ends as the oracle says."""
+    res = _check_edge(rt, edge, path, monkeypatch)
+    assert res["off"][0] != 2, res

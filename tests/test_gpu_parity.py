@@ -464,6 +464,117 @@ def test_line_search_cap_matches_oracle(rt):
     assert ok.mean() >= 0.98
 
 
+DEFAULT_OPTIONS = dict(max_iter=200, tol_stat=1e-6, tol_eq=1e-8, tol_ineq=1e-8, tol_comp=1e-6, mu0=1.0, acc_obj_tol=1e-8, ls_max=25)
+
+
+def _raw_solver(rt, monkeypatch, desc, B, **fields):
+    """A handle whose rmpc_desc is make_desc's with the option fields overwritten as given (raw: no default of the Python
+    side in between)."""
+    from robot_mpcs_amd import _lib
+
+    def raw(d, device=0, _make=_lib.make_desc):
+        cd = _make(d, device)
+        for k, v in fields.items():
+            setattr(cd, k, v)
+            got = getattr(cd, k)
+            assert got == v or (v != v and got != got), (k, v, got)
+        return cd
+
+    with monkeypatch.context() as m:
+        m.setattr(_lib, "make_desc", raw)
+        return rt["Solver"](desc, max_batch=B)
+
+
+def _solve_with_raw_options(rt, monkeypatch, sc, B, **fields):
+    s = _raw_solver(rt, monkeypatch, sc.desc, B, **fields)
+    r = s.solve(sc.xinit, sc.x0, sc.params)
+    path = s.last_solve_path()
+    fused = s.is_fused()
+    s.close()
+    return r, path, fused
+
+
+@pytest.mark.parametrize("name,kw,fused,kernel", [("cfg2", {}, True, "k_fused"), ("cfg4", {}, True, "k_fused_arm"),
+                                                  ("cfg2", {"time_horizon": 40}, False, "")],
+                         ids=["cfg2-fused", "cfg4-fused_arm", "cfg2-N40-pass"])
+def test_zeroed_options_mean_the_documented_defaults(rt, name, kw, fused, kernel, monkeypatch):
+    """The descriptor's rules for option fields that are zero, negative or NaN (include/rmpc.h, solver options): max_iter,
+    the tolerances, mu0, acc_obj_tol and ls_max then take their defaults -- bit-identical results to a descriptor that
+    spells the defaults out, acc_iters explicit on both sides -- while acc_iters <= 0 switches the acceptable stop OFF
+    (it does not mean the default 8): 0 and -3 are equal to each other, no instance returns 2, and the solve agrees with
+    the oracle at acc_iters = 0 (test_zeroed_acc_iters_is_off_not_the_default: an input on which 8 and off differ)."""
+    for k in ("RMPC_NO_FUSED", "RMPC_RIC_LANE", "RMPC_NO_MIGRATE", "RMPC_NO_SPEC", "RMPC_ARM_TWO_PARTS"):
+        monkeypatch.delenv(k, raising=False)
+    B = 16
+    sc = rt["make_scenario"](name, B=B, seed=21, **kw)
+    assert sc.desc["options"]["acc_iters"] == 8
+    keys = ("z", "exitflag", "iters", "obj", "kkt")
+    nan = float("nan")
+    explicit, path, is_fused = _solve_with_raw_options(rt, monkeypatch, sc, B, acc_iters=8, **DEFAULT_OPTIONS)
+    assert is_fused == fused and path["fused"] == fused, path
+    if kernel:
+        s = rt["Solver"](sc.desc, max_batch=B)
+        assert s.debug_step(sc.xinit, sc.x0, sc.params)["path"]["fused"] == kernel
+        s.close()
+    variants = {
+        "zero": dict(max_iter=0, tol_stat=0.0, tol_eq=0.0, tol_ineq=0.0, tol_comp=0.0, mu0=0.0, acc_obj_tol=0.0, ls_max=0),
+        "negative": dict(max_iter=-1, tol_stat=-1.0, tol_eq=-1e-8, tol_ineq=-0.0, tol_comp=-1e-6, mu0=-1.0, acc_obj_tol=-1.0, ls_max=-7),
+        "nan": dict(DEFAULT_OPTIONS, tol_stat=nan, tol_eq=nan, tol_ineq=nan, tol_comp=nan, mu0=nan, acc_obj_tol=nan),
+    }
+    for label, fields in variants.items():
+        got, p, _ = _solve_with_raw_options(rt, monkeypatch, sc, B, acc_iters=8, **fields)
+        print("%s %s %s: flags %s iterations %s" % (name, kw, label, got["exitflag"].tolist(), got["iters"].tolist()))
+        assert p == path, (label, p, path)
+        for k in keys:
+            assert np.array_equal(got[k], explicit[k]), (label, k)
+    # acc_iters: zero and negative are both "off"
+    off0, _, _ = _solve_with_raw_options(rt, monkeypatch, sc, B, acc_iters=0, **DEFAULT_OPTIONS)
+    off3, _, _ = _solve_with_raw_options(rt, monkeypatch, sc, B, acc_iters=-3, **variants["zero"])
+    for k in keys:
+        assert np.array_equal(off0[k], off3[k]), k
+    assert not (off0["exitflag"] == 2).any(), off0["exitflag"]
+    d = dict(sc.desc, options=dict(sc.desc["options"], acc_iters=0))
+    cpu = rt["Oracle"](d).solve_batch(sc.xinit, sc.x0, sc.params)
+    print("%s %s acc_iters off: flags gpu %s cpu %s, iterations gpu %s cpu %s" % (
+        name, kw, off0["exitflag"].tolist(), cpu["exitflag"].tolist(), off0["iters"].tolist(), cpu["iters"].tolist()))
+    check_plan(off0, cpu, sc.desc["nx"] + sc.desc["ns"])
+    np.testing.assert_allclose(off0["obj"], cpu["obj"], rtol=1e-9, atol=1e-9)
+
+
+def test_zeroed_acc_iters_is_off_not_the_default(rt, monkeypatch):
+    """On the cold batches above the acceptable stop does not fire at its default window of 8, so "0 means 8" and "0 means
+    off" would return the same.  Here it does fire: the warm second step of decision_cases' chain3 flag-2 witness (cfg2,
+    seed 3, instance 5: flag 2 at acc_iters = 8).  Handles created with a raw acc_iters of 8, 0 and -3, fed the same two
+    steps: 8 ends the witness with flag 2 like the oracle; 0 and -3 are equal bit for bit, do not, and agree with the
+    oracle at acc_iters = 0 in flag and iterations."""
+    import decision_cases as dc
+    case = next(c for c in dc.CASES if c.cls == "chain3" and c.name == "cfg2" and not c.kw and not c.opts and "flag2" in c.branches)
+    sc, o, loop = dc.loop_of(rt["make_scenario"], rt["Oracle"], case)
+    b = case.witness
+    cv = case._replace(opts={"acc_iters": 0})
+    sc0 = dc.scenario_of(rt["make_scenario"], cv)
+    off = dc.oracle_loop(sc0, rt["Oracle"](sc0.desc), cv, inputs=loop)
+    for k in ("RMPC_NO_FUSED", "RMPC_RIC_LANE", "RMPC_NO_MIGRATE", "RMPC_NO_SPEC"):
+        monkeypatch.delenv(k, raising=False)
+    res = {}
+    for acc in (8, 0, -3):
+        s = _raw_solver(rt, monkeypatch, sc.desc, case.B, acc_iters=acc)
+        s.set_warm_start(True)
+        res[acc] = [s.solve(step["x"], step["x0"], sc.params) for step in loop]
+        s.close()
+    cpu8, cpu0 = loop[-1]["cpu"], off[-1]["cpu"]
+    print("acc_iters 8: witness flag gpu %d cpu %d, iterations gpu %d cpu %d | off: flag gpu %d (raw 0) %d (raw -3) cpu %d, iterations gpu %d cpu %d" % (
+        res[8][-1]["exitflag"][b], cpu8["exitflag"][b], res[8][-1]["iters"][b], cpu8["iters"][b],
+        res[0][-1]["exitflag"][b], res[-3][-1]["exitflag"][b], cpu0["exitflag"][b], res[0][-1]["iters"][b], cpu0["iters"][b]))
+    assert cpu8["exitflag"][b] == 2 and cpu0["exitflag"][b] != 2
+    assert res[8][-1]["exitflag"][b] == 2 and res[8][-1]["iters"][b] == cpu8["iters"][b]
+    for t in range(len(loop)):
+        for k in ("z", "exitflag", "iters", "obj", "kkt"):
+            assert np.array_equal(res[0][t][k], res[-3][t][k]), (t, k)
+        assert not (res[0][t]["exitflag"] == 2).any()
+    assert res[0][-1]["exitflag"][b] == cpu0["exitflag"][b] and res[0][-1]["iters"][b] == cpu0["iters"][b]
+
+
 def test_iteration_cap_returns_usable_plan(rt):
     sc = rt["make_scenario"]("cfg2", B=32, seed=3)
     d = dict(sc.desc); d["options"] = dict(d["options"], max_iter=4)

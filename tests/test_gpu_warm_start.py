@@ -3,7 +3,7 @@
 import numpy as np
 import pytest
 
-from pass_batch_cases import NO_FUSED, strided_sample
+from pass_batch_cases import NO_FUSED, STALL_MIGRATION, carried_stall_decides, strided_sample
 
 pytestmark = pytest.mark.gpu
 
@@ -25,14 +25,24 @@ def _ids(cases, n):
                      + [k[5:].lower() + v for k, v in sorted(c[n + 1].items())]) for c in cases]
 
 
-# (name, B, steps, make_scenario overrides, environment at rmpc_create, fused): the fused handles, and the pass kernels --
-# k_sweep's warm first pass and k_save_duals behind every solve -- through the models that are there anyway (4 and 8
-# joints: ric_backward; a horizon of 40 stages), the arm's and the boxer's own recursions and the lane-per-instance one
+BENCH = {"max_iter": 20, "acc_iters": 3}     # what bench.py runs (its robot types at max_iter 20; decision_cases.BENCH)
+
+# (name, B, steps, make_scenario overrides, environment at rmpc_create, fused, option overrides): the fused handles, and
+# the pass kernels -- k_sweep's warm first pass and k_save_duals behind every solve -- through the models that are there
+# anyway (4 and 8 joints: ric_backward; a horizon of 40 stages), the arm's and the boxer's own recursions and the
+# lane-per-instance one; then the benchmark's options, instance for instance: an iteration limit that binds in the cold
+# step and an acceptable window of 3, on the fused kernels and on the arm's pass kernels
 CLOSED_LOOP_CASES = [
-    ("cfg2", 24, 8, {}, {}, True), ("cfg3", 24, 8, {}, {}, True), ("cfg4", 8, 6, {}, {}, True), ("wc_boxer", 16, 6, {}, {}, True),
-    ("chain4", 16, 6, {}, {}, False), ("chain8", 8, 5, {}, {}, False), ("cfg2", 24, 6, {"time_horizon": 40}, {}, False),
-    ("cfg4", 8, 6, {}, NO_FUSED, False), ("cfg3", 24, 6, {}, NO_FUSED, False), ("cfg2", 24, 6, {}, dict(NO_FUSED, **LANE), False),
+    ("cfg2", 24, 8, {}, {}, True, {}), ("cfg3", 24, 8, {}, {}, True, {}), ("cfg4", 8, 6, {}, {}, True, {}), ("wc_boxer", 16, 6, {}, {}, True, {}),
+    ("chain4", 16, 6, {}, {}, False, {}), ("chain8", 8, 5, {}, {}, False, {}), ("cfg2", 24, 6, {"time_horizon": 40}, {}, False, {}),
+    ("cfg4", 8, 6, {}, NO_FUSED, False, {}), ("cfg3", 24, 6, {}, NO_FUSED, False, {}), ("cfg2", 24, 6, {}, dict(NO_FUSED, **LANE), False, {}),
+    ("cfg2", 24, 6, {}, {}, True, BENCH), ("cfg3", 24, 6, {}, {}, True, BENCH), ("cfg4", 8, 6, {}, {}, True, BENCH),
+    ("cfg4", 8, 6, {}, NO_FUSED, False, BENCH),
 ]
+
+
+def _closed_loop_ids():
+    return [i + ("-bench" if c[6] else "") for i, c in zip(_ids(CLOSED_LOOP_CASES, 3), CLOSED_LOOP_CASES)]
 
 
 @pytest.fixture(scope="module")
@@ -45,15 +55,17 @@ def rt():
     return dict(Oracle=Oracle, Solver=Solver, make_scenario=make_scenario)
 
 
-@pytest.mark.parametrize("name,B,steps,kw,env,fused", CLOSED_LOOP_CASES, ids=_ids(CLOSED_LOOP_CASES, 3))
-def test_warm_started_closed_loop_matches_oracle(rt, name, B, steps, kw, env, fused, monkeypatch):
+@pytest.mark.parametrize("name,B,steps,kw,env,fused,opts", CLOSED_LOOP_CASES, ids=_closed_loop_ids())
+def test_warm_started_closed_loop_matches_oracle(rt, name, B, steps, kw, env, fused, opts, monkeypatch):
     """previous_plan initialisation + multiplier warm start, plant = the model's ERK2 map.  Every step: same exit
     flags (1 <-> 2 flips only at the tolerance), applied control within 1e-6, and the warm start pays:
     fewer iterations than the cold first step.  Fused handles and handles of the pass kernels (there the multipliers of
-    a finished solve reach the next one through k_save_duals and the warm first pass of k_sweep)."""
+    a finished solve reach the next one through k_save_duals and the warm first pass of k_sweep).  ``opts``: option
+    overrides, the same on both sides (the oracle is built from them)."""
     from robot_mpcs_amd.fleet import flags_consistent
     _set_env(monkeypatch, env)
     sc = rt["make_scenario"](name, B=B, seed=41, **kw)
+    sc.desc["options"] = dict(sc.desc["options"], **opts)
     o = rt["Oracle"](sc.desc)
     s = rt["Solver"](sc.desc, max_batch=B)
     assert s.is_fused() == fused
@@ -191,6 +203,60 @@ def test_warm_loop_across_a_migration(rt, monkeypatch):
         x0 = np.where(good[:, None, None], np.concatenate([z[:, 1:], z[:, -1:]], axis=1), x0)
         x = np.where(good[:, None], z[:, 1, :nx], x)
     a.close(); b.close()
+
+
+def test_stall_counter_crosses_a_migration(rt, monkeypatch):
+    """The acceptable stop's ``stall`` word through k_migrate, where its carried value decides an exit
+    (pass_batch_cases.STALL_MIGRATION: 1280 unicycles on the pass kernels, a window of 3 stagnant iterations, two
+    warm-started control steps).  The warm second step migrates at the first look, and among its survivors are instances
+    whose run of three stagnant iterations began BEFORE the move and ends the solve with flag 2 after it.  A handle that
+    migrates against a twin created under RMPC_NO_MIGRATE, the compact workspace poisoned beforehand: both steps bit
+    for bit the same -- a counter k_migrate left behind is read as whatever the compact workspace holds, and those
+    instances stop at another iteration.  That such instances exist is asserted on the oracle's census, per
+    instance: survivor, flag 2, the last run begun within the passes before the migration (so: not reset after it), and
+    the device returns the oracle's flag and iteration count for them."""
+    name, B, seed, opts, env = STALL_MIGRATION
+    _set_env(monkeypatch, env)
+    sc = rt["make_scenario"](name, B=B, seed=seed)
+    sc.desc["options"] = dict(sc.desc["options"], **opts)
+    a = rt["Solver"](sc.desc, max_batch=B); a.set_warm_start(True)
+    monkeypatch.setenv("RMPC_NO_MIGRATE", "1")     # (read once, at rmpc_create)
+    b = rt["Solver"](sc.desc, max_batch=B); b.set_warm_start(True)
+    assert not a.is_fused() and not b.is_fused()
+    a.poison_lds()     # (the compact workspace too: NaN patterns, -1 as an int)
+    o = rt["Oracle"](sc.desc)
+    nx = o.nx
+    x, x0 = sc.xinit.copy(), sc.x0.copy()
+    steps = []
+    for t in range(2):
+        ra, rb = a.solve(x, x0, sc.params), b.solve(x, x0, sc.params)
+        pa, pb = a.last_solve_path(), b.last_solve_path()
+        print("stall migration step %d: %s | twin %s | flags %s" % (t, pa, pb, {int(f): int((ra["exitflag"] == f).sum()) for f in np.unique(ra["exitflag"])}))
+        assert not pa["fused"] and not pb["fused"] and pb["migrated_at"] == -1, (t, pa, pb)
+        assert pa["migrated_at"] >= 8 and pa["survivors"] >= 8, (t, pa)
+        for k in ("z", "exitflag", "iters", "obj", "kkt"):
+            assert np.array_equal(ra[k], rb[k]), (t, k, np.flatnonzero((ra[k] != rb[k]).reshape(B, -1).any(axis=1)))
+        steps.append((x.copy(), x0.copy(), ra, pa))
+        good = ra["exitflag"] >= 0
+        z = ra["z"]
+        x0 = np.where(good[:, None, None], np.concatenate([z[:, 1:], z[:, -1:]], axis=1), x0)
+        x = np.where(good[:, None], z[:, 1, :nx], x)
+    a.close(); b.close()
+    # ---- the oracle's census of the instances the device ended with flag 2 in the warm step ----
+    (xa, x0a, r0, _), (xb, x0b, r1, p1) = steps
+    carried = []
+    for i in np.flatnonzero(r1["exitflag"] == 2)[:32]:
+        c0 = o.solve_warm(xa[i], x0a[i], sc.params[i])
+        if c0["exitflag"] < 0 or c0["exitflag"] != r0["exitflag"][i]:
+            continue
+        ok, c1 = carried_stall_decides(o, sc.desc, xb[i], x0b[i], sc.params[i], c0["duals"], p1["migrated_at"])
+        if ok:
+            print("    instance %d: oracle flag %d after %d iterations and %d passes, stagnant from iteration %d on; device flag %d, %d iterations" % (
+                i, c1["exitflag"], c1["iters"], c1["passes"], c1["iters"] - opts["acc_iters"] + 1, r1["exitflag"][i], r1["iters"][i]))
+            assert r1["iters"][i] == c1["iters"], (i, r1["iters"][i], c1["iters"])
+            carried.append(int(i))
+    print("stall migration: %d survivors moved after %d passes; the carried counter decides the exit of %s" % (p1["survivors"], p1["migrated_at"], carried))
+    assert len(carried) >= 3, carried
 
 
 def test_mixed_fleet_shard_closed_loop(rt):
