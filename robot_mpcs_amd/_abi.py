@@ -17,7 +17,10 @@ raises ``RmpcError`` with the text that was not understood; nothing is skipped.
 The headers beside it are read the same way into tables of their own: ``include/rmpc_grid_large.h`` into
 ``large_constants`` / ``large_prototypes``, ``include/rmpc_assign_opt.h`` into ``assign_constants`` /
 ``assign_prototypes``, ``include/rmpc_tours.h`` into ``tours_constants`` / ``tours_prototypes``,
-``include/rmpc_timed_tours.h`` into ``timed_tours_constants`` / ``timed_tours_structs`` / ``timed_tours_prototypes``.
+``include/rmpc_timed_tours.h`` into ``timed_tours_constants`` / ``timed_tours_structs`` / ``timed_tours_prototypes``,
+``include/rmpc_timed_replan.h`` into ``timed_replan_constants`` / ``timed_replan_structs`` / ``timed_replan_prototypes``
+(it takes a pointer to the timed tours' struct, which ``parse`` is told of; uint64_t, the word of its reservation table,
+is typed for it).
 """
 import ctypes as C
 import os
@@ -32,8 +35,10 @@ ASSIGN_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_assign_opt.h")
 TOURS_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_tours.h")
 # the timed tours: likewise, with a struct of its own
 TIMED_TOURS_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_timed_tours.h")
+# the lifelong timed tours: likewise
+TIMED_REPLAN_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_timed_replan.h")
 
-_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "int": C.c_int, "long long": C.c_longlong}
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double, "int": C.c_int, "long long": C.c_longlong}
 _DECLARATION = re.compile(r"(?:const\s+)?(long long|\w+)(\s+|\s*(?:\*\s*)+)(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)")
 _DECLARATOR = re.compile(r"((?:\*\s*)*)(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)")
 
@@ -98,8 +103,9 @@ def _ctype(text, structs, constants, returns=False):
     raise RmpcError(f"rmpc.h: cannot type {text.strip()!r}")
 
 
-def parse(text):
-    """(constants, structs, prototypes) of a header's text"""
+def parse(text, known=None):
+    """(constants, structs, prototypes) of a header's text; ``known``: structs of a header it includes, which its
+    prototypes may point to"""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     constants = {k: int(a or b) for k, a, b in
                  re.findall(r"^[ \t]*#[ \t]*define[ \t]+(RMPC_\w+)[ \t]+(?:(\d+)|\((-\d+)\))[ \t]*$", text, flags=re.M)}
@@ -121,7 +127,7 @@ def parse(text):
         if m:
             name, restype = _ctype(m.group(1), structs, constants, returns=True)
             args = [] if m.group(2).strip() == "void" else m.group(2).split(",")
-            prototypes[name] = (restype, [_ctype(a, structs, constants)[1] for a in args])
+            prototypes[name] = (restype, [_ctype(a, {**(known or {}), **structs}, constants)[1] for a in args])
         elif s.split() != "typedef struct rmpc_handle rmpc_handle".split():
             raise RmpcError(f"rmpc.h: not a form the binding knows: {s!r}")
     if rest.split() != ["}"] * braces:
@@ -129,10 +135,10 @@ def parse(text):
     return constants, structs, prototypes
 
 
-def _read(path):
+def _read(path, known=None):
     try:
         with open(path) as f:
-            return parse(f.read())
+            return parse(f.read(), known)
     except OSError as e:
         raise RmpcError(f"{path} not found: the binding is derived from it ({e})") from None
 
@@ -142,3 +148,4 @@ large_constants, _, large_prototypes = _read(LARGE_HEADER)
 assign_constants, _, assign_prototypes = _read(ASSIGN_HEADER)
 tours_constants, _, tours_prototypes = _read(TOURS_HEADER)
 timed_tours_constants, timed_tours_structs, timed_tours_prototypes = _read(TIMED_TOURS_HEADER)
+timed_replan_constants, timed_replan_structs, timed_replan_prototypes = _read(TIMED_REPLAN_HEADER, timed_tours_structs)

@@ -39,6 +39,7 @@ ScanSearchArgs = _abi.structs["rmpc_scan_search"]     # rmpc_scan_match's fields
 TracksArgs = _abi.structs["rmpc_tracks"]              # one scan of B robots through the moving-obstacle tracker
 TimedPlanArgs = _abi.structs["rmpc_timed_plan"]       # one prioritised space-time plan of B robots for G orders
 TimedToursArgs = _abi.timed_tours_structs["rmpc_timed_tours"]     # the same through every robot's stops (rmpc_timed_tours.h)
+TimedReplanArgs = _abi.timed_replan_structs["rmpc_timed_replan"]  # what a re-plan adds to it (rmpc_timed_replan.h)
 
 # every symbol include/rmpc.h declares
 EXPORTED_SYMBOLS = list(_abi.prototypes)
@@ -50,6 +51,8 @@ ASSIGN_OPT_SYMBOLS = list(_abi.assign_prototypes)
 TOURS_SYMBOLS = list(_abi.tours_prototypes)
 # and every symbol include/rmpc_timed_tours.h declares
 TIMED_TOURS_SYMBOLS = list(_abi.timed_tours_prototypes)
+# and every symbol include/rmpc_timed_replan.h declares
+TIMED_REPLAN_SYMBOLS = list(_abi.timed_replan_prototypes)
 
 _lib = None
 
@@ -119,10 +122,10 @@ def load_library(path: str = LIB_PATH):
         pass
     L = C.CDLL(path)
     # the declarations of include/rmpc.h, include/rmpc_grid_large.h, include/rmpc_assign_opt.h, include/rmpc_tours.h
-    # and include/rmpc_timed_tours.h, nothing else
+    # include/rmpc_timed_tours.h and include/rmpc_timed_replan.h, nothing else
     for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items(),
                                       *_abi.assign_prototypes.items(), *_abi.tours_prototypes.items(),
-                                      *_abi.timed_tours_prototypes.items()):
+                                      *_abi.timed_tours_prototypes.items(), *_abi.timed_replan_prototypes.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
@@ -878,6 +881,57 @@ def timed_tours_follow_device(paths, idx_in, idx_out, pos, goal, W: int, x0: flo
                _ptr(idx_out), _ptr(pos), int(pos.stride(0)), int(W), float(x0), float(y0), float(cell), float(threshold),
                int(sep2), int(lag), _ptr(goal), None if blocked is None else _ptr(blocked), int(serve_at.shape[1]),
                _ptr(serve_at), _ptr(leg), _ptr(served), int(now), float(stop_tol), _stream_arg(stream))
+
+
+# limits and the status of the lifelong timed tours (include/rmpc_timed_replan.h)
+TIMED_RESERVE_MAX_PATHS, TIMED_KEPT = (_abi.timed_replan_constants["RMPC_TIMED_" + n] for n in ("RESERVE_MAX_PATHS", "KEPT"))
+
+
+def timed_reserve_words(H: int, W: int, T: int) -> int:
+    """the 64-bit words of a reservation table: T + 1 layers of H ceil(W / 64) (``rmpc_timed_reserve_words``)"""
+    L = load_library()
+    n = L.rmpc_timed_reserve_words(int(H), int(W), int(T))
+    if n < 0:
+        raise RmpcError("rmpc_timed_reserve_words failed: " + L.rmpc_last_error().decode())
+    return int(n)
+
+
+def timed_reserve_device(cells, res, H: int, W: int, sep2: int, lag: int = 1, use=None, clear: bool = True, stream=None):
+    """cells (P, T + 1) int32, use (P,) int32 or None, res an int64 tensor of ``timed_reserve_words(H, W, T)`` words --
+    contiguous device tensors: the discs of the cells on the map stamped into the table, after emptying it when
+    ``clear`` (``rmpc_timed_reserve_device``)."""
+    T = int(cells.shape[1]) - 1
+    if res.element_size() != 8 or res.numel() < timed_reserve_words(H, W, T):
+        raise ValueError("timed_reserve_device: need res of timed_reserve_words(H, W, T) 64-bit words")
+    _grid_call("rmpc_timed_reserve_device", int(H), int(W), T, int(cells.shape[0]), _ptr(cells),
+               None if use is None else _ptr(use), int(sep2), int(lag), int(bool(clear)), _ptr(res), _stream_arg(stream))
+
+
+def timed_replan_work_bytes(H: int, W: int, T: int, G: int) -> int:
+    """bytes of workspace of ``timed_tours_replan_device`` (``rmpc_timed_replan_work_bytes``)"""
+    L = load_library()
+    n = L.rmpc_timed_replan_work_bytes(int(H), int(W), int(T), int(G))
+    if n < 0:
+        raise RmpcError("rmpc_timed_replan_work_bytes failed: " + L.rmpc_last_error().decode())
+    return int(n)
+
+
+def timed_replan_args(work, res0=None, active=None, begin=None, clash=None) -> TimedReplanArgs:
+    """The ``rmpc_timed_replan`` of one re-plan: work a uint8 tensor of ``timed_replan_work_bytes``, res0 the reservation
+    table (64-bit words) or None, active, begin, clash (B,) int32 or None -- contiguous device tensors."""
+    a = TimedReplanArgs()
+    a.struct_size = C.sizeof(TimedReplanArgs)
+    opt = lambda t: None if t is None else t.data_ptr()
+    a.res0, a.active, a.begin, a.clash = opt(res0), opt(active), opt(begin), opt(clash)
+    a.work, a.work_bytes = work.data_ptr(), int(work.numel() * work.element_size())
+    a._keep = (work, res0, active, begin, clash)
+    return a
+
+
+def timed_tours_replan_device(args: TimedToursArgs, replan: TimedReplanArgs, stream=None):
+    """``timed_tours_plan_device`` inside the layer frame of a plan under way: around the reserved routes, for the
+    active robots, each from its begin layer (``rmpc_timed_tours_replan_device``).  ``args.work`` is not read."""
+    _grid_call("rmpc_timed_tours_replan_device", C.byref(args), C.byref(replan), _stream_arg(stream))
 
 
 class Solver:

@@ -150,7 +150,9 @@ __device__ __forceinline__ void timed_backtrack(const timed_word *hist, int L, i
   }
 }
 
-// stamping: the cells that conflict with path[t] into res[s], |s - t| <= lag, one (t, disc row, s) per thread and pass
+// stamping: the cells that conflict with path[t] into res[s], |s - t| <= lag, one (t, disc row, s) per thread and pass;
+// with kOnMap a path[t] outside [0, H W) stamps nothing (the plans' own paths never hold one)
+template <bool kOnMap = false>
 __device__ __forceinline__ void timed_stamp(timed_word *res, const int *__restrict__ path, int H, int W, int Wd, int L, int T,
                                             int lag, int rad, int sep2, int tid, int nt) {
   const int side = 2 * rad + 1, nl = 2 * lag + 1;
@@ -160,6 +162,7 @@ __device__ __forceinline__ void timed_stamp(timed_word *res, const int *__restri
     const int dr = rem / nl - rad, sl = t - lag + (rem - (rem / nl) * nl);
     if (sl < 0 || sl > T) continue;
     const int c = path[t], r = c / W + dr, col = c % W;
+    if (kOnMap && (c < 0 || c >= H * W)) continue;
     if (r < 0 || r >= H) continue;
     const int h = timed_half_width(dr, rad, sep2);
     const int lo = col - h > 0 ? col - h : 0, hi = col + h < W - 1 ? col + h : W - 1;

@@ -19,6 +19,7 @@
 #include "../../include/rmpc_assign_opt.h"
 #include "../../include/rmpc_tours.h"
 #include "../../include/rmpc_timed_tours.h"
+#include "../../include/rmpc_timed_replan.h"
 #include "rmpc_err.hpp"
 
 namespace rmpc {
@@ -106,6 +107,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_search.hpp"
 #include "rmpc_timed.hpp"
 #include "rmpc_timed_tours.hpp"
+#include "rmpc_timed_replan.hpp"
 #include "rmpc_track.hpp"
 
 using namespace rmpc;
@@ -832,12 +834,14 @@ static int timed_tours_stops_check(const std::string &who, int K) {
   return 0;
 }
 
-int rmpc_timed_tours_plan_device(const rmpc_timed_tours *p, void *stream) {
+// the argument checks of rmpc_timed_tours_plan_device; own_work: p->work is the call's workspace
+static int timed_tours_args_check(const rmpc_timed_tours *p, bool own_work) {
   const char *who = "timed tours";
   if (!p) return fail("null argument");
   if (p->struct_size != (int)sizeof(rmpc_timed_tours)) return fail("rmpc_timed_tours.struct_size mismatch");
   if (!p->grid || !p->start_cell || !p->stops || !p->len || !p->park_index || !p->fields || !p->goal_cells || !p->orders ||
-      !p->work || !p->paths || !p->status || !p->arrive || !p->key || !p->best || !p->serve_at || !p->served || !p->unserved)
+      (own_work && !p->work) || !p->paths || !p->status || !p->arrive || !p->key || !p->best || !p->serve_at || !p->served ||
+      !p->unserved)
     return fail("null argument");
   if (grid_check(p->H, p->W, p->movement) || grid_cells_check(who, p->H, p->W, false) ||
       timed_common_check(who, p->B, p->T, p->sep2, p->lag) || grid_fields_check(who, p->Gf, p->H, p->W) ||
@@ -849,18 +853,29 @@ int rmpc_timed_tours_plan_device(const rmpc_timed_tours *p, void *stream) {
     return fail("timed tours: need 1 <= G <= RMPC_TIMED_MAX_ORDERS = " + std::to_string(RMPC_TIMED_MAX_ORDERS));
   if (!grid_fits((long long)p->G * p->B, p->T + 1)) return fail("timed tours: G*B*(T+1) must not exceed INT_MAX");
   if (!grid_fits((long long)p->G * p->B, p->K)) return fail("timed tours: G*B*K must not exceed INT_MAX");
+  if (!own_work) return 0;
   const int64_t need = rmpc_timed_tours_work_bytes(p->H, p->W, p->T, p->G);
   if (need < 0) return -1;
   if (p->work_bytes < need)
     return fail("timed tours: the workspace holds " + std::to_string(p->work_bytes) + " bytes, " + std::to_string(need) +
                 " are needed (rmpc_timed_tours_work_bytes)");
-  if (use_device_of(p->grid)) return -1;
+  return 0;
+}
+
+static TimedGeom timed_geom(int H, int W, int T, int sep2) {
   TimedGeom q;
-  q.Wd = (p->W + 63) / 64;
-  q.L = p->H * q.Wd;
+  q.Wd = (W + 63) / 64;
+  q.L = H * q.Wd;
   q.rad = 0;
-  while ((q.rad + 1) * (q.rad + 1) < p->sep2) q.rad++;
-  q.per_order = timed_order_words(p->H, p->W, p->T);
+  while ((q.rad + 1) * (q.rad + 1) < sep2) q.rad++;
+  q.per_order = timed_order_words(H, W, T);
+  return q;
+}
+
+int rmpc_timed_tours_plan_device(const rmpc_timed_tours *p, void *stream) {
+  if (timed_tours_args_check(p, true)) return -1;
+  if (use_device_of(p->grid)) return -1;
+  const TimedGeom q = timed_geom(p->H, p->W, p->T, p->sep2);
   const size_t hist = (size_t)(p->T + 1) * q.L * sizeof(timed_word);
   const int nt = q.L <= 64 ? 64 : (q.L <= 128 ? 128 : kTimedThreads);      // a power of two: the end cell's reduction
   if (hist <= (size_t)kTimedHistLds)
@@ -888,6 +903,64 @@ int rmpc_timed_tours_follow_device(int B, int T, const int32_t *d_paths, const i
   hipLaunchKernelGGL(k_timed_tours_follow, dim3(B), dim3(256), 0, (hipStream_t)stream, (const int *)d_paths, B, T,
                      (const int *)d_idx_in, (int *)d_idx_out, d_pos, stride, W, x0, y0, cell, threshold, sep2, lag, d_goal,
                      (int *)d_blocked, K, (const int *)d_serve_at, (int *)d_leg, (int *)d_served, now, stop_tol);
+  return launch_status();
+}
+
+/* lifelong timed tours (rmpc_timed_replan.hpp, include/rmpc_timed_replan.h) */
+int64_t rmpc_timed_reserve_words(int H, int W, int T) {
+  if (grid_cells_check("timed reserve", H, W, false)) return -1;
+  if (T < 1 || T > RMPC_TIMED_MAX_T) return fail("timed reserve: need 1 <= T <= RMPC_TIMED_MAX_T");
+  return (int64_t)(T + 1) * H * ((W + 63) / 64);
+}
+
+int rmpc_timed_reserve_device(int H, int W, int T, int P, const int32_t *d_cells, const int32_t *d_use, int sep2, int lag,
+                              int clear, uint64_t *d_res, void *stream) {
+  const char *who = "timed reserve";
+  if (!d_cells || !d_res) return fail("null argument");
+  if (grid_cells_check(who, H, W, false) || timed_common_check(who, 1, T, sep2, lag)) return -1;
+  if (P < 1 || P > RMPC_TIMED_RESERVE_MAX_PATHS)
+    return fail("timed reserve: need 1 <= P <= RMPC_TIMED_RESERVE_MAX_PATHS = " + std::to_string(RMPC_TIMED_RESERVE_MAX_PATHS));
+  if (use_device_of(d_res)) return -1;
+  const TimedGeom q = timed_geom(H, W, T, sep2);
+  if (clear) {
+    const hipError_t e = hipMemsetAsync(d_res, 0, (size_t)(T + 1) * q.L * sizeof(timed_word), (hipStream_t)stream);
+    if (e != hipSuccess) return fail(std::string("timed reserve: hipMemsetAsync: ") + hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(k_timed_reserve, dim3(P), dim3(kTimedThreads), 0, (hipStream_t)stream, H, W, T, (const int *)d_cells,
+                     (const int *)d_use, sep2, lag, q.rad, q.Wd, q.L, (timed_word *)d_res);
+  return launch_status();
+}
+
+int64_t rmpc_timed_replan_work_bytes(int H, int W, int T, int G) {
+  if (grid_cells_check("timed replan", H, W, false)) return -1;
+  if (T < 1 || T > RMPC_TIMED_MAX_T || G < 1 || G > RMPC_TIMED_MAX_ORDERS)
+    return fail("timed replan: need 1 <= T <= RMPC_TIMED_MAX_T and 1 <= G <= RMPC_TIMED_MAX_ORDERS");
+  return ((int64_t)G * timed_order_words(H, W, T) + timed_standing_words(H, W)) * (int64_t)sizeof(timed_word);
+}
+
+int rmpc_timed_tours_replan_device(const rmpc_timed_tours *p, const rmpc_timed_replan *x, void *stream) {
+  if (!x) return fail("null argument");
+  if (x->struct_size != (int)sizeof(rmpc_timed_replan)) return fail("rmpc_timed_replan.struct_size mismatch");
+  if (timed_tours_args_check(p, false)) return -1;
+  if (!x->work) return fail("null argument");
+  const int64_t need = rmpc_timed_replan_work_bytes(p->H, p->W, p->T, p->G);
+  if (need < 0) return -1;
+  if (x->work_bytes < need)
+    return fail("timed replan: the workspace holds " + std::to_string(x->work_bytes) + " bytes, " + std::to_string(need) +
+                " are needed (rmpc_timed_replan_work_bytes)");
+  if (use_device_of(p->grid)) return -1;
+  const TimedGeom q = timed_geom(p->H, p->W, p->T, p->sep2);
+  timed_word *const work = (timed_word *)x->work;
+  hipLaunchKernelGGL(k_timed_standing, dim3((p->H * p->W + 255) / 256), dim3(256), 0, (hipStream_t)stream, *p, *x, q.Wd, q.L,
+                     work + (size_t)p->G * q.per_order);
+  const size_t hist = (size_t)(p->T + 1) * q.L * sizeof(timed_word);
+  const int nt = q.L <= 64 ? 64 : (q.L <= 128 ? 128 : kTimedThreads);      // a power of two: the end cell's reduction
+  if (hist <= (size_t)kTimedHistLds)
+    hipLaunchKernelGGL(k_timed_tours_replan<true>, dim3(p->G), dim3(nt), hist, (hipStream_t)stream, *p, *x, q, work);
+  else
+    hipLaunchKernelGGL(k_timed_tours_replan<false>, dim3(p->G), dim3(nt), 0, (hipStream_t)stream, *p, *x, q, work);
+  hipLaunchKernelGGL(k_timed_tours_best, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int64_t *)p->key,
+                     (const int *)p->unserved, p->G, (int *)p->best);
   return launch_status();
 }
 

@@ -6,7 +6,8 @@ and adds the batched, device-resident fleet API (``plan_batch``, ``RouteFollower
 fleet's conflict-free timed routes (``TimedRoutes``, ``TimedFollower``) and the pairing of robots with goals at the least
 sum of route costs (``GoalAssigner``) and tours of several goals per robot with a follower that stops at them
 (``TourPlanner``, ``TourFollower``; ``rmpc_tours_device`` / ``rmpc_follow_tour_device``, include/rmpc_tours.h) and the two
-together, timed tours through every robot's stops (``TimedTours``, ``TimedTourFollower``; include/rmpc_timed_tours.h).  The work is done
+together, timed tours through every robot's stops (``TimedTours``, ``TimedTourFollower``; include/rmpc_timed_tours.h), re-planned
+for part of the fleet while it is under way (``LifelongTours``, ``rebase``; include/rmpc_timed_replan.h).  The work is done
 by the ``rmpc_grid_*_device`` / ``rmpc_follow_path_device`` / ``rmpc_timed_*_device`` kernels (include/rmpc.h); there is no CPU path.  Importing
 the package needs no GPU.
 """
@@ -18,6 +19,7 @@ from .dispatch import GoalAssigner
 from .timed import TimedFollower, TimedRoutes, pick_spaced_routes, priority_orders
 from .tours import TourFollower, TourPlanner
 from .timed_tours import TimedTourFollower, TimedTours, pick_spaced_tours
+from .lifelong import LifelongTours, rebase
 
-__all__ = ["FREE", "OCC", "OccupancyGridMap", "a_star", "GlobalPlanner", "GoalAssigner", "RouteFollower", "TimedFollower", "TimedRoutes", "TimedTourFollower", "TimedTours", "TourFollower", "TourPlanner", "cell_xy", "cells_from_positions",
-           "pick_routes", "pick_spaced_routes", "pick_spaced_tours", "plan_batch", "png_values", "priority_orders", "replan", "shelf_map", "store_routes"]
+__all__ = ["FREE", "OCC", "OccupancyGridMap", "a_star", "GlobalPlanner", "GoalAssigner", "LifelongTours", "RouteFollower", "TimedFollower", "TimedRoutes", "TimedTourFollower", "TimedTours", "TourFollower", "TourPlanner", "cell_xy", "cells_from_positions",
+           "pick_routes", "pick_spaced_routes", "pick_spaced_tours", "plan_batch", "png_values", "priority_orders", "rebase", "replan", "shelf_map", "store_routes"]

@@ -142,6 +142,16 @@ class TimedTourFollower:
         self.idx, self._next = self._next, self.idx
         self.now += 1
 
+    def replace(self, paths, serve_at, idx, leg):
+        """swaps in new ``paths`` (B, T + 1), ``serve_at`` (B, K), indices and legs (B,) int32 -- a re-plan in the old
+        plan's layer frame (``lifelong.rebase``); ``served`` starts again at -1 for the new stops.  The tensors are
+        copied where they are not contiguous int32 already; idx and leg are always copied."""
+        import torch
+        self.paths, self.serve_at = paths.contiguous(), serve_at.contiguous()
+        self.idx, self.leg = idx.to(torch.int32).clone(), leg.to(torch.int32).clone()
+        self._next = torch.zeros_like(self.idx)
+        self.served = torch.full_like(self.serve_at, -1)
+
     def served_count(self):
         """() int64 on the device: the stops served so far"""
         return (self.served >= 0).sum()

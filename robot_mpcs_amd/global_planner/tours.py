@@ -95,32 +95,36 @@ class TourPlanner:
         self._sized(int(s.shape[0]))
         return s
 
-    def assign(self, start_cells, stream=None):
+    def assign(self, start_cells, available=None, stream=None):
         """start_cells (B,) -> (tours (B, K) int32, tour_len (B,) int32) on the device: every robot's goals in the order
-        it visits them, as indices into goal_cells.  Enqueues on ``stream`` (a ``torch.cuda.Stream``; None = the current
-        one) and never synchronises."""
+        it visits them, as indices into goal_cells.  ``available`` (B,): a robot whose entry is 0 gets start costs of
+        +inf, which the tours' rule never takes, and so no goal; None = every robot.  Enqueues on ``stream`` (a
+        ``torch.cuda.Stream``; None = the current one) and never synchronises."""
         import torch
         with torch.cuda.stream(stream):     # (None: the current one stays)
-            self._assign(self._starts(start_cells))
+            self._assign(self._starts(start_cells), available)
             return self.tours, self.tour_len
 
-    def _assign(self, s):
+    def _assign(self, s, available=None):
         import torch
         st = torch.cuda.current_stream(self.grid.device).cuda_stream
         _lib.grid_route_costs_device(self.grid, self.fields, s, self.start_cost, self.movement, self.occ, self.factor, stream=st)
+        if available is not None:
+            out = _dev_tensor(available, torch.int32, self.grid.device).reshape(-1) == 0
+            self.start_cost.masked_fill_(out[:, None], float("inf"))
         _lib.tours_device(self.start_cost, self.task_cost, self.tours, self.tour_len, self.tour_cost, self.mode, self.scale,
                           self.max_rounds, self.owner, self.count, self.total, self.span, self.build_steps, self.rounds,
                           self.work, stream=st)
 
-    def plan(self, start_cells, stream=None):
-        """``assign``, then the route of every robot through its goals: (paths (B, K max_len) int32, lens (B,) int32,
+    def plan(self, start_cells, stream=None, available=None):
+        """``assign`` (``available`` as there), then the route of every robot through its goals: (paths (B, K max_len) int32, lens (B,) int32,
         stop_at (B, K) int32).  Leg k runs from the cell before it (the start, then goal k - 1) down the field of goal k;
         the legs are joined without the doubled junction cell, and stop_at [b][k] is the index of goal k in the robot's
         path, -1 past its tour -- what ``TourFollower`` takes.  lens = 0 for a robot without a goal."""
         import torch
         with torch.cuda.stream(stream):
             s = self._starts(start_cells)
-            self._assign(s)
+            self._assign(s, available)
             st = torch.cuda.current_stream(self.grid.device).cuda_stream
             at = s
             for k in range(self.K):

@@ -1,0 +1,352 @@
+"""The lifelong timed tours' rules restated on the CPU from include/rmpc_timed_replan.h: ``reserve_ref`` and
+``replan_ref`` work on boolean layers as ``timed_tours_reference.plan_ref`` does (``replan_ref`` is that function with
+the header's changes 1 to 5), ``replan_walk`` a cell at a time on sets against the list of paths, reserved and planned,
+with no table, ``rebase_ref`` is ``robot_mpcs_amd.global_planner.lifelong.rebase`` in numpy.
+tests/test_timed_replan_cpu.py holds the two against each other and against hand-worked cases,
+tests/test_gpu_timed_replan.py holds the device against ``reserve_ref`` and ``replan_ref`` bit for bit."""
+import numpy as np
+
+from global_planner_reference import MOVES
+from timed_reference import OUTSIDE, _d2, _end_cell, _is_permutation
+from timed_tours_reference import _blank, _finish, _problem, _skipped
+
+KEPT = -9
+
+
+def reserve_ref(H, W, T, cells, sep2, lag=1, use=None, res=None):
+    """rmpc_timed_reserve_device on boolean layers (T + 1, H, W): ``res`` None = cleared first, else ORed into a copy"""
+    res = np.zeros((T + 1, H, W), dtype=bool) if res is None else np.array(res, dtype=bool)
+    rows, cols = np.mgrid[0:H, 0:W]
+    for p, path in enumerate(np.asarray(cells).reshape(-1, T + 1)):
+        if use is not None and int(use[p]) == 0:
+            continue
+        for t, c in enumerate(int(c) for c in path):
+            if 0 <= c < H * W:
+                res[max(0, t - lag):min(T, t + lag) + 1] |= (rows - c // W) ** 2 + (cols - c % W) ** 2 < sep2
+    return res
+
+
+def table_words(res):
+    """boolean layers (T + 1, H, W) -> the table's words (T + 1) * H * ceil(W / 64) as uint64"""
+    T1, H, W = res.shape
+    Wd = (W + 63) // 64
+    pad = np.zeros((T1, H, Wd * 64), dtype=np.uint64)
+    pad[:, :, :W] = res
+    return (pad.reshape(T1, H, Wd, 64) << np.arange(64, dtype=np.uint64)).sum(axis=3, dtype=np.uint64).ravel()
+
+
+def _roles(start, stops, lens, park_index, active, begin, HW, K, Gf, T):
+    """(kept, skip, begin) per robot: changes 2 and 3"""
+    B = len(start)
+    begin = np.zeros(B, dtype=np.int64) if begin is None else np.asarray(begin, dtype=np.int64)
+    kept = [active is not None and int(active[b]) == 0 for b in range(B)]
+    skip = [not kept[b] and (not 0 <= int(begin[b]) <= T or
+                             _skipped(int(start[b]), int(lens[b]), stops[b], int(park_index[b]), HW, K, Gf)) for b in range(B)]
+    return kept, skip, begin
+
+
+def _finish_replan(out, valid, lens, kept, K, T, clash):
+    lens = [0 if kept[b] else int(v) for b, v in enumerate(lens)]        # a kept robot's stops are not unserved
+    out = _finish(out, valid, lens, K, T)
+    out["clash"] = np.asarray(clash, dtype=np.int32)
+    return out
+
+
+def replan_ref(grid, start, stops, lens, park_index, fields, goal_cells, orders, T, sep2, lag=1, dwell=0, movement=4, occ=0.8,
+               res0=None, active=None, begin=None):
+    """The rule of rmpc_timed_tours_replan_device on boolean layers: ``plan_ref``'s dict and clash (B,) int32.  res0
+    (T + 1, H, W) bool or None; active, begin (B,) or None."""
+    grid, stops, orders, H, W, B, K, Gf, G = _problem(grid, start, stops, lens, park_index, fields, orders)
+    HW = H * W
+    free = ~(grid >= occ)
+    rows, cols = np.mgrid[0:H, 0:W]
+    disc = lambda c: (rows - c // W) ** 2 + (cols - c % W) ** 2 < sep2
+    moves = [(dc, dr) for dc, dr, _ in MOVES[movement]]
+    kept, skip, begin = _roles(start, stops, lens, park_index, active, begin, HW, K, Gf, T)
+    planned = [b for b in range(B) if not kept[b] and not skip[b]]
+    clash = [int(b in planned and res0 is not None and bool(res0[begin[b], int(start[b]) // W, int(start[b]) % W]))
+             for b in range(B)]
+    out = _blank(G, B, T, K)
+    valid = [_is_permutation(orders[g], B) for g in range(G)]
+    for g in range(G):
+        if not valid[g]:
+            continue
+        res = np.zeros((T + 1, H, W), dtype=bool) if res0 is None else np.array(res0, dtype=bool)       # change 1
+        for b in (int(b) for b in orders[g]):
+            if kept[b]:                                                                                 # change 2
+                out["status"][g, b], out["arrive"][g, b] = KEPT, 0
+                continue
+            if skip[b]:
+                out["status"][g, b] = OUTSIDE
+                continue
+            # change 4: stand[t] = the cells that conflict with the start of another planned robot r, t <= begin[r] + lag
+            stand = np.zeros((T + 1, H, W), dtype=bool)
+            for r in planned:
+                if r != b:
+                    stand[:min(T, int(begin[r]) + lag) + 1] |= disc(int(start[r]))
+            reach = np.zeros((T + 1, H, W), dtype=bool)
+            p = np.full(T + 1, -1, dtype=np.int32)
+
+            def sweep(t):
+                pad = np.pad(reach[t - 1], 1)
+                n = reach[t - 1].copy()
+                for dc, dr in moves:
+                    n |= pad[1 - dr:1 - dr + H, 1 - dc:1 - dc + W]
+                n &= free & ~res[t] & ~stand[t]
+                reach[t] = n
+                return n.any()
+
+            def back(c, te, t0):
+                """p[t0 .. te - 1] from (te, c)"""
+                for t in range(te, t0, -1):
+                    r, col = divmod(c, W)
+                    if not reach[t - 1, r, col]:
+                        for dc, dr in moves:
+                            rr, cc = r - dr, col - dc
+                            if 0 <= rr < H and 0 <= cc < W and reach[t - 1, rr, cc]:
+                                c = rr * W + cc
+                                break
+                    p[t - 1] = c
+
+            def end_leg(D, t0, f):
+                te = f - 1 if f else T
+                end = _end_cell(np.flatnonzero(reach[te].ravel()), np.asarray(D).ravel())
+                p[te:] = end
+                back(end, te, t0)
+                return te, end
+
+            t0, at, n = int(begin[b]), int(start[b]), int(lens[b])                                      # change 3
+            p[:t0 + 1] = at
+            status = arrive = None
+            for j in range(n):
+                gi = int(stops[b, j])
+                s = int(goal_cells[gi])
+                inside = 0 <= s < HW
+                reach[t0:] = False
+                reach[t0, at // W, at % W] = True
+                a, f, t = None, 0, t0
+                while True:
+                    if inside and reach[t, s // W, s % W] and t + dwell <= T and not any(
+                            res[u, s // W, s % W] or stand[u, s // W, s % W] for u in range(t + 1, t + dwell + 1)):
+                        a = t
+                        break
+                    if t == T:
+                        break
+                    t += 1
+                    if not sweep(t):
+                        f = t
+                        break
+                if a is None:
+                    end_leg(fields[gi], t0, f)
+                    status, arrive = f, T + 1
+                    break
+                p[a:a + dwell + 1] = s
+                back(s, a, t0)
+                out["serve_at"][g, b, j] = a
+                out["served"][g, b] += 1
+                t0, at = a + dwell, s
+            if status is None:
+                reach[t0:] = False
+                reach[t0, at // W, at % W] = True
+                f = 0
+                for t in range(t0 + 1, T + 1):
+                    if not sweep(t):
+                        f = t
+                        break
+                te, end = end_leg(fields[int(park_index[b])], t0, f)
+                status, arrive = f, T + 1
+                if end == int(goal_cells[int(park_index[b])]):
+                    arrive = te
+                    while arrive > t0 and p[arrive - 1] == end:
+                        arrive -= 1
+            out["paths"][g, b], out["status"][g, b], out["arrive"][g, b] = p, status, arrive
+            for t in range(T + 1):
+                res[max(0, t - lag):min(T, t + lag) + 1] |= disc(int(p[t]))
+    return _finish_replan(out, valid, lens, kept, K, T, clash)
+
+
+def replan_walk(grid, start, stops, lens, park_index, fields, goal_cells, orders, T, sep2, lag=1, dwell=0, movement=4, occ=0.8,
+                reserved_paths=(), active=None, begin=None):
+    """The same rule a cell at a time, with no table: ``reserved_paths`` is a list of (path (T + 1,), sep2) that stand for
+    res0 (cells outside the map reserve nothing); a cell is reserved at t when it conflicts with a cell that one of them,
+    or a robot planned earlier, holds within lag layers of t."""
+    grid, stops, orders, H, W, B, K, Gf, G = _problem(grid, start, stops, lens, park_index, fields, orders)
+    HW = H * W
+    moves = [(dc, dr) for dc, dr, _ in MOVES[movement]]
+    kept, skip, begin = _roles(start, stops, lens, park_index, active, begin, HW, K, Gf, T)
+    fixed = [([int(c) for c in q], int(s2)) for q, s2 in reserved_paths]
+    window = lambda t: range(max(0, t - lag), min(T, t + lag) + 1)
+
+    def fixed_at(c, t):
+        return any(0 <= q[u] < HW and _d2(c, q[u], W) < s2 for q, s2 in fixed for u in window(t))
+
+    clash = [int(not kept[b] and not skip[b] and fixed_at(int(start[b]), int(begin[b]))) for b in range(B)]
+    out = _blank(G, B, T, K)
+    valid = [_is_permutation(orders[g], B) for g in range(G)]
+    for g in range(G):
+        if not valid[g]:
+            continue
+        planned = []
+        for b in (int(b) for b in orders[g]):
+            if kept[b]:
+                out["status"][g, b], out["arrive"][g, b] = KEPT, 0
+                continue
+            if skip[b]:
+                out["status"][g, b] = OUTSIDE
+                continue
+            others = [(int(start[r]), int(begin[r]) + lag) for r in range(B) if r != b and not kept[r] and not skip[r]]
+
+            def reserved(c, t):
+                """what rule 3 and the held test ask beyond the grid"""
+                if any(t <= until and _d2(c, sr, W) < sep2 for sr, until in others):
+                    return True
+                return fixed_at(c, t) or any(_d2(c, int(q[u]), W) < sep2 for q in planned for u in window(t))
+
+            def grow(layer, t):
+                cand = set()
+                for c in layer:
+                    r, col = divmod(c, W)
+                    cand.add(c)
+                    for dc, dr in moves:
+                        if 0 <= r + dr < H and 0 <= col + dc < W:
+                            cand.add((r + dr) * W + col + dc)
+                return {c for c in cand if not grid[c // W, c % W] >= occ and not reserved(c, t)}
+
+            def trace(layers, c):
+                """the cells from the first layer to the last one, ending on c: wait first, else the first move"""
+                cells = [c]
+                for layer in reversed(layers[:-1]):
+                    if c not in layer:
+                        r, col = divmod(c, W)
+                        for dc, dr in moves:
+                            rr, cc = r - dr, col - dc
+                            if 0 <= rr < H and 0 <= cc < W and rr * W + cc in layer:
+                                c = rr * W + cc
+                                break
+                    cells.append(c)
+                return cells[::-1]
+
+            at, status, arrive, serve = int(start[b]), None, T + 1, []
+            p = [at] * (int(begin[b]) + 1)                   # the standing layers; the last cell is where the robot stands
+            todo = [int(goal_cells[int(v)]) for v in stops[b, :int(lens[b])]] + [None]        # None: the parking leg
+            for j, s in enumerate(todo):
+                t0 = len(p) - 1
+                layers, f, a = [{at}], 0, None
+                while True:
+                    t = t0 + len(layers) - 1
+                    if s is not None and s in layers[-1] and t + dwell <= T and not any(
+                            reserved(s, u) for u in range(t + 1, t + dwell + 1)):
+                        a = t
+                        break
+                    if t == T:
+                        break
+                    nxt = grow(layers[-1], t + 1)
+                    if not nxt:
+                        f = t + 1
+                        break
+                    layers.append(nxt)
+                if a is not None:
+                    p = p[:t0] + trace(layers, s) + [s] * dwell
+                    serve.append(a)
+                    at = s
+                    continue
+                gi = int(park_index[b]) if s is None else int(stops[b, j])
+                end = _end_cell(np.array(sorted(layers[-1])), np.asarray(fields[gi]).ravel())
+                p = p[:t0] + trace(layers, end)
+                te = len(p) - 1
+                p += [end] * (T - te)
+                status = f
+                if s is None and end == int(goal_cells[gi]):
+                    arrive = te
+                    while arrive > t0 and p[arrive - 1] == end:
+                        arrive -= 1
+                break
+            out["paths"][g, b], out["status"][g, b], out["arrive"][g, b] = p, status, arrive
+            out["serve_at"][g, b, :len(serve)], out["served"][g, b] = serve, len(serve)
+            planned.append(p)
+    return _finish_replan(out, valid, lens, kept, K, T, clash)
+
+
+def rebase_ref(paths, serve_at, idx, leg, active):
+    """``lifelong.rebase`` in numpy: (paths', serve_at', idx', begin, start, m).  paths (B, T + 1), serve_at (B, K), idx,
+    leg, active (B,)."""
+    paths, serve_at = np.asarray(paths), np.asarray(serve_at)
+    B, T = paths.shape[0], paths.shape[1] - 1
+    idx = np.clip(np.asarray(idx), 0, T)
+    e = idx.copy()
+    for b in range(B):
+        while active[b] and e[b] > 0 and paths[b, e[b] - 1] == paths[b, idx[b]]:
+            e[b] -= 1
+    m = int(e.min())
+    shifted = paths[:, np.minimum(np.arange(T + 1) + m, T)]
+    sa = np.full_like(serve_at, -1)
+    for b in range(B):
+        for j in range(serve_at.shape[1]):
+            if j >= leg[b] and serve_at[b, j] >= 0:
+                sa[b, j] = serve_at[b, j] - m
+    new_idx = (e - m).astype(np.int32)
+    return shifted.astype(np.int32), sa.astype(np.int32), new_idx, new_idx.copy(), paths[np.arange(B), idx].astype(np.int32), m
+
+
+# ---- LifelongTours, composed from the restatements ----------------------------------------------------------------------
+def _pad(a, K):
+    out = np.full((a.shape[0], K), -1, dtype=np.int32)
+    out[:, :a.shape[1]] = a
+    return out
+
+
+def _tours(grid, fields, at, picks, K, available=None):
+    """the tours' restatement for robots on the cells ``at`` over the fields of ``picks``; unavailable robots get +inf"""
+    from assignment_reference import route_costs_ref
+    from tours_reference import tours_problem_ref
+    start_cost = route_costs_ref(grid, fields, at)
+    if available is not None:
+        start_cost[np.asarray(available) == 0] = np.inf
+    out = tours_problem_ref(start_cost, route_costs_ref(grid, fields, picks), min(K, len(picks)))
+    return _pad(out["tours"], K), out["len"].astype(np.int32)
+
+
+def _left(picks, tours, served, rows):
+    placed = {int(t) for b in np.flatnonzero(rows) for t in tours[b, :int(served[b])]}
+    return np.array([int(c) for i, c in enumerate(picks) if i not in placed], dtype=np.int32)
+
+
+def start_ref(grid, starts, picks, K, T, sep2, lag, dwell, orders, movement=8):
+    """``LifelongTours.start``: (state, picks left); state = dict(paths (B, T + 1), serve_at (B, K), idx, leg, nstops (B,))"""
+    from timed_reference import fields_for
+    from timed_tours_reference import plan_ref
+    starts, picks = np.asarray(starts, np.int32), np.asarray(picks, np.int32)
+    B, Tn = len(starts), len(picks)
+    fields = fields_for(grid, picks, movement)
+    tours, lens = _tours(grid, fields, starts, picks, K)
+    park = np.where(lens > 0, tours[np.arange(B), np.maximum(lens, 1) - 1], Tn + np.arange(B)).astype(np.int32)
+    out = plan_ref(grid, starts, np.maximum(tours, 0), lens, park, np.concatenate([fields, fields_for(grid, starts, movement)]),
+                   np.concatenate([picks, starts]), orders, T, sep2, lag, dwell, movement)
+    g = int(out["best"][0])
+    state = dict(paths=out["paths"][g].copy(), serve_at=out["serve_at"][g].copy(), idx=np.zeros(B, np.int32),
+                 leg=np.zeros(B, np.int32), nstops=out["served"][g].copy(), failures=int((out["status"][g] > 0).sum()), clash=0)
+    return state, _left(picks, tours, out["served"][g], np.ones(B, bool))
+
+
+def dispatch_ref(grid, state, picks, K, T, sep2, lag, dwell, orders, movement=8):
+    """``LifelongTours.dispatch(picks, "idle")`` on ``state`` (changed in place) -> the picks left"""
+    from timed_reference import fields_for
+    picks = np.asarray(picks, np.int32)
+    H, W = grid.shape
+    paths, sa, idx, leg = state["paths"], state["serve_at"], state["idx"], state["leg"]
+    B, Tn = len(idx), len(picks)
+    here = paths[np.arange(B), np.clip(idx, 0, T)]
+    idle = ((leg >= state["nstops"]) & (here == paths[:, T])).astype(np.int32)
+    p1, sa1, idx1, begin, start, m = rebase_ref(paths, sa, idx, leg, idle)
+    fields = fields_for(grid, picks, movement)
+    tours, lens = _tours(grid, fields, start, picks, K, idle)
+    goal_cells = np.concatenate([picks, np.repeat(start, K), start]).astype(np.int32)
+    park = np.where(lens > 0, tours[np.arange(B), np.maximum(lens, 1) - 1], Tn + B * K + np.arange(B)).astype(np.int32)
+    res0 = reserve_ref(H, W, T, p1, sep2, lag, use=1 - idle)
+    out = replan_ref(grid, start, np.maximum(tours, 0), lens, park, fields_for(grid, goal_cells, movement), goal_cells, orders, T,
+                     sep2, lag, dwell, movement, res0=res0, active=idle, begin=begin)
+    g, on = int(out["best"][0]), idle.astype(bool)
+    state.update(paths=np.where(on[:, None], out["paths"][g], p1), serve_at=np.where(on[:, None], out["serve_at"][g], sa1),
+                 idx=idx1, leg=np.where(on, 0, leg).astype(np.int32), nstops=np.where(on, out["served"][g], state["nstops"]),
+                 failures=state["failures"] + int((out["status"][g] > 0).sum()), clash=state["clash"] + int(out["clash"].sum()))
+    return _left(picks, tours, out["served"][g], on)
