@@ -1,8 +1,9 @@
 // rmpc_timed_replan.hpp -- lifelong timed tours (include/rmpc_timed_replan.h), included by rmpc_world.hip
 // behind rmpc_timed.hpp and rmpc_timed_tours.hpp: the reservation table as a public input (k_timed_reserve stamps given
 // paths into it), and k_timed_tours_replan, which is k_timed_tours_plan on a table that starts filled, with kept
-// robots, a begin layer per robot and the standing rule.  The layer sweep, end-cell reduction, backtrack and stamping
-// are those of rmpc_timed.hpp, called as they stand.
+// robots, a begin layer per robot and the standing rule.  The route of a robot is timed_robot of rmpc_timed.hpp, reached
+// through timed_tours_robot of rmpc_timed_tours.hpp as in k_timed_tours_plan; the standing rule is its template
+// parameter, TimedStandingRule below.
 //
 // The standing rule asks of a cell c and a layer t whether c conflicts with the start of another active robot r with
 // t <= begin[r] + lag.  until(c) = the largest begin[r] + lag over the robots whose start conflicts with c answers it for
@@ -92,22 +93,42 @@ __global__ __launch_bounds__(256) void k_timed_standing(rmpc_timed_tours p, rmpc
   st.top[3 * c] = v1; st.top[3 * c + 1] = o1; st.top[3 * c + 2] = v2;
 }
 
-// mask[w] = the cells with until_b(c) >= t; returns this thread's least until_b(c) >= t (INT_MAX without one): the mask
-// holds for every layer up to the least of them
-__device__ __forceinline__ int timed_standing_mask(const int *__restrict__ top, int b, int t, timed_word *__restrict__ mask,
-                                                   int W, int Wd, int L, int tid, int nt) {
-  int least = INT_MAX;
-  for (int w = tid; w < L; w += nt) {
-    const int r = w / Wd, c0 = (w - r * Wd) * 64;
-    timed_word word = 0;
-    for (int bb = 0; bb < 64 && c0 + bb < W; bb++) {
-      const int u = timed_until(top, r * W + c0 + bb, b);
-      if (u >= t) { word |= 1ull << bb; least = u < least ? u : least; }
-    }
-    mask[w] = word;
+// The standing rule as a start rule of timed_robot (rmpc_timed.hpp): `mask` = the cells with until_b(c) >= t, rebuilt when
+// t passes the least until_b(c) that it holds; it binds up to the largest begin + lag of the other planned robots.
+struct TimedStandingRule {
+  TimedDims d;
+  TimedStanding st;
+  timed_word *mask;
+  int *mask_least;           // (one word of LDS) the least until_b(c) >= t over the cells of the mask
+  int b, bound, mask_to;     // the robot, the last layer the rule binds in, the last layer the mask holds for
+
+  __device__ __forceinline__ void prepare(int robot, int) {
+    b = robot;
+    bound = st.all[1] == b ? st.all[2] : st.all[0];
+    mask_to = -1;
   }
-  return least;
-}
+  __device__ __forceinline__ bool early(int t) {
+    const bool binds = t <= bound;
+    if (binds && t > mask_to) {                          // (uniform)
+      if (d.tid == 0) *mask_least = INT_MAX;
+      __syncthreads();
+      int least = INT_MAX;                               // this thread's
+      const int *const top = st.top;
+      const int robot = b;
+      timed_pack_rows(mask, d, [&](int c) {
+        const int u = timed_until(top, c, robot);
+        if (u < t) return false;
+        least = u < least ? u : least;
+        return true;
+      });
+      if (least != INT_MAX) atomicMin(mask_least, least);
+      __syncthreads();
+      mask_to = *mask_least == INT_MAX ? bound : *mask_least;
+    }
+    return binds;
+  }
+  __device__ __forceinline__ int closed_until(int sc, int, timed_word) const { return timed_until(st.top, sc, b); }
+};
 
 // One workgroup per path: rule 8 for the cells that lie on the map
 __global__ __launch_bounds__(kTimedThreads) void k_timed_reserve(int H, int W, int T, const int *__restrict__ cells,
@@ -118,158 +139,49 @@ __global__ __launch_bounds__(kTimedThreads) void k_timed_reserve(int H, int W, i
   timed_stamp<true>(res, cells + (size_t)p * (T + 1), H, W, Wd, L, T, lag, rad, sep2, threadIdx.x, kTimedThreads);
 }
 
-// One workgroup per priority order, as k_timed_tours_plan; `mask` is the workspace's word row that holds `later` there.
+// One workgroup per priority order, as k_timed_tours_plan, on a table that starts as res0, with kept robots, a begin
+// layer per robot and the standing rule, whose mask is the workspace's word row that holds `later` there.
 template <bool kLds>
 __global__ __launch_bounds__(kTimedThreads) void k_timed_tours_replan(rmpc_timed_tours p, rmpc_timed_replan x, TimedGeom q,
                                                                       timed_word *__restrict__ work) {
-#pragma clang fp contract(off)
-  extern __shared__ timed_word timed_lds[];
-  __shared__ unsigned seen[RMPC_TIMED_MAX_ROBOTS / 32];
   __shared__ double red_d[kTimedThreads];
   __shared__ int red_c[kTimedThreads];
   __shared__ int mask_least;
-  const int g = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int H = p.H, W = p.W, HW = H * W, B = p.B, T = p.T, K = p.K, Wd = q.Wd, L = q.L, lag = p.lag, sep2 = p.sep2, rad = q.rad;
-  const int dwell = p.dwell;
+  const int g = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, B = p.B, T = p.T, K = p.K;
+  const TimedDims d = {p.H, p.W, q.Wd, q.L, T, p.lag, p.sep2, q.rad, p.movement, tid, nt};
   const int *const ord = p.orders + (size_t)g * B;
-  int *const status = p.status + (size_t)g * B, *const arrive = p.arrive + (size_t)g * B;
-  int *const served = p.served + (size_t)g * B;
-  int *const paths = p.paths + (size_t)g * B * (T + 1);
-  int *const serve_at = p.serve_at + (size_t)g * B * K;
-
-  // the order must be a permutation of 0 .. B - 1
-  for (int i = tid; i < RMPC_TIMED_MAX_ROBOTS / 32; i += nt) seen[i] = 0;
-  __syncthreads();
-  bool bad = false;
-  for (int k = tid; k < B; k += nt) {
-    const int v = ord[k];
-    if (v < 0 || v >= B) bad = true;
-    else {
-      const unsigned bit = 1u << (v & 31);
-      if (atomicOr(&seen[v >> 5], bit) & bit) bad = true;
-    }
-  }
-  if (__syncthreads_or(bad)) {
-    for (int k = tid; k < B; k += nt) { status[k] = RMPC_TIMED_BAD_ORDER; arrive[k] = T + 1; served[k] = 0; }
-    for (size_t i = tid; i < (size_t)B * (T + 1); i += nt) paths[i] = -1;
-    for (size_t i = tid; i < (size_t)B * K; i += nt) serve_at[i] = -1;
-    if (tid == 0) { p.key[g] = INT64_MAX; p.unserved[g] = INT_MAX; }
+  const TimedOut o = timed_tours_out(p, g);
+  if (timed_order_bad(ord, B, tid, nt)) {
+    timed_bad_order<true>(o, B, T, K, tid, nt);
     return;
   }
 
-  timed_word *const res = work + (size_t)g * q.per_order;
-  timed_word *const hist = kLds ? timed_lds : res + (size_t)(T + 1) * L;
-  timed_word *const freeb = res + 2 * (size_t)(T + 1) * L;
-  timed_word *const mask = freeb + L;
-  const TimedStanding st = timed_standing_at(work + (size_t)gridDim.x * q.per_order);
-
-  for (size_t i = tid; i < (size_t)(T + 1) * L; i += nt) res[i] = x.res0 ? x.res0[i] : 0ull;
-  for (int w = tid; w < L; w += nt) {
-    const int r = w / Wd, c0 = (w - r * Wd) * 64;
-    timed_word word = 0;
-    for (int b = 0; b < 64 && c0 + b < W; b++)
-      if (!(p.grid[r * W + c0 + b] >= p.occ_threshold)) word |= 1ull << b;
-    freeb[w] = word;
-  }
+  const TimedWork wk = timed_work_at<kLds>(work, g, q, T);
+  for (size_t i = tid; i < (size_t)(T + 1) * d.L; i += nt) wk.res[i] = x.res0 ? x.res0[i] : 0ull;
+  timed_free_mask(wk.freeb, p.grid, p.occ_threshold, d);
   __syncthreads();
+  TimedStandingRule rule = {d, timed_standing_at(work + (size_t)gridDim.x * q.per_order), wk.mask, &mask_least, 0, 0, 0};
 
-  long long fails = 0, late = 0, sum = 0, uns = 0;       // (thread 0's)
+  TimedKey key;
   for (int k = 0; k < B; k++) {
-    const int b = ord[k], n = p.len[b], e = st.eff[b];
-    int *const path = paths + (size_t)b * (T + 1);
-    int *const sa = serve_at + (size_t)b * K;
-    for (int j = tid; j < K; j += nt) sa[j] = -1;
+    const int b = ord[k], e = rule.st.eff[b];
+    for (int j = tid; j < K; j += nt) o.serve_at[(size_t)b * K + j] = -1;
     if (e < 0) {
-      for (int t = tid; t <= T; t += nt) path[t] = -1;
+      for (int t = tid; t <= T; t += nt) o.paths[(size_t)b * (T + 1) + t] = -1;
       if (tid == 0) {
-        served[b] = 0;
-        if (e == kTimedKept) { status[b] = RMPC_TIMED_KEPT; arrive[b] = 0; }
+        o.served[b] = 0;
+        if (e == kTimedKept) { o.status[b] = RMPC_TIMED_KEPT; o.arrive[b] = 0; }
         else {
-          status[b] = RMPC_GRID_OUTSIDE; arrive[b] = T + 1;
-          late++; sum += T + 1; uns += n >= 0 && n <= K ? n : 0;
+          o.status[b] = RMPC_GRID_OUTSIDE; o.arrive[b] = T + 1;
+          key.skipped(T, p.len[b], K);
         }
       }
       continue;
     }
-    const int s = p.start_cell[b], begin = e - lag;
-    // the standing rule binds up to the largest begin + lag of the other planned robots
-    const int bound = st.all[1] == b ? st.all[2] : st.all[0];
-    int mask_to = -1;                  // the mask in `mask` holds for the layers up to this one
-    for (int t = tid; t < begin; t += nt) path[t] = s;
-
-    int t0 = begin, at = s, done = 0;  // the state; done: stops served
-    int f = 0, te = 0, end = 0;        // how the last leg ended
-    bool failed = false;
-    for (int j = 0; j <= n && !failed; j++) {              // leg n is the parking leg (rule 4)
-      const bool parking = j == n;
-      const int gi = parking ? p.park_index[b] : p.stops[(size_t)b * K + j];
-      const int sc = parking ? -1 : p.goal_cells[gi];
-      const bool inside = sc >= 0 && sc < HW;              // a stop outside the map is in no layer
-      const int sw = inside ? (sc / W) * Wd + ((sc % W) >> 6) : 0;
-      const timed_word sbit = inside ? 1ull << ((sc % W) & 63) : 0ull;
-      timed_seed_layer(hist + (size_t)t0 * L, Wd, L, at / W, at % W, tid, nt);
-      __syncthreads();
-      int a = -1;
-      f = 0;
-      for (int t = t0; t <= T; t++) {                      // at most T - t0 layers
-        if (t > t0) {
-          const bool early = t <= bound;
-          if (early && t > mask_to) {                      // (uniform)
-            if (tid == 0) mask_least = INT_MAX;
-            __syncthreads();
-            const int least = timed_standing_mask(st.top, b, t, mask, W, Wd, L, tid, nt);
-            if (least != INT_MAX) atomicMin(&mask_least, least);
-            __syncthreads();
-            mask_to = mask_least == INT_MAX ? bound : mask_least;
-          }
-          const bool any = timed_sweep_layer(hist + (size_t)(t - 1) * L, hist + (size_t)t * L, res + (size_t)t * L, freeb,
-                                             mask, early, H, Wd, L, p.movement, tid, nt);
-          if (!__syncthreads_or(any)) { f = t; break; }
-        }
-        if (!parking && t + dwell <= T && (hist[(size_t)t * L + sw] & sbit)) {
-          bool held = true;
-          const int until = timed_until(st.top, sc, b);
-          for (int u = t + 1; u <= t + dwell && held; u++) {
-            if (__hip_atomic_load(res + (size_t)u * L + sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & sbit) held = false;
-            if (u <= until) held = false;
-          }
-          if (held) { a = t; break; }
-        }
-      }
-      if (a < 0) {
-        // rules 3 and 4: the robot goes as near the leg's goal as it got and stays
-        te = f ? f - 1 : T;
-        end = timed_end_cell(p.fields + (size_t)gi * HW, hist + (size_t)te * L, W, Wd, L, red_d, red_c, tid, nt);
-        failed = !parking;
-        break;
-      }
-      for (int u = a + tid; u <= a + dwell; u += nt) path[u] = sc;
-      if (tid == 0) {
-        timed_backtrack(hist, L, H, W, Wd, p.movement, path, sc, a, t0);
-        sa[j] = a;
-      }
-      t0 = a + dwell; at = sc; done++;
-      __syncthreads();                                     // the backtrack has read the layers the next leg overwrites
-    }
-    for (int t = te + tid; t <= T; t += nt) path[t] = end;
-    if (tid == 0) {
-      timed_backtrack(hist, L, H, W, Wd, p.movement, path, end, te, t0);
-      int a = T + 1;
-      if (!failed && end == p.goal_cells[p.park_index[b]]) {
-        a = te;
-        while (a > t0 && path[a - 1] == end) a--;
-      }
-      status[b] = f; arrive[b] = a; served[b] = done;
-      fails += f > 0; late += a > T; sum += a; uns += n - done;
-    }
-    __syncthreads();
-    timed_stamp(res, path, H, W, Wd, L, T, lag, rad, sep2, tid, nt);
-    __syncthreads();
+    rule.prepare(b, p.start_cell[b]);
+    timed_tours_robot(p, o, d, wk, rule, b, e - d.lag, key, red_d, red_c);
   }
-  if (tid == 0) {
-    p.key[g] = (int64_t)((fails << 44) | (late << 32) | sum);
-    p.unserved[g] = (int)uns;
-  }
+  if (tid == 0) { *o.key = key.key(); *o.unserved = (int)key.uns; }
 }
 
 }  // namespace rmpc

@@ -208,6 +208,17 @@ static int grid_descent(const char *who, Kernel kernel, int H, int W, const doub
   return launch_status();
 }
 
+// rmpc_timed_plan_device, rmpc_timed_tours_plan_device and rmpc_timed_tours_replan_device: one workgroup per order of
+// a planner kernel, `lds` with the history in LDS where it fits, `mem` with it in the workspace beyond.  It stands here,
+// with the other launch templates and not in the timed block below, because a template cannot lie inside extern "C".
+template <class Kernel, class... Args>
+static void timed_launch(Kernel lds, Kernel mem, int G, int T, const TimedGeom &q, void *stream, Args... args) {
+  const size_t hist = (size_t)(T + 1) * q.L * sizeof(timed_word);
+  const int nt = q.L <= 64 ? 64 : (q.L <= 128 ? 128 : kTimedThreads);      // a power of two: the end cell's reduction
+  if (hist <= (size_t)kTimedHistLds) hipLaunchKernelGGL(lds, dim3(G), dim3(nt), hist, (hipStream_t)stream, args...);
+  else hipLaunchKernelGGL(mem, dim3(G), dim3(nt), 0, (hipStream_t)stream, args...);
+}
+
 extern "C" {
 
 int rmpc_advance_obstacles_device(int B, int nobst, double dt, double arena, double *d_obst_dyn, void *stream) {
@@ -763,12 +774,36 @@ static int timed_common_check(const std::string &who, int B, int T, int sep2, in
   return 0;
 }
 
-int64_t rmpc_timed_plan_work_bytes(int H, int W, int T, int G) {
-  if (grid_cells_check("timed plan", H, W, false)) return -1;
+// the bytes of workspace of G orders, with `standing` those of the standing rule behind them; -1 for arguments that
+// have none
+static int64_t timed_work_bytes(const std::string &who, int H, int W, int T, int G, bool standing) {
+  if (grid_cells_check(who, H, W, false)) return -1;
   if (T < 1 || T > RMPC_TIMED_MAX_T || G < 1 || G > RMPC_TIMED_MAX_ORDERS)
-    return fail("timed plan: need 1 <= T <= RMPC_TIMED_MAX_T and 1 <= G <= RMPC_TIMED_MAX_ORDERS");
-  return (int64_t)G * timed_order_words(H, W, T) * (int64_t)sizeof(timed_word);
+    return fail(who + ": need 1 <= T <= RMPC_TIMED_MAX_T and 1 <= G <= RMPC_TIMED_MAX_ORDERS");
+  const long long shared = standing ? timed_standing_words(H, W) : 0;
+  return ((int64_t)G * timed_order_words(H, W, T) + shared) * (int64_t)sizeof(timed_word);
 }
+
+// whether `have` bytes are fewer than `need`, the answer of the entry rmpc_<entry>_work_bytes
+static int timed_work_check(const std::string &who, const char *entry, int64_t have, int64_t need) {
+  if (need < 0) return -1;
+  if (have < need)
+    return fail(who + ": the workspace holds " + std::to_string(have) + " bytes, " + std::to_string(need) +
+                " are needed (rmpc_" + entry + "_work_bytes)");
+  return 0;
+}
+
+static TimedGeom timed_geom(int H, int W, int T, int sep2) {
+  TimedGeom q;
+  q.Wd = (W + 63) / 64;
+  q.L = H * q.Wd;
+  q.rad = 0;
+  while ((q.rad + 1) * (q.rad + 1) < sep2) q.rad++;
+  q.per_order = timed_order_words(H, W, T);
+  return q;
+}
+
+int64_t rmpc_timed_plan_work_bytes(int H, int W, int T, int G) { return timed_work_bytes("timed plan", H, W, T, G, false); }
 
 int rmpc_timed_plan_device(const rmpc_timed_plan *p, void *stream) {
   const char *who = "timed plan";
@@ -783,24 +818,10 @@ int rmpc_timed_plan_device(const rmpc_timed_plan *p, void *stream) {
   if (p->G < 1 || p->G > RMPC_TIMED_MAX_ORDERS)
     return fail("timed plan: need 1 <= G <= RMPC_TIMED_MAX_ORDERS = " + std::to_string(RMPC_TIMED_MAX_ORDERS));
   if (!grid_fits((long long)p->G * p->B, p->T + 1)) return fail("timed plan: G*B*(T+1) must not exceed INT_MAX");
-  const int64_t need = rmpc_timed_plan_work_bytes(p->H, p->W, p->T, p->G);
-  if (need < 0) return -1;
-  if (p->work_bytes < need)
-    return fail("timed plan: the workspace holds " + std::to_string(p->work_bytes) + " bytes, " + std::to_string(need) +
-                " are needed (rmpc_timed_plan_work_bytes)");
+  if (timed_work_check(who, "timed_plan", p->work_bytes, rmpc_timed_plan_work_bytes(p->H, p->W, p->T, p->G))) return -1;
   if (use_device_of(p->grid)) return -1;
-  TimedGeom q;
-  q.Wd = (p->W + 63) / 64;
-  q.L = p->H * q.Wd;
-  q.rad = 0;
-  while ((q.rad + 1) * (q.rad + 1) < p->sep2) q.rad++;
-  q.per_order = timed_order_words(p->H, p->W, p->T);
-  const size_t hist = (size_t)(p->T + 1) * q.L * sizeof(timed_word);
-  const int nt = q.L <= 64 ? 64 : (q.L <= 128 ? 128 : kTimedThreads);      // a power of two: the end cell's reduction
-  if (hist <= (size_t)kTimedHistLds)
-    hipLaunchKernelGGL(k_timed_plan<true>, dim3(p->G), dim3(nt), hist, (hipStream_t)stream, *p, q, (timed_word *)p->work);
-  else
-    hipLaunchKernelGGL(k_timed_plan<false>, dim3(p->G), dim3(nt), 0, (hipStream_t)stream, *p, q, (timed_word *)p->work);
+  const TimedGeom q = timed_geom(p->H, p->W, p->T, p->sep2);
+  timed_launch(k_timed_plan<true>, k_timed_plan<false>, p->G, p->T, q, stream, *p, q, (timed_word *)p->work);
   hipLaunchKernelGGL(k_timed_best, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int64_t *)p->key, p->G, (int *)p->best);
   return launch_status();
 }
@@ -821,12 +842,7 @@ int rmpc_timed_follow_device(int B, int T, const int32_t *d_paths, const int32_t
 }
 
 /* timed tours (rmpc_timed_tours.hpp, include/rmpc_timed_tours.h) */
-int64_t rmpc_timed_tours_work_bytes(int H, int W, int T, int G) {
-  if (grid_cells_check("timed tours", H, W, false)) return -1;
-  if (T < 1 || T > RMPC_TIMED_MAX_T || G < 1 || G > RMPC_TIMED_MAX_ORDERS)
-    return fail("timed tours: need 1 <= T <= RMPC_TIMED_MAX_T and 1 <= G <= RMPC_TIMED_MAX_ORDERS");
-  return (int64_t)G * timed_order_words(H, W, T) * (int64_t)sizeof(timed_word);
-}
+int64_t rmpc_timed_tours_work_bytes(int H, int W, int T, int G) { return timed_work_bytes("timed tours", H, W, T, G, false); }
 
 static int timed_tours_stops_check(const std::string &who, int K) {
   if (K < 1 || K > RMPC_TIMED_TOURS_MAX_STOPS)
@@ -854,34 +870,14 @@ static int timed_tours_args_check(const rmpc_timed_tours *p, bool own_work) {
   if (!grid_fits((long long)p->G * p->B, p->T + 1)) return fail("timed tours: G*B*(T+1) must not exceed INT_MAX");
   if (!grid_fits((long long)p->G * p->B, p->K)) return fail("timed tours: G*B*K must not exceed INT_MAX");
   if (!own_work) return 0;
-  const int64_t need = rmpc_timed_tours_work_bytes(p->H, p->W, p->T, p->G);
-  if (need < 0) return -1;
-  if (p->work_bytes < need)
-    return fail("timed tours: the workspace holds " + std::to_string(p->work_bytes) + " bytes, " + std::to_string(need) +
-                " are needed (rmpc_timed_tours_work_bytes)");
-  return 0;
-}
-
-static TimedGeom timed_geom(int H, int W, int T, int sep2) {
-  TimedGeom q;
-  q.Wd = (W + 63) / 64;
-  q.L = H * q.Wd;
-  q.rad = 0;
-  while ((q.rad + 1) * (q.rad + 1) < sep2) q.rad++;
-  q.per_order = timed_order_words(H, W, T);
-  return q;
+  return timed_work_check(who, "timed_tours", p->work_bytes, rmpc_timed_tours_work_bytes(p->H, p->W, p->T, p->G));
 }
 
 int rmpc_timed_tours_plan_device(const rmpc_timed_tours *p, void *stream) {
   if (timed_tours_args_check(p, true)) return -1;
   if (use_device_of(p->grid)) return -1;
   const TimedGeom q = timed_geom(p->H, p->W, p->T, p->sep2);
-  const size_t hist = (size_t)(p->T + 1) * q.L * sizeof(timed_word);
-  const int nt = q.L <= 64 ? 64 : (q.L <= 128 ? 128 : kTimedThreads);      // a power of two: the end cell's reduction
-  if (hist <= (size_t)kTimedHistLds)
-    hipLaunchKernelGGL(k_timed_tours_plan<true>, dim3(p->G), dim3(nt), hist, (hipStream_t)stream, *p, q, (timed_word *)p->work);
-  else
-    hipLaunchKernelGGL(k_timed_tours_plan<false>, dim3(p->G), dim3(nt), 0, (hipStream_t)stream, *p, q, (timed_word *)p->work);
+  timed_launch(k_timed_tours_plan<true>, k_timed_tours_plan<false>, p->G, p->T, q, stream, *p, q, (timed_word *)p->work);
   hipLaunchKernelGGL(k_timed_tours_best, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int64_t *)p->key,
                      (const int *)p->unserved, p->G, (int *)p->best);
   return launch_status();
@@ -932,10 +928,7 @@ int rmpc_timed_reserve_device(int H, int W, int T, int P, const int32_t *d_cells
 }
 
 int64_t rmpc_timed_replan_work_bytes(int H, int W, int T, int G) {
-  if (grid_cells_check("timed replan", H, W, false)) return -1;
-  if (T < 1 || T > RMPC_TIMED_MAX_T || G < 1 || G > RMPC_TIMED_MAX_ORDERS)
-    return fail("timed replan: need 1 <= T <= RMPC_TIMED_MAX_T and 1 <= G <= RMPC_TIMED_MAX_ORDERS");
-  return ((int64_t)G * timed_order_words(H, W, T) + timed_standing_words(H, W)) * (int64_t)sizeof(timed_word);
+  return timed_work_bytes("timed replan", H, W, T, G, true);
 }
 
 int rmpc_timed_tours_replan_device(const rmpc_timed_tours *p, const rmpc_timed_replan *x, void *stream) {
@@ -943,22 +936,14 @@ int rmpc_timed_tours_replan_device(const rmpc_timed_tours *p, const rmpc_timed_r
   if (x->struct_size != (int)sizeof(rmpc_timed_replan)) return fail("rmpc_timed_replan.struct_size mismatch");
   if (timed_tours_args_check(p, false)) return -1;
   if (!x->work) return fail("null argument");
-  const int64_t need = rmpc_timed_replan_work_bytes(p->H, p->W, p->T, p->G);
-  if (need < 0) return -1;
-  if (x->work_bytes < need)
-    return fail("timed replan: the workspace holds " + std::to_string(x->work_bytes) + " bytes, " + std::to_string(need) +
-                " are needed (rmpc_timed_replan_work_bytes)");
+  if (timed_work_check("timed replan", "timed_replan", x->work_bytes, rmpc_timed_replan_work_bytes(p->H, p->W, p->T, p->G)))
+    return -1;
   if (use_device_of(p->grid)) return -1;
   const TimedGeom q = timed_geom(p->H, p->W, p->T, p->sep2);
   timed_word *const work = (timed_word *)x->work;
   hipLaunchKernelGGL(k_timed_standing, dim3((p->H * p->W + 255) / 256), dim3(256), 0, (hipStream_t)stream, *p, *x, q.Wd, q.L,
                      work + (size_t)p->G * q.per_order);
-  const size_t hist = (size_t)(p->T + 1) * q.L * sizeof(timed_word);
-  const int nt = q.L <= 64 ? 64 : (q.L <= 128 ? 128 : kTimedThreads);      // a power of two: the end cell's reduction
-  if (hist <= (size_t)kTimedHistLds)
-    hipLaunchKernelGGL(k_timed_tours_replan<true>, dim3(p->G), dim3(nt), hist, (hipStream_t)stream, *p, *x, q, work);
-  else
-    hipLaunchKernelGGL(k_timed_tours_replan<false>, dim3(p->G), dim3(nt), 0, (hipStream_t)stream, *p, *x, q, work);
+  timed_launch(k_timed_tours_replan<true>, k_timed_tours_replan<false>, p->G, p->T, q, stream, *p, *x, q, work);
   hipLaunchKernelGGL(k_timed_tours_best, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int64_t *)p->key,
                      (const int *)p->unserved, p->G, (int *)p->best);
   return launch_status();
