@@ -14,7 +14,10 @@ Two scenarios: ``store`` draws starts and goals as the other store examples do, 
 among starts and among goals (``pick_spaced_routes``); ``head-on`` puts a robot at each end of four aisles and sends
 it to the other end, so that each pair meets head-on in its aisle.
 
-    python examples/fleet_store_timed.py [--robots 16] [--steps 400] [--seed 0] [--scenario store|head-on]
+    python examples/fleet_store_timed.py [--robots 16] [--steps 400] [--seed 0] [--scenario store|head-on] [--repair 0]
+
+``--repair R`` has the timed mode repair every priority order on the device for up to R rounds: the robots
+that failed or came late are planned first in the next round.
 
 Prints one JSON line per mode: the report fields of the store examples, the arrivals (the end link within
 ARRIVE_TOL["cfg3"] of the final goal), the least distance between two end links less r_i + r_j, for the timed mode
@@ -63,7 +66,7 @@ def head_on_routes(raw, ok, pairs):
     return np.array(starts, np.int32), np.array(goals, np.int32)
 
 
-def run(B=16, steps=400, seed=0, dev="cuda:0", mode="timed", scenario="store", threshold=None, orders=ORDERS):
+def run(B=16, steps=400, seed=0, dev="cuda:0", mode="timed", scenario="store", threshold=None, orders=ORDERS, repair=0):
     import torch
     from robot_mpcs_amd.fleet import Arrivals, MixedFleetShard, event_ms
     from robot_mpcs_amd import _lib
@@ -96,7 +99,7 @@ def run(B=16, steps=400, seed=0, dev="cuda:0", mode="timed", scenario="store", t
         follower = fleet.follower(threshold, paths, lens)
         routes = int((lens > 0).sum().item())
     else:
-        tr = TimedRoutes(g_inf, 4, 0.8, T, SEP2, lag=LAG, orders=orders, seed=seed, device=dev)
+        tr = TimedRoutes(g_inf, 4, 0.8, T, SEP2, lag=LAG, orders=orders, seed=seed, device=dev, repair=repair)
         paths, status, arrive, best = tr.plan(d_starts, d_goals)
         b = int(best.item())                            # (the one host read of the plan: which order to follow)
         follower = TimedFollower(paths[b].contiguous(), S.W, S.x0, S.y0, S.cell, threshold, SEP2, LAG)
@@ -105,6 +108,8 @@ def run(B=16, steps=400, seed=0, dev="cuda:0", mode="timed", scenario="store", t
         extra = dict(best_order=b, plan_failures=int((st > 0).sum()), plan_late=int((ar > T).sum()),
                      plan_last_arrival_layer=int(ar.max()), plan_failures_by_order=(status > 0).sum(dim=1).cpu().tolist(),
                      plan_ms=round(event_ms(lambda: tr.plan(d_starts, d_goals), 5), 4))
+        if repair:
+            extra.update(repair=repair, rounds_run=tr.rounds_run.cpu().tolist(), round_best=tr.round_best.cpu().tolist())
     final = torch.from_numpy(cell_xy(goals, S.W, S.x0, S.y0, S.cell)).to(dev)
     tol = MixedFleetShard.ARRIVE_TOL["cfg3"]
     arrivals = Arrivals(B, dev)
@@ -141,11 +146,12 @@ def main():
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--scenario", default="store")
+    ap.add_argument("--repair", type=int, default=0, help="rounds of order repair on the device (DESIGN.md 27)")
     a = ap.parse_args()
     import __graft_entry__ as g
     g.build()
     for mode in ("plain", "timed"):
-        print(json.dumps(run(a.robots, a.steps, a.seed, mode=mode, scenario=a.scenario)))
+        print(json.dumps(run(a.robots, a.steps, a.seed, mode=mode, scenario=a.scenario, repair=a.repair)))
 
 
 if __name__ == "__main__":

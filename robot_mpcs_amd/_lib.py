@@ -40,6 +40,7 @@ TracksArgs = _abi.structs["rmpc_tracks"]              # one scan of B robots thr
 TimedPlanArgs = _abi.structs["rmpc_timed_plan"]       # one prioritised space-time plan of B robots for G orders
 TimedToursArgs = _abi.timed_tours_structs["rmpc_timed_tours"]     # the same through every robot's stops (rmpc_timed_tours.h)
 TimedReplanArgs = _abi.timed_replan_structs["rmpc_timed_replan"]  # what a re-plan adds to it (rmpc_timed_replan.h)
+TimedRepairArgs = _abi.timed_repair_structs["rmpc_timed_repair"]  # rmpc_timed_plan's members, then the repair's (rmpc_timed_repair.h)
 
 # every symbol include/rmpc.h declares
 EXPORTED_SYMBOLS = list(_abi.prototypes)
@@ -53,6 +54,8 @@ TOURS_SYMBOLS = list(_abi.tours_prototypes)
 TIMED_TOURS_SYMBOLS = list(_abi.timed_tours_prototypes)
 # and every symbol include/rmpc_timed_replan.h declares
 TIMED_REPLAN_SYMBOLS = list(_abi.timed_replan_prototypes)
+# and every symbol include/rmpc_timed_repair.h declares
+TIMED_REPAIR_SYMBOLS = list(_abi.timed_repair_prototypes)
 
 _lib = None
 
@@ -122,10 +125,11 @@ def load_library(path: str = LIB_PATH):
         pass
     L = C.CDLL(path)
     # the declarations of include/rmpc.h, include/rmpc_grid_large.h, include/rmpc_assign_opt.h, include/rmpc_tours.h
-    # include/rmpc_timed_tours.h and include/rmpc_timed_replan.h, nothing else
+    # include/rmpc_timed_tours.h, include/rmpc_timed_replan.h and include/rmpc_timed_repair.h, nothing else
     for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items(),
                                       *_abi.assign_prototypes.items(), *_abi.tours_prototypes.items(),
-                                      *_abi.timed_tours_prototypes.items(), *_abi.timed_replan_prototypes.items()):
+                                      *_abi.timed_tours_prototypes.items(), *_abi.timed_replan_prototypes.items(),
+                                      *_abi.timed_repair_prototypes.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
@@ -932,6 +936,50 @@ def timed_tours_replan_device(args: TimedToursArgs, replan: TimedReplanArgs, str
     """``timed_tours_plan_device`` inside the layer frame of a plan under way: around the reserved routes, for the
     active robots, each from its begin layer (``rmpc_timed_tours_replan_device``).  ``args.work`` is not read."""
     _grid_call("rmpc_timed_tours_replan_device", C.byref(args), C.byref(replan), _stream_arg(stream))
+
+
+# the limit of the timed routes with repaired orders (include/rmpc_timed_repair.h)
+TIMED_MAX_ROUNDS = _abi.timed_repair_constants["RMPC_TIMED_MAX_ROUNDS"]
+
+
+def timed_plan_repair_work_bytes(H: int, W: int, T: int, G: int, B: int) -> int:
+    """bytes of workspace of ``timed_plan_repair_device`` (``rmpc_timed_plan_repair_work_bytes``)"""
+    L = load_library()
+    n = L.rmpc_timed_plan_repair_work_bytes(int(H), int(W), int(T), int(G), int(B))
+    if n < 0:
+        raise RmpcError("rmpc_timed_plan_repair_work_bytes failed: " + L.rmpc_last_error().decode())
+    return int(n)
+
+
+def timed_repair_args(grid, start_cell, goal_index, fields, goal_cells, orders, work, paths, status, arrive, key, best,
+                      order_out, rounds_run, round_best, rounds: int, movement: int = 4, occ_threshold: float = 0.8,
+                      sep2: int = 9, lag: int = 1) -> TimedRepairArgs:
+    """The ``rmpc_timed_repair`` of one plan: ``timed_plan_args`` with work a uint8 tensor of
+    ``timed_plan_repair_work_bytes``, the number of repair rounds, and the outputs order_out (G, B), rounds_run,
+    round_best (G,) int32 -- contiguous device tensors."""
+    a = TimedRepairArgs()
+    a.struct_size = C.sizeof(TimedRepairArgs)
+    a.H, a.W, a.movement = int(grid.shape[0]), int(grid.shape[1]), int(movement)
+    a.grid, a.occ_threshold = grid.data_ptr(), float(occ_threshold)
+    a.B, a.Gf = int(start_cell.shape[0]), int(fields.shape[0])
+    a.start_cell, a.goal_index, a.fields, a.goal_cells = (start_cell.data_ptr(), goal_index.data_ptr(), fields.data_ptr(),
+                                                          goal_cells.data_ptr())
+    a.T, a.sep2, a.lag, a.G = int(paths.shape[2]) - 1, int(sep2), int(lag), int(orders.shape[0])
+    a.orders = orders.data_ptr()
+    a.work, a.work_bytes = work.data_ptr(), int(work.numel() * work.element_size())
+    a.paths, a.status, a.arrive, a.key, a.best = (paths.data_ptr(), status.data_ptr(), arrive.data_ptr(), key.data_ptr(),
+                                                  best.data_ptr())
+    a.rounds = int(rounds)
+    a.order_out, a.rounds_run, a.round_best = order_out.data_ptr(), rounds_run.data_ptr(), round_best.data_ptr()
+    a._keep = (grid, start_cell, goal_index, fields, goal_cells, orders, work, paths, status, arrive, key, best, order_out,
+               rounds_run, round_best)
+    return a
+
+
+def timed_plan_repair_device(args: TimedRepairArgs, stream=None):
+    """``timed_plan_device`` round after round per order: the robots that failed or came late are planned first in the
+    next round, and every row reports its best round (``rmpc_timed_plan_repair_device``)."""
+    _grid_call("rmpc_timed_plan_repair_device", C.byref(args), _stream_arg(stream))
 
 
 class Solver:

@@ -20,6 +20,7 @@
 #include "../../include/rmpc_tours.h"
 #include "../../include/rmpc_timed_tours.h"
 #include "../../include/rmpc_timed_replan.h"
+#include "../../include/rmpc_timed_repair.h"
 #include "rmpc_err.hpp"
 
 namespace rmpc {
@@ -108,6 +109,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_timed.hpp"
 #include "rmpc_timed_tours.hpp"
 #include "rmpc_timed_replan.hpp"
+#include "rmpc_timed_repair.hpp"
 #include "rmpc_track.hpp"
 
 using namespace rmpc;
@@ -805,10 +807,9 @@ static TimedGeom timed_geom(int H, int W, int T, int sep2) {
 
 int64_t rmpc_timed_plan_work_bytes(int H, int W, int T, int G) { return timed_work_bytes("timed plan", H, W, T, G, false); }
 
-int rmpc_timed_plan_device(const rmpc_timed_plan *p, void *stream) {
-  const char *who = "timed plan";
-  if (!p) return fail("null argument");
-  if (p->struct_size != (int)sizeof(rmpc_timed_plan)) return fail("rmpc_timed_plan.struct_size mismatch");
+// the argument checks of rmpc_timed_plan_device but for its workspace; `type`: the struct the caller filled
+static int timed_plan_args_check(const rmpc_timed_plan *p, const std::string &who, const char *type) {
+  if (p->struct_size != (int)sizeof(rmpc_timed_plan)) return fail(std::string(type) + ".struct_size mismatch");
   if (!p->grid || !p->start_cell || !p->goal_index || !p->fields || !p->goal_cells || !p->orders || !p->work || !p->paths ||
       !p->status || !p->arrive || !p->key || !p->best)
     return fail("null argument");
@@ -816,8 +817,15 @@ int rmpc_timed_plan_device(const rmpc_timed_plan *p, void *stream) {
       timed_common_check(who, p->B, p->T, p->sep2, p->lag) || grid_fields_check(who, p->Gf, p->H, p->W))
     return -1;
   if (p->G < 1 || p->G > RMPC_TIMED_MAX_ORDERS)
-    return fail("timed plan: need 1 <= G <= RMPC_TIMED_MAX_ORDERS = " + std::to_string(RMPC_TIMED_MAX_ORDERS));
-  if (!grid_fits((long long)p->G * p->B, p->T + 1)) return fail("timed plan: G*B*(T+1) must not exceed INT_MAX");
+    return fail(who + ": need 1 <= G <= RMPC_TIMED_MAX_ORDERS = " + std::to_string(RMPC_TIMED_MAX_ORDERS));
+  if (!grid_fits((long long)p->G * p->B, p->T + 1)) return fail(who + ": G*B*(T+1) must not exceed INT_MAX");
+  return 0;
+}
+
+int rmpc_timed_plan_device(const rmpc_timed_plan *p, void *stream) {
+  const char *who = "timed plan";
+  if (!p) return fail("null argument");
+  if (timed_plan_args_check(p, who, "rmpc_timed_plan")) return -1;
   if (timed_work_check(who, "timed_plan", p->work_bytes, rmpc_timed_plan_work_bytes(p->H, p->W, p->T, p->G))) return -1;
   if (use_device_of(p->grid)) return -1;
   const TimedGeom q = timed_geom(p->H, p->W, p->T, p->sep2);
@@ -946,6 +954,45 @@ int rmpc_timed_tours_replan_device(const rmpc_timed_tours *p, const rmpc_timed_r
   timed_launch(k_timed_tours_replan<true>, k_timed_tours_replan<false>, p->G, p->T, q, stream, *p, *x, q, work);
   hipLaunchKernelGGL(k_timed_tours_best, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int64_t *)p->key,
                      (const int *)p->unserved, p->G, (int *)p->best);
+  return launch_status();
+}
+
+/* timed routes with repaired orders (rmpc_timed_repair.hpp, include/rmpc_timed_repair.h) */
+int64_t rmpc_timed_plan_repair_work_bytes(int H, int W, int T, int G, int B) {
+  const char *who = "timed repair";
+  const int64_t plan = timed_work_bytes(who, H, W, T, G, false);
+  if (plan < 0) return -1;
+  if (B < 1 || B > RMPC_TIMED_MAX_ROBOTS)
+    return fail(std::string(who) + ": need 1 <= B <= RMPC_TIMED_MAX_ROBOTS = " + std::to_string(RMPC_TIMED_MAX_ROBOTS));
+  return plan + (int64_t)G * timed_repair_words(T, B) * (int64_t)sizeof(timed_word);
+}
+
+int rmpc_timed_plan_repair_device(const rmpc_timed_repair *x, void *stream) {
+  const char *who = "timed repair";
+  if (!x) return fail("null argument");
+  if (x->struct_size != (int)sizeof(rmpc_timed_repair)) return fail("rmpc_timed_repair.struct_size mismatch");
+  // the members up to `best` are rmpc_timed_plan's: the plan's own checks and kernels' parts take them as such
+  rmpc_timed_plan p;
+  p.struct_size = (int32_t)sizeof(rmpc_timed_plan);
+  p.H = x->H; p.W = x->W; p.movement = x->movement;
+  p.grid = x->grid; p.occ_threshold = x->occ_threshold;
+  p.B = x->B; p.Gf = x->Gf;
+  p.start_cell = x->start_cell; p.goal_index = x->goal_index; p.fields = x->fields; p.goal_cells = x->goal_cells;
+  p.T = x->T; p.sep2 = x->sep2; p.lag = x->lag; p.G = x->G;
+  p.orders = x->orders;
+  p.work = x->work; p.work_bytes = x->work_bytes;
+  p.paths = x->paths; p.status = x->status; p.arrive = x->arrive; p.key = x->key; p.best = x->best;
+  if (!x->order_out || !x->rounds_run || !x->round_best) return fail("null argument");
+  if (timed_plan_args_check(&p, who, "rmpc_timed_repair")) return -1;
+  if (x->rounds < 0 || x->rounds > RMPC_TIMED_MAX_ROUNDS)
+    return fail(std::string(who) + ": need 0 <= rounds <= RMPC_TIMED_MAX_ROUNDS = " + std::to_string(RMPC_TIMED_MAX_ROUNDS));
+  if (timed_work_check(who, "timed_plan_repair", p.work_bytes, rmpc_timed_plan_repair_work_bytes(p.H, p.W, p.T, p.G, p.B)))
+    return -1;
+  if (use_device_of(p.grid)) return -1;
+  const TimedGeom q = timed_geom(p.H, p.W, p.T, p.sep2);
+  const TimedRepair rep = {x->rounds, (int *)x->order_out, (int *)x->rounds_run, (int *)x->round_best};
+  timed_launch(k_timed_plan_repair<true>, k_timed_plan_repair<false>, p.G, p.T, q, stream, p, rep, q, (timed_word *)p.work);
+  hipLaunchKernelGGL(k_timed_best, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int64_t *)p.key, p.G, (int *)p.best);
   return launch_status();
 }
 

@@ -36,10 +36,13 @@ class TimedRoutes:
     """Space-time routes on ``grid`` (H, W) (numpy or device tensor) over the window t = 0 .. T: two robots of one
     order that both have status 0 are never closer than ``sep2`` (squared cells) within ``lag`` layers of each other.
     ``orders``: a (G, B) array of permutations, or their number G (``priority_orders`` at the first ``plan``).
-    ``plan(start_cells, goal_cells)`` launches the fields of the distinct goals and the plan and reads nothing back."""
+    ``plan(start_cells, goal_cells)`` launches the fields of the distinct goals and the plan and reads nothing back.
+    ``repair`` = R > 0: every order is repaired on the device for up to R rounds (``rmpc_timed_plan_repair_device``,
+    DESIGN.md 27): the robots that failed or came late are planned first in the next round; ``self.order_out`` (G, B) is
+    then the order each row's plan belongs to, ``self.rounds_run`` and ``self.round_best`` (G,) what the search did."""
 
     def __init__(self, grid, movement, occupancy_threshold, T, sep2, lag=1, orders=4, occupancy_cost_factor=3.0, seed=0,
-                 device=None):
+                 device=None, repair=0):
         import torch
         if movement not in MOVES:
             raise ValueError("Unknown movement")
@@ -48,6 +51,9 @@ class TimedRoutes:
         self.device, self.movement, self.threshold = dev, MOVES[movement], float(occupancy_threshold)
         self.cost_factor, self.T, self.sep2, self.lag, self.seed = float(occupancy_cost_factor), int(T), int(sep2), int(lag), seed
         self.orders = orders if isinstance(orders, int) else _dev_tensor(np.asarray(orders), torch.int32, dev)
+        self.repair = int(repair)
+        if not 0 <= self.repair <= _lib.TIMED_MAX_ROUNDS:
+            raise ValueError("repair must lie in [0, TIMED_MAX_ROUNDS]")
         self.work = None
 
     def plan(self, start_cells, goal_cells, stream=None):
@@ -69,7 +75,11 @@ class TimedRoutes:
         Gf = int(uniq.shape[0])
         fields = torch.empty((Gf, H, W), dtype=torch.float64, device=dev)
         fstatus = torch.empty(Gf, dtype=torch.int32, device=dev)
-        if self.work is None:
+        if self.repair:                                       # (the repair's workspace grows with B)
+            nbytes = _lib.timed_plan_repair_work_bytes(H, W, self.T, G, B)
+            if self.work is None or self.work.numel() < nbytes:
+                self.work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        elif self.work is None:
             self.work = torch.empty(_lib.timed_plan_work_bytes(H, W, self.T, G), dtype=torch.uint8, device=dev)
         paths = torch.empty((G, B, self.T + 1), dtype=torch.int32, device=dev)
         status = torch.empty((G, B), dtype=torch.int32, device=dev)
@@ -78,9 +88,19 @@ class TimedRoutes:
         best = torch.empty(1, dtype=torch.int32, device=dev)
         st = _lib.stream_handle(stream, dev)
         _lib.grid_fields_device(g, uniq, fields, fstatus, self.movement, self.threshold, self.cost_factor, stream=st)
-        args = _lib.timed_plan_args(g, s, inv, fields, uniq, self.orders, self.work, paths, status, arrive, self.key, best,
-                                    movement=self.movement, occ_threshold=self.threshold, sep2=self.sep2, lag=self.lag)
-        _lib.timed_plan_device(args, stream=st)
+        if self.repair:
+            self.order_out = torch.empty((G, B), dtype=torch.int32, device=dev)
+            self.rounds_run = torch.empty(G, dtype=torch.int32, device=dev)
+            self.round_best = torch.empty(G, dtype=torch.int32, device=dev)
+            args = _lib.timed_repair_args(g, s, inv, fields, uniq, self.orders, self.work, paths, status, arrive, self.key,
+                                          best, self.order_out, self.rounds_run, self.round_best, self.repair,
+                                          movement=self.movement, occ_threshold=self.threshold, sep2=self.sep2, lag=self.lag)
+            _lib.timed_plan_repair_device(args, stream=st)
+        else:
+            args = _lib.timed_plan_args(g, s, inv, fields, uniq, self.orders, self.work, paths, status, arrive, self.key,
+                                        best, movement=self.movement, occ_threshold=self.threshold, sep2=self.sep2,
+                                        lag=self.lag)
+            _lib.timed_plan_device(args, stream=st)
         self.fields, self.field_status = fields, fstatus
         return paths, status, arrive, best
 

@@ -1,0 +1,303 @@
+"""The repair of failing priority orders (include/rmpc_timed_repair.h), what needs no GPU: the restatement
+of tests/timed_repair_reference.py on hand-worked cases, the three properties that follow from the rule against
+``plan_ref`` on random maps, the count of rows the rule improves there, and the header, the binding and the entry's
+refusals.  tests/test_gpu_timed_repair.py holds the device to the restatement."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from timed_reference import BAD_ORDER, INT64_MAX, OUTSIDE, conflicts, fields_for, plan_ref
+from timed_repair_reference import bad_robots, bay_corridor, next_order, repair_ref, two_by_three
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOLS = ["rmpc_timed_plan_repair_work_bytes", "rmpc_timed_plan_repair_device"]
+KEYS = ("paths", "status", "arrive", "key", "best")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    g.build()
+    from robot_mpcs_amd import _lib
+    return _lib
+
+
+def _case(grid, goals, movement=4):
+    goal_cells = np.unique(np.asarray(goals))
+    return np.searchsorted(goal_cells, goals), fields_for(grid, goal_cells, movement), goal_cells
+
+
+def _repair(grid, starts, goals, orders, T, sep2, rounds, lag=1, movement=4):
+    gi, fields, goal_cells = _case(grid, goals, movement)
+    return repair_ref(grid, starts, gi, fields, goal_cells, orders, T, sep2, lag, movement, rounds=rounds)
+
+
+# ---- hand-worked cases -----------------------------------------------------------------------------------------------
+def test_the_partition_is_stable():
+    assert next_order([4, 2, 0, 3, 1], np.array([1, 0, 0, 1, 1], bool)) == [4, 0, 3, 2, 1]
+    assert bad_robots([0, 3, 0, OUTSIDE, BAD_ORDER], [5, 9, 9, 9, 9], 8).tolist() == [False, True, True, False, False]
+
+
+def test_bay_corridor_the_swapped_order_has_no_failure():
+    """Robot 0 walks the corridor from 7 to 13, robot 1 from 13 to 7; the only bay is at robot 0's end.  In the identity
+    order robot 0 walks 7 .. 13 and holds; robot 1 is squeezed as in the 1 x 7 swap: layers {12, 13}, {11, 12, 13},
+    {12, 13}, {13}, then nothing: status 5.  It is bad, so round 1 plans it first: it walks 13 .. 7 and holds, and robot 0
+    steps to 8, into the bay (cell 1) at layer 2 -- robot 1 holds the bay's mouth 8 at layer 5, which reserves it in
+    layers 4 .. 6 -- is back on 8 at layer 7 and on its goal at layer 12."""
+    g = bay_corridor()
+    r = _repair(g, [7, 13], [13, 7], [[0, 1]], 14, 1, rounds=1)
+    assert r["tried"][0] == [[0, 1], [1, 0]] and r["nbad"][0] == [1, 0]
+    assert r["order_out"][0].tolist() == [1, 0] and r["round_best"][0] == 1 and r["rounds_run"][0] == 2
+    assert r["status"][0].tolist() == [0, 0] and r["arrive"][0].tolist() == [12, 6] and r["key"][0] == 18
+    assert r["paths"][0, 0].tolist() == [7, 8, 1, 1, 1, 1, 1, 8, 9, 10, 11, 12, 13, 13, 13]
+    assert r["paths"][0, 1].tolist() == list(range(13, 6, -1)) + [7] * 8
+    assert conflicts(r["paths"][0], r["status"][0], 7, 1, 1) == []
+    # more rounds change nothing: round 1 has no bad robot
+    assert _repair(g, [7, 13], [13, 7], [[0, 1]], 14, 1, rounds=5)["rounds_run"][0] == 2
+    # without a round of repair the failure stays
+    r0 = _repair(g, [7, 13], [13, 7], [[0, 1]], 14, 1, rounds=0)
+    assert r0["status"][0].tolist() == [0, 5] and r0["paths"][0, 1].tolist() == [13] * 15
+    assert r0["order_out"][0].tolist() == [0, 1] and r0["round_best"][0] == 0 and r0["rounds_run"][0] == 1
+    assert r0["key"][0] == (1 << 44) | (1 << 32) | (6 + 15)
+
+
+def test_corridor_swap_fails_in_every_order_and_ties_go_to_the_earlier_round():
+    """1 x 7, the two robots at the ends bound for each other's: whoever is ranked second fails at layer 5, so the orders
+    alternate until R caps the rounds; every round has the key (1 fail, 1 late, 6 + 9), and the output is round 0."""
+    for R in (0, 1, 3, 4):
+        r = _repair(np.zeros((1, 7)), [0, 6], [6, 0], [[0, 1], [1, 0]], 8, 1, rounds=R)
+        assert r["tried"][0] == [[0, 1] if i % 2 == 0 else [1, 0] for i in range(R + 1)]
+        assert r["rounds_run"].tolist() == [R + 1] * 2 and r["round_best"].tolist() == [0, 0]
+        assert r["keys"][0] == [(1 << 44) | (1 << 32) | 15] * (R + 1) == r["keys"][1]
+        assert r["order_out"].tolist() == [[0, 1], [1, 0]]
+        assert r["status"].tolist() == [[0, 5], [5, 0]] and r["paths"][0, 1].tolist() == [6] * 9
+        assert r["best"][0] == 0
+
+
+def test_the_search_stops_when_the_bad_robots_are_the_prefix_already():
+    """1 x 5 with a wall on cell 3: robot 0 (cell 0, bound for cell 4 behind the wall) is late in every order and never
+    fails, robot 1 (cell 2 to cell 1) arrives.  From [0, 1] the next order is [0, 1] again: one round.  From [1, 0] round 1
+    is [0, 1], whose next order is itself: two rounds, however many are allowed."""
+    g = np.zeros((1, 5))
+    g[0, 3] = 1.0
+    r = _repair(g, [0, 2], [4, 1], [[0, 1], [1, 0]], 4, 1, rounds=6)
+    assert r["tried"][0] == [[0, 1]] and r["tried"][1] == [[1, 0], [0, 1]]
+    assert r["rounds_run"].tolist() == [1, 2] and r["nbad"][0] == [1] and r["nbad"][1] == [1, 1]
+    assert r["status"].tolist() == [[0, 0], [0, 0]] and np.all(r["arrive"][:, 0] == 5)
+
+
+def test_a_skipped_robot_is_never_bad_and_a_row_that_is_no_permutation():
+    """the 1 x 7 swap with a robot that starts outside the map between the two: it is skipped in every round, counts as
+    late in the key and is never moved to the front; the row [0, 0, 1] is reported as the plan reports it"""
+    r = _repair(np.zeros((1, 7)), [0, -1, 6], [6, 3, 0], [[0, 1, 2], [0, 0, 1], [2, 1, 0]], 8, 1, rounds=2)
+    assert r["tried"][0] == [[0, 1, 2], [2, 0, 1], [0, 2, 1]] and r["tried"][2] == [[2, 1, 0], [0, 2, 1], [2, 0, 1]]
+    assert r["status"][0].tolist() == [0, OUTSIDE, 5] and r["nbad"][0] == [1, 1, 1]
+    assert r["status"][1].tolist() == [BAD_ORDER] * 3 and np.all(r["paths"][1] == -1) and r["key"][1] == INT64_MAX
+    assert r["order_out"][1].tolist() == [-1] * 3 and r["rounds_run"].tolist() == [3, 0, 3]
+    assert r["round_best"].tolist() == [0, -1, 0] and r["best"][0] == 0
+    none = _repair(np.zeros((1, 7)), [0, 6], [6, 0], [[0, 0], [2, 1]], 8, 1, rounds=2)
+    assert none["best"][0] == -1 and none["rounds_run"].tolist() == [0, 0]
+
+
+def test_a_late_robot_that_did_not_fail_is_promoted():
+    """2 x 3, cells 1 2 over 3 4 5 (cell 0 is occupied), T = 3.  Robot 0 goes from 5 to 4, robot 1 from 3 to 2, which
+    takes three steps through 4.  In the identity order robot 0 is on 4 from layer 1 on, which reserves 4 in every layer:
+    robot 1 can only stand on 3 -- status 0, never there: late.  Round 1 plans it first: 3, 4, 1, 2, arriving at T;
+    robot 0 waits on 5 while 4 is reserved (layers 0 .. 2) and steps onto it at layer 3."""
+    r = _repair(two_by_three(), [5, 3], [4, 2], [[0, 1]], 3, 1, rounds=1)
+    assert r["keys"][0] == [(1 << 32) | (1 + 4), 3 + 3] and r["tried"][0] == [[0, 1], [1, 0]]
+    assert r["paths"][0].tolist() == [[5, 5, 5, 4], [3, 4, 1, 2]] and r["status"][0].tolist() == [0, 0]
+    assert r["round_best"][0] == 1 and r["order_out"][0].tolist() == [1, 0]
+    r0 = _repair(two_by_three(), [5, 3], [4, 2], [[0, 1]], 3, 1, rounds=0)
+    assert r0["paths"][0].tolist() == [[5, 4, 4, 4], [3, 3, 3, 3]] and r0["arrive"][0].tolist() == [1, 4]
+
+
+def test_a_window_one_layer_short_promotes_the_late_robot_and_keeps_round_0_when_that_is_worse():
+    """the bay case of tests/test_timed_cpu.py (bay above column 5), where rank 1 arrives at layer 12, with T = 11: it is
+    late without failing and is planned first in round 1; robot 0 then has no bay at its end and fails, which is the
+    worse key: the row reports round 0."""
+    g = np.ones((3, 7))
+    g[1, :] = 0.0
+    g[0, 5] = 0.0
+    r = _repair(g, [7, 13], [13, 7], [[0, 1]], 11, 1, rounds=1)
+    assert r["tried"][0] == [[0, 1], [1, 0]] and r["keys"][0][0] == (1 << 32) | (6 + 12)
+    assert r["keys"][0][1] >> 44 == 1 and r["round_best"][0] == 0 and r["rounds_run"][0] == 2
+    assert r["order_out"][0].tolist() == [0, 1] and r["status"][0].tolist() == [0, 0] and r["arrive"][0].tolist() == [6, 12]
+
+
+# ---- the properties, on the random maps of the plan's guarantee test ----------------------------------------------------
+B_RANDOM, DENSITY = 8, 0.15          # the guarantee test's maps with 8 robots instead of 6 (census in DESIGN.md 27)
+
+
+def random_cases(lag, movement, B=B_RANDOM, density=DENSITY):
+    rng = np.random.default_rng(100 * lag + movement)
+    for _ in range(3):
+        g = (rng.uniform(size=(12, 12)) < density).astype(float)
+        free = rng.permutation(np.flatnonzero(g.ravel() < 0.5))
+        starts = []
+        for c in free:
+            if len(starts) < B and all((c // 12 - q // 12) ** 2 + (c % 12 - q % 12) ** 2 >= 4 for q in starts):
+                starts.append(int(c))
+        yield g, np.array(starts), np.array([int(c) for c in free[-B:]]), [np.arange(B), rng.permutation(B)]
+
+
+@pytest.fixture(scope="module")
+def random_runs():
+    """every random case once: (lag, movement, the case, its fields, the repair at R = 3)"""
+    runs = []
+    for lag, movement in ((1, 4), (2, 8), (2, 4), (1, 8)):
+        for g, starts, goals, orders in random_cases(lag, movement):
+            gi, fields, goal_cells = _case(g, goals, movement)
+            args = (g, starts, gi, fields, goal_cells)
+            runs.append((lag, movement, args, orders, repair_ref(*args, orders, 30, 4, lag, movement, rounds=3)))
+    return runs
+
+
+def test_property_a_without_rounds_it_is_the_plan(random_runs):
+    for lag, movement, args, orders, _ in random_runs:
+        want = plan_ref(*args, orders, 30, 4, lag, movement)
+        got = repair_ref(*args, orders, 30, 4, lag, movement, rounds=0)
+        for k in KEYS:
+            assert np.array_equal(got[k], want[k]), k
+        assert np.array_equal(got["order_out"], np.asarray(orders)) and got["rounds_run"].tolist() == [1, 1]
+        assert got["round_best"].tolist() == [0, 0]
+
+
+def test_property_b_the_outputs_are_the_plan_of_order_out(random_runs):
+    for lag, movement, args, orders, r in random_runs:
+        want = plan_ref(*args, r["order_out"], 30, 4, lag, movement)
+        for k in KEYS:
+            assert np.array_equal(r[k], want[k]), k
+        for o in range(2):
+            assert conflicts(r["paths"][o], r["status"][o], 12, 4, lag) == []
+
+
+def test_property_c_the_key_never_rises_and_ties_keep_the_earlier_round(random_runs):
+    for lag, movement, args, orders, r in random_runs:
+        for o in range(2):
+            keys = r["keys"][o]
+            assert r["key"][o] == min(keys) <= keys[0] and r["round_best"][o] == keys.index(min(keys))
+            assert len(keys) == r["rounds_run"][o] <= 4
+            assert sorted(r["order_out"][o].tolist()) == list(range(B_RANDOM))
+
+
+def test_the_rule_is_not_vacuous_on_these_maps(random_runs):
+    """rows whose round 0 has a bad robot, and those among them whose output has fewer.  Measured: 22 of
+    the 24 rows have a bad robot in round 0, 12 of them end with fewer."""
+    had = better = 0
+    for lag, movement, args, orders, r in random_runs:
+        for o in range(2):
+            first, out = r["nbad"][o][0], r["nbad"][o][int(r["round_best"][o])]
+            had += first > 0
+            better += out < first
+    print("rows", 2 * len(random_runs), "with a bad robot in round 0:", had, "with fewer in the output:", better)
+    assert better >= 1
+
+
+# ---- the header and the binding ------------------------------------------------------------------------------------------
+def test_symbols_are_declared_by_the_new_header_and_exported(lib):
+    from robot_mpcs_amd import _abi
+    assert lib.TIMED_REPAIR_SYMBOLS == SYMBOLS == list(_abi.timed_repair_prototypes)
+    code = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "rmpc_timed_repair.h")).read(), flags=re.S)
+    assert sorted(set(re.findall(r"\b(rmpc_\w+)\s*\(", code))) == sorted(SYMBOLS)
+    L = lib.load_library()
+    for sym in SYMBOLS:
+        fn = getattr(L, sym)
+        assert (fn.restype, list(fn.argtypes)) == tuple(_abi.timed_repair_prototypes[sym])
+    vp, i = C.c_void_p, C.c_int
+    S, P = _abi.timed_repair_structs["rmpc_timed_repair"], _abi.structs["rmpc_timed_plan"]
+    assert _abi.timed_repair_prototypes[SYMBOLS[0]] == (C.c_int64, [i] * 5)
+    assert _abi.timed_repair_prototypes[SYMBOLS[1]] == (i, [C.POINTER(S), vp])
+    assert _abi.timed_repair_constants == {"RMPC_TIMED_MAX_ROUNDS": 16} and lib.TIMED_MAX_ROUNDS == 16
+    # the plan's members in the plan's layout, then the repair's
+    n = len(P._fields_)
+    assert S._fields_[:n] == P._fields_ and all(getattr(S, k).offset == getattr(P, k).offset for k, _ in P._fields_)
+    assert S._fields_[n:] == [("rounds", C.c_int32), ("order_out", vp), ("rounds_run", vp), ("round_best", vp)]
+    assert list(_abi.timed_repair_structs) == ["rmpc_timed_repair"] and (C.sizeof(P), C.sizeof(S)) == (152, 184)
+    # the other headers declare what they declared, and the version stands
+    assert len(lib.EXPORTED_SYMBOLS) == 65 and len(lib.TIMED_REPLAN_SYMBOLS) == 4
+    assert not set(SYMBOLS) & (set(_abi.prototypes) | set(_abi.timed_tours_prototypes) | set(_abi.timed_replan_prototypes))
+    with open(os.path.join(ROOT, "robot_mpcs_amd", "csrc", "sources.txt")) as f:
+        listed = f.read().split()
+    assert "include/rmpc_timed_repair.h" in listed and "robot_mpcs_amd/csrc/rmpc_timed_repair.hpp" in listed
+
+
+def test_sizes(lib):
+    L = lib.load_library()
+    # the orders' parts are the plan's; behind them per row a slot of B paths, status and arrive, and two orders
+    for H, W, T, G, B in ((7, 5, 9, 2, 3), (65, 70, 70, 3, 6), (128, 128, 1023, 1024, 1024), (1, 1, 1, 1, 1), (20, 20, 3, 2, 300)):
+        extra = lib.timed_plan_repair_work_bytes(H, W, T, G, B) - lib.timed_plan_work_bytes(H, W, T, G)
+        assert extra == G * 8 * ((B * (T + 1) + 4 * B + 1) // 2)
+    for a in ((0, 5, 9, 2, 3), (129, 128, 9, 1, 3), (7, 5, 0, 2, 3), (7, 5, 1024, 2, 3), (7, 5, 9, 0, 3), (7, 5, 9, 1025, 3),
+              (7, 5, 9, 2, 0), (7, 5, 9, 2, 1025)):
+        assert L.rmpc_timed_plan_repair_work_bytes(*a) == -1 and L.rmpc_last_error().decode().startswith("timed repair")
+        with pytest.raises(lib.RmpcError, match="timed repair"):
+            lib.timed_plan_repair_work_bytes(*a)
+
+
+P_ = 0x1000      # a host-side fake pointer: a refusal never dereferences it
+I_MAX = 2 ** 31 - 1
+NULL = "null argument"
+ARGS = dict(H=7, W=5, movement=4, grid=P_, occ_threshold=0.8, B=3, Gf=2, start_cell=P_, goal_index=P_, fields=P_,
+            goal_cells=P_, T=9, sep2=2, lag=1, G=2, orders=P_, work=P_, work_bytes=1 << 20, paths=P_, status=P_, arrive=P_,
+            key=P_, best=P_, rounds=2, order_out=P_, rounds_run=P_, round_best=P_)
+REFUSALS = [(dict([(k, None)]), NULL) for k, v in ARGS.items() if v == P_]
+REFUSALS += [(dict(rounds=-1), "timed repair: need 0 <= rounds <= RMPC_TIMED_MAX_ROUNDS = 16"),
+             (dict(rounds=17), "timed repair: need 0 <= rounds"), (dict(rounds=I_MAX), "timed repair: need 0 <= rounds"),
+             (dict(B=0), "timed repair: need 1 <= B"), (dict(B=1025), "timed repair: need 1 <= B"),
+             (dict(T=0), "timed repair: need 1 <= T"), (dict(T=1024), "timed repair: need 1 <= T"),
+             (dict(sep2=0), "timed repair: need 1 <= sep2"), (dict(sep2=4097), "timed repair: need 1 <= sep2"),
+             (dict(lag=0), "timed repair: lag must lie"), (dict(lag=5), "timed repair: lag must lie"),
+             (dict(G=0), "timed repair: need 1 <= G"), (dict(G=1025), "timed repair: need 1 <= G"),
+             (dict(movement=6), ""), (dict(H=0), ""), (dict(W=0), ""), (dict(H=129, W=128), ""), (dict(Gf=0), ""),
+             (dict(Gf=I_MAX), ""),
+             (dict(struct_size=183), "rmpc_timed_repair.struct_size mismatch"),
+             (dict(struct_size=152), "rmpc_timed_repair.struct_size mismatch"),
+             (dict(work_bytes=0), "timed repair: the workspace holds 0 bytes"),
+             (dict(work_bytes=-1), "timed repair: the workspace holds -1 bytes")]
+
+
+@pytest.mark.parametrize("bad,want", REFUSALS, ids=[",".join("%s=%s" % kv for kv in b.items()) for b, _ in REFUSALS])
+def test_the_entry_refuses_with_a_message_and_without_a_gpu(lib, bad, want):
+    L = lib.load_library()
+    a = lib.TimedRepairArgs()
+    a.struct_size = C.sizeof(lib.TimedRepairArgs)
+    for k, v in dict(ARGS, **bad).items():
+        setattr(a, k, v)
+    assert L.rmpc_timed_plan_repair_device(C.byref(a), None) == -1
+    msg = L.rmpc_last_error().decode()
+    assert msg.startswith(want) and msg, (msg, want)
+    assert L.rmpc_timed_plan_repair_device(None, None) == -1 and L.rmpc_last_error().decode() == NULL
+
+
+def test_a_workspace_one_byte_short_and_the_plans_size_are_refused(lib):
+    L = lib.load_library()
+    a = lib.TimedRepairArgs()
+    a.struct_size = C.sizeof(lib.TimedRepairArgs)
+    for k, v in ARGS.items():
+        setattr(a, k, v)
+    for n in (lib.timed_plan_repair_work_bytes(7, 5, 9, 2, 3) - 1, lib.timed_plan_work_bytes(7, 5, 9, 2)):
+        a.work_bytes = n
+        assert L.rmpc_timed_plan_repair_device(C.byref(a), None) == -1
+        assert "are needed (rmpc_timed_plan_repair_work_bytes)" in L.rmpc_last_error().decode()
+
+
+def test_the_plans_entry_refuses_as_before(lib):
+    """the plan's checks moved into a function the two entries share: its messages are what they were"""
+    L = lib.load_library()
+    a = lib.TimedPlanArgs()
+    a.struct_size = C.sizeof(lib.TimedPlanArgs)
+    for k, v in ARGS.items():
+        if hasattr(a, k):
+            setattr(a, k, v)
+    for bad, want in ((dict(G=0), "timed plan: need 1 <= G <= RMPC_TIMED_MAX_ORDERS = 1024"),
+                      (dict(struct_size=151), "rmpc_timed_plan.struct_size mismatch"), (dict(grid=None), NULL),
+                      (dict(B=1025), "timed plan: need 1 <= B"), (dict(work_bytes=8), "timed plan: the workspace holds 8 bytes")):
+        b = lib.TimedPlanArgs.from_buffer_copy(a)
+        for k, v in bad.items():
+            setattr(b, k, v)
+        assert L.rmpc_timed_plan_device(C.byref(b), None) == -1
+        assert L.rmpc_last_error().decode().startswith(want)
