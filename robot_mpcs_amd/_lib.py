@@ -277,6 +277,15 @@ def _grid_call(name, *args):
         raise RmpcError(name + " failed: " + L.rmpc_last_error().decode())
 
 
+def _size_query(name, *ints):
+    """a host-only size function of the library: its count, or RmpcError when it answers -1"""
+    L = load_library()
+    n = getattr(L, name)(*(int(v) for v in ints))
+    if n < 0:
+        raise RmpcError(name + " failed: " + L.rmpc_last_error().decode())
+    return int(n)
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
@@ -557,11 +566,7 @@ ASSIGN_OPT_MAX_Q = _abi.assign_constants["RMPC_ASSIGN_OPT_MAX_Q"]
 def assign_optimal_work_bytes(G: int, B: int, T: int) -> int:
     """The bytes of workspace ``assign_optimal_device`` needs for G problems of B x T
     (``rmpc_assign_optimal_work_bytes``; host only)."""
-    L = load_library()
-    n = L.rmpc_assign_optimal_work_bytes(int(G), int(B), int(T))
-    if n < 0:
-        raise RmpcError("rmpc_assign_optimal_work_bytes failed: " + L.rmpc_last_error().decode())
-    return int(n)
+    return _size_query("rmpc_assign_optimal_work_bytes", G, B, T)
 
 
 def assign_optimal_device(cost, assign, scale: float = 1024.0, total=None, count=None, steps=None, work=None, stream=None):
@@ -598,11 +603,7 @@ TOURS_MODES = {"sum": 0, "span": 1, 0: 0, 1: 1}
 def tours_work_bytes(G: int, B: int, T: int) -> int:
     """The bytes of workspace ``tours_device`` needs for G problems of B robots and T tasks (``rmpc_tours_work_bytes``;
     host only)."""
-    L = load_library()
-    n = L.rmpc_tours_work_bytes(int(G), int(B), int(T))
-    if n < 0:
-        raise RmpcError("rmpc_tours_work_bytes failed: " + L.rmpc_last_error().decode())
-    return int(n)
+    return _size_query("rmpc_tours_work_bytes", G, B, T)
 
 
 def tours_device(start_cost, task_cost, tours, lens, cost, mode="span", scale: float = 1024.0, max_rounds: int = 1 << 30,
@@ -720,11 +721,7 @@ def scan_search_top_nodes(nxy: int, nth: int, top_log2: int) -> int:
 
 def scan_search_work_bytes(B: int, nxy: int, nth: int, top_log2: int) -> int:
     """bytes of workspace of ``scan_search_device`` (``rmpc_scan_search_work_bytes``)"""
-    L = load_library()
-    n = L.rmpc_scan_search_work_bytes(int(B), int(nxy), int(nth), int(top_log2))
-    if n < 0:
-        raise RmpcError("rmpc_scan_search_work_bytes failed: " + L.rmpc_last_error().decode())
-    return int(n)
+    return _size_query("rmpc_scan_search_work_bytes", B, nxy, nth, top_log2)
 
 
 def scan_search_args(match: ScanMatchArgs, pyr, top_log2: int, work, active=None, leaves=None,
@@ -790,11 +787,24 @@ TIMED_MAX_ROBOTS, TIMED_MAX_T, TIMED_MAX_ORDERS, TIMED_MAX_SEP2, TIMED_MAX_LAG, 
 
 def timed_plan_work_bytes(H: int, W: int, T: int, G: int) -> int:
     """bytes of workspace of ``timed_plan_device`` (``rmpc_timed_plan_work_bytes``)"""
-    L = load_library()
-    n = L.rmpc_timed_plan_work_bytes(int(H), int(W), int(T), int(G))
-    if n < 0:
-        raise RmpcError("rmpc_timed_plan_work_bytes failed: " + L.rmpc_last_error().decode())
-    return int(n)
+    return _size_query("rmpc_timed_plan_work_bytes", H, W, T, G)
+
+
+def _timed_common(cls, grid, start_cell, fields, goal_cells, orders, work, paths, status, arrive, key, best, movement,
+                  occ_threshold, sep2, lag):
+    """a ``cls`` with what rmpc_timed_plan, rmpc_timed_tours and rmpc_timed_repair have in common filled in"""
+    a = cls()
+    a.struct_size = C.sizeof(cls)
+    a.H, a.W, a.movement = int(grid.shape[0]), int(grid.shape[1]), int(movement)
+    a.grid, a.occ_threshold = grid.data_ptr(), float(occ_threshold)
+    a.B, a.Gf = int(start_cell.shape[0]), int(fields.shape[0])
+    a.start_cell, a.fields, a.goal_cells = start_cell.data_ptr(), fields.data_ptr(), goal_cells.data_ptr()
+    a.T, a.sep2, a.lag, a.G = int(paths.shape[2]) - 1, int(sep2), int(lag), int(orders.shape[0])
+    a.orders = orders.data_ptr()
+    a.work, a.work_bytes = work.data_ptr(), int(work.numel() * work.element_size())
+    a.paths, a.status, a.arrive, a.key, a.best = (paths.data_ptr(), status.data_ptr(), arrive.data_ptr(), key.data_ptr(),
+                                                  best.data_ptr())
+    return a
 
 
 def timed_plan_args(grid, start_cell, goal_index, fields, goal_cells, orders, work, paths, status, arrive, key, best,
@@ -802,18 +812,9 @@ def timed_plan_args(grid, start_cell, goal_index, fields, goal_cells, orders, wo
     """The ``rmpc_timed_plan`` of one plan: grid (H, W) fp64, start_cell, goal_index (B,) int32, fields (Gf, H, W) fp64,
     goal_cells (Gf,) int32, orders (G, B) int32, work a uint8 tensor of ``timed_plan_work_bytes``, paths (G, B, T + 1),
     status, arrive (G, B) int32, key (G,) int64, best (1,) int32 -- contiguous device tensors."""
-    a = TimedPlanArgs()
-    a.struct_size = C.sizeof(TimedPlanArgs)
-    a.H, a.W, a.movement = int(grid.shape[0]), int(grid.shape[1]), int(movement)
-    a.grid, a.occ_threshold = grid.data_ptr(), float(occ_threshold)
-    a.B, a.Gf = int(start_cell.shape[0]), int(fields.shape[0])
-    a.start_cell, a.goal_index, a.fields, a.goal_cells = (start_cell.data_ptr(), goal_index.data_ptr(), fields.data_ptr(),
-                                                          goal_cells.data_ptr())
-    a.T, a.sep2, a.lag, a.G = int(paths.shape[2]) - 1, int(sep2), int(lag), int(orders.shape[0])
-    a.orders = orders.data_ptr()
-    a.work, a.work_bytes = work.data_ptr(), int(work.numel() * work.element_size())
-    a.paths, a.status, a.arrive, a.key, a.best = (paths.data_ptr(), status.data_ptr(), arrive.data_ptr(), key.data_ptr(),
-                                                  best.data_ptr())
+    a = _timed_common(TimedPlanArgs, grid, start_cell, fields, goal_cells, orders, work, paths, status, arrive, key, best,
+                      movement, occ_threshold, sep2, lag)
+    a.goal_index = goal_index.data_ptr()
     a._keep = (grid, start_cell, goal_index, fields, goal_cells, orders, work, paths, status, arrive, key, best)
     return a
 
@@ -839,11 +840,7 @@ TIMED_TOURS_MAX_STOPS, TIMED_TOURS_MAX_DWELL = (_abi.timed_tours_constants["RMPC
 
 def timed_tours_work_bytes(H: int, W: int, T: int, G: int) -> int:
     """bytes of workspace of ``timed_tours_plan_device`` (``rmpc_timed_tours_work_bytes``)"""
-    L = load_library()
-    n = L.rmpc_timed_tours_work_bytes(int(H), int(W), int(T), int(G))
-    if n < 0:
-        raise RmpcError("rmpc_timed_tours_work_bytes failed: " + L.rmpc_last_error().decode())
-    return int(n)
+    return _size_query("rmpc_timed_tours_work_bytes", H, W, T, G)
 
 
 def timed_tours_args(grid, start_cell, stops, lens, park_index, fields, goal_cells, orders, work, paths, status, arrive, key,
@@ -851,19 +848,10 @@ def timed_tours_args(grid, start_cell, stops, lens, park_index, fields, goal_cel
                      sep2: int = 9, lag: int = 1) -> TimedToursArgs:
     """The ``rmpc_timed_tours`` of one plan: ``timed_plan_args`` with stops (B, K), lens, park_index (B,) int32 in place
     of goal_index, and the outputs serve_at (G, B, K), served (G, B), unserved (G,) int32 -- contiguous device tensors."""
-    a = TimedToursArgs()
-    a.struct_size = C.sizeof(TimedToursArgs)
-    a.H, a.W, a.movement = int(grid.shape[0]), int(grid.shape[1]), int(movement)
-    a.grid, a.occ_threshold = grid.data_ptr(), float(occ_threshold)
-    a.B, a.Gf = int(start_cell.shape[0]), int(fields.shape[0])
-    a.start_cell, a.K, a.dwell = start_cell.data_ptr(), int(stops.shape[1]), int(dwell)
+    a = _timed_common(TimedToursArgs, grid, start_cell, fields, goal_cells, orders, work, paths, status, arrive, key, best,
+                      movement, occ_threshold, sep2, lag)
+    a.K, a.dwell = int(stops.shape[1]), int(dwell)
     a.stops, a.len, a.park_index = stops.data_ptr(), lens.data_ptr(), park_index.data_ptr()
-    a.fields, a.goal_cells = fields.data_ptr(), goal_cells.data_ptr()
-    a.T, a.sep2, a.lag, a.G = int(paths.shape[2]) - 1, int(sep2), int(lag), int(orders.shape[0])
-    a.orders = orders.data_ptr()
-    a.work, a.work_bytes = work.data_ptr(), int(work.numel() * work.element_size())
-    a.paths, a.status, a.arrive, a.key, a.best = (paths.data_ptr(), status.data_ptr(), arrive.data_ptr(), key.data_ptr(),
-                                                  best.data_ptr())
     a.serve_at, a.served, a.unserved = serve_at.data_ptr(), served.data_ptr(), unserved.data_ptr()
     a._keep = (grid, start_cell, stops, lens, park_index, fields, goal_cells, orders, work, paths, status, arrive, key, best,
                serve_at, served, unserved)
@@ -893,11 +881,7 @@ TIMED_RESERVE_MAX_PATHS, TIMED_KEPT = (_abi.timed_replan_constants["RMPC_TIMED_"
 
 def timed_reserve_words(H: int, W: int, T: int) -> int:
     """the 64-bit words of a reservation table: T + 1 layers of H ceil(W / 64) (``rmpc_timed_reserve_words``)"""
-    L = load_library()
-    n = L.rmpc_timed_reserve_words(int(H), int(W), int(T))
-    if n < 0:
-        raise RmpcError("rmpc_timed_reserve_words failed: " + L.rmpc_last_error().decode())
-    return int(n)
+    return _size_query("rmpc_timed_reserve_words", H, W, T)
 
 
 def timed_reserve_device(cells, res, H: int, W: int, sep2: int, lag: int = 1, use=None, clear: bool = True, stream=None):
@@ -913,11 +897,7 @@ def timed_reserve_device(cells, res, H: int, W: int, sep2: int, lag: int = 1, us
 
 def timed_replan_work_bytes(H: int, W: int, T: int, G: int) -> int:
     """bytes of workspace of ``timed_tours_replan_device`` (``rmpc_timed_replan_work_bytes``)"""
-    L = load_library()
-    n = L.rmpc_timed_replan_work_bytes(int(H), int(W), int(T), int(G))
-    if n < 0:
-        raise RmpcError("rmpc_timed_replan_work_bytes failed: " + L.rmpc_last_error().decode())
-    return int(n)
+    return _size_query("rmpc_timed_replan_work_bytes", H, W, T, G)
 
 
 def timed_replan_args(work, res0=None, active=None, begin=None, clash=None) -> TimedReplanArgs:
@@ -944,11 +924,7 @@ TIMED_MAX_ROUNDS = _abi.timed_repair_constants["RMPC_TIMED_MAX_ROUNDS"]
 
 def timed_plan_repair_work_bytes(H: int, W: int, T: int, G: int, B: int) -> int:
     """bytes of workspace of ``timed_plan_repair_device`` (``rmpc_timed_plan_repair_work_bytes``)"""
-    L = load_library()
-    n = L.rmpc_timed_plan_repair_work_bytes(int(H), int(W), int(T), int(G), int(B))
-    if n < 0:
-        raise RmpcError("rmpc_timed_plan_repair_work_bytes failed: " + L.rmpc_last_error().decode())
-    return int(n)
+    return _size_query("rmpc_timed_plan_repair_work_bytes", H, W, T, G, B)
 
 
 def timed_repair_args(grid, start_cell, goal_index, fields, goal_cells, orders, work, paths, status, arrive, key, best,
@@ -957,18 +933,9 @@ def timed_repair_args(grid, start_cell, goal_index, fields, goal_cells, orders, 
     """The ``rmpc_timed_repair`` of one plan: ``timed_plan_args`` with work a uint8 tensor of
     ``timed_plan_repair_work_bytes``, the number of repair rounds, and the outputs order_out (G, B), rounds_run,
     round_best (G,) int32 -- contiguous device tensors."""
-    a = TimedRepairArgs()
-    a.struct_size = C.sizeof(TimedRepairArgs)
-    a.H, a.W, a.movement = int(grid.shape[0]), int(grid.shape[1]), int(movement)
-    a.grid, a.occ_threshold = grid.data_ptr(), float(occ_threshold)
-    a.B, a.Gf = int(start_cell.shape[0]), int(fields.shape[0])
-    a.start_cell, a.goal_index, a.fields, a.goal_cells = (start_cell.data_ptr(), goal_index.data_ptr(), fields.data_ptr(),
-                                                          goal_cells.data_ptr())
-    a.T, a.sep2, a.lag, a.G = int(paths.shape[2]) - 1, int(sep2), int(lag), int(orders.shape[0])
-    a.orders = orders.data_ptr()
-    a.work, a.work_bytes = work.data_ptr(), int(work.numel() * work.element_size())
-    a.paths, a.status, a.arrive, a.key, a.best = (paths.data_ptr(), status.data_ptr(), arrive.data_ptr(), key.data_ptr(),
-                                                  best.data_ptr())
+    a = _timed_common(TimedRepairArgs, grid, start_cell, fields, goal_cells, orders, work, paths, status, arrive, key, best,
+                      movement, occ_threshold, sep2, lag)
+    a.goal_index = goal_index.data_ptr()
     a.rounds = int(rounds)
     a.order_out, a.rounds_run, a.round_best = order_out.data_ptr(), rounds_run.data_ptr(), round_best.data_ptr()
     a._keep = (grid, start_cell, goal_index, fields, goal_cells, orders, work, paths, status, arrive, key, best, order_out,

@@ -2,7 +2,7 @@
 // rmpc_grid_fields_large_device and rmpc_grid_fields_seeded_large_device (rmpc_world.hip, include/rmpc_grid_large.h) are
 // plain C++ that runs before any HIP call.  Every call below is refused (-1 with the entry's message); the pointers are
 // never read.
-//   bash tests/host/run_grid_large_refusals.sh
+//   bash tests/host/run_refusals.sh grid_large
 #include "../../robot_mpcs_amd/csrc/rmpc_world.hip"
 
 #include <cstdio>

@@ -1,7 +1,7 @@
 // The host side of wide-window localisation under AddressSanitizer + UBSan, as a program of its own: the argument checks
 // of rmpc_grid_min_pyramid_device and rmpc_scan_search_device and the work-size query (rmpc_world.hip) are plain C++ that
 // runs before any HIP call.  Every call below is refused (-1 with the entry's message); the pointers are never read.
-//   bash tests/host/run_search_refusals.sh
+//   bash tests/host/run_refusals.sh search
 #include "../../robot_mpcs_amd/csrc/rmpc_world.hip"
 
 #include <cstdio>

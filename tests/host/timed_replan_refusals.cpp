@@ -2,7 +2,7 @@
 // of rmpc_timed_reserve_device and rmpc_timed_tours_replan_device and the two size queries (rmpc_world.hip) are plain
 // C++ that runs before any HIP call.  Every call below is refused (-1 with the entry's message); the pointers are never
 // read.
-//   bash tests/host/run_timed_replan_refusals.sh
+//   bash tests/host/run_refusals.sh timed_replan
 #include "../../robot_mpcs_amd/csrc/rmpc_world.hip"
 
 #include <cstdio>

@@ -1,7 +1,7 @@
 // The host side of the timed tours under AddressSanitizer + UBSan, as a program of its own: the argument checks of
 // rmpc_timed_tours_plan_device and rmpc_timed_tours_follow_device and the work-size query (rmpc_world.hip) are plain C++
 // that runs before any HIP call.  Every call below is refused (-1 with the entry's message); the pointers are never read.
-//   bash tests/host/run_timed_tours_refusals.sh
+//   bash tests/host/run_refusals.sh timed_tours
 #include "../../robot_mpcs_amd/csrc/rmpc_world.hip"
 
 #include <cmath>

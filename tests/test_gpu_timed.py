@@ -8,65 +8,41 @@ import pytest
 
 from example_loader import load_example
 from gpu_support import DEV, _t
+from timed_cases import random_case as _random_case
 from timed_reference import BAD_ORDER, OUTSIDE, conflicts, fields_for, follow_ref, plan_ref, store_case
+from timed_support import POISON, goal_index, load_runtime, poisoned, same, stage, workspace
 
 pytestmark = pytest.mark.gpu
 
-POISON = -559038737          # 0xDEADBEEF as an int32
 KEYS = ("paths", "status", "arrive", "key", "best")
 
 
 @pytest.fixture(scope="module")
 def rt():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    from robot_mpcs_amd import _lib
-    return dict(torch=torch, lib=_lib)
+    return load_runtime()
 
 
 def _device_plan(rt, grid, starts, goals, orders, T, sep2, lag=1, movement=4, occ=0.8, stream=None):
     """-> (device results as numpy, the restatement's) for the same fields"""
     torch, lib = rt["torch"], rt["lib"]
-    grid = np.asarray(grid, dtype=float)
-    H, W = grid.shape
-    goal_cells = np.unique(np.asarray(goals)).astype(np.int32)
-    gi = np.searchsorted(goal_cells, goals).astype(np.int32)
-    orders = np.atleast_2d(np.asarray(orders)).astype(np.int32)
-    G, B = orders.shape
-    i32 = torch.int32
-    d_grid, d_gc, d_gi = _t(torch, grid), _t(torch, goal_cells, i32), _t(torch, gi, i32)
-    d_s, d_o = _t(torch, np.asarray(starts), i32), _t(torch, orders, i32)
-    fields = torch.full((len(goal_cells), H, W), math.nan, dtype=torch.float64, device=DEV)
-    fstat = torch.full((len(goal_cells),), POISON, dtype=i32, device=DEV)
-    work = torch.full((lib.timed_plan_work_bytes(H, W, T, G),), 0xA5, dtype=torch.uint8, device=DEV)
-    out = dict(paths=torch.full((G, B, T + 1), POISON, dtype=i32, device=DEV),
-               status=torch.full((G, B), POISON, dtype=i32, device=DEV), arrive=torch.full((G, B), POISON, dtype=i32, device=DEV),
-               key=torch.full((G,), POISON, dtype=torch.int64, device=DEV), best=torch.full((1,), POISON, dtype=i32, device=DEV))
-    lib.grid_fields_device(d_grid, d_gc, fields, fstat, movement, occ, 3.0, stream=stream)
-    args = lib.timed_plan_args(d_grid, d_s, d_gi, fields, d_gc, d_o, work, out["paths"], out["status"], out["arrive"],
-                               out["key"], out["best"], movement=movement, occ_threshold=occ, sep2=sep2, lag=lag)
+    goal_cells, gi = goal_index(goals)
+    d = stage(rt, grid, goal_cells, orders, movement, occ, stream, starts=starts, gi=gi)
+    (G, B), (H, W) = d["orders"].shape, d["grid"].shape
+    work = workspace(torch, lib.timed_plan_work_bytes(H, W, T, G))
+    out = poisoned(torch, KEYS, G, B, T)
+    args = lib.timed_plan_args(d["grid"], d["starts"], d["gi"], d["fields"], d["cells"], d["orders"], work, out["paths"],
+                               out["status"], out["arrive"], out["key"], out["best"], movement=movement, occ_threshold=occ,
+                               sep2=sep2, lag=lag)
     lib.timed_plan_device(args, stream=stream)
     torch.cuda.synchronize()
     got = {k: v.cpu().numpy() for k, v in out.items()}
-    want = plan_ref(grid, starts, gi, fields.cpu().numpy(), goal_cells, orders, T, sep2, lag, movement, occ)
+    want = plan_ref(np.asarray(grid, dtype=float), starts, gi, d["fields"].cpu().numpy(), goal_cells, orders, T, sep2, lag,
+                    movement, occ)
     return got, want
 
 
 def _same(got, want):
-    for k in KEYS:
-        assert np.array_equal(got[k], want[k]), (k, got[k], want[k])
-
-
-def _random_case(H, W, B, seed, density=0.15, sep2=4):
-    rng = np.random.default_rng(seed)
-    g = (rng.uniform(size=(H, W)) < density).astype(float)
-    free = rng.permutation(np.flatnonzero(g.ravel() < 0.5))
-    starts = []
-    for c in free:
-        if len(starts) < B and all((c // W - q // W) ** 2 + (c % W - q % W) ** 2 >= sep2 for q in starts):
-            starts.append(int(c))
-    return g, np.array(starts, np.int32), free[-B:].astype(np.int32), rng
+    same(got, want, KEYS)
 
 
 # ---- the plan ----------------------------------------------------------------------------------------------------------

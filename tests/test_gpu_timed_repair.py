@@ -2,65 +2,41 @@
 restatement of tests/timed_repair_reference.py, bit for bit; every launch writes into poisoned outputs and a workspace
 filled with 0xA5.  The restatement ranks end cells on the fields the device computed, so that both compare the same
 doubles.  The store cases at the end need no restatement: they hold the entry to rmpc_timed_plan_device."""
-import math
-
 import numpy as np
 import pytest
 
 from gpu_support import DEV, _t
+from timed_cases import random_case as _random_case
 from timed_reference import BAD_ORDER, OUTSIDE, conflicts, store_case
 from timed_repair_reference import bay_corridor, repair_ref, two_by_three
+from timed_support import goal_index, load_runtime, poisoned, same, stage, workspace
 
 pytestmark = pytest.mark.gpu
 
-POISON = -559038737          # 0xDEADBEEF as an int32
 PLAN_KEYS = ("paths", "status", "arrive", "key", "best")
 KEYS = PLAN_KEYS + ("order_out", "rounds_run", "round_best")
 
 
 @pytest.fixture(scope="module")
 def rt():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    from robot_mpcs_amd import _lib
-    return dict(torch=torch, lib=_lib)
+    return load_runtime()
 
 
 def _inputs(rt, grid, starts, goals, orders, movement, occ, stream=None):
     """the device tensors of a case and its fields, as (dict, numpy goal index, numpy goal cells)"""
-    torch, lib = rt["torch"], rt["lib"]
-    grid = np.asarray(grid, dtype=float)
-    H, W = grid.shape
-    goal_cells = np.unique(np.asarray(goals)).astype(np.int32)
-    gi = np.searchsorted(goal_cells, goals).astype(np.int32)
-    i32 = torch.int32
-    d = dict(grid=_t(torch, grid), gc=_t(torch, goal_cells, i32), gi=_t(torch, gi, i32),
-             s=_t(torch, np.asarray(starts), i32), o=_t(torch, np.atleast_2d(np.asarray(orders)).astype(np.int32), i32))
-    d["fields"] = torch.full((len(goal_cells), H, W), math.nan, dtype=torch.float64, device=DEV)
-    fstat = torch.full((len(goal_cells),), POISON, dtype=i32, device=DEV)
-    lib.grid_fields_device(d["grid"], d["gc"], d["fields"], fstat, movement, occ, 3.0, stream=stream)
-    return d, gi, goal_cells
-
-
-def _poisoned(torch, G, B, T, repair=True):
-    i32 = torch.int32
-    full = lambda *s, dt=i32: torch.full(s, POISON, dtype=dt, device=DEV)
-    out = dict(paths=full(G, B, T + 1), status=full(G, B), arrive=full(G, B), key=full(G, dt=torch.int64), best=full(1))
-    if repair:
-        out.update(order_out=full(G, B), rounds_run=full(G), round_best=full(G))
-    return out
+    goal_cells, gi = goal_index(goals)
+    return stage(rt, grid, goal_cells, orders, movement, occ, stream, starts=starts, gi=gi), gi, goal_cells
 
 
 def _launch_repair(rt, d, T, sep2, rounds, lag, movement, occ, work=None, stream=None):
     """one launch into poisoned outputs -> (the outputs as numpy, the workspace)"""
     torch, lib = rt["torch"], rt["lib"]
-    (G, B), (H, W) = d["o"].shape, d["grid"].shape
+    (G, B), (H, W) = d["orders"].shape, d["grid"].shape
     if work is None:
-        work = torch.full((lib.timed_plan_repair_work_bytes(H, W, T, G, B),), 0xA5, dtype=torch.uint8, device=DEV)
-    out = _poisoned(torch, G, B, T)
-    args = lib.timed_repair_args(d["grid"], d["s"], d["gi"], d["fields"], d["gc"], d["o"], work, out["paths"], out["status"],
-                                 out["arrive"], out["key"], out["best"], out["order_out"], out["rounds_run"],
+        work = workspace(torch, lib.timed_plan_repair_work_bytes(H, W, T, G, B))
+    out = poisoned(torch, KEYS, G, B, T)
+    args = lib.timed_repair_args(d["grid"], d["starts"], d["gi"], d["fields"], d["cells"], d["orders"], work, out["paths"],
+                                 out["status"], out["arrive"], out["key"], out["best"], out["order_out"], out["rounds_run"],
                                  out["round_best"], rounds, movement=movement, occ_threshold=occ, sep2=sep2, lag=lag)
     lib.timed_plan_repair_device(args, stream=stream)
     torch.cuda.synchronize()
@@ -71,10 +47,11 @@ def _launch_plan(rt, d, orders, T, sep2, lag, movement, occ):
     """rmpc_timed_plan_device on the same inputs with the device tensor ``orders``"""
     torch, lib = rt["torch"], rt["lib"]
     (G, B), (H, W) = orders.shape, d["grid"].shape
-    work = torch.full((lib.timed_plan_work_bytes(H, W, T, G),), 0xA5, dtype=torch.uint8, device=DEV)
-    out = _poisoned(torch, G, B, T, repair=False)
-    args = lib.timed_plan_args(d["grid"], d["s"], d["gi"], d["fields"], d["gc"], orders, work, out["paths"], out["status"],
-                               out["arrive"], out["key"], out["best"], movement=movement, occ_threshold=occ, sep2=sep2, lag=lag)
+    work = workspace(torch, lib.timed_plan_work_bytes(H, W, T, G))
+    out = poisoned(torch, PLAN_KEYS, G, B, T)
+    args = lib.timed_plan_args(d["grid"], d["starts"], d["gi"], d["fields"], d["cells"], orders, work, out["paths"],
+                               out["status"], out["arrive"], out["key"], out["best"], movement=movement, occ_threshold=occ,
+                               sep2=sep2, lag=lag)
     lib.timed_plan_device(args)
     torch.cuda.synchronize()
     return {k: v.cpu().numpy() for k, v in out.items()}
@@ -90,20 +67,7 @@ def _device_repair(rt, grid, starts, goals, orders, T, sep2, rounds, lag=1, move
 
 
 def _same(got, want, keys=KEYS):
-    for k in keys:
-        assert np.array_equal(got[k], want[k]), (k, got[k], want[k])
-
-
-def _random_case(H, W, B, seed, density=0.15, sep2=4):
-    rng = np.random.default_rng(seed)
-    g = (rng.uniform(size=(H, W)) < density).astype(float)
-    free = rng.permutation(np.flatnonzero(g.ravel() < 0.5))
-    starts = []
-    for c in free:
-        if len(starts) < B and all((c // W - q // W) ** 2 + (c % W - q % W) ** 2 >= sep2 for q in starts):
-            starts.append(int(c))
-    assert len(starts) == B
-    return g, np.array(starts, np.int32), free[-B:].astype(np.int32), rng
+    same(got, want, keys)
 
 
 # ---- against the restatement ----------------------------------------------------------------------------------------------
@@ -235,7 +199,7 @@ def store(rt):
 
 
 def test_property_a_without_rounds_it_is_the_plan(rt, store):
-    plan = _launch_plan(rt, store["d"], store["d"]["o"], 128, 9, 1, 4, 0.8)
+    plan = _launch_plan(rt, store["d"], store["d"]["orders"], 128, 9, 1, 4, 0.8)
     _same(store["r0"], plan, PLAN_KEYS)
     assert np.array_equal(store["r0"]["order_out"], store["orders"])
     assert store["r0"]["rounds_run"].tolist() == [1] * 4 and store["r0"]["round_best"].tolist() == [0] * 4

@@ -3,38 +3,25 @@ include/rmpc_timed_replan.h) against the numpy restatement of test
 every launch writes into poisoned outputs and a workspace of 0xA5.  The restatement ranks end cells on the fields the
 device computed, so that both compare the same doubles.  The shapes are those of tests/test_gpu_timed_tours.py: the
 smallest that reach each code path."""
-import math
-
 import numpy as np
 import pytest
 
 from example_loader import load_example
 from gpu_support import DEV, _t
+from timed_cases import random_tours_case as _random_case, walkers as _walkers
 from timed_reference import BAD_ORDER, OUTSIDE
 from timed_replan_reference import KEPT, rebase_ref, replan_ref, reserve_ref, table_words
+from timed_support import load_runtime, poisoned, same, stage, workspace
 from timed_tours_reference import INT32_MAX, store_tours_case
-from test_gpu_timed_tours import _random_case
 
 pytestmark = pytest.mark.gpu
 
-POISON = -559038737          # 0xDEADBEEF as an int32
 KEYS = ("paths", "status", "arrive", "serve_at", "served", "key", "unserved", "best", "clash")
 
 
 @pytest.fixture(scope="module")
 def rt():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    from robot_mpcs_amd import _lib
-    return dict(torch=torch, lib=_lib)
-
-
-def _outputs(torch, G, B, T, K):
-    i32 = torch.int32
-    full = lambda *s, dt=i32: torch.full(s, POISON, dtype=dt, device=DEV)
-    return dict(paths=full(G, B, T + 1), status=full(G, B), arrive=full(G, B), key=full(G, dt=torch.int64), best=full(1),
-                serve_at=full(G, B, K), served=full(G, B), unserved=full(G), clash=full(B))
+    return load_runtime()
 
 
 def _device_reserve(rt, H, W, T, cells, sep2, lag=1, use=None, res=None, stream=None):
@@ -50,55 +37,56 @@ def _device_reserve(rt, H, W, T, cells, sep2, lag=1, use=None, res=None, stream=
     return res, res.cpu().numpy().view(np.uint64)
 
 
+def _staged(rt, grid, starts, cells, stops, lens, park, orders, T, movement, occ, stream, keys):
+    """the case on the device, and poisoned outputs ``keys`` for it"""
+    stops = np.asarray(stops, dtype=np.int32).reshape(len(starts), -1)
+    d = stage(rt, grid, cells, orders, movement, occ, stream, starts=starts, stops=stops, lens=lens, park=park)
+    G, B = d["orders"].shape
+    return d, poisoned(rt["torch"], keys, G, B, T, stops.shape[1])
+
+
+def _tours_args(lib, d, out, work, sep2, lag, dwell, movement, occ):
+    return lib.timed_tours_args(d["grid"], d["starts"], d["stops"], d["lens"], d["park"], d["fields"], d["cells"], d["orders"],
+                                work, out["paths"], out["status"], out["arrive"], out["key"], out["best"], out["serve_at"],
+                                out["served"], out["unserved"], dwell=dwell, movement=movement, occ_threshold=occ, sep2=sep2,
+                                lag=lag)
+
+
+def _device_tours_plan(rt, grid, starts, cells, stops, lens, park, orders, T, sep2, lag=1, dwell=0, movement=4, occ=0.8):
+    """rmpc_timed_tours_plan_device on the same case -> its results as numpy"""
+    torch, lib = rt["torch"], rt["lib"]
+    d, out = _staged(rt, grid, starts, cells, stops, lens, park, orders, T, movement, occ, None, KEYS[:-1])
+    (G, B), (H, W) = d["orders"].shape, d["grid"].shape
+    work = workspace(torch, lib.timed_tours_work_bytes(H, W, T, G))
+    lib.timed_tours_plan_device(_tours_args(lib, d, out, work, sep2, lag, dwell, movement, occ))
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
 def _device_replan(rt, grid, starts, cells, stops, lens, park, orders, T, sep2, lag=1, dwell=0, movement=4, occ=0.8, res0=None,
                    active=None, begin=None, stream=None, work=None, restate=True):
     """-> (device results as numpy, the restatement's) for the same fields; res0: boolean layers or None"""
     torch, lib = rt["torch"], rt["lib"]
-    grid = np.asarray(grid, dtype=float)
-    H, W = grid.shape
-    cells = np.asarray(cells, dtype=np.int32)
-    stops = np.asarray(stops, dtype=np.int32).reshape(len(starts), -1)
-    orders = np.atleast_2d(np.asarray(orders)).astype(np.int32)
-    (G, B), K = orders.shape, stops.shape[1]
-    i32 = torch.int32
-    d_grid, d_cells, d_o = _t(torch, grid), _t(torch, cells, i32), _t(torch, orders, i32)
-    d_s, d_stops, d_len, d_park = (_t(torch, np.asarray(a), i32) for a in (starts, stops, lens, park))
-    fields = torch.full((len(cells), H, W), math.nan, dtype=torch.float64, device=DEV)
-    fstat = torch.full((len(cells),), POISON, dtype=i32, device=DEV)
+    d, out = _staged(rt, grid, starts, cells, stops, lens, park, orders, T, movement, occ, stream, KEYS)
+    (G, B), (H, W) = d["orders"].shape, d["grid"].shape
     if work is None:
-        work = torch.full((lib.timed_replan_work_bytes(H, W, T, G),), 0xA5, dtype=torch.uint8, device=DEV)
-    out = _outputs(torch, G, B, T, K)
-    lib.grid_fields_device(d_grid, d_cells, fields, fstat, movement, occ, 3.0, stream=stream)
-    args = lib.timed_tours_args(d_grid, d_s, d_stops, d_len, d_park, fields, d_cells, d_o, work[:0], out["paths"], out["status"],
-                                out["arrive"], out["key"], out["best"], out["serve_at"], out["served"], out["unserved"],
-                                dwell=dwell, movement=movement, occ_threshold=occ, sep2=sep2, lag=lag)
+        work = workspace(torch, lib.timed_replan_work_bytes(H, W, T, G))
+    args = _tours_args(lib, d, out, work[:0], sep2, lag, dwell, movement, occ)
     args.work, args.work_bytes = None, 0                   # (not read)
     d_res = None if res0 is None else _t(torch, table_words(res0).view(np.int64), torch.int64)
-    opt = lambda a: None if a is None else _t(torch, np.asarray(a), i32)
+    opt = lambda a: None if a is None else _t(torch, np.asarray(a), torch.int32)
     x = lib.timed_replan_args(work, d_res, opt(active), opt(begin), out["clash"])
     lib.timed_tours_replan_device(args, x, stream=stream)
     torch.cuda.synchronize()
     got = {k: v.cpu().numpy() for k, v in out.items()}
-    want = replan_ref(grid, starts, stops, lens, park, fields.cpu().numpy(), cells, orders, T, sep2, lag, dwell, movement, occ,
-                      res0=res0, active=active, begin=begin) if restate else None
+    want = replan_ref(np.asarray(grid, dtype=float), starts, stops, lens, park, d["fields"].cpu().numpy(),
+                      np.asarray(cells, dtype=np.int32), orders, T, sep2, lag, dwell, movement, occ, res0=res0, active=active,
+                      begin=begin) if restate else None
     return got, want
 
 
 def _same(got, want, keys=KEYS):
-    for k in keys:
-        assert np.array_equal(got[k], want[k]), (k, got[k], want[k])
-
-
-def _walkers(rng, H, W, T, n):
-    """n random walks of T + 1 cells, a tenth of them -1"""
-    out = []
-    for _ in range(n):
-        r, c, path = int(rng.integers(0, H)), int(rng.integers(0, W)), []
-        for t in range(T + 1):
-            r, c = min(max(r + int(rng.integers(-1, 2)), 0), H - 1), min(max(c + int(rng.integers(-1, 2)), 0), W - 1)
-            path.append(-1 if rng.uniform() < 0.1 else r * W + c)
-        out.append(path)
-    return np.array(out, np.int32)
+    same(got, want, keys)
 
 
 SHAPES = [
@@ -191,10 +179,9 @@ def test_hand_cases(rt):
                                                                (65, 70, 6, 70, 2, 4, 1, 5, 2)])
 def test_c1_and_c2_against_the_timed_tours_entry_itself(rt, H, W, B, T, K, movement, lag, sep2, dwell):
     torch, lib = rt["torch"], rt["lib"]
-    from test_gpu_timed_tours import _device_plan
     c, rng = _random_case(H, W, B, K, 7 * H + W + T, sep2=sep2)
     orders = np.stack([np.arange(B), rng.permutation(B)]).astype(np.int32)
-    full, _ = _device_plan(rt, orders=orders, T=T, sep2=sep2, lag=lag, dwell=dwell, movement=movement, **c)
+    full = _device_tours_plan(rt, orders=orders, T=T, sep2=sep2, lag=lag, dwell=dwell, movement=movement, **c)
     # C1: no table, all active, begin 0
     for extra in (dict(), dict(active=np.ones(B, np.int32), begin=np.zeros(B, np.int32))):
         got, _ = _device_replan(rt, orders=orders, T=T, sep2=sep2, lag=lag, dwell=dwell, movement=movement, restate=False,
@@ -248,7 +235,7 @@ def test_twice_on_one_workspace_and_on_a_side_stream(rt):
     orders = [np.arange(5), rng.permutation(5)]
     res0 = reserve_ref(12, 9, 20, _walkers(rng, 12, 9, 20, 2), 4, 1)
     kw = dict(orders=orders, T=20, sep2=4, dwell=1, movement=8, res0=res0, active=[1, 1, 0, 1, 1], begin=[0, 3, 0, 7, 1])
-    work = torch.full((lib.timed_replan_work_bytes(12, 9, 20, 2),), 0xA5, dtype=torch.uint8, device=DEV)
+    work = workspace(torch, lib.timed_replan_work_bytes(12, 9, 20, 2))
     a, want = _device_replan(rt, work=work, **kw, **c)
     _same(a, want)
     b, _ = _device_replan(rt, work=work, restate=False, **kw, **c)        # what the first left in it

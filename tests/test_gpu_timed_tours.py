@@ -9,83 +9,45 @@ import pytest
 
 from example_loader import load_example
 from gpu_support import DEV, _t
+from timed_cases import random_tours_case as _random_case
 from timed_reference import BAD_ORDER, OUTSIDE, conflicts
+from timed_support import POISON, load_runtime, poisoned, same, stage, workspace
 from timed_tours_reference import INT32_MAX, follow_ref, plan_ref, store_tours_case
 
 pytestmark = pytest.mark.gpu
 
-POISON = -559038737          # 0xDEADBEEF as an int32
 KEYS = ("paths", "status", "arrive", "serve_at", "served", "key", "unserved", "best")
 
 
 @pytest.fixture(scope="module")
 def rt():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    from robot_mpcs_amd import _lib
-    return dict(torch=torch, lib=_lib)
-
-
-def _outputs(torch, G, B, T, K):
-    i32 = torch.int32
-    full = lambda *s, dt=i32: torch.full(s, POISON, dtype=dt, device=DEV)
-    return dict(paths=full(G, B, T + 1), status=full(G, B), arrive=full(G, B), key=full(G, dt=torch.int64), best=full(1),
-                serve_at=full(G, B, K), served=full(G, B), unserved=full(G))
+    return load_runtime()
 
 
 def _device_plan(rt, grid, starts, cells, stops, lens, park, orders, T, sep2, lag=1, dwell=0, movement=4, occ=0.8, stream=None,
                  work=None):
     """-> (device results as numpy, the restatement's) for the same fields"""
     torch, lib = rt["torch"], rt["lib"]
-    grid = np.asarray(grid, dtype=float)
-    H, W = grid.shape
-    cells = np.asarray(cells, dtype=np.int32)
     stops = np.asarray(stops, dtype=np.int32).reshape(len(starts), -1)
-    orders = np.atleast_2d(np.asarray(orders)).astype(np.int32)
-    (G, B), K = orders.shape, stops.shape[1]
-    i32 = torch.int32
-    d_grid, d_cells, d_o = _t(torch, grid), _t(torch, cells, i32), _t(torch, orders, i32)
-    d_s, d_stops, d_len, d_park = (_t(torch, np.asarray(a), i32) for a in (starts, stops, lens, park))
-    fields = torch.full((len(cells), H, W), math.nan, dtype=torch.float64, device=DEV)
-    fstat = torch.full((len(cells),), POISON, dtype=i32, device=DEV)
+    d = stage(rt, grid, cells, orders, movement, occ, stream, starts=starts, stops=stops, lens=lens, park=park)
+    (G, B), (H, W) = d["orders"].shape, d["grid"].shape
     if work is None:
-        work = torch.full((lib.timed_tours_work_bytes(H, W, T, G),), 0xA5, dtype=torch.uint8, device=DEV)
-    out = _outputs(torch, G, B, T, K)
-    lib.grid_fields_device(d_grid, d_cells, fields, fstat, movement, occ, 3.0, stream=stream)
-    args = lib.timed_tours_args(d_grid, d_s, d_stops, d_len, d_park, fields, d_cells, d_o, work, out["paths"], out["status"],
-                                out["arrive"], out["key"], out["best"], out["serve_at"], out["served"], out["unserved"],
-                                dwell=dwell, movement=movement, occ_threshold=occ, sep2=sep2, lag=lag)
+        work = workspace(torch, lib.timed_tours_work_bytes(H, W, T, G))
+    out = poisoned(torch, KEYS, G, B, T, stops.shape[1])
+    args = lib.timed_tours_args(d["grid"], d["starts"], d["stops"], d["lens"], d["park"], d["fields"], d["cells"], d["orders"],
+                                work, out["paths"], out["status"], out["arrive"], out["key"], out["best"], out["serve_at"],
+                                out["served"], out["unserved"], dwell=dwell, movement=movement, occ_threshold=occ, sep2=sep2,
+                                lag=lag)
     lib.timed_tours_plan_device(args, stream=stream)
     torch.cuda.synchronize()
     got = {k: v.cpu().numpy() for k, v in out.items()}
-    want = plan_ref(grid, starts, stops, lens, park, fields.cpu().numpy(), cells, orders, T, sep2, lag, dwell, movement, occ)
+    want = plan_ref(np.asarray(grid, dtype=float), starts, stops, lens, park, d["fields"].cpu().numpy(),
+                    np.asarray(cells, dtype=np.int32), orders, T, sep2, lag, dwell, movement, occ)
     return got, want
 
 
 def _same(got, want, keys=KEYS):
-    for k in keys:
-        assert np.array_equal(got[k], want[k]), (k, got[k], want[k])
-
-
-def _random_case(H, W, B, K, seed, density=0.15, sep2=4, Gf=None, lens=None):
-    """a random map, B starts pairwise sep2 apart, Gf = 3 B free cells to stop at; a robot's stops are the K cells nearest
-    to its start, the nearest first, so that short windows serve some and miss some; tours of mixed length"""
-    rng = np.random.default_rng(seed)
-    g = (rng.uniform(size=(H, W)) < density).astype(float)
-    free = rng.permutation(np.flatnonzero(g.ravel() < 0.5))
-    starts = []
-    for c in free:
-        if len(starts) < B and all((c // W - q // W) ** 2 + (c % W - q % W) ** 2 >= sep2 for q in starts):
-            starts.append(int(c))
-    assert len(starts) == B
-    Gf = 3 * B if Gf is None else Gf
-    cells = free[-Gf:].astype(np.int32)
-    near = lambda s: np.argsort(np.maximum(abs(cells // W - s // W), abs(cells % W - s % W)), kind="stable")
-    stops = np.stack([np.resize(near(s), K) for s in starts]).astype(np.int32)
-    lens = (np.arange(B) % (K + 1) if lens is None else np.full(B, lens)).astype(np.int32)
-    park = rng.integers(0, Gf, B).astype(np.int32)
-    return dict(grid=g, starts=np.array(starts, np.int32), cells=cells, stops=stops, lens=lens, park=park), rng
+    same(got, want, keys)
 
 
 # ---- the plan ----------------------------------------------------------------------------------------------------------
@@ -190,7 +152,7 @@ def test_twice_on_one_workspace_and_on_a_side_stream(rt):
     torch, lib = rt["torch"], rt["lib"]
     c, rng = _random_case(12, 9, 5, 3, 21)
     orders = [np.arange(5), rng.permutation(5)]
-    work = torch.full((lib.timed_tours_work_bytes(12, 9, 20, 2),), 0xA5, dtype=torch.uint8, device=DEV)
+    work = workspace(torch, lib.timed_tours_work_bytes(12, 9, 20, 2))
     a, want = _device_plan(rt, orders=orders, T=20, sep2=4, dwell=1, movement=8, work=work, **c)
     _same(a, want)
     b, _ = _device_plan(rt, orders=orders, T=20, sep2=4, dwell=1, movement=8, work=work, **c)     # what the first left in it
@@ -213,8 +175,8 @@ def test_without_stops_it_is_the_timed_plan_itself(rt, H, W, B, T, movement, lag
     d_grid, d_cells = _t(torch, c["grid"]), _t(torch, c["cells"], i32)
     fields = torch.empty((len(c["cells"]), H, W), dtype=torch.float64, device=DEV)
     lib.grid_fields_device(d_grid, d_cells, fields, torch.empty(len(c["cells"]), dtype=i32, device=DEV), movement, 0.8, 3.0)
-    out = _outputs(torch, 2, B, T, 1)
-    work = torch.full((lib.timed_plan_work_bytes(H, W, T, 2),), 0xA5, dtype=torch.uint8, device=DEV)
+    out = poisoned(torch, ("paths", "status", "arrive", "key", "best"), 2, B, T)
+    work = workspace(torch, lib.timed_plan_work_bytes(H, W, T, 2))
     args = lib.timed_plan_args(d_grid, _t(torch, c["starts"], i32), _t(torch, c["park"], i32), fields, d_cells,
                                _t(torch, orders, i32), work, out["paths"], out["status"], out["arrive"], out["key"], out["best"],
                                movement=movement, sep2=sep2, lag=lag)

@@ -3,26 +3,21 @@ of tests/timed_repair_reference.py on hand-worked cases, the three properties th
 ``plan_ref`` on random maps, the count of rows the rule improves there, and the header, the binding and the entry's
 refusals.  tests/test_gpu_timed_repair.py holds the device to the restatement."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from timed_reference import BAD_ORDER, INT64_MAX, OUTSIDE, conflicts, fields_for, plan_ref
 from timed_repair_reference import bad_robots, bay_corridor, next_order, repair_ref, two_by_three
+from timed_support import I_MAX, NULL, P_, check_header, filled, load_lib, refused
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["rmpc_timed_plan_repair_work_bytes", "rmpc_timed_plan_repair_device"]
 KEYS = ("paths", "status", "arrive", "key", "best")
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    g.build()
-    from robot_mpcs_amd import _lib
-    return _lib
+    return load_lib()
 
 
 def _case(grid, goals, movement=4):
@@ -201,12 +196,7 @@ def test_the_rule_is_not_vacuous_on_these_maps(random_runs):
 def test_symbols_are_declared_by_the_new_header_and_exported(lib):
     from robot_mpcs_amd import _abi
     assert lib.TIMED_REPAIR_SYMBOLS == SYMBOLS == list(_abi.timed_repair_prototypes)
-    code = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "rmpc_timed_repair.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(rmpc_\w+)\s*\(", code))) == sorted(SYMBOLS)
-    L = lib.load_library()
-    for sym in SYMBOLS:
-        fn = getattr(L, sym)
-        assert (fn.restype, list(fn.argtypes)) == tuple(_abi.timed_repair_prototypes[sym])
+    check_header(lib, "rmpc_timed_repair", SYMBOLS, _abi.timed_repair_prototypes)
     vp, i = C.c_void_p, C.c_int
     S, P = _abi.timed_repair_structs["rmpc_timed_repair"], _abi.structs["rmpc_timed_plan"]
     assert _abi.timed_repair_prototypes[SYMBOLS[0]] == (C.c_int64, [i] * 5)
@@ -220,9 +210,6 @@ def test_symbols_are_declared_by_the_new_header_and_exported(lib):
     # the other headers declare what they declared, and the version stands
     assert len(lib.EXPORTED_SYMBOLS) == 65 and len(lib.TIMED_REPLAN_SYMBOLS) == 4
     assert not set(SYMBOLS) & (set(_abi.prototypes) | set(_abi.timed_tours_prototypes) | set(_abi.timed_replan_prototypes))
-    with open(os.path.join(ROOT, "robot_mpcs_amd", "csrc", "sources.txt")) as f:
-        listed = f.read().split()
-    assert "include/rmpc_timed_repair.h" in listed and "robot_mpcs_amd/csrc/rmpc_timed_repair.hpp" in listed
 
 
 def test_sizes(lib):
@@ -238,9 +225,6 @@ def test_sizes(lib):
             lib.timed_plan_repair_work_bytes(*a)
 
 
-P_ = 0x1000      # a host-side fake pointer: a refusal never dereferences it
-I_MAX = 2 ** 31 - 1
-NULL = "null argument"
 ARGS = dict(H=7, W=5, movement=4, grid=P_, occ_threshold=0.8, B=3, Gf=2, start_cell=P_, goal_index=P_, fields=P_,
             goal_cells=P_, T=9, sep2=2, lag=1, G=2, orders=P_, work=P_, work_bytes=1 << 20, paths=P_, status=P_, arrive=P_,
             key=P_, best=P_, rounds=2, order_out=P_, rounds_run=P_, round_best=P_)
@@ -263,22 +247,14 @@ REFUSALS += [(dict(rounds=-1), "timed repair: need 0 <= rounds <= RMPC_TIMED_MAX
 @pytest.mark.parametrize("bad,want", REFUSALS, ids=[",".join("%s=%s" % kv for kv in b.items()) for b, _ in REFUSALS])
 def test_the_entry_refuses_with_a_message_and_without_a_gpu(lib, bad, want):
     L = lib.load_library()
-    a = lib.TimedRepairArgs()
-    a.struct_size = C.sizeof(lib.TimedRepairArgs)
-    for k, v in dict(ARGS, **bad).items():
-        setattr(a, k, v)
-    assert L.rmpc_timed_plan_repair_device(C.byref(a), None) == -1
-    msg = L.rmpc_last_error().decode()
-    assert msg.startswith(want) and msg, (msg, want)
+    a = filled(lib.TimedRepairArgs, ARGS, **bad)
+    refused(L, L.rmpc_timed_plan_repair_device(C.byref(a), None), want)
     assert L.rmpc_timed_plan_repair_device(None, None) == -1 and L.rmpc_last_error().decode() == NULL
 
 
 def test_a_workspace_one_byte_short_and_the_plans_size_are_refused(lib):
     L = lib.load_library()
-    a = lib.TimedRepairArgs()
-    a.struct_size = C.sizeof(lib.TimedRepairArgs)
-    for k, v in ARGS.items():
-        setattr(a, k, v)
+    a = filled(lib.TimedRepairArgs, ARGS)
     for n in (lib.timed_plan_repair_work_bytes(7, 5, 9, 2, 3) - 1, lib.timed_plan_work_bytes(7, 5, 9, 2)):
         a.work_bytes = n
         assert L.rmpc_timed_plan_repair_device(C.byref(a), None) == -1
@@ -288,11 +264,7 @@ def test_a_workspace_one_byte_short_and_the_plans_size_are_refused(lib):
 def test_the_plans_entry_refuses_as_before(lib):
     """the plan's checks moved into a function the two entries share: its messages are what they were"""
     L = lib.load_library()
-    a = lib.TimedPlanArgs()
-    a.struct_size = C.sizeof(lib.TimedPlanArgs)
-    for k, v in ARGS.items():
-        if hasattr(a, k):
-            setattr(a, k, v)
+    a = filled(lib.TimedPlanArgs, {k: v for k, v in ARGS.items() if hasattr(lib.TimedPlanArgs, k)})
     for bad, want in ((dict(G=0), "timed plan: need 1 <= G <= RMPC_TIMED_MAX_ORDERS = 1024"),
                       (dict(struct_size=151), "rmpc_timed_plan.struct_size mismatch"), (dict(grid=None), NULL),
                       (dict(B=1025), "timed plan: need 1 <= B"), (dict(work_bytes=8), "timed plan: the workspace holds 8 bytes")):

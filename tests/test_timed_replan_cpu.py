@@ -3,8 +3,6 @@ tests/timed_replan_reference.py on hand-worked cases and against each other, the
 to the timed tours' restatement, the guarantee (C4) with a pair checker of its own, clash (C5), ``rebase`` on torch CPU
 tensors, the sixth header and its tables, and the refusals of the four entries."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,9 +10,9 @@ import pytest
 import timed_reference as timed
 from timed_reference import BAD_ORDER, OUTSIDE, fields_for
 from timed_replan_reference import KEPT, rebase_ref, replan_ref, replan_walk, reserve_ref, table_words
+from timed_support import I_MAX, NULL, P_, check_header, filled, load_lib, refused
 from timed_tours_reference import INT32_MAX, plan_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["rmpc_timed_reserve_words", "rmpc_timed_reserve_device", "rmpc_timed_replan_work_bytes",
            "rmpc_timed_tours_replan_device"]
 BOTH = (replan_ref, replan_walk)
@@ -23,10 +21,7 @@ OUT = ("paths", "status", "arrive", "serve_at", "served", "unserved", "key", "be
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    g.build()
-    from robot_mpcs_amd import _lib
-    return _lib
+    return load_lib()
 
 
 def one(fn, grid, starts, cells, stops, lens, park, T, sep2=1, lag=1, dwell=0, orders=None, movement=4, reserved=(), active=None,
@@ -360,12 +355,7 @@ def test_rebase_on_torch_cpu_tensors_is_rebase_ref():
 def test_symbols_are_declared_by_the_new_header_and_exported(lib):
     from robot_mpcs_amd import _abi
     assert lib.TIMED_REPLAN_SYMBOLS == SYMBOLS == list(_abi.timed_replan_prototypes)
-    code = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "rmpc_timed_replan.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(rmpc_\w+)\s*\(", code))) == sorted(SYMBOLS)
-    L = lib.load_library()
-    for sym in SYMBOLS:
-        fn = getattr(L, sym)
-        assert (fn.restype, list(fn.argtypes)) == tuple(_abi.timed_replan_prototypes[sym])
+    check_header(lib, "rmpc_timed_replan", SYMBOLS, _abi.timed_replan_prototypes)
     vp, i = C.c_void_p, C.c_int
     S, P = _abi.timed_replan_structs["rmpc_timed_replan"], _abi.timed_tours_structs["rmpc_timed_tours"]
     assert _abi.timed_replan_prototypes[SYMBOLS[0]] == (C.c_int64, [i] * 3)
@@ -380,9 +370,6 @@ def test_symbols_are_declared_by_the_new_header_and_exported(lib):
     # the other headers declare what they declared, and the version stands
     assert len(lib.EXPORTED_SYMBOLS) == 65 and len(lib.TIMED_TOURS_SYMBOLS) == 3 and C.sizeof(P) == 200
     assert not set(SYMBOLS) & (set(_abi.prototypes) | set(_abi.timed_tours_prototypes))
-    with open(os.path.join(ROOT, "robot_mpcs_amd", "csrc", "sources.txt")) as f:
-        listed = f.read().split()
-    assert "include/rmpc_timed_replan.h" in listed and "robot_mpcs_amd/csrc/rmpc_timed_replan.hpp" in listed
 
 
 def test_the_reader_types_a_64_bit_word_and_a_struct_of_an_included_header():
@@ -414,9 +401,6 @@ def test_sizes(lib):
             lib.timed_replan_work_bytes(*a)
 
 
-P_ = 0x1000      # a host-side fake pointer: a refusal never dereferences it
-I_MAX = 2 ** 31 - 1
-NULL = "null argument"
 PLAN = dict(H=7, W=5, movement=4, grid=P_, occ_threshold=0.8, B=3, Gf=2, start_cell=P_, K=2, dwell=1, stops=P_, len=P_,
             park_index=P_, fields=P_, goal_cells=P_, T=9, sep2=2, lag=1, G=2, orders=P_, work=None, work_bytes=0, paths=P_,
             status=P_, arrive=P_, key=P_, best=P_, serve_at=P_, served=P_, unserved=P_)
@@ -442,15 +426,9 @@ REFUSALS += [(dict(K=0), {}, "timed tours: need 1 <= K"), (dict(K=65), {}, "time
 @pytest.mark.parametrize("bad,badx,want", REFUSALS, ids=[",".join("%s=%s" % kv for kv in {**b, **x}.items()) for b, x, _ in REFUSALS])
 def test_replan_entry_refuses_with_a_message_and_without_a_gpu(lib, bad, badx, want):
     L = lib.load_library()
-    a, x = lib.TimedToursArgs(), lib.TimedReplanArgs()
-    a.struct_size, x.struct_size = C.sizeof(lib.TimedToursArgs), C.sizeof(lib.TimedReplanArgs)
-    for k, v in dict(PLAN, **bad).items():                   # (the tours' own work is NULL: it is not read)
-        setattr(a, k, v)
-    for k, v in dict(EXTRA, **badx).items():
-        setattr(x, k, v)
-    assert L.rmpc_timed_tours_replan_device(C.byref(a), C.byref(x), None) == -1
-    msg = L.rmpc_last_error().decode()
-    assert msg.startswith(want) and msg, (msg, want)
+    a = filled(lib.TimedToursArgs, PLAN, **bad)              # (the tours' own work is NULL: it is not read)
+    x = filled(lib.TimedReplanArgs, EXTRA, **badx)
+    refused(L, L.rmpc_timed_tours_replan_device(C.byref(a), C.byref(x), None), want)
     if not badx:
         assert L.rmpc_timed_tours_replan_device(None, C.byref(x), None) == -1 and L.rmpc_last_error().decode() == NULL
     assert L.rmpc_timed_tours_replan_device(C.byref(a), None, None) == -1 and L.rmpc_last_error().decode() == NULL
@@ -458,11 +436,8 @@ def test_replan_entry_refuses_with_a_message_and_without_a_gpu(lib, bad, badx, w
 
 def test_a_workspace_one_byte_short_is_refused(lib):
     L = lib.load_library()
-    a, x = lib.TimedToursArgs(), lib.TimedReplanArgs()
-    a.struct_size, x.struct_size = C.sizeof(lib.TimedToursArgs), C.sizeof(lib.TimedReplanArgs)
-    for k, v in PLAN.items():
-        setattr(a, k, v)
-    x.work, x.work_bytes = P_, lib.timed_replan_work_bytes(7, 5, 9, 2) - 1
+    a = filled(lib.TimedToursArgs, PLAN)
+    x = filled(lib.TimedReplanArgs, {}, work=P_, work_bytes=lib.timed_replan_work_bytes(7, 5, 9, 2) - 1)
     assert L.rmpc_timed_tours_replan_device(C.byref(a), C.byref(x), None) == -1
     assert "are needed (rmpc_timed_replan_work_bytes)" in L.rmpc_last_error().decode()
 

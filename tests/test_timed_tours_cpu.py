@@ -4,17 +4,15 @@ plan's restatement, the rule's properties, the follower's restatement, the store
 the fifth header and its tables, and every refusal of the three entries."""
 import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
 import timed_reference as timed
 from timed_reference import OUTSIDE, conflicts, fields_for
+from timed_support import I_MAX, NULL, P_, check_header, filled, load_lib, refused
 from timed_tours_reference import INT32_MAX, follow_ref, plan_ref, plan_walk, store_tours_case
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["rmpc_timed_tours_work_bytes", "rmpc_timed_tours_plan_device", "rmpc_timed_tours_follow_device"]
 BOTH = (plan_ref, plan_walk)
 OUT = ("paths", "status", "arrive", "serve_at", "served", "unserved", "key", "best")
@@ -23,10 +21,7 @@ STORE_SEED = 0      # the first seed whose best of 16 orders has no failure and 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    g.build()
-    from robot_mpcs_amd import _lib
-    return _lib
+    return load_lib()
 
 
 def one(fn, grid, starts, cells, stops, lens, park, T, sep2=1, lag=1, dwell=0, orders=None, movement=4):
@@ -400,12 +395,7 @@ def test_store_case_best_order_serves_everything():
 def test_symbols_are_declared_by_the_new_header_and_exported(lib):
     from robot_mpcs_amd import _abi
     assert lib.TIMED_TOURS_SYMBOLS == SYMBOLS == list(_abi.timed_tours_prototypes)
-    code = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "rmpc_timed_tours.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(rmpc_\w+)\s*\(", code))) == sorted(SYMBOLS)
-    L = lib.load_library()
-    for sym in SYMBOLS:
-        fn = getattr(L, sym)
-        assert (fn.restype, list(fn.argtypes)) == tuple(_abi.timed_tours_prototypes[sym])
+    check_header(lib, "rmpc_timed_tours", SYMBOLS, _abi.timed_tours_prototypes)
     vp, i, d = C.c_void_p, C.c_int, C.c_double
     S = _abi.timed_tours_structs["rmpc_timed_tours"]
     assert _abi.timed_tours_prototypes[SYMBOLS[0]] == (C.c_int64, [i] * 4)
@@ -422,9 +412,6 @@ def test_symbols_are_declared_by_the_new_header_and_exported(lib):
     # the other headers declare what they declared
     assert len(lib.EXPORTED_SYMBOLS) == 65 and len(lib.TOURS_SYMBOLS) == 3
     assert not set(SYMBOLS) & (set(_abi.prototypes) | set(_abi.tours_prototypes))
-    with open(os.path.join(ROOT, "robot_mpcs_amd", "csrc", "sources.txt")) as f:
-        listed = f.read().split()
-    assert "include/rmpc_timed_tours.h" in listed and "robot_mpcs_amd/csrc/rmpc_timed_tours.hpp" in listed
 
 
 def test_work_bytes_is_the_timed_plans(lib):
@@ -437,12 +424,9 @@ def test_work_bytes_is_the_timed_plans(lib):
             lib.timed_tours_work_bytes(*a)
 
 
-P_ = 0x1000      # a host-side fake pointer: a refusal never dereferences it
-I_MAX = 2 ** 31 - 1
 PLAN = dict(H=7, W=5, movement=4, grid=P_, occ_threshold=0.8, B=3, Gf=2, start_cell=P_, K=2, dwell=1, stops=P_, len=P_,
             park_index=P_, fields=P_, goal_cells=P_, T=9, sep2=2, lag=1, G=2, orders=P_, work=P_, work_bytes=1 << 20, paths=P_,
             status=P_, arrive=P_, key=P_, best=P_, serve_at=P_, served=P_, unserved=P_)
-NULL = "null argument"
 PLAN_REFUSALS = [(dict([(k, None)]), NULL) for k, v in PLAN.items() if v == P_]
 PLAN_REFUSALS += [(dict(K=k), "timed tours: need 1 <= K <= RMPC_TIMED_TOURS_MAX_STOPS = 64") for k in (0, 65, -1, I_MAX)]
 PLAN_REFUSALS += [(dict(dwell=v), "timed tours: need 0 <= dwell <= RMPC_TIMED_TOURS_MAX_DWELL = 64") for v in (-1, 65, I_MAX)]
@@ -464,14 +448,9 @@ PLAN_REFUSALS += [(dict(B=0), "timed tours: need 1 <= B"), (dict(B=1025), "timed
 @pytest.mark.parametrize("bad,want", PLAN_REFUSALS, ids=[",".join("%s=%s" % kv for kv in b.items()) for b, _ in PLAN_REFUSALS])
 def test_plan_entry_refuses_with_a_message_and_without_a_gpu(lib, bad, want):
     L = lib.load_library()
-    a = lib.TimedToursArgs()
-    a.struct_size = C.sizeof(lib.TimedToursArgs)
     assert set(bad) <= set(PLAN) | {"struct_size"}
-    for k, v in dict(PLAN, **bad).items():
-        setattr(a, k, v)
-    assert L.rmpc_timed_tours_plan_device(C.byref(a), None) == -1
-    msg = L.rmpc_last_error().decode()
-    assert msg.startswith(want) and msg, (msg, want)
+    a = filled(lib.TimedToursArgs, PLAN, **bad)
+    refused(L, L.rmpc_timed_tours_plan_device(C.byref(a), None), want)
     assert L.rmpc_timed_tours_plan_device(None, None) == -1 and L.rmpc_last_error().decode() == NULL
 
 

@@ -1,7 +1,10 @@
 """The timed tours' rules restated on the CPU from include/rmpc_timed_tours.h (rmpc_timed_tours_plan_device,
 rmpc_timed_tours_follow_device): ``plan_ref`` works on boolean layers and a reservation table, ``plan_walk`` a cell at a
-time on sets against the paths already planned (no table), ``follow_ref`` is the follower's simultaneous step.
-tests/test_timed_tours_cpu.py holds the two against each other and against hand-worked cases,
+time on sets against the paths already planned (no table), ``follow_ref`` is the follower's simultaneous step.  Each
+formulation states its search once, ``_plan_layers`` and ``_plan_sets``, with the start rule, the table an order starts
+from, the robots not planned and the begin layers as parameters: tests/timed_replan_reference.py calls the same two with
+the re-plan's.  The two share what surrounds the search (``_skipped``, ``_blank``, ``_finish``, ``_problem`` and the helpers
+of tests/timed_reference.py) and no part of it; neither calls the other.  tests/test_timed_tours_cpu.py holds the two against each other and against hand-worked cases,
 tests/test_gpu_timed_tours.py holds the device against ``plan_ref`` and ``follow_ref`` bit for bit.  Grids, cells and
 moves are those of tests/timed_reference.py."""
 import numpy as np
@@ -50,32 +53,31 @@ def _problem(grid, start, stops, lens, park_index, fields, orders):
     return grid, stops, orders, grid.shape[0], grid.shape[1], len(start), stops.shape[1], len(fields), orders.shape[0]
 
 
-def plan_ref(grid, start, stops, lens, park_index, fields, goal_cells, orders, T, sep2, lag=1, dwell=0, movement=4, occ=0.8):
-    """The rule of rmpc_timed_tours_plan_device on boolean layers and a reservation table: dict(paths (G, B, T + 1),
-    status, arrive, served (G, B), serve_at (G, B, K), unserved (G,), best (1,) int32, key (G,) int64).  stops (B, K),
-    lens, park_index (B,)."""
-    grid, stops, orders, H, W, B, K, Gf, G = _problem(grid, start, stops, lens, park_index, fields, orders)
+def _plan_layers(problem, start, lens, park_index, fields, goal_cells, T, sep2, lag, dwell, movement, occ, res0, roles, begin,
+                 start_rule):
+    """The route search on boolean layers and a reservation table, once for the tours and the re-plan -> (out, valid).
+    ``problem`` is ``_problem``'s tuple; res0 (T + 1, H, W) bool is the table every order starts from, or None;
+    roles[b] is None for a robot to plan, else the (status, arrive) it gets unplanned; begin[b] is the layer up to which
+    a planned robot stands on its start; ``start_rule(disc, order, k, b)`` gives the layers (T + 1, H, W) that the
+    starts of other robots bar from the robot b at rank k of ``order``, ``disc(c)`` being the cells in conflict with c."""
+    grid, stops, orders, H, W, B, K, Gf, G = problem
     HW = H * W
     free = ~(grid >= occ)
     rows, cols = np.mgrid[0:H, 0:W]
     disc = lambda c: (rows - c // W) ** 2 + (cols - c % W) ** 2 < sep2
     moves = [(dc, dr) for dc, dr, _ in MOVES[movement]]
-    skip = [_skipped(int(start[b]), int(lens[b]), stops[b], int(park_index[b]), HW, K, Gf) for b in range(B)]
     out = _blank(G, B, T, K)
     valid = [_is_permutation(orders[g], B) for g in range(G)]
     for g in range(G):
         if not valid[g]:
             continue
-        res = np.zeros((T + 1, H, W), dtype=bool)
+        res = np.zeros((T + 1, H, W), dtype=bool) if res0 is None else np.array(res0, dtype=bool)
         order = [int(b) for b in orders[g]]
         for k, b in enumerate(order):
-            if skip[b]:
-                out["status"][g, b] = OUTSIDE
+            if roles[b] is not None:
+                out["status"][g, b], out["arrive"][g, b] = roles[b]
                 continue
-            later = np.zeros((H, W), dtype=bool)
-            for j in order[k + 1:]:
-                if not skip[j]:
-                    later |= disc(int(start[j]))
+            stand = start_rule(disc, order, k, b)
             reach = np.zeros((T + 1, H, W), dtype=bool)
             p = np.full(T + 1, -1, dtype=np.int32)
 
@@ -84,9 +86,7 @@ def plan_ref(grid, start, stops, lens, park_index, fields, goal_cells, orders, T
                 n = reach[t - 1].copy()
                 for dc, dr in moves:
                     n |= pad[1 - dr:1 - dr + H, 1 - dc:1 - dc + W]
-                n &= free & ~res[t]
-                if t <= lag:
-                    n &= ~later
+                n &= free & ~res[t] & ~stand[t]
                 reach[t] = n
                 return n.any()
 
@@ -109,7 +109,8 @@ def plan_ref(grid, start, stops, lens, park_index, fields, goal_cells, orders, T
                 back(end, te, t0)
                 return te, end
 
-            t0, at, n = 0, int(start[b]), int(lens[b])
+            t0, at, n = int(begin[b]), int(start[b]), int(lens[b])
+            p[:t0 + 1] = at
             status = arrive = None
             for j in range(n):
                 gi = int(stops[b, j])
@@ -120,7 +121,7 @@ def plan_ref(grid, start, stops, lens, park_index, fields, goal_cells, orders, T
                 a, f, t = None, 0, t0
                 while True:
                     if inside and reach[t, s // W, s % W] and t + dwell <= T and not any(
-                            res[u, s // W, s % W] or (u <= lag and later[s // W, s % W]) for u in range(t + 1, t + dwell + 1)):
+                            res[u, s // W, s % W] or stand[u, s // W, s % W] for u in range(t + 1, t + dwell + 1)):
                         a = t
                         break
                     if t == T:
@@ -155,16 +156,41 @@ def plan_ref(grid, start, stops, lens, park_index, fields, goal_cells, orders, T
             out["paths"][g, b], out["status"][g, b], out["arrive"][g, b] = p, status, arrive
             for t in range(T + 1):
                 res[max(0, t - lag):min(T, t + lag) + 1] |= disc(int(p[t]))
+    return out, valid
+
+
+def plan_ref(grid, start, stops, lens, park_index, fields, goal_cells, orders, T, sep2, lag=1, dwell=0, movement=4, occ=0.8):
+    """The rule of rmpc_timed_tours_plan_device on boolean layers and a reservation table: dict(paths (G, B, T + 1),
+    status, arrive, served (G, B), serve_at (G, B, K), unserved (G,), best (1,) int32, key (G,) int64).  stops (B, K),
+    lens, park_index (B,)."""
+    problem = _problem(grid, start, stops, lens, park_index, fields, orders)
+    grid, stops, orders, H, W, B, K, Gf, G = problem
+    skip = [_skipped(int(start[b]), int(lens[b]), stops[b], int(park_index[b]), H * W, K, Gf) for b in range(B)]
+
+    def later_starts(disc, order, k, b):
+        """rule 3: the starts of the robots ranked behind b, during t <= lag"""
+        stand = np.zeros((T + 1, H, W), dtype=bool)
+        for j in order[k + 1:]:
+            if not skip[j]:
+                stand[:lag + 1] |= disc(int(start[j]))
+        return stand
+
+    out, valid = _plan_layers(problem, start, lens, park_index, fields, goal_cells, T, sep2, lag, dwell, movement, occ, None,
+                              [(OUTSIDE, T + 1) if s else None for s in skip], np.zeros(B, dtype=np.int64), later_starts)
     return _finish(out, valid, lens, K, T)
 
 
-def plan_walk(grid, start, stops, lens, park_index, fields, goal_cells, orders, T, sep2, lag=1, dwell=0, movement=4, occ=0.8):
-    """The same rule a cell at a time: layers are sets of cells, and a cell is reserved at t when it conflicts with a
-    cell that a robot planned earlier holds within lag layers of t (no reservation table)."""
-    grid, stops, orders, H, W, B, K, Gf, G = _problem(grid, start, stops, lens, park_index, fields, orders)
+def _plan_sets(problem, start, lens, park_index, fields, goal_cells, T, sep2, lag, dwell, movement, occ, fixed, roles, begin,
+               start_rule):
+    """The same search a cell at a time, once for the tours and the re-plan -> (out, valid): layers are sets of cells,
+    and there is no table.  ``fixed`` is a list of (path (T + 1,), sep2) that every order starts from; a cell is reserved
+    at t when it conflicts with a cell that one of them, or a robot planned earlier, holds within lag layers of t, or
+    with a start (cell, until) of ``start_rule(order, k, b)`` while t <= until.  roles and begin as in the layers."""
+    grid, stops, orders, H, W, B, K, Gf, G = problem
     HW = H * W
     moves = [(dc, dr) for dc, dr, _ in MOVES[movement]]
-    skipped = lambda b: _skipped(int(start[b]), int(lens[b]), stops[b], int(park_index[b]), HW, K, Gf)
+    fixed = [([int(c) for c in q], int(s2)) for q, s2 in fixed]
+    window = lambda t: range(max(0, t - lag), min(T, t + lag) + 1)
     out = _blank(G, B, T, K)
     valid = [_is_permutation(orders[g], B) for g in range(G)]
     for g in range(G):
@@ -172,16 +198,18 @@ def plan_walk(grid, start, stops, lens, park_index, fields, goal_cells, orders, 
             continue
         order, planned = [int(b) for b in orders[g]], []
         for k, b in enumerate(order):
-            if skipped(b):
-                out["status"][g, b] = OUTSIDE
+            if roles[b] is not None:
+                out["status"][g, b], out["arrive"][g, b] = roles[b]
                 continue
-            later = [int(start[j]) for j in order[k + 1:] if not skipped(j)]
+            others = start_rule(order, k, b)
 
             def reserved(c, t):
                 """what rule 3 and the held test ask beyond the grid"""
-                if t <= lag and any(_d2(c, sj, W) < sep2 for sj in later):
+                if any(t <= until and _d2(c, sr, W) < sep2 for sr, until in others):
                     return True
-                return any(_d2(c, int(q[u]), W) < sep2 for q in planned for u in range(max(0, t - lag), min(T, t + lag) + 1))
+                if any(0 <= q[u] < HW and _d2(c, q[u], W) < s2 for q, s2 in fixed for u in window(t)):
+                    return True
+                return any(_d2(c, int(q[u]), W) < sep2 for q in planned for u in window(t))
 
             def grow(layer, t):
                 cand = set()
@@ -193,8 +221,8 @@ def plan_walk(grid, start, stops, lens, park_index, fields, goal_cells, orders, 
                             cand.add((r + dr) * W + col + dc)
                 return {c for c in cand if not grid[c // W, c % W] >= occ and not reserved(c, t)}
 
-            def trace(layers, t0, c):
-                """the cells from layer t0 to the last one, ending on c: wait first, else the first move"""
+            def trace(layers, c):
+                """the cells from the first layer to the last one, ending on c: wait first, else the first move"""
                 cells = [c]
                 for layer in reversed(layers[:-1]):
                     if c not in layer:
@@ -207,10 +235,11 @@ def plan_walk(grid, start, stops, lens, park_index, fields, goal_cells, orders, 
                     cells.append(c)
                 return cells[::-1]
 
-            p, serve, at, status, arrive = [], [], int(start[b]), None, T + 1
+            at, status, arrive, serve = int(start[b]), None, T + 1, []
+            p = [at] * (int(begin[b]) + 1)                   # the standing layers; the last cell is where the robot stands
             todo = [int(goal_cells[int(v)]) for v in stops[b, :int(lens[b])]] + [None]        # None: the parking leg
             for j, s in enumerate(todo):
-                t0 = len(p) - 1 if p else 0                 # (the last cell written is where the robot stands)
+                t0 = len(p) - 1
                 layers, f, a = [{at}], 0, None
                 while True:
                     t = t0 + len(layers) - 1
@@ -226,13 +255,13 @@ def plan_walk(grid, start, stops, lens, park_index, fields, goal_cells, orders, 
                         break
                     layers.append(nxt)
                 if a is not None:
-                    p = p[:t0] + trace(layers, t0, s) + [s] * dwell
+                    p = p[:t0] + trace(layers, s) + [s] * dwell
                     serve.append(a)
                     at = s
                     continue
                 gi = int(park_index[b]) if s is None else int(stops[b, j])
                 end = _end_cell(np.array(sorted(layers[-1])), np.asarray(fields[gi]).ravel())
-                p = p[:t0] + trace(layers, t0, end)
+                p = p[:t0] + trace(layers, end)
                 te = len(p) - 1
                 p += [end] * (T - te)
                 status = f
@@ -244,6 +273,18 @@ def plan_walk(grid, start, stops, lens, park_index, fields, goal_cells, orders, 
             out["paths"][g, b], out["status"][g, b], out["arrive"][g, b] = p, status, arrive
             out["serve_at"][g, b, :len(serve)], out["served"][g, b] = serve, len(serve)
             planned.append(p)
+    return out, valid
+
+
+def plan_walk(grid, start, stops, lens, park_index, fields, goal_cells, orders, T, sep2, lag=1, dwell=0, movement=4, occ=0.8):
+    """The same rule a cell at a time: layers are sets of cells, and a cell is reserved at t when it conflicts with a
+    cell that a robot planned earlier holds within lag layers of t (no reservation table)."""
+    problem = _problem(grid, start, stops, lens, park_index, fields, orders)
+    grid, stops, orders, H, W, B, K, Gf, G = problem
+    skipped = lambda b: _skipped(int(start[b]), int(lens[b]), stops[b], int(park_index[b]), H * W, K, Gf)
+    later_starts = lambda order, k, b: [(int(start[j]), lag) for j in order[k + 1:] if not skipped(j)]       # rule 3
+    out, valid = _plan_sets(problem, start, lens, park_index, fields, goal_cells, T, sep2, lag, dwell, movement, occ, (),
+                            [(OUTSIDE, T + 1) if skipped(b) else None for b in range(B)], [0] * B, later_starts)
     return _finish(out, valid, lens, K, T)
 
 
