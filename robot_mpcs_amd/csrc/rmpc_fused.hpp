@@ -261,7 +261,8 @@ __device__ __noinline__ RMPC_ONE_WAVE void fused_sweep_step_call(__attribute__((
   if constexpr (FIRSTC != 0) {
     // the first pass of a solve takes no step: nothing to merge
     r.amin_p = amin_p_in; r.amin_d = amin_d_in; r.gphi = gphi_in;
-    if (live) sweep_body<C, -1, ldouble, V, FIRSTC>(sk, v, io, k, true, nostep, 0.0, 0.0, mu, r.q);
+    // (MERGED: the later passes of this instance take their step lengths from PHASE 1 below, never from step_body)
+    if (live) sweep_body<C, -1, ldouble, V, FIRSTC, 0, true>(sk, v, io, k, true, nostep, 0.0, 0.0, mu, r.q);
   } else {
     // One set of requests per pass: the top of the sweep (PHASE 1) asks for every word of the stage once and forms
     // the step lengths from the loaded values while the words only the sweep needs are still on their way; the sweep

@@ -46,12 +46,15 @@ struct StepRow {
     if constexpr (C::NS > 0) gdz += dz[C::NX];
     row(mu, gdz, g, tv, lv);
   }
-  // single-variable row (j, u) (present: v_row(j, u) >= 0); gl: its stored value (general rows only)
-  template <class V, int NV_>
+  // single-variable row (j, u) (present: v_row(j, u) >= 0); gl: its stored value (general rows only), or (LIM: the
+  // merged call, which does not store it -- ROWWORDS in sweep_body) its limit: the value is formed as the sweep forms it
+  template <class V, bool LIM = false, int NV_>
   __device__ __forceinline__ void var_row(const V &v, const int k, const double mu, const int j, const int u, const double (&z)[NV_],
                                           const double (&dz)[NV_], const double gl, const double tv, const double lv) {
     const bool general = v.v_poff(j, u) >= 0;
-    const double gvv = general ? gl : ((k == 0 && j < C::NX) ? 1.0 : (double)v.v_sgn(j, u) * (z[j] - v.v_val(j, u)));
+    double gvv;
+    if constexpr (LIM) gvv = (k == 0 && j < C::NX) ? 1.0 : (double)v.v_sgn(j, u) * (z[j] - (general ? gl : v.v_val(j, u)));
+    else gvv = general ? gl : ((k == 0 && j < C::NX) ? 1.0 : (double)v.v_sgn(j, u) * (z[j] - v.v_val(j, u)));
     double gdz = (double)v.v_sgn(j, u) * dz[j];
     if constexpr (C::NS > 0) { if (v.v_soft(j, u)) gdz += dz[C::NX]; }
     row(mu, gdz, gvv, tv, lv);
@@ -135,7 +138,9 @@ struct SweepK { int N; double dt; int use_curv; };
 // single-variable rows (top) -- and forms the step lengths of the stage from the loaded values (slen: what step_body
 // computes, same rows in the same order); 2 continues from the registers of `top` with the step lengths the caller
 // reduced over the stages in between, and requests none of tc, lc, gro, jqo, zc, dzp again.
-template <class C, int EARLY_MODE = -1, class RP = gdouble, class V = RtView, int FIRSTC = -1, int PHASE = 0>
+// MERGED: every later pass of the caller takes its step lengths from PHASE 1, none from step_body (both copies of
+// fused_sweep_step_call).
+template <class C, int EARLY_MODE = -1, class RP = gdouble, class V = RtView, int FIRSTC = -1, int PHASE = 0, bool MERGED = (PHASE != 0)>
 __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const SweepIO<RP> &io, const int k,
                                            const bool first_rt, const bool nostep, const double alpha, const double adual,
                                            const double mu, Partials &out, ldouble *const qacc = nullptr,
@@ -150,6 +155,14 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
   SecStamps st;
   st.start();
   constexpr int NQ = C::NQ, NX = C::NX, NS = C::NS, NU = C::NU, NV = C::NV;
+  // (ROWWORDS, the scope of ROWSUMS / FINROWS below in the merged call: the value of a general single-variable row --
+  //  a limit of q or u from the parameters -- is sg * (z[j] - limit) of the STORED z[j], 1 on the pinned stage.  Its only
+  //  reader was the next step-length computation, which here is PHASE 1 of the same call: that asks for the limit instead
+  //  of the stored value and forms it as PHASE 2 forms `gold`, the expression that formed the stored word -- one
+  //  subtraction and a sign, the same bits, NaN and -0 included -- and neither copy of the call stores it: 12 stores per
+  //  stage and pass less, and the 12 lines of `grow` are never fetched.  PHASE 2 asks for the limits again (the line has
+  //  just been read): held across the reduction they cost the call 18 registers more than it had.  DESIGN.md 5.1)
+  constexpr bool ROWWORDS = MERGED && (C::ROBOT == RMPC_ROBOT_CHAIN) && NQ <= 3 && NS == 0 && V::SPEC && EARLY_MODE < 0;
   const int N = M.N;
   const unsigned loff = io.loff;
   const size_t SS = io.SS;
@@ -266,19 +279,26 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
   if constexpr (PHASE == 1) {
     // ---- merged form: the rest of the stage's requests, then the step lengths from the loaded values -------------
     // (what step_body does, on the words the sweep holds anyway; only the cost gradient and the stored values of the
-    //  general rows are requested for the step lengths alone)
+    //  general rows -- ROWWORDS: their limits, ahead of the rest -- are requested for the step lengths alone)
     double gfv[NV], gl[NV][kVarRows];
+#pragma unroll
+    for (int j = 0; j < NV; j++) {
+#pragma unroll
+      for (int u = 0; u < kVarRows; u++) {
+        gl[j][u] = 0.0;
+        if constexpr (ROWWORDS) { if (v.v_row(j, u) >= 0 && v.v_poff(j, u) >= 0) gl[j][u] = P(v.v_poff(j, u)); }
+      }
+    }
 #pragma unroll
     for (int j = 0; j < NV; j++) {
       gfv[j] = gfa[IDXL(j)];
 #pragma unroll
       for (int u = 0; u < kVarRows; u++) {
         const int i = v.v_row(j, u);
-        gl[j][u] = 0.0;
         if (i < 0) continue;   // (static rows)
         T.vt[j][u] = tc[IDXL(i)];
         T.vl[j][u] = lc[IDXL(i)];
-        if (v.v_poff(j, u) >= 0) gl[j][u] = gro[IDXL(i)];
+        if constexpr (!ROWWORDS) { if (v.v_poff(j, u) >= 0) gl[j][u] = gro[IDXL(i)]; }
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -293,7 +313,7 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
 #pragma unroll
       for (int u = 0; u < kVarRows; u++) {
         if (v.v_row(j, u) < 0) continue;
-        sr.template var_row<V>(v, k, mu, j, u, zo, dzo, gl[j][u], T.vt[j][u], T.vl[j][u]);
+        sr.template var_row<V, ROWWORDS>(v, k, mu, j, u, zo, dzo, gl[j][u], T.vt[j][u], T.vl[j][u]);
       }
     }
     return;
@@ -450,7 +470,8 @@ __device__ __forceinline__ void sweep_body(const SweepK M, const V &v, const Swe
       }
       double g = h;
       if constexpr (NS > 0) { if (soft) g += sl; }
-      if (v.v_poff(j, u) >= 0) grn[IDXL(i)] = g;  // general rows keep their value for k_step
+      // general rows keep their value for k_step (ROWWORDS: the merged call forms it again, nothing reads the word)
+      if constexpr (!ROWWORDS) { if (v.v_poff(j, u) >= 0) grn[IDXL(i)] = g; }
       // the same row at the current iterate (what k_step read back or recomputed)
       double gold = neutral ? 1.0 : sg * (zo[j] - Bv.lim[u]);
       double gdz = sg * dzo[j];
