@@ -56,6 +56,8 @@ TIMED_TOURS_SYMBOLS = list(_abi.timed_tours_prototypes)
 TIMED_REPLAN_SYMBOLS = list(_abi.timed_replan_prototypes)
 # and every symbol include/rmpc_timed_repair.h declares
 TIMED_REPAIR_SYMBOLS = list(_abi.timed_repair_prototypes)
+# and every symbol include/rmpc_any_angle.h declares
+ANY_ANGLE_SYMBOLS = list(_abi.any_angle_prototypes)
 
 _lib = None
 
@@ -125,11 +127,12 @@ def load_library(path: str = LIB_PATH):
         pass
     L = C.CDLL(path)
     # the declarations of include/rmpc.h, include/rmpc_grid_large.h, include/rmpc_assign_opt.h, include/rmpc_tours.h
-    # include/rmpc_timed_tours.h, include/rmpc_timed_replan.h and include/rmpc_timed_repair.h, nothing else
+    # include/rmpc_timed_tours.h, include/rmpc_timed_replan.h, include/rmpc_timed_repair.h and include/rmpc_any_angle.h,
+    # nothing else
     for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items(),
                                       *_abi.assign_prototypes.items(), *_abi.tours_prototypes.items(),
                                       *_abi.timed_tours_prototypes.items(), *_abi.timed_replan_prototypes.items(),
-                                      *_abi.timed_repair_prototypes.items()):
+                                      *_abi.timed_repair_prototypes.items(), *_abi.any_angle_prototypes.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
@@ -377,6 +380,49 @@ def follow_path_device(path, length, idx, pos, goal, W: int, x0: float, y0: floa
     _grid_call("rmpc_follow_path_device", int(path.shape[0]), _ptr(path), _ptr(length), int(path.shape[1]), _ptr(idx),
                _ptr(pos), int(pos.stride(0)), int(W), float(x0), float(y0), float(cell), float(threshold), _ptr(goal),
                _stream_arg(stream))
+
+
+# the limit of the follower that looks ahead (include/rmpc_any_angle.h)
+VISIBLE_MAX_REACH = _abi.any_angle_constants["RMPC_VISIBLE_MAX_REACH"]
+
+
+def shorten_work_bytes(H: int, W: int) -> int:
+    """The bytes of workspace ``grid_shorten_device`` needs on an (H, W) map: the header's RMPC_SHORTEN_WORK_BYTES."""
+    return 4 * int(H) * ((int(W) + 31) // 32)
+
+
+def grid_visible_device(grid, cell_from, cell_to, visible, occ_threshold: float = 0.8, stream=None):
+    """grid (H, W) fp64; cell_from, cell_to, visible (P,) int32: 1 where the second cell is in line of sight of the
+    first, 0 where not, -1 for a cell outside the map (``rmpc_grid_visible_device``, include/rmpc_any_angle.h)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    _grid_call("rmpc_grid_visible_device", H, W, _ptr(grid), float(occ_threshold), int(cell_from.shape[0]), _ptr(cell_from),
+               _ptr(cell_to), _ptr(visible), _stream_arg(stream))
+
+
+def grid_shorten_device(grid, path, length, out, out_length, work, reach: int = 0, keep=None, src=None,
+                        occ_threshold: float = 0.8, stream=None):
+    """path, out (B, max_len) int32, length, out_length (B,) int32; keep, src (B, max_len) int32 or None; work: a
+    contiguous device tensor of at least ``shorten_work_bytes(H, W)`` bytes: every route pulled tight by line of sight
+    (``rmpc_grid_shorten_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    if tuple(out.shape) != tuple(path.shape) or any(t is not None and tuple(t.shape) != tuple(path.shape) for t in (keep, src)):
+        raise ValueError("grid_shorten_device: out, keep and src must have the shape of path")
+    if not work.is_contiguous() or work.numel() * work.element_size() < shorten_work_bytes(H, W):
+        raise ValueError("grid_shorten_device: need a contiguous workspace of shorten_work_bytes(H, W) bytes")
+    _grid_call("rmpc_grid_shorten_device", H, W, _ptr(grid), float(occ_threshold), int(path.shape[0]), _ptr(path),
+               _ptr(length), int(path.shape[1]), int(reach), None if keep is None else _ptr(keep), _ptr(out),
+               _ptr(out_length), None if src is None else _ptr(src), _ptr(work), _stream_arg(stream))
+
+
+def follow_visible_device(path, length, idx, pos, goal, grid, x0: float, y0: float, cell: float, reach: int = 16,
+                          look_ahead: float = 1.3, blocked=None, occ_threshold: float = 0.8, stream=None):
+    """``follow_path_device`` with a look-ahead that sees: every robot's waypoint moves on to the farthest route cell
+    within ``reach`` cells and ``look_ahead`` metres that is in line of sight on grid (H, W) fp64; blocked (B,) int32 or
+    None: 1 where no cell qualified (``rmpc_follow_visible_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    _grid_call("rmpc_follow_visible_device", int(path.shape[0]), _ptr(path), _ptr(length), int(path.shape[1]), _ptr(idx),
+               _ptr(pos), int(pos.stride(0)), H, W, _ptr(grid), float(occ_threshold), float(x0), float(y0), float(cell),
+               int(reach), float(look_ahead), _ptr(goal), None if blocked is None else _ptr(blocked), _stream_arg(stream))
 
 
 def lidar_args(pose, points, boxes=None, circles=None, angle_min: float = -np.pi, angle_max: float = np.pi,

@@ -21,6 +21,7 @@
 #include "../../include/rmpc_timed_tours.h"
 #include "../../include/rmpc_timed_replan.h"
 #include "../../include/rmpc_timed_repair.h"
+#include "../../include/rmpc_any_angle.h"
 #include "rmpc_err.hpp"
 
 namespace rmpc {
@@ -111,6 +112,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_timed_replan.hpp"
 #include "rmpc_timed_repair.hpp"
 #include "rmpc_track.hpp"
+#include "rmpc_any_angle.hpp"
 
 using namespace rmpc;
 
@@ -993,6 +995,73 @@ int rmpc_timed_plan_repair_device(const rmpc_timed_repair *x, void *stream) {
   const TimedRepair rep = {x->rounds, (int *)x->order_out, (int *)x->rounds_run, (int *)x->round_best};
   timed_launch(k_timed_plan_repair<true>, k_timed_plan_repair<false>, p.G, p.T, q, stream, p, rep, q, (timed_word *)p.work);
   hipLaunchKernelGGL(k_timed_best, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int64_t *)p.key, p.G, (int *)p.best);
+  return launch_status();
+}
+
+/* line of sight, shortened routes and the follower that looks ahead (rmpc_any_angle.hpp, include/rmpc_any_angle.h,
+ * DESIGN.md 28): every refusal comes before the first HIP call */
+static int any_angle_map_check(const std::string &who, int H, int W) {
+  if (H < 1 || W < 1) return fail(who + ": need H, W >= 1");
+  if ((long long)H * W > RMPC_GRID_LARGE_MAX_CELLS)
+    return fail(who + ": " + std::to_string(H) + "x" + std::to_string(W) + " map exceeds RMPC_GRID_LARGE_MAX_CELLS = " +
+                std::to_string(RMPC_GRID_LARGE_MAX_CELLS) + " cells");
+  return 0;
+}
+
+int rmpc_grid_visible_device(int H, int W, const double *d_grid, double occ_threshold, int P, const int32_t *d_from,
+                             const int32_t *d_to, int32_t *d_visible, void *stream) {
+  const std::string who = "grid visible";
+  if (!d_grid || !d_from || !d_to || !d_visible) return fail("null argument");
+  if (any_angle_map_check(who, H, W)) return -1;
+  if (P < 1) return fail(who + ": need P >= 1");
+  if (use_device_of(d_grid)) return -1;
+  hipLaunchKernelGGL(k_grid_visible, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, occ_threshold,
+                     P, (const int *)d_from, (const int *)d_to, (int *)d_visible);
+  return launch_status();
+}
+
+int rmpc_grid_shorten_device(int H, int W, const double *d_grid, double occ_threshold, int B, const int32_t *d_path,
+                             const int32_t *d_len, int max_len, int reach, const int32_t *d_keep, int32_t *d_out,
+                             int32_t *d_out_len, int32_t *d_src, void *d_work, void *stream) {
+  const std::string who = "grid shorten";
+  if (!d_grid || !d_path || !d_len || !d_out || !d_out_len || !d_work) return fail("null argument");
+  if (any_angle_map_check(who, H, W) || grid_paths_check(who, B, max_len)) return -1;
+  if (reach < 0) return fail(who + ": reach must be >= 0 (0: the whole path)");
+  if (d_out == d_path) return fail(who + ": d_out may not be d_path");
+  if (use_device_of(d_grid)) return -1;
+  const bool lds = max_len <= kShortenLdsCells;
+#ifdef RMPC_SHORTEN_READS_GRID      // the measurement of DESIGN.md 28: no bit image, the walks read the doubles
+  const OccGrid occ{d_grid, W, occ_threshold};
+#else
+  const int waves = H * ((W + 63) / 64);
+  hipLaunchKernelGGL(k_grid_occ_bits, dim3((waves + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, occ_threshold,
+                     (unsigned *)d_work);
+  const OccBits occ{(const unsigned *)d_work, (W + 31) / 32};
+#endif
+  auto kernel = lds ? k_grid_shorten<true, decltype(occ)> : k_grid_shorten<false, decltype(occ)>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(64), lds ? (size_t)max_len * sizeof(int) : 0, (hipStream_t)stream, occ, H, W, B,
+                     (const int *)d_path, (const int *)d_len, max_len, reach, (const int *)d_keep, (int *)d_out,
+                     (int *)d_out_len, (int *)d_src);
+  return launch_status();
+}
+
+int rmpc_follow_visible_device(int B, const int32_t *d_path, const int32_t *d_len, int max_len, int32_t *d_idx,
+                               const double *d_pos, int stride, int H, int W, const double *d_grid, double occ_threshold,
+                               double x0, double y0, double cell, int reach, double look_ahead, double *d_goal,
+                               int32_t *d_blocked, void *stream) {
+  const std::string who = "follow visible";
+  if (!d_path || !d_len || !d_idx || !d_pos || !d_grid || !d_goal) return fail("null argument");
+  if (grid_paths_check(who, B, max_len) || any_angle_map_check(who, H, W)) return -1;
+  if (stride < 2 || !grid_fits(B, stride)) return fail(who + ": need stride >= 2 and B*stride <= INT_MAX");
+  if (reach < 1 || reach > RMPC_VISIBLE_MAX_REACH)
+    return fail(who + ": need 1 <= reach <= RMPC_VISIBLE_MAX_REACH = " + std::to_string(RMPC_VISIBLE_MAX_REACH));
+  if (!(cell > 0.0) || std::isinf(cell)) return fail(who + ": cell must be finite and > 0");
+  if (!(look_ahead > 0.0) || std::isinf(look_ahead) || look_ahead < 2.0 * cell)
+    return fail(who + ": look_ahead must be finite and >= 2 cell");
+  if (use_device_of(d_path)) return -1;
+  hipLaunchKernelGGL(k_follow_visible, dim3((B + kFollowWaves - 1) / kFollowWaves), dim3(64 * kFollowWaves), 0,
+                     (hipStream_t)stream, (const int *)d_path, (const int *)d_len, max_len, (int *)d_idx, d_pos, stride, B, H,
+                     W, d_grid, occ_threshold, x0, y0, cell, reach, look_ahead, d_goal, (int *)d_blocked);
   return launch_status();
 }
 
