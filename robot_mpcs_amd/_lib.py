@@ -58,6 +58,8 @@ TIMED_REPLAN_SYMBOLS = list(_abi.timed_replan_prototypes)
 TIMED_REPAIR_SYMBOLS = list(_abi.timed_repair_prototypes)
 # and every symbol include/rmpc_any_angle.h declares
 ANY_ANGLE_SYMBOLS = list(_abi.any_angle_prototypes)
+# and every symbol include/rmpc_corridor.h declares
+CORRIDOR_SYMBOLS = list(_abi.corridor_prototypes)
 
 _lib = None
 
@@ -127,12 +129,13 @@ def load_library(path: str = LIB_PATH):
         pass
     L = C.CDLL(path)
     # the declarations of include/rmpc.h, include/rmpc_grid_large.h, include/rmpc_assign_opt.h, include/rmpc_tours.h
-    # include/rmpc_timed_tours.h, include/rmpc_timed_replan.h, include/rmpc_timed_repair.h and include/rmpc_any_angle.h,
-    # nothing else
+    # include/rmpc_timed_tours.h, include/rmpc_timed_replan.h, include/rmpc_timed_repair.h, include/rmpc_any_angle.h and
+    # include/rmpc_corridor.h, nothing else
     for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items(),
                                       *_abi.assign_prototypes.items(), *_abi.tours_prototypes.items(),
                                       *_abi.timed_tours_prototypes.items(), *_abi.timed_replan_prototypes.items(),
-                                      *_abi.timed_repair_prototypes.items(), *_abi.any_angle_prototypes.items()):
+                                      *_abi.timed_repair_prototypes.items(), *_abi.any_angle_prototypes.items(),
+                                      *_abi.corridor_prototypes.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
@@ -423,6 +426,40 @@ def follow_visible_device(path, length, idx, pos, goal, grid, x0: float, y0: flo
     _grid_call("rmpc_follow_visible_device", int(path.shape[0]), _ptr(path), _ptr(length), int(path.shape[1]), _ptr(idx),
                _ptr(pos), int(pos.stride(0)), H, W, _ptr(grid), float(occ_threshold), float(x0), float(y0), float(cell),
                int(reach), float(look_ahead), _ptr(goal), None if blocked is None else _ptr(blocked), _stream_arg(stream))
+
+
+# the limit of the corridors' reach (include/rmpc_corridor.h)
+CORRIDOR_MAX_REACH = _abi.corridor_constants["RMPC_CORRIDOR_MAX_REACH"]
+
+
+def corridor_sums_bytes(H: int, W: int) -> int:
+    """The bytes of the summed-area table ``grid_occ_sums_device`` writes for an (H, W) map: the header's
+    RMPC_CORRIDOR_SUMS_BYTES."""
+    return 4 * (int(H) + 1) * (int(W) + 1)
+
+
+def grid_occ_sums_device(grid, sums, occ_threshold: float = 0.8, stream=None):
+    """grid (H, W) fp64 -> sums (H + 1, W + 1) int32, contiguous: the summed-area table of the occupancy
+    (``rmpc_grid_occ_sums_device``, include/rmpc_corridor.h)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    if tuple(sums.shape) != (H + 1, W + 1) or sums.element_size() != 4 or not sums.is_contiguous() or not grid.is_contiguous():
+        raise ValueError("grid_occ_sums_device: need a contiguous grid (H, W) and a contiguous int32 sums (H + 1, W + 1)")
+    _grid_call("rmpc_grid_occ_sums_device", H, W, _ptr(grid), float(occ_threshold), _ptr(sums), _stream_arg(stream))
+
+
+def grid_corridor_device(sums, points, planes, x0: float, y0: float, cell: float, reach: int = 8, slot0: int = 0,
+                         rect=None, status=None, stream=None):
+    """sums (H + 1, W + 1) int32 from ``grid_occ_sums_device``, points (B, N, 3) fp64, planes (B, N, nobst, 4) fp64 whose
+    slots slot0 .. slot0 + 3 are written, rect (B, N, 4) and status (B, N) int32 or None: one rectangle of free cells
+    and its four faces per (robot, stage) (``rmpc_grid_corridor_device``)."""
+    H, W = int(sums.shape[0]) - 1, int(sums.shape[1]) - 1
+    B, N, nobst = int(points.shape[0]), int(points.shape[1]), int(planes.shape[2])
+    if tuple(planes.shape) != (B, N, nobst, 4) or tuple(points.shape) != (B, N, 3) or \
+            (rect is not None and tuple(rect.shape) != (B, N, 4)) or (status is not None and tuple(status.shape) != (B, N)):
+        raise ValueError("grid_corridor_device: need points (B, N, 3), planes (B, N, nobst, 4), rect (B, N, 4), status (B, N)")
+    _grid_call("rmpc_grid_corridor_device", H, W, _ptr(sums), float(x0), float(y0), float(cell), B, N, _ptr(points),
+               int(reach), nobst, int(slot0), _ptr(planes), None if rect is None else _ptr(rect),
+               None if status is None else _ptr(status), _stream_arg(stream))
 
 
 def lidar_args(pose, points, boxes=None, circles=None, angle_min: float = -np.pi, angle_max: float = np.pi,

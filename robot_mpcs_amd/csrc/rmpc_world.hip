@@ -22,6 +22,7 @@
 #include "../../include/rmpc_timed_replan.h"
 #include "../../include/rmpc_timed_repair.h"
 #include "../../include/rmpc_any_angle.h"
+#include "../../include/rmpc_corridor.h"
 #include "rmpc_err.hpp"
 
 namespace rmpc {
@@ -113,6 +114,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_timed_repair.hpp"
 #include "rmpc_track.hpp"
 #include "rmpc_any_angle.hpp"
+#include "rmpc_corridor.hpp"
 
 using namespace rmpc;
 
@@ -1062,6 +1064,41 @@ int rmpc_follow_visible_device(int B, const int32_t *d_path, const int32_t *d_le
   hipLaunchKernelGGL(k_follow_visible, dim3((B + kFollowWaves - 1) / kFollowWaves), dim3(64 * kFollowWaves), 0,
                      (hipStream_t)stream, (const int *)d_path, (const int *)d_len, max_len, (int *)d_idx, d_pos, stride, B, H,
                      W, d_grid, occ_threshold, x0, y0, cell, reach, look_ahead, d_goal, (int *)d_blocked);
+  return launch_status();
+}
+
+/* safe corridors from the map (rmpc_corridor.hpp, include/rmpc_corridor.h): every refusal comes before
+ * the first HIP call */
+int rmpc_grid_occ_sums_device(int H, int W, const double *d_grid, double occ_threshold, int32_t *d_sums, void *stream) {
+  const std::string who = "grid occ sums";
+  if (!d_grid || !d_sums) return fail("null argument");
+  if (any_angle_map_check(who, H, W)) return -1;
+  if (!std::isfinite(occ_threshold)) return fail(who + ": occ_threshold must be finite");
+  if (use_device_of(d_grid)) return -1;
+  hipLaunchKernelGGL(k_occ_row_sums, dim3((H + kSumsRowWaves - 1) / kSumsRowWaves), dim3(64 * kSumsRowWaves), 0,
+                     (hipStream_t)stream, d_grid, H, W, occ_threshold, (int *)d_sums);
+  hipLaunchKernelGGL(k_occ_col_sums, dim3((W + 1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, H, W, (int *)d_sums);
+  return launch_status();
+}
+
+int rmpc_grid_corridor_device(int H, int W, const int32_t *d_sums, double x0, double y0, double cell, int B, int N,
+                              const double *d_points, int reach, int nobst, int slot0, double *d_planes, int32_t *d_rect,
+                              int32_t *d_status, void *stream) {
+  const std::string who = "grid corridor";
+  if (!d_sums || !d_points || !d_planes) return fail("null argument");
+  if (any_angle_map_check(who, H, W)) return -1;
+  if (B < 1 || N < 1) return fail(who + ": need B, N >= 1");
+  if (reach < 1 || reach > RMPC_CORRIDOR_MAX_REACH)
+    return fail(who + ": need 1 <= reach <= RMPC_CORRIDOR_MAX_REACH = " + std::to_string(RMPC_CORRIDOR_MAX_REACH));
+  if (slot0 < 0 || nobst < 4 || slot0 > nobst - 4) return fail(who + ": need 0 <= slot0 and slot0 + 4 <= nobst");
+  if (!grid_fits(B, N) || !grid_fits((long long)B * N, nobst) || !grid_fits((long long)B * N * nobst, 4))
+    return fail(who + ": B*N*nobst*4 must not exceed INT_MAX");
+  if (!(cell > 0.0) || std::isinf(cell)) return fail(who + ": cell must be finite and > 0");
+  if (!std::isfinite(x0) || !std::isfinite(y0)) return fail(who + ": x0 and y0 must be finite");
+  if (use_device_of(d_sums)) return -1;
+  const int n = B * N;
+  hipLaunchKernelGGL(k_grid_corridor, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int *)d_sums, H, W, x0,
+                     y0, cell, n, d_points, reach, nobst, slot0, d_planes, (int *)d_rect, (int *)d_status);
   return launch_status();
 }
 

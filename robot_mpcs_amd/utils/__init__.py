@@ -1,0 +1,3 @@
+from .corridor import MapCorridors
+
+__all__ = ["MapCorridors"]
