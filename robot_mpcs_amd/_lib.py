@@ -60,6 +60,9 @@ TIMED_REPAIR_SYMBOLS = list(_abi.timed_repair_prototypes)
 ANY_ANGLE_SYMBOLS = list(_abi.any_angle_prototypes)
 # and every symbol include/rmpc_corridor.h declares
 CORRIDOR_SYMBOLS = list(_abi.corridor_prototypes)
+# and every symbol include/rmpc_traffic.h declares
+TRAFFIC_SYMBOLS = list(_abi.traffic_prototypes)
+TrafficCostsArgs = _abi.traffic_structs["rmpc_traffic_costs"]     # the edge costs of the traffic-aware fields (rmpc_traffic.h)
 
 _lib = None
 
@@ -129,13 +132,13 @@ def load_library(path: str = LIB_PATH):
         pass
     L = C.CDLL(path)
     # the declarations of include/rmpc.h, include/rmpc_grid_large.h, include/rmpc_assign_opt.h, include/rmpc_tours.h
-    # include/rmpc_timed_tours.h, include/rmpc_timed_replan.h, include/rmpc_timed_repair.h, include/rmpc_any_angle.h and
-    # include/rmpc_corridor.h, nothing else
+    # include/rmpc_timed_tours.h, include/rmpc_timed_replan.h, include/rmpc_timed_repair.h, include/rmpc_any_angle.h,
+    # include/rmpc_corridor.h and include/rmpc_traffic.h, nothing else
     for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items(),
                                       *_abi.assign_prototypes.items(), *_abi.tours_prototypes.items(),
                                       *_abi.timed_tours_prototypes.items(), *_abi.timed_replan_prototypes.items(),
                                       *_abi.timed_repair_prototypes.items(), *_abi.any_angle_prototypes.items(),
-                                      *_abi.corridor_prototypes.items()):
+                                      *_abi.corridor_prototypes.items(), *_abi.traffic_prototypes.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
@@ -460,6 +463,83 @@ def grid_corridor_device(sums, points, planes, x0: float, y0: float, cell: float
     _grid_call("rmpc_grid_corridor_device", H, W, _ptr(sums), float(x0), float(y0), float(cell), B, N, _ptr(points),
                int(reach), nobst, int(slot0), _ptr(planes), None if rect is None else _ptr(rect),
                None if status is None else _ptr(status), _stream_arg(stream))
+
+
+# the limits of the traffic-aware routes (include/rmpc_traffic.h)
+TRAFFIC_PLANES, TRAFFIC_MAX_EDGE, TRAFFIC_MAX_CAP_VISIT, TRAFFIC_MAX_CAP_CONTRA, TRAFFIC_INF = (
+    _abi.traffic_constants["RMPC_TRAFFIC_" + n] for n in ("PLANES", "MAX_EDGE", "MAX_CAP_VISIT", "MAX_CAP_CONTRA", "INF"))
+
+
+def traffic_costs(base_axial: int = 1000, base_diag: int = 1414, w_visit: int = 300, cap_visit: int = 32,
+                  w_contra: int = 700, cap_contra: int = 15) -> TrafficCostsArgs:
+    """The ``rmpc_traffic_costs`` of include/rmpc_traffic.h.  The defaults are the weights of the rule's numpy prototype,
+    a documented starting point nobody has tuned, with caps that keep the largest edge cost
+    1414 + 300 * 32 + 700 * 15 = 21514 below ``TRAFFIC_MAX_EDGE``."""
+    c = TrafficCostsArgs()
+    c.struct_size = C.sizeof(TrafficCostsArgs)
+    c.base_axial, c.base_diag = int(base_axial), int(base_diag)
+    c.w_visit, c.cap_visit, c.w_contra, c.cap_contra = int(w_visit), int(cap_visit), int(w_contra), int(cap_contra)
+    return c
+
+
+def _flow_check(name, flow, H, W):
+    if tuple(flow.shape) != (TRAFFIC_PLANES, H, W) or flow.element_size() != 4 or not flow.is_contiguous():
+        raise ValueError(name + ": need a contiguous int32 flow table (%d, H, W)" % TRAFFIC_PLANES)
+
+
+def grid_traffic_add_device(flow, path, length, sign: int = 1, select=None, stream=None):
+    """flow (9, H, W) int32, path (B, max_len) int32, length (B,) int32, select (B,) int32 or None: adds ``sign`` times
+    the routes of the robots with length > 0 (and select != 0) to the flow table (``rmpc_grid_traffic_add_device``,
+    include/rmpc_traffic.h)."""
+    H, W = int(flow.shape[1]), int(flow.shape[2])
+    _flow_check("grid_traffic_add_device", flow, H, W)
+    B = int(path.shape[0])
+    if tuple(length.shape) != (B,) or (select is not None and tuple(select.shape) != (B,)) or not path.is_contiguous():
+        raise ValueError("grid_traffic_add_device: need a contiguous path (B, max_len), length (B,) and select (B,)")
+    _grid_call("rmpc_grid_traffic_add_device", H, W, B, _ptr(path), _ptr(length), int(path.shape[1]),
+               None if select is None else _ptr(select), int(sign), _ptr(flow), _stream_arg(stream))
+
+
+def grid_fields_traffic_device(grid, flow, costs, goal_cells, fields, status, movement: int = 8, occ_threshold: float = 0.8,
+                               sweeps=None, stream=None):
+    """grid (H, W) fp64, flow (9, H, W) int32, costs a ``traffic_costs()``, goal_cells (G,) int32, fields (G, H, W) int32,
+    status (G,) int32, sweeps (G,) int32 or None: one cost-to-go field per goal on the edge costs of the flow table
+    (``rmpc_grid_fields_traffic_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    G = int(goal_cells.shape[0])
+    _flow_check("grid_fields_traffic_device", flow, H, W)
+    if tuple(fields.shape) != (G, H, W) or fields.element_size() != 4 or not fields.is_contiguous() or not grid.is_contiguous():
+        raise ValueError("grid_fields_traffic_device: need a contiguous grid (H, W) and contiguous int32 fields (G, H, W)")
+    _grid_call("rmpc_grid_fields_traffic_device", H, W, _ptr(grid), float(occ_threshold), _ptr(flow), C.byref(costs), G,
+               _ptr(goal_cells), int(movement), _ptr(fields), _ptr(status), None if sweeps is None else _ptr(sweeps),
+               _stream_arg(stream))
+
+
+def grid_paths_traffic_device(grid, flow, costs, fields, goal_cells, start_cell, goal_index, path, length, movement: int = 8,
+                              occ_threshold: float = 0.8, stream=None):
+    """start_cell, goal_index (B,) int32, path (B, max_len) int32, length (B,) int32: descent of the traffic-aware
+    fields (G, H, W) int32 on the table and costs they were made with (``rmpc_grid_paths_traffic_device``)."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    G, B = int(goal_cells.shape[0]), int(start_cell.shape[0])
+    _flow_check("grid_paths_traffic_device", flow, H, W)
+    if tuple(fields.shape)[1:] != (H, W) or int(fields.shape[0]) < G or fields.element_size() != 4 or \
+            not fields.is_contiguous() or tuple(goal_index.shape) != (B,) or int(path.shape[0]) != B or \
+            tuple(length.shape) != (B,) or not path.is_contiguous():
+        raise ValueError("grid_paths_traffic_device: need int32 fields (G, H, W), start_cell, goal_index, length (B,) and "
+                         "a contiguous path (B, max_len)")
+    _grid_call("rmpc_grid_paths_traffic_device", H, W, _ptr(grid), float(occ_threshold), _ptr(flow), C.byref(costs), G,
+               _ptr(fields), _ptr(goal_cells), B, _ptr(start_cell), _ptr(goal_index), int(movement), int(path.shape[1]),
+               _ptr(path), _ptr(length), _stream_arg(stream))
+
+
+def grid_traffic_score_device(flow, score, base_axial: int = 1000, base_diag: int = 1414, stream=None):
+    """flow (9, H, W) int32 -> score (3,) int64: (L, V, C) of the table (``rmpc_grid_traffic_score_device``)."""
+    H, W = int(flow.shape[1]), int(flow.shape[2])
+    _flow_check("grid_traffic_score_device", flow, H, W)
+    if tuple(score.shape) != (3,) or score.element_size() != 8 or not score.is_contiguous():
+        raise ValueError("grid_traffic_score_device: need a contiguous int64 score (3,)")
+    _grid_call("rmpc_grid_traffic_score_device", H, W, _ptr(flow), int(base_axial), int(base_diag), _ptr(score),
+               _stream_arg(stream))
 
 
 def lidar_args(pose, points, boxes=None, circles=None, angle_min: float = -np.pi, angle_max: float = np.pi,

@@ -4,7 +4,8 @@
 // (rmpc_assign.hpp), the minimum-cost assignment of robots to goals (rmpc_assign_opt.hpp, include/rmpc_assign_opt.h),
 // tours of several tasks per robot and the follower that stops at them (rmpc_tours.hpp, include/rmpc_tours.h),
 // localisation by scan matching (rmpc_locate.hpp), the fleet's timed routes (rmpc_timed.hpp), timed tours through
-// every robot's stops (rmpc_timed_tours.hpp, include/rmpc_timed_tours.h), with
+// every robot's stops (rmpc_timed_tours.hpp, include/rmpc_timed_tours.h), traffic-aware routes on a table of the fleet's
+// flow (rmpc_traffic.hpp, include/rmpc_traffic.h), with
 // their entries of the C ABI.  None of them
 // takes a handle: each call runs on the device its first pointer lives on, on the stream it is given.  A translation
 // unit of its own, which needs rmpc.h, the HIP runtime and the error channel only -- nothing of the solver.
@@ -23,6 +24,7 @@
 #include "../../include/rmpc_timed_repair.h"
 #include "../../include/rmpc_any_angle.h"
 #include "../../include/rmpc_corridor.h"
+#include "../../include/rmpc_traffic.h"
 #include "rmpc_err.hpp"
 
 namespace rmpc {
@@ -115,6 +117,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_track.hpp"
 #include "rmpc_any_angle.hpp"
 #include "rmpc_corridor.hpp"
+#include "rmpc_traffic.hpp"
 
 using namespace rmpc;
 
@@ -1099,6 +1102,96 @@ int rmpc_grid_corridor_device(int H, int W, const int32_t *d_sums, double x0, do
   const int n = B * N;
   hipLaunchKernelGGL(k_grid_corridor, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int *)d_sums, H, W, x0,
                      y0, cell, n, d_points, reach, nobst, slot0, d_planes, (int *)d_rect, (int *)d_status);
+  return launch_status();
+}
+
+/* traffic-aware routes (rmpc_traffic.hpp, include/rmpc_traffic.h): every refusal comes before the first
+ * HIP call */
+static int traffic_map_check(const std::string &who, int H, int W) {
+  if (H < 1 || W < 1) return fail(who + ": need H, W >= 1");
+  if ((long long)H * W > RMPC_GRID_MAX_CELLS)
+    return fail(who + ": " + std::to_string(H) + "x" + std::to_string(W) + " map exceeds RMPC_GRID_MAX_CELLS = " +
+                std::to_string(RMPC_GRID_MAX_CELLS) + " cells");
+  return 0;
+}
+static int traffic_costs_check(const std::string &who, const rmpc_traffic_costs *c, TrafficCosts *out) {
+  if (c->struct_size != (int)sizeof(rmpc_traffic_costs)) return fail("rmpc_traffic_costs.struct_size mismatch");
+  if (c->base_axial < 1 || c->base_diag < 1) return fail(who + ": base_axial and base_diag must be >= 1");
+  if (c->w_visit < 0 || c->w_contra < 0 || c->cap_visit < 0 || c->cap_contra < 0)
+    return fail(who + ": weights and caps must be >= 0");
+  if (c->cap_visit > RMPC_TRAFFIC_MAX_CAP_VISIT)
+    return fail(who + ": cap_visit exceeds RMPC_TRAFFIC_MAX_CAP_VISIT = " + std::to_string(RMPC_TRAFFIC_MAX_CAP_VISIT));
+  if (c->cap_contra > RMPC_TRAFFIC_MAX_CAP_CONTRA)
+    return fail(who + ": cap_contra exceeds RMPC_TRAFFIC_MAX_CAP_CONTRA = " + std::to_string(RMPC_TRAFFIC_MAX_CAP_CONTRA));
+  const long long edge = (long long)(c->base_axial > c->base_diag ? c->base_axial : c->base_diag) +
+                         (long long)c->w_visit * c->cap_visit + (long long)c->w_contra * c->cap_contra;
+  if (edge > RMPC_TRAFFIC_MAX_EDGE)
+    return fail(who + ": the largest edge cost " + std::to_string(edge) + " exceeds RMPC_TRAFFIC_MAX_EDGE = " +
+                std::to_string(RMPC_TRAFFIC_MAX_EDGE));
+  *out = TrafficCosts{c->base_axial, c->base_diag, c->w_visit, c->cap_visit, c->w_contra, c->cap_contra};
+  return 0;
+}
+static int traffic_movement_check(const std::string &who, int movement) {
+  return movement != 4 && movement != 8 ? fail(who + ": movement must be 4 or 8") : 0;
+}
+
+int rmpc_grid_traffic_add_device(int H, int W, int B, const int32_t *d_path, const int32_t *d_len, int max_len,
+                                 const int32_t *d_select, int sign, int32_t *d_flow, void *stream) {
+  const std::string who = "grid traffic add";
+  if (!d_path || !d_len || !d_flow) return fail("null argument");
+  if (traffic_map_check(who, H, W) || grid_paths_check(who, B, max_len)) return -1;
+  if (sign != 1 && sign != -1) return fail(who + ": sign must be +1 or -1");
+  if (use_device_of(d_path)) return -1;
+  const long long n = (long long)B * max_len;
+  hipLaunchKernelGGL(k_traffic_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, H, W, B,
+                     (const int *)d_path, (const int *)d_len, max_len, (const int *)d_select, sign, (int *)d_flow);
+  return launch_status();
+}
+
+int rmpc_grid_fields_traffic_device(int H, int W, const double *d_grid, double occ_threshold, const int32_t *d_flow,
+                                    const rmpc_traffic_costs *costs, int G, const int32_t *d_goal_cells, int movement,
+                                    int32_t *d_fields, int32_t *d_status, int32_t *d_sweeps, void *stream) {
+  const std::string who = "grid fields traffic";
+  TrafficCosts k;
+  if (!d_grid || !d_flow || !costs || !d_goal_cells || !d_fields || !d_status) return fail("null argument");
+  if (traffic_map_check(who, H, W) || traffic_movement_check(who, movement) || grid_fields_check(who, G, H, W)) return -1;
+  if (std::isnan(occ_threshold)) return fail(who + ": occ_threshold must not be a NaN");
+  if (traffic_costs_check(who, costs, &k) || use_device_of(d_grid)) return -1;
+  hipLaunchKernelGGL(k_traffic_fields, dim3(G), dim3(kGridThreads), 0, (hipStream_t)stream, d_grid, H, W, occ_threshold,
+                     (const int *)d_flow, k, (const int *)d_goal_cells, movement, (int *)d_fields, (int *)d_status,
+                     (int *)d_sweeps);
+  return launch_status();
+}
+
+int rmpc_grid_paths_traffic_device(int H, int W, const double *d_grid, double occ_threshold, const int32_t *d_flow,
+                                   const rmpc_traffic_costs *costs, int G, const int32_t *d_fields,
+                                   const int32_t *d_goal_cells, int B, const int32_t *d_start_cell,
+                                   const int32_t *d_goal_index, int movement, int max_len, int32_t *d_path, int32_t *d_len,
+                                   void *stream) {
+  const std::string who = "grid paths traffic";
+  TrafficCosts k;
+  if (!d_grid || !d_flow || !costs || !d_fields || !d_goal_cells || !d_start_cell || !d_goal_index || !d_path || !d_len)
+    return fail("null argument");
+  if (traffic_map_check(who, H, W) || traffic_movement_check(who, movement) || grid_fields_check(who, G, H, W) ||
+      grid_paths_check(who, B, max_len))
+    return -1;
+  if (std::isnan(occ_threshold)) return fail(who + ": occ_threshold must not be a NaN");
+  if (traffic_costs_check(who, costs, &k) || use_device_of(d_grid)) return -1;
+  hipLaunchKernelGGL(k_traffic_paths, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_grid, H, W, occ_threshold,
+                     (const int *)d_flow, k, (const int *)d_fields, (const int *)d_goal_cells, G, (const int *)d_start_cell,
+                     (const int *)d_goal_index, B, movement, max_len, (int *)d_path, (int *)d_len);
+  return launch_status();
+}
+
+int rmpc_grid_traffic_score_device(int H, int W, const int32_t *d_flow, int base_axial, int base_diag, int64_t *d_score,
+                                   void *stream) {
+  const std::string who = "grid traffic score";
+  if (!d_flow || !d_score) return fail("null argument");
+  if (traffic_map_check(who, H, W)) return -1;
+  if (base_axial < 1 || base_diag < 1) return fail(who + ": base_axial and base_diag must be >= 1");
+  if (use_device_of(d_flow)) return -1;
+  hipLaunchKernelGGL(k_traffic_score, dim3(1), dim3(kTrafficScoreThreads), 0, (hipStream_t)stream, H, W, (const int *)d_flow,
+                     base_axial, base_diag, (long long *)d_score);
   return launch_status();
 }
 
