@@ -63,6 +63,9 @@ CORRIDOR_SYMBOLS = list(_abi.corridor_prototypes)
 # and every symbol include/rmpc_traffic.h declares
 TRAFFIC_SYMBOLS = list(_abi.traffic_prototypes)
 TrafficCostsArgs = _abi.traffic_structs["rmpc_traffic_costs"]     # the edge costs of the traffic-aware fields (rmpc_traffic.h)
+# and every symbol include/rmpc_cbs.h declares
+CBS_SYMBOLS = list(_abi.cbs_prototypes)
+CbsArgs = _abi.cbs_structs["rmpc_cbs"]                            # one conflict-based search over the timed routes (rmpc_cbs.h)
 
 _lib = None
 
@@ -133,12 +136,13 @@ def load_library(path: str = LIB_PATH):
     L = C.CDLL(path)
     # the declarations of include/rmpc.h, include/rmpc_grid_large.h, include/rmpc_assign_opt.h, include/rmpc_tours.h
     # include/rmpc_timed_tours.h, include/rmpc_timed_replan.h, include/rmpc_timed_repair.h, include/rmpc_any_angle.h,
-    # include/rmpc_corridor.h and include/rmpc_traffic.h, nothing else
+    # include/rmpc_corridor.h, include/rmpc_traffic.h and include/rmpc_cbs.h, nothing else
     for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items(),
                                       *_abi.assign_prototypes.items(), *_abi.tours_prototypes.items(),
                                       *_abi.timed_tours_prototypes.items(), *_abi.timed_replan_prototypes.items(),
                                       *_abi.timed_repair_prototypes.items(), *_abi.any_angle_prototypes.items(),
-                                      *_abi.corridor_prototypes.items(), *_abi.traffic_prototypes.items()):
+                                      *_abi.corridor_prototypes.items(), *_abi.traffic_prototypes.items(),
+                                      *_abi.cbs_prototypes.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
@@ -1110,6 +1114,48 @@ def timed_plan_repair_device(args: TimedRepairArgs, stream=None):
     """``timed_plan_device`` round after round per order: the robots that failed or came late are planned first in the
     next round, and every row reports its best round (``rmpc_timed_plan_repair_device``)."""
     _grid_call("rmpc_timed_plan_repair_device", C.byref(args), _stream_arg(stream))
+
+
+# limits, outcomes and the places of info of the conflict-based search (include/rmpc_cbs.h)
+CBS_MAX_ROBOTS, CBS_MAX_NODES, CBS_MAX_EXPAND, CBS_MAX_ROUNDS, CBS_INF, CBS_INFO = (
+    _abi.cbs_constants["RMPC_CBS_" + n] for n in ("MAX_ROBOTS", "MAX_NODES", "MAX_EXPAND", "MAX_ROUNDS", "INF", "INFO"))
+CBS_SOLVED, CBS_INFEASIBLE, CBS_POOL, CBS_ROUNDS, CBS_BAD_STATE = (
+    _abi.cbs_constants["RMPC_CBS_" + n] for n in ("SOLVED", "INFEASIBLE", "POOL", "ROUNDS", "BAD_STATE"))
+CBS_INFO_NAMES = ("OUTCOME", "NODE", "CONFLICT_FREE", "COST", "BOUND", "CREATED", "EXPANDED", "ROUNDS_RUN")
+CBS_OUTCOME, CBS_NODE, CBS_CONFLICT_FREE, CBS_COST, CBS_BOUND, CBS_CREATED, CBS_EXPANDED, CBS_ROUNDS_RUN = (
+    _abi.cbs_constants["RMPC_CBS_" + n] for n in CBS_INFO_NAMES)
+
+
+def cbs_work_bytes(H: int, W: int, T: int, B: int, nodes: int, expand: int) -> int:
+    """bytes of workspace of ``cbs_device`` (``rmpc_cbs_work_bytes``)"""
+    return _size_query("rmpc_cbs_work_bytes", H, W, T, B, nodes, expand)
+
+
+def cbs_args(grid, start_cell, goal_index, fields, goal_cells, work, paths, status, arrive, info, nodes: int, expand: int,
+             rounds: int, resume: bool = False, movement: int = 4, occ_threshold: float = 0.8, sep2: int = 9,
+             lag: int = 1) -> CbsArgs:
+    """The ``rmpc_cbs`` of one call: grid (H, W) fp64, start_cell, goal_index (B,) int32, fields (Gf, H, W) fp64,
+    goal_cells (Gf,) int32, work a uint8 tensor of ``cbs_work_bytes``, paths (B, T + 1), status, arrive (B,) and info
+    (CBS_INFO,) int32 -- contiguous device tensors."""
+    a = CbsArgs()
+    a.struct_size = C.sizeof(CbsArgs)
+    a.H, a.W, a.movement = int(grid.shape[0]), int(grid.shape[1]), int(movement)
+    a.grid, a.occ_threshold = grid.data_ptr(), float(occ_threshold)
+    a.B, a.Gf = int(start_cell.shape[0]), int(fields.shape[0])
+    a.start_cell, a.goal_index = start_cell.data_ptr(), goal_index.data_ptr()
+    a.fields, a.goal_cells = fields.data_ptr(), goal_cells.data_ptr()
+    a.T, a.sep2, a.lag = int(paths.shape[1]) - 1, int(sep2), int(lag)
+    a.nodes, a.expand, a.rounds, a.resume = int(nodes), int(expand), int(rounds), int(bool(resume))
+    a.work, a.work_bytes = work.data_ptr(), int(work.numel() * work.element_size())
+    a.paths, a.status, a.arrive, a.info = paths.data_ptr(), status.data_ptr(), arrive.data_ptr(), info.data_ptr()
+    a._keep = (grid, start_cell, goal_index, fields, goal_cells, work, paths, status, arrive, info)
+    return a
+
+
+def cbs_device(args: CbsArgs, stream=None):
+    """``args.rounds`` rounds of conflict-based search over the timed routes, from the root or, with ``args.resume``,
+    from the state the workspace holds (``rmpc_cbs_device``)."""
+    _grid_call("rmpc_cbs_device", C.byref(args), _stream_arg(stream))
 
 
 class Solver:

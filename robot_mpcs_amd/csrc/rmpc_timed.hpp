@@ -308,8 +308,9 @@ struct TimedEnd {
 // The route of one robot from cell s at layer begin through its n stops (legs 0 .. n - 1, each a sweep that ends at the
 // first layer in which the stop is reached and can be held for dwell layers) and on to the cell nearest its parking goal
 // (leg n): path, status and arrive, then the path stamped into res.  Without kStops there are no stops (n is not read):
-// the parking leg alone.  serve_at [n] takes the layers at which the stops are reached.  Ends behind a barrier.
-template <bool kStops, class Rule>
+// the parking leg alone.  serve_at [n] takes the layers at which the stops are reached.  Without kStamp nothing is stamped
+// (rmpc_cbs.hpp: a route under a table of constraints).  Ends behind a barrier.
+template <bool kStops, bool kStamp = true, class Rule>
 __device__ __forceinline__ TimedEnd timed_robot(const TimedDims &d, const TimedWork &wk, Rule &rule, const double *__restrict__ fields,
                                                 const int *__restrict__ goal_cells, int s, int begin, int n_stops,
                                                 const int *__restrict__ stops, int park, int dwell, int *__restrict__ path,
@@ -377,8 +378,10 @@ __device__ __forceinline__ TimedEnd timed_robot(const TimedDims &d, const TimedW
     *status = f; *arrive = a;
   }
   __syncthreads();
-  timed_stamp(res, path, H, W, Wd, L, T, d.lag, d.rad, d.sep2, tid, nt);
-  __syncthreads();
+  if (kStamp) {
+    timed_stamp(res, path, H, W, Wd, L, T, d.lag, d.rad, d.sep2, tid, nt);
+    __syncthreads();
+  }
   return {f, a, done};
 }
 

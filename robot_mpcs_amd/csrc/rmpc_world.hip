@@ -22,6 +22,7 @@
 #include "../../include/rmpc_timed_tours.h"
 #include "../../include/rmpc_timed_replan.h"
 #include "../../include/rmpc_timed_repair.h"
+#include "../../include/rmpc_cbs.h"
 #include "../../include/rmpc_any_angle.h"
 #include "../../include/rmpc_corridor.h"
 #include "../../include/rmpc_traffic.h"
@@ -114,6 +115,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_timed_tours.hpp"
 #include "rmpc_timed_replan.hpp"
 #include "rmpc_timed_repair.hpp"
+#include "rmpc_cbs.hpp"
 #include "rmpc_track.hpp"
 #include "rmpc_any_angle.hpp"
 #include "rmpc_corridor.hpp"
@@ -1000,6 +1002,59 @@ int rmpc_timed_plan_repair_device(const rmpc_timed_repair *x, void *stream) {
   const TimedRepair rep = {x->rounds, (int *)x->order_out, (int *)x->rounds_run, (int *)x->round_best};
   timed_launch(k_timed_plan_repair<true>, k_timed_plan_repair<false>, p.G, p.T, q, stream, p, rep, q, (timed_word *)p.work);
   hipLaunchKernelGGL(k_timed_best, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int64_t *)p.key, p.G, (int *)p.best);
+  return launch_status();
+}
+
+/* optimal timed routes: conflict-based search (rmpc_cbs.hpp, include/rmpc_cbs.h): every refusal comes
+ * before the first HIP call */
+static int cbs_sizes_check(const std::string &who, int H, int W, int T, int B, int nodes, int expand) {
+  if (grid_cells_check(who, H, W, false)) return -1;
+  if (T < 1 || T > RMPC_TIMED_MAX_T) return fail(who + ": need 1 <= T <= RMPC_TIMED_MAX_T = " + std::to_string(RMPC_TIMED_MAX_T));
+  if (B < 1 || B > RMPC_CBS_MAX_ROBOTS)
+    return fail(who + ": need 1 <= B <= RMPC_CBS_MAX_ROBOTS = " + std::to_string(RMPC_CBS_MAX_ROBOTS));
+  if (nodes < 1 || nodes > RMPC_CBS_MAX_NODES)
+    return fail(who + ": need 1 <= nodes <= RMPC_CBS_MAX_NODES = " + std::to_string(RMPC_CBS_MAX_NODES));
+  if (expand < 1 || expand > RMPC_CBS_MAX_EXPAND)
+    return fail(who + ": need 1 <= expand <= RMPC_CBS_MAX_EXPAND = " + std::to_string(RMPC_CBS_MAX_EXPAND));
+  return 0;
+}
+
+int64_t rmpc_cbs_work_bytes(int H, int W, int T, int B, int nodes, int expand) {
+  if (cbs_sizes_check("cbs", H, W, T, B, nodes, expand)) return -1;
+  return cbs_layout(H, W, T, B, nodes, expand).total;
+}
+
+// what names a search in its workspace: a resumed call must bring the sizes and rules the search was started with
+static int cbs_magic(const rmpc_cbs *p) {
+  uint32_t m = 0x43425331u;
+  for (int v : {p->H, p->W, p->movement, p->B, p->Gf, p->T, p->sep2, p->lag, p->nodes, p->expand}) m = (m ^ (uint32_t)v) * 16777619u;
+  return (int)(m | 1u);
+}
+
+int rmpc_cbs_device(const rmpc_cbs *p, void *stream) {
+  const std::string who = "cbs";
+  if (!p) return fail("null argument");
+  if (p->struct_size != (int)sizeof(rmpc_cbs)) return fail("rmpc_cbs.struct_size mismatch");
+  if (!p->grid || !p->start_cell || !p->goal_index || !p->fields || !p->goal_cells || !p->work || !p->paths || !p->status ||
+      !p->arrive || !p->info)
+    return fail("null argument");
+  if (grid_check(p->H, p->W, p->movement) || cbs_sizes_check(who, p->H, p->W, p->T, p->B, p->nodes, p->expand) ||
+      timed_common_check(who, p->B, p->T, p->sep2, p->lag) || grid_fields_check(who, p->Gf, p->H, p->W))
+    return -1;
+  if (p->rounds < 0 || p->rounds > RMPC_CBS_MAX_ROUNDS)
+    return fail(who + ": need 0 <= rounds <= RMPC_CBS_MAX_ROUNDS = " + std::to_string(RMPC_CBS_MAX_ROUNDS));
+  if (timed_work_check(who, "cbs", p->work_bytes, rmpc_cbs_work_bytes(p->H, p->W, p->T, p->B, p->nodes, p->expand))) return -1;
+  if (use_device_of(p->grid)) return -1;
+  TimedGeom q = timed_geom(p->H, p->W, p->T, p->sep2);
+  const CbsLayout y = cbs_layout(p->H, p->W, p->T, p->B, p->nodes, p->expand);
+  q.per_order = y.slot_words;
+  const int magic = cbs_magic(p);
+  if (!p->resume) timed_launch(k_cbs_root<true>, k_cbs_root<false>, 1, p->T, q, stream, *p, q, y, magic);
+  for (int r = 0; r < p->rounds; r++) {
+    hipLaunchKernelGGL(k_cbs_select, dim3(1), dim3(256), 0, (hipStream_t)stream, *p, y, magic, r == 0, 0);
+    timed_launch(k_cbs_expand<true>, k_cbs_expand<false>, 2 * p->expand, p->T, q, stream, *p, q, y);
+  }
+  hipLaunchKernelGGL(k_cbs_select, dim3(1), dim3(256), 0, (hipStream_t)stream, *p, y, magic, p->rounds == 0, 1);
   return launch_status();
 }
 
