@@ -24,7 +24,8 @@ is typed for it), ``include/rmpc_timed_repair.h`` into ``timed_repair_constants`
 ``timed_repair_prototypes``, ``include/rmpc_any_angle.h`` into ``any_angle_constants`` / ``any_angle_prototypes`` (its
 work-size macro takes arguments: not a constant, passed over), ``include/rmpc_corridor.h`` into ``corridor_constants`` /
 ``corridor_prototypes`` (likewise), ``include/rmpc_traffic.h`` into ``traffic_constants`` / ``traffic_structs`` /
-``traffic_prototypes``, ``include/rmpc_cbs.h`` into ``cbs_constants`` / ``cbs_structs`` / ``cbs_prototypes``.
+``traffic_prototypes``, ``include/rmpc_cbs.h`` into ``cbs_constants`` / ``cbs_structs`` / ``cbs_prototypes``,
+``include/rmpc_ecbs.h`` into ``ecbs_constants`` / ``ecbs_structs`` / ``ecbs_prototypes``.
 """
 import ctypes as C
 import os
@@ -51,6 +52,8 @@ CORRIDOR_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_corridor.h")
 TRAFFIC_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_traffic.h")
 # optimal timed routes: conflict-based search: likewise, with a struct of its own
 CBS_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_cbs.h")
+# bounded-suboptimal timed routes: focal conflict-based search: likewise
+ECBS_HEADER = os.path.join(os.path.dirname(HEADER), "rmpc_ecbs.h")
 
 _SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double, "int": C.c_int, "long long": C.c_longlong}
 _DECLARATION = re.compile(r"(?:const\s+)?(long long|\w+)(\s+|\s*(?:\*\s*)+)(\w+)\s*((?:\[\s*\w+\s*\]\s*)*)")
@@ -168,3 +171,4 @@ any_angle_constants, _, any_angle_prototypes = _read(ANY_ANGLE_HEADER)
 corridor_constants, _, corridor_prototypes = _read(CORRIDOR_HEADER)
 traffic_constants, traffic_structs, traffic_prototypes = _read(TRAFFIC_HEADER)
 cbs_constants, cbs_structs, cbs_prototypes = _read(CBS_HEADER)
+ecbs_constants, ecbs_structs, ecbs_prototypes = _read(ECBS_HEADER)

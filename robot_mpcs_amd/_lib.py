@@ -66,6 +66,9 @@ TrafficCostsArgs = _abi.traffic_structs["rmpc_traffic_costs"]     # the edge cos
 # and every symbol include/rmpc_cbs.h declares
 CBS_SYMBOLS = list(_abi.cbs_prototypes)
 CbsArgs = _abi.cbs_structs["rmpc_cbs"]                            # one conflict-based search over the timed routes (rmpc_cbs.h)
+# and every symbol include/rmpc_ecbs.h declares
+ECBS_SYMBOLS = list(_abi.ecbs_prototypes)
+EcbsArgs = _abi.ecbs_structs["rmpc_ecbs"]                         # rmpc_cbs's members, then the weight (rmpc_ecbs.h)
 
 _lib = None
 
@@ -136,13 +139,13 @@ def load_library(path: str = LIB_PATH):
     L = C.CDLL(path)
     # the declarations of include/rmpc.h, include/rmpc_grid_large.h, include/rmpc_assign_opt.h, include/rmpc_tours.h
     # include/rmpc_timed_tours.h, include/rmpc_timed_replan.h, include/rmpc_timed_repair.h, include/rmpc_any_angle.h,
-    # include/rmpc_corridor.h, include/rmpc_traffic.h and include/rmpc_cbs.h, nothing else
+    # include/rmpc_corridor.h, include/rmpc_traffic.h, include/rmpc_cbs.h and include/rmpc_ecbs.h, nothing else
     for name, (restype, argtypes) in (*_abi.prototypes.items(), *_abi.large_prototypes.items(),
                                       *_abi.assign_prototypes.items(), *_abi.tours_prototypes.items(),
                                       *_abi.timed_tours_prototypes.items(), *_abi.timed_replan_prototypes.items(),
                                       *_abi.timed_repair_prototypes.items(), *_abi.any_angle_prototypes.items(),
                                       *_abi.corridor_prototypes.items(), *_abi.traffic_prototypes.items(),
-                                      *_abi.cbs_prototypes.items()):
+                                      *_abi.cbs_prototypes.items(), *_abi.ecbs_prototypes.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.rmpc_desc_size() != C.sizeof(RmpcDesc):
@@ -1156,6 +1159,44 @@ def cbs_device(args: CbsArgs, stream=None):
     """``args.rounds`` rounds of conflict-based search over the timed routes, from the root or, with ``args.resume``,
     from the state the workspace holds (``rmpc_cbs_device``)."""
     _grid_call("rmpc_cbs_device", C.byref(args), _stream_arg(stream))
+
+
+# the focal conflict-based search (include/rmpc_ecbs.h): limits and outcomes are the conflict-based search's
+ECBS_MAX_W_DEN, ECBS_MAX_W, ECBS_INFO, ECBS_LB, ECBS_NCONF = (
+    _abi.ecbs_constants["RMPC_ECBS_" + n] for n in ("MAX_W_DEN", "MAX_W", "INFO", "LB", "NCONF"))
+ECBS_INFO_NAMES = CBS_INFO_NAMES + ("LB", "NCONF")
+
+
+def ecbs_work_bytes(H: int, W: int, T: int, B: int, nodes: int, expand: int) -> int:
+    """bytes of workspace of ``ecbs_device`` (``rmpc_ecbs_work_bytes``)"""
+    return _size_query("rmpc_ecbs_work_bytes", H, W, T, B, nodes, expand)
+
+
+def ecbs_args(grid, start_cell, goal_index, fields, goal_cells, work, paths, status, arrive, info, nodes: int, expand: int,
+              rounds: int, w=(11, 10), resume: bool = False, movement: int = 4, occ_threshold: float = 0.8, sep2: int = 9,
+              lag: int = 1) -> EcbsArgs:
+    """The ``rmpc_ecbs`` of one call: the tensors of ``cbs_args`` with work of ``ecbs_work_bytes`` and info (ECBS_INFO,)
+    int32, and the weight ``w = (w_num, w_den)``."""
+    a = EcbsArgs()
+    a.struct_size = C.sizeof(EcbsArgs)
+    a.H, a.W, a.movement = int(grid.shape[0]), int(grid.shape[1]), int(movement)
+    a.grid, a.occ_threshold = grid.data_ptr(), float(occ_threshold)
+    a.B, a.Gf = int(start_cell.shape[0]), int(fields.shape[0])
+    a.start_cell, a.goal_index = start_cell.data_ptr(), goal_index.data_ptr()
+    a.fields, a.goal_cells = fields.data_ptr(), goal_cells.data_ptr()
+    a.T, a.sep2, a.lag = int(paths.shape[1]) - 1, int(sep2), int(lag)
+    a.nodes, a.expand, a.rounds, a.resume = int(nodes), int(expand), int(rounds), int(bool(resume))
+    a.work, a.work_bytes = work.data_ptr(), int(work.numel() * work.element_size())
+    a.paths, a.status, a.arrive, a.info = paths.data_ptr(), status.data_ptr(), arrive.data_ptr(), info.data_ptr()
+    a.w_num, a.w_den = int(w[0]), int(w[1])
+    a._keep = (grid, start_cell, goal_index, fields, goal_cells, work, paths, status, arrive, info)
+    return a
+
+
+def ecbs_device(args: EcbsArgs, stream=None):
+    """``args.rounds`` rounds of focal conflict-based search over the timed routes, from the root or, with
+    ``args.resume``, from the state the workspace holds (``rmpc_ecbs_device``)."""
+    _grid_call("rmpc_ecbs_device", C.byref(args), _stream_arg(stream))
 
 
 class Solver:

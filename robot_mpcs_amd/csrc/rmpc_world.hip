@@ -23,6 +23,7 @@
 #include "../../include/rmpc_timed_replan.h"
 #include "../../include/rmpc_timed_repair.h"
 #include "../../include/rmpc_cbs.h"
+#include "../../include/rmpc_ecbs.h"
 #include "../../include/rmpc_any_angle.h"
 #include "../../include/rmpc_corridor.h"
 #include "../../include/rmpc_traffic.h"
@@ -116,6 +117,7 @@ __global__ __launch_bounds__(256) void k_fsd(const double *__restrict__ points, 
 #include "rmpc_timed_replan.hpp"
 #include "rmpc_timed_repair.hpp"
 #include "rmpc_cbs.hpp"
+#include "rmpc_ecbs.hpp"
 #include "rmpc_track.hpp"
 #include "rmpc_any_angle.hpp"
 #include "rmpc_corridor.hpp"
@@ -228,6 +230,20 @@ static void timed_launch(Kernel lds, Kernel mem, int G, int T, const TimedGeom &
   const int nt = q.L <= 64 ? 64 : (q.L <= 128 ? 128 : kTimedThreads);      // a power of two: the end cell's reduction
   if (hist <= (size_t)kTimedHistLds) hipLaunchKernelGGL(lds, dim3(G), dim3(nt), hist, (hipStream_t)stream, args...);
   else hipLaunchKernelGGL(mem, dim3(G), dim3(nt), 0, (hipStream_t)stream, args...);
+}
+
+// rmpc_ecbs_device: the history in LDS as timed_launch decides it, the three int32 rows of H W cells behind it when
+// they are small; the workgroup is timed_launch's
+template <class Kernel, class... Args>
+static void ecbs_launch(Kernel both, Kernel hist, Kernel rows, Kernel none, int G, int H, int W, int T, const TimedGeom &q,
+                        void *stream, Args... args) {
+  const size_t hb = (size_t)(T + 1) * q.L * sizeof(timed_word), rb = 3 * sizeof(int) * (size_t)H * W;
+  const bool hl = hb <= (size_t)kTimedHistLds, rl = rb <= (size_t)kEcbsRowsLds;
+  const int nt = q.L <= 64 ? 64 : (q.L <= 128 ? 128 : kTimedThreads);
+  const Kernel kernel = hl ? (rl ? both : hist) : (rl ? rows : none);
+  const size_t lds = (hl ? hb : 0) + (rl ? rb : 0);            // up to 100 KB beside 14 KB of static LDS
+  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, dim3(G), dim3(nt), lds, (hipStream_t)stream, args...);
 }
 
 extern "C" {
@@ -1055,6 +1071,54 @@ int rmpc_cbs_device(const rmpc_cbs *p, void *stream) {
     timed_launch(k_cbs_expand<true>, k_cbs_expand<false>, 2 * p->expand, p->T, q, stream, *p, q, y);
   }
   hipLaunchKernelGGL(k_cbs_select, dim3(1), dim3(256), 0, (hipStream_t)stream, *p, y, magic, p->rounds == 0, 1);
+  return launch_status();
+}
+
+/* bounded-suboptimal timed routes: focal conflict-based search (rmpc_ecbs.hpp, include/rmpc_ecbs.h): every
+ * refusal comes before the first HIP call */
+int64_t rmpc_ecbs_work_bytes(int H, int W, int T, int B, int nodes, int expand) {
+  if (cbs_sizes_check("ecbs", H, W, T, B, nodes, expand)) return -1;
+  return ecbs_layout(H, W, T, B, nodes, expand).total;
+}
+
+static int ecbs_magic(const rmpc_ecbs *p) {
+  uint32_t m = 0x45434253u;
+  for (int v : {p->H, p->W, p->movement, p->B, p->Gf, p->T, p->sep2, p->lag, p->nodes, p->expand, p->w_num, p->w_den})
+    m = (m ^ (uint32_t)v) * 16777619u;
+  return (int)(m | 1u);
+}
+
+int rmpc_ecbs_device(const rmpc_ecbs *p, void *stream) {
+  const std::string who = "ecbs";
+  if (!p) return fail("null argument");
+  if (p->struct_size != (int)sizeof(rmpc_ecbs)) return fail("rmpc_ecbs.struct_size mismatch");
+  if (!p->grid || !p->start_cell || !p->goal_index || !p->fields || !p->goal_cells || !p->work || !p->paths || !p->status ||
+      !p->arrive || !p->info)
+    return fail("null argument");
+  if (grid_check(p->H, p->W, p->movement) || cbs_sizes_check(who, p->H, p->W, p->T, p->B, p->nodes, p->expand) ||
+      timed_common_check(who, p->B, p->T, p->sep2, p->lag) || grid_fields_check(who, p->Gf, p->H, p->W))
+    return -1;
+  if (p->rounds < 0 || p->rounds > RMPC_CBS_MAX_ROUNDS)
+    return fail(who + ": need 0 <= rounds <= RMPC_CBS_MAX_ROUNDS = " + std::to_string(RMPC_CBS_MAX_ROUNDS));
+  if (p->w_den < 1 || p->w_den > RMPC_ECBS_MAX_W_DEN)
+    return fail(who + ": need 1 <= w_den <= RMPC_ECBS_MAX_W_DEN = " + std::to_string(RMPC_ECBS_MAX_W_DEN));
+  if (p->w_num < p->w_den || (long long)p->w_num > (long long)RMPC_ECBS_MAX_W * p->w_den)
+    return fail(who + ": need w_den <= w_num <= RMPC_ECBS_MAX_W * w_den, RMPC_ECBS_MAX_W = " + std::to_string(RMPC_ECBS_MAX_W));
+  if (timed_work_check(who, "ecbs", p->work_bytes, rmpc_ecbs_work_bytes(p->H, p->W, p->T, p->B, p->nodes, p->expand))) return -1;
+  if (use_device_of(p->grid)) return -1;
+  TimedGeom q = timed_geom(p->H, p->W, p->T, p->sep2);
+  const EcbsLayout y = ecbs_layout(p->H, p->W, p->T, p->B, p->nodes, p->expand);
+  q.per_order = y.slot_words;
+  const int magic = ecbs_magic(p);
+  if (!p->resume)
+    ecbs_launch(k_ecbs_root<true, true>, k_ecbs_root<true, false>, k_ecbs_root<false, true>, k_ecbs_root<false, false>, 1, p->H, p->W,
+                p->T, q, stream, *p, q, y, magic);
+  for (int r = 0; r < p->rounds; r++) {
+    hipLaunchKernelGGL(k_ecbs_select, dim3(1), dim3(256), 0, (hipStream_t)stream, *p, y, magic, r == 0, 0);
+    ecbs_launch(k_ecbs_expand<true, true>, k_ecbs_expand<true, false>, k_ecbs_expand<false, true>, k_ecbs_expand<false, false>,
+                2 * p->expand, p->H, p->W, p->T, q, stream, *p, q, y);
+  }
+  hipLaunchKernelGGL(k_ecbs_select, dim3(1), dim3(256), 0, (hipStream_t)stream, *p, y, magic, p->rounds == 0, 1);
   return launch_status();
 }
 

@@ -11,7 +11,8 @@ for part of the fleet while it is under way (``LifelongTours``, ``rebase``; incl
 routes: line of sight on the grid, routes pulled tight by it and a follower that looks ahead (``visible``, ``shorten_routes``,
 ``route_lengths``, ``VisibleFollower``; include/rmpc_any_angle.h), and routes that know about each other: congestion and
 contraflow costs from a table of the fleet's flow (``TrafficRoutes``; include/rmpc_traffic.h), and timed routes with the
-least sum of arrivals, or a lower bound on it, by conflict-based search (``OptimalTimedRoutes``; include/rmpc_cbs.h).  The work is done
+least sum of arrivals, or a lower bound on it, by conflict-based search (``OptimalTimedRoutes``; include/rmpc_cbs.h),
+or plans the whole fleet within a stated factor of that sum by focal search (``BoundedTimedRoutes``; include/rmpc_ecbs.h).  The work is done
 by the ``rmpc_grid_*_device`` / ``rmpc_follow_path_device`` / ``rmpc_timed_*_device`` kernels (include/rmpc.h); there is no CPU path.  Importing
 the package needs no GPU.
 """
@@ -26,7 +27,7 @@ from .timed_tours import TimedTourFollower, TimedTours, pick_spaced_tours
 from .lifelong import LifelongTours, rebase
 from .any_angle import VisibleFollower, route_lengths, shorten_routes, visible
 from .traffic import TrafficRoutes
-from .optimal import OptimalTimedRoutes
+from .optimal import BoundedTimedRoutes, OptimalTimedRoutes
 
-__all__ = ["FREE", "OCC", "OccupancyGridMap", "a_star", "GlobalPlanner", "GoalAssigner", "LifelongTours", "OptimalTimedRoutes", "RouteFollower", "TimedFollower", "TimedRoutes", "TimedTourFollower", "TimedTours", "TourFollower", "TourPlanner", "TrafficRoutes", "VisibleFollower", "cell_xy", "cells_from_positions",
+__all__ = ["BoundedTimedRoutes", "FREE", "OCC", "OccupancyGridMap", "a_star", "GlobalPlanner", "GoalAssigner", "LifelongTours", "OptimalTimedRoutes", "RouteFollower", "TimedFollower", "TimedRoutes", "TimedTourFollower", "TimedTours", "TourFollower", "TourPlanner", "TrafficRoutes", "VisibleFollower", "cell_xy", "cells_from_positions",
            "pick_routes", "pick_spaced_routes", "pick_spaced_tours", "plan_batch", "png_values", "priority_orders", "rebase", "replan", "route_lengths", "shelf_map", "shorten_routes", "store_routes", "visible"]
